@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- hot-path benchmark of the MI355X-native Gaussian rasterizer.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1: launched by torch.distributed.run)
 
 A "step" is one frame: one forward pass of the rasterizer over the resident synthetic scene for
 the next pose of the 24-pose inference orbit (reference scripts/inference.py:655-667 renders
@@ -11,7 +11,11 @@ with N GPUs rank r renders poses r, r+N, ... (no collective on the data path; we
 every rank renders K frames).  Scene tensors and camera matrices are resident in HBM before
 the timed region starts.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
+The timed region is exactly K steps; `value` and `ms_per_step` are that block's.  --dump-outputs DIR writes what the
+timed path returned in its last step as DIR/<name>.npy (inputs are seeded: the same arguments, the same inputs).
+
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the K steps and reports them.  With --full
+(repeated timed blocks and the other entry point beside `value`, then) the line also carries
   "roofline":     dominant kernel's ALGORITHMIC bytes (SURVEY.md 8d / DESIGN.md 6) / its mean
                   duration, measured with HIP events on the launch stream inside the timed region;
   "cpu_baseline": the CPU oracle (oracle/, a restatement -- the reference has no CPU path)
@@ -59,6 +63,30 @@ def algorithmic_bytes(P, P_v, R, R_p, W, H, M, sh):
         "blend_bwd": 112 * R_p + 20 * W * H + 8 * T,
         "preprocess_bwd": P_v * (96 + (15 + c3 if sh else 0)) + P_v * (64 + c3),
     }
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every named array (tensor or ndarray) as DIR/<name>.npy -- float32 when that holds the values
+    exactly, else float64; empty arrays are skipped.  The 64 MB budget is shared out smallest array first, each taking
+    at most an equal share of what is left; an array larger than its share is written as a sample of its flattened
+    elements drawn with a fixed seed, so every run with the same arguments writes the same elements."""
+    arrays = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v for k, v in arrays.items() if v.size}
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for n, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].size, k))):
+        a = arrays[name]
+        a32 = a.astype(np.float32)
+        a = a32 if a.dtype == np.float32 or np.array_equal(a32, a) else a.astype(np.float64)
+        share = left // (len(arrays) - n)
+        if a.nbytes > share:
+            rng = np.random.default_rng(0)
+            a = a.reshape(-1)[np.unique(rng.integers(0, a.size, size=share // a.itemsize))]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def main():
@@ -131,6 +159,13 @@ def main():
                     help="HIP streams the frame loop alternates over (frames are independent; 1 = serial); "
                          "default 3 (measured optimum for both paths: C3 forward 4 520 / 4 700 / 4 690 frames/s "
                          "with 2 / 3 / 4 streams on one box)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-stage times and frame latency, roofline, repeated timed "
+                         "blocks, the other entry point, CPU baselines and the secondary C2 line (default: set up, warm "
+                         "up, time exactly --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; larger outputs as a fixed, seeded sample)")
     args = ap.parse_args()
     if args.streams is None:
         args.streams = 3
@@ -397,17 +432,19 @@ def main():
     default_stream = torch.cuda.current_stream(dev)
 
     def run_frames(lo, hi, step_fn=None):
+        """Frames lo .. hi-1; returns what the last one returned (frame hi-1's outputs, for --dump-outputs)."""
         step_fn = step_fn or step_main
+        last = [None]
         if args.host_threads <= 1:
             # torch.cuda.set_stream, not the `with torch.cuda.stream(...)` context: the context manager costs the calling
             # thread 6 us per frame (tools/host_profile_api.py), a tenth of what it needs to enqueue a frame
             try:
                 for i in range(lo, hi):
                     torch.cuda.set_stream(streams[i % len(streams)])
-                    step_fn(poses[i])
+                    last[0] = step_fn(poses[i])
             finally:
                 torch.cuda.set_stream(default_stream)
-            return
+            return last[0]
         # One host thread per stream.  The reference API returns num_rendered as a Python int, so every
         # call blocks its caller until the frame's scan has run; with a single host thread that wait
         # (plus the enqueue) is the frame period.  The library is re-entrant (per-thread read-back
@@ -419,86 +456,140 @@ def main():
             torch.cuda.set_device(dev)
             with torch.cuda.stream(streams[t % len(streams)]):
                 for i in range(lo + t, hi, args.host_threads):
-                    step_fn(poses[i])
+                    r = step_fn(poses[i])
+                    if i == hi - 1:
+                        last[0] = r
 
         th = [threading.Thread(target=worker, args=(t,)) for t in range(args.host_threads)]
         for x in th:
             x.start()
         for x in th:
             x.join()
+        return last[0]
 
-    # ---- per-stage pass FIRST: the same frame loop with HIP events on the launch streams (the event pairs are
-    # barrier packets and cost a few us per frame, so they stay out of `value`).  (1) exactly as the timed region
-    # -- frames alternating over the streams, kernels of neighbouring frames overlapping -- which is what a
-    # rocprofv3 --kernel-trace of this command averages over; (2) one stream, every kernel alone on the GPU.
-    # Running it before the timed region also means the clocks are up and the capacity hints are learnt whatever
-    # W the caller chose (measured: with W = 5 and K = 20 straight after start-up a frame costs 0.29 ms, not 0.255).
-    # These untimed frames are reported as `pre_frames` next to `warmup`.
+    # ---- burn-in: learn the capacity hints (first frames take the staged path) and bring the clocks up whatever W the
+    # caller chose (measured: with W = 5 and K = 20 straight after start-up a frame costs 0.29 ms, not 0.255).  These
+    # untimed frames are reported as `pre_frames` next to `warmup`.
     n_burn, n_inst, n_alone = 240, 96, 48
     poses_pre = [rank + i * world for i in range(4 + n_inst)]
-    for i in range(n_burn):  # learn the capacity hints (first frames take the staged path) and bring the clocks up
+    for i in range(n_burn):
         with torch.cuda.stream(streams[i % len(streams)]):
             step_fn(poses_pre[i % 24])
-    N.set_option("timing", 1)
-    N.stage_ms()  # reset accumulators
-    barrier()
-    t1 = time.perf_counter()
-    for i in range(4, 4 + n_inst):
-        with torch.cuda.stream(streams[i % len(streams)]):
+    pre_frames = n_burn
+    if args.full:
+        # ---- per-stage pass (--full): the same frame loop with HIP events on the launch streams (the event pairs are
+        # barrier packets and cost a few us per frame, so they stay out of `value`).  (1) exactly as the timed region
+        # -- frames alternating over the streams, kernels of neighbouring frames overlapping -- which is what a
+        # rocprofv3 --kernel-trace of this command averages over; (2) one stream, every kernel alone on the GPU.
+        N.set_option("timing", 1)
+        N.stage_ms()  # reset accumulators
+        barrier()
+        t1 = time.perf_counter()
+        for i in range(4, 4 + n_inst):
+            with torch.cuda.stream(streams[i % len(streams)]):
+                step_fn(poses_pre[i])
+        barrier()
+        elapsed_instrumented = (time.perf_counter() - t1) * args.steps / n_inst
+        stage = N.stage_ms()
+        for i in range(4, 4 + n_alone):
             step_fn(poses_pre[i])
-    barrier()
-    elapsed_instrumented = (time.perf_counter() - t1) * args.steps / n_inst
-    stage = N.stage_ms()
-    for i in range(4, 4 + n_alone):
-        step_fn(poses_pre[i])
-    barrier()
-    stage_alone = N.stage_ms()
-    N.set_option("timing", 0)
-    # one frame alone on the GPU, enqueue -> finished (what a caller that needs THIS frame waits for); the
-    # headline `value` is a throughput with len(streams) frames in flight
-    barrier()
-    t1 = time.perf_counter()
-    for i in range(4, 4 + 24):
-        step_fn(poses_pre[i])
-        torch.cuda.synchronize()
-    frame_latency_ms = 1e3 * (time.perf_counter() - t1) / 24
-    pre_frames = n_burn + n_inst + n_alone + 24
+        barrier()
+        stage_alone = N.stage_ms()
+        N.set_option("timing", 0)
+        # one frame alone on the GPU, enqueue -> finished (what a caller that needs THIS frame waits for); the
+        # headline `value` is a throughput with len(streams) frames in flight
+        barrier()
+        t1 = time.perf_counter()
+        for i in range(4, 4 + 24):
+            step_fn(poses_pre[i])
+            torch.cuda.synchronize()
+        frame_latency_ms = 1e3 * (time.perf_counter() - t1) / 24
+        pre_frames += n_inst + n_alone + 24
 
-    # ---- W untimed warm-up frames, then the timed region: EXACTLY K frames, barrier + synchronize on both sides
-    # A block of K frames can be a few milliseconds (K = 20 at C3: 4.5 ms), which a single clock reading does not
-    # resolve reliably (round 2: the driver's K = 20 line read 12 % below the K = 1000 one).  So the timed block of
-    # EXACTLY K frames is repeated, each repetition bracketed the same way, until the blocks add up to >= 0.25 s
-    # (at most 64 of them); `value` is K frames over the MEDIAN block, min / max are reported beside it.
+    # ---- W untimed warm-up frames, then the timed region: EXACTLY K frames, barrier + synchronize on both sides;
+    # `value` and `ms_per_step` are that block's.  A block of K frames can be a few milliseconds (K = 20 at C3: 4.5 ms),
+    # which a single clock reading does not resolve reliably (round 2: the driver's K = 20 line read 12 % below the
+    # K = 1000 one), so --full repeats the block, each repetition bracketed the same way, until the blocks add up to
+    # >= 0.25 s (at most 64 of them), and reports their median, min and max beside `value`.
+    def timed_block(lo, step):
+        barrier()
+        t0 = time.perf_counter()
+        last = run_frames(lo, lo + args.steps, step)
+        barrier()
+        el = time.perf_counter() - t0
+        if world > 1:
+            tt = torch.tensor([el], dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            el = float(tt.item())
+        return el, last
+
     def timed_blocks(step, budget_s=0.25):
         run_frames(0, args.warmup, step)
         blocks, nxt = [], args.warmup
         while True:
-            barrier()
-            t0 = time.perf_counter()
-            run_frames(nxt, nxt + args.steps, step)
-            barrier()
-            el = time.perf_counter() - t0
-            if world > 1:
-                tt = torch.tensor([el], dtype=torch.float64, device=dev)
-                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-                el = float(tt.item())
+            el, _ = timed_block(nxt, step)
             blocks.append(el)
             nxt += args.steps
             if sum(blocks) >= budget_s or len(blocks) >= 64:  # (the same decision on every rank: `el` is the max over ranks)
                 return blocks
 
-    block_s = timed_blocks(step_main)
-    elapsed = float(np.median(block_s))
+    run_frames(0, args.warmup, step_main)
+    elapsed, last_out = timed_block(args.warmup, step_main)
     total_frames = args.steps * world
     fps = total_frames / elapsed
-    # the same K-frame blocks through the other entry point (see step_main above), reported beside `value`
-    other_blocks = None
-    if not args.backward:
-        other_blocks = timed_blocks(fwd.api if args.native_int_api else fwd, 0.15)
+    if args.dump_outputs and rank == 0:
+        if args.backward:  # (forward args, forward outputs, gradients)
+            _, o, g = last_out
+            named = dict(zip(("num_rendered", "image", "radii"), ([o[0]],) + tuple(o[1:3])))
+            named.update(zip(("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale",
+                              "dL_drot"), g))
+        elif args.native_int_api:  # (forward args, (num_rendered, image, radii, state buffers))
+            o = last_out[1]
+            named = dict(zip(("num_rendered", "image", "radii"), ([o[0]],) + tuple(o[1:3])))
+        else:  # GaussianRasterizer.forward: (image, radii)
+            named = dict(zip(("image", "radii"), last_out))
+        dump_outputs(args.dump_outputs, named)
+    del last_out
+    block_s = other_blocks = None
+    if args.full:
+        block_s = [elapsed] + timed_blocks(step_main)
+        # the same K-frame blocks through the other entry point (see step_main above), reported beside `value`
+        if not args.backward:
+            other_blocks = timed_blocks(fwd.api if args.native_int_api else fwd, 0.15)
 
     out = None
     ranks_info = args.collect_ranks()  # (a collective for N > 1: every rank calls it)
+    mode = "forward+backward" if args.backward else "forward"
     if rank == 0:
+        out = {
+            "metric": ("rendered frames/sec (fwd+bwd) @ %d Gaussians, %dx%d" if args.backward else
+                       "rendered frames/sec (fwd) @ %d Gaussians, %dx%d") % (P, W, H),
+            "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "pre_frames": pre_frames,
+            "value_is": "K frames / the time of one timed block of exactly K frames",
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "entry_point": ("native module, positional rasterize_gaussians() -> (num_rendered:int, ...): one host wait "
+                            "per frame" if (args.native_int_api or args.backward) else
+                            "Python API GaussianRasterizer.forward -> (image, radii), dgr/__init__.py:223-273: num_rendered "
+                            "is not part of it and is not waited for"),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic (gcity-synth-v1 %s, seed %d)" % (cfg["scene"], cfg["seed"])
+                    + ("; A/B: Gaussians RENUMBERED along a Morton curve -- not the workload" if args.scene_order != "seeded" else ""),
+            "config": {"workload": "%s: %s %d Gaussians, %dx%d, SH degree %d, %s, 24-pose orbit"
+                                   % (args.config, cfg["scene"], P, W, H, cfg["sh_degree"], mode),
+                       "parallelism": "frames sharded round-robin, one frame per GPU, no data-path collective; "
+                                      "%d HIP streams per GPU alternate over consecutive frames (`value` is a throughput "
+                                      "with that many frames in flight; --full's `frame_latency_ms` is one frame alone)" % len(streams),
+                       "exp": "%s (bit-exact vs oracle)" % NUMERICS,
+                       "tile_sort": "every list sorted whole (--sort-whole)" if args.sort_whole else
+                                    "lists beyond 1024 entries sorted lazily, as far as the blend walks (default)",
+                       "cull": ("STATIC SCENE (--static-scene): a second line, not the headline -- the cull streams a cached "
+                                "16-byte (mean, bound) record per Gaussian built once for the scene; same frames bit for bit")
+                               if args.static_scene else "stateless: every frame reads means, scales, rotations (default)",
+                       "options_set_on_the_command_line": list(args.opt)},
+            "ranks": ranks_info,
+        }
+    if rank == 0 and args.full:
         # ---- per-frame workload statistics over the same poses (untimed) --------------------
         R_mean, Rp_mean, Pv_mean = frame_statistics(
             fwd, [poses[i] for i in range(args.warmup, args.warmup + min(args.steps, len(cams)))], P, W, H)
@@ -606,44 +697,19 @@ def main():
                                 "percent of peak by construction; the HBM-bound kernel of the frame is the streaming cull "
                                 "inside `preprocess` (DESIGN.md section 5)")
 
-        mode = "forward+backward" if args.backward else "forward"
-        out = {
-            "metric": ("rendered frames/sec (fwd+bwd) @ %d Gaussians, %dx%d" if args.backward else
-                       "rendered frames/sec (fwd) @ %d Gaussians, %dx%d") % (P, W, H),
-            "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "pre_frames": pre_frames,
+        out.update({
             "repeats": len(block_s), "value_min": round(total_frames / max(block_s), 3),
             "value_max": round(total_frames / min(block_s), 3),
-            "value_is": "K frames / the median of `repeats` timed blocks of exactly K frames each",
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "value_median_of_repeats": round(total_frames / float(np.median(block_s)), 3),
+            "repeats_are": "`repeats` timed blocks of exactly K frames each, the first of them the block of `value`",
             "ms_per_step_with_stage_events": round(1e3 * elapsed_instrumented / args.steps, 4),
             "frame_latency_ms": round(frame_latency_ms, 4),
-            "entry_point": ("native module, positional rasterize_gaussians() -> (num_rendered:int, ...): one host wait "
-                            "per frame" if (args.native_int_api or args.backward) else
-                            "Python API GaussianRasterizer.forward -> (image, radii), dgr/__init__.py:223-273: num_rendered "
-                            "is not part of it and is not waited for"),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (gcity-synth-v1 %s, seed %d)" % (cfg["scene"], cfg["seed"])
-                    + ("; A/B: Gaussians RENUMBERED along a Morton curve -- not the workload" if args.scene_order != "seeded" else ""),
-            "config": {"workload": "%s: %s %d Gaussians, %dx%d, SH degree %d, %s, 24-pose orbit"
-                                   % (args.config, cfg["scene"], P, W, H, cfg["sh_degree"], mode),
-                       "parallelism": "frames sharded round-robin, one frame per GPU, no data-path collective; "
-                                      "%d HIP streams per GPU alternate over consecutive frames (`value` is a throughput "
-                                      "with that many frames in flight; `frame_latency_ms` is one frame alone)" % len(streams),
-                       "exp": "%s (bit-exact vs oracle)" % NUMERICS,
-                       "tile_sort": "every list sorted whole (--sort-whole)" if args.sort_whole else
-                                    "lists beyond 1024 entries sorted lazily, as far as the blend walks (default)",
-                       "cull": ("STATIC SCENE (--static-scene): a second line, not the headline -- the cull streams a cached "
-                                "16-byte (mean, bound) record per Gaussian built once for the scene; same frames bit for bit")
-                               if args.static_scene else "stateless: every frame reads means, scales, rotations (default)",
-                       "options_set_on_the_command_line": list(args.opt)},
             "frame_stats": {"num_rendered": R_mean, "consumed_entries_Rp": Rp_mean, "visible": Pv_mean,
                             "tiles": T_tiles, "entries_per_tile": round(R_mean / T_tiles, 1),
                             "ns_per_instance": round(1e9 * elapsed / args.steps / max(R_mean, 1.0), 4)},
             "stages_ms": stages,
             "roofline": roofline,
-            "ranks": ranks_info,
-        }
+        })
         if other_blocks:
             oel = float(np.median(other_blocks))
             out["other_entry_point"] = {
@@ -801,6 +867,7 @@ def main():
                 fb3(3 + i)
             torch.cuda.synchronize()
             out["secondary"]["render_960x540_then_crop_ms"] = round(1e3 * (time.perf_counter() - t1) / n2, 4)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -863,9 +930,11 @@ def grid_encoder_bench(args, torch, dist, dev, world, rank, barrier, copy_ceilin
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"encoding": y, "dL_dx": x.grad, "dL_dembeddings": enc.embeddings.grad})
     E.set_option("timing", 1)
     E.stage_ms()
     for _ in range(min(args.steps, 20)):
@@ -963,17 +1032,22 @@ def visibility_bench(args, torch, dist, synth, dev, world, rank, barrier, copy_c
     vstreams = [torch.cuda.Stream(device=dev) for _ in range(max(1, args.streams))]
 
     def run(lo, hi):
+        last = None
         for i in range(lo, hi):
             with torch.cuda.stream(vstreams[i % len(vstreams)]):
-                frame(rank + i * world)
+                last = frame(rank + i * world)
+        return last
 
     run(0, 36)  # stream queues, allocator pools and clocks up before the contract's W warm-up frames
     run(0, args.warmup)
     barrier()
     t0 = time.perf_counter()
-    run(args.warmup, args.warmup + args.steps)
+    last = run(args.warmup, args.warmup + args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("points", "visible_point_map", "instance_map"), last)))
+    del last
     V.set_option("timing", 1)
     V.stage_ms()
     run(0, min(args.steps, 36))          # as the timed region: frames alternating over the streams
@@ -1100,9 +1174,12 @@ def inference_loop_bench(args, torch, dist, synth, Wrapper, dev, world, rank, ba
     loop = InferenceLoop(lambda p, cp, cq: wr(p, cp, cq), device=dev, n_streams=args.streams,
                          render_uint8_fn=None if args.float_frames else (lambda p, cp, cq: wr(p, cp, cq, as_uint8=True)))
     sink = [0]
+    last_frame = {}
 
     def consume(i, frame):  # what a video writer would do with the frame: touch it
         sink[0] += int(frame[0, 0, 0])
+        if args.dump_outputs and i == args.steps - 1:  # (the buffer is reused: copy the last frame of a block)
+            last_frame["frame"] = frame.copy()
 
     def run(n):
         poses = [orbit[(rank + i * world) % len(orbit)] for i in range(n)]
@@ -1111,6 +1188,8 @@ def inference_loop_bench(args, torch, dist, synth, Wrapper, dev, world, rank, ba
 
     run(max(args.warmup, 24))
     block_s = []
+    # the timed block of exactly K frames gives `value`; --full repeats it (until 0.5 s, at most 16 blocks) for the
+    # min / max beside it
     while True:
         barrier()
         t0 = time.perf_counter()
@@ -1122,9 +1201,11 @@ def inference_loop_bench(args, torch, dist, synth, Wrapper, dev, world, rank, ba
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
         block_s.append(el)
-        if sum(block_s) >= 0.5 or len(block_s) >= 16:
+        if len(block_s) == 1 and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_frame)
+        if not args.full or sum(block_s) >= 0.5 or len(block_s) >= 16:
             break
-    elapsed = float(np.median(block_s))
+    elapsed = block_s[0]
     if rank == 0:
         print(json.dumps({
             "metric": "inference-loop frames/sec (points [N,14] -> wrapper -> uint8 frame on the host)",
@@ -1180,10 +1261,13 @@ def train_step_bench(args, torch, dist, N, synth, Wrapper, dev, world, rank, bar
     barrier()
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
-        step(i)
+        last = step(i)
     host_s = time.perf_counter() - t0  # the host has enqueued every step; the GPU may still be working
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # DDPTrainStep.step: (loss, image[, buckets])
+        dump_outputs(args.dump_outputs, {"loss": last[0].reshape(1), "image": last[1]})
+    del last
 
     # ---- the rasterizer leg alone (what the product calls per frame): helpers -> wrapper -> autograd, loss, backward
     leaf = base_points.clone().requires_grad_(True)

@@ -51,8 +51,29 @@ def test_committed_bench_lines_follow_the_contract():
 
 def test_bench_cli_surface():
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--help"]).decode()
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--path", "--train-step"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--path", "--train-step", "--full", "--dump-outputs"):
         assert flag in out
+
+
+def test_dump_outputs_budget_and_sample(tmp_path):
+    """--dump-outputs: float32 where exact (else float64), small arrays whole, 64 MB in all, the same sample every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"image": rng.random((3, 1080, 1920), dtype=np.float32), "radii": rng.integers(0, 99, 5_000_000, dtype=np.int32),
+              "num_rendered": [123456789012], "big": rng.random(30_000_000, dtype=np.float32), "empty": np.zeros(0)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(got) == ["big", "image", "num_rendered", "radii"]
+    assert got["num_rendered"].dtype == np.float64 and got["num_rendered"][0] == 123456789012
+    assert got["radii"].dtype == np.float32 and np.array_equal(got["radii"], arrays["radii"])
+    assert got["image"].dtype == np.float32 and got["image"].size < arrays["image"].size
+    assert np.isin(got["big"], arrays["big"]).all()
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / (k + ".npy"))))
 
 
 def test_round5_lines_and_the_static_scene_second_line():

@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O
 cd $R
 TAG=${2:-r06_ab}
-B="python bench.py --no-cpu-baseline --no-secondary"
+B="python bench.py --full --no-cpu-baseline --no-secondary"
 while IFS= read -r o; do
   [ -z "$o" ] && continue
   $B $o 2>$O/${TAG}_err.txt | tail -1 | python -c "

@@ -7,6 +7,6 @@ for rep in 1 2; do
   for kv in "$@"; do
     name=${kv%%=*}; path=${kv#*=}
     tag=$(echo "$bargs" | tr -c 'A-Za-z0-9\n' '_')
-    GCR_LIB_PATH=$path python bench.py $bargs --no-cpu-baseline --no-secondary >> "$out/${name}${tag}.jsonl" 2>> "$out/${name}${tag}.err"
+    GCR_LIB_PATH=$path python bench.py --full $bargs --no-cpu-baseline --no-secondary >> "$out/${name}${tag}.jsonl" 2>> "$out/${name}${tag}.err"
   done
 done

@@ -5,7 +5,7 @@ TAG=${1:-k6}; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out; mkdir -p $O
-B="python $R/bench.py --steps 8 --warmup 2"
+B="python $R/bench.py --full --steps 8 --warmup 2"
 : > $O/${TAG}_k6_pmc.txt
 for v in ship "$@"; do
   echo "== $v" >> $O/${TAG}_k6_pmc.txt

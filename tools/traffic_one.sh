@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 out=$1; shift; what=$1; shift
 cd /tmp && export TMPDIR=/tmp
 d=/tmp/traffic_$$
-B="python $R/bench.py --no-cpu-baseline --no-secondary --steps 8 --warmup 2 $*"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary --steps 8 --warmup 2 $*"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d ${d}_f -o p -- $B > /dev/null 2>&1 < /dev/null
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d ${d}_w -o p -- $B > /dev/null 2>&1 < /dev/null
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY \
