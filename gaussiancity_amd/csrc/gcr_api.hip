@@ -61,28 +61,53 @@ struct Opts {
   int band_sort_min;  // process-wide only (no field in gcr_options: the record keeps its size)
   int stream_policy;  // process-wide only
 };
+
+// One row per option of gcr_set_option / gcr_get_option: its process-wide value, how gcr_set_option normalises what it
+// is given, and where a call finds it (the gcr_options field that overrides it, the Opts field it resolves to; null =
+// neither).  A per-call field >= 0 is read as != 0, bwd_piece clamped like the process-wide value.
+int opt_raw(int v) { return v; }
+int opt_bool(int v) { return v != 0; }
+int opt_piece(int v) { return v < GCR_PIECE_MIN ? GCR_PIECE_MIN : (v > GCR_PIECE_MAX ? GCR_PIECE_MAX : v); }
+struct OptionRow {
+  const char* name;
+  std::atomic<int>* global;
+  int (*normalize)(int);
+  int Opts::*resolved;
+  int32_t gcr_options::*per_call;
+};
+const OptionRow g_options[] = {
+    {"timing", &g_timing, opt_raw, nullptr, nullptr},
+    {"force_radix", &g_force_radix, opt_raw, &Opts::force_radix, &gcr_options::force_radix},
+    {"force_global_cursor", &g_force_global_cursor, opt_raw, &Opts::force_global_cursor, &gcr_options::force_global_cursor},
+    {"split_preprocess", &g_split_preprocess, opt_raw, &Opts::split_preprocess, &gcr_options::split_preprocess},
+    {"sort_in_blend", &g_sort_in_blend, opt_raw, &Opts::sort_in_blend, &gcr_options::sort_in_blend},
+    {"lazy_sort", &g_lazy_sort, opt_bool, &Opts::lazy_sort, &gcr_options::lazy_sort},
+    {"deterministic_backward", &g_deterministic, opt_bool, &Opts::deterministic, &gcr_options::deterministic_backward},
+    {"bwd_wave_units", &g_bwd_wave_units, opt_bool, &Opts::bwd_wave_units, &gcr_options::bwd_wave_units},
+    {"bwd_piece", &g_bwd_piece, opt_piece, &Opts::bwd_piece, &gcr_options::bwd_piece},
+    {"band_sort_min", &g_band_sort_min, [](int v) { return v < 0 ? -1 : v; }, &Opts::band_sort_min, nullptr},
+    {"stream_policy", &g_stream_policy, [](int v) { return v < 0 ? -1 : (v != 0); }, &Opts::stream_policy, nullptr},
+    {"rescue_hold", &g_rescue_hold, opt_bool, nullptr, nullptr},
+    {"gate_polls", &g_gate_polls, [](int v) { return v < 1 ? 1 : v; }, nullptr, nullptr},
+#ifdef GCR_EXPERIMENTS
+    {"k7_skip_flush", &g_k7_skip_flush, opt_raw, nullptr, nullptr},
+    {"k6_debug", &g_k6_debug, opt_raw, nullptr, nullptr},
+#endif
+};
+const OptionRow* find_option(const char* name) {
+  if (name)
+    for (const OptionRow& o : g_options)
+      if (!strcmp(name, o.name)) return &o;
+  return nullptr;
+}
 Opts resolve_options(const gcr_options* o) {
-  Opts r;
-  r.lazy_sort = g_lazy_sort.load();
-  r.sort_in_blend = g_sort_in_blend.load();
-  r.bwd_piece = g_bwd_piece.load();
-  r.deterministic = g_deterministic.load();
-  r.split_preprocess = g_split_preprocess.load();
-  r.force_radix = g_force_radix.load();
-  r.force_global_cursor = g_force_global_cursor.load();
-  r.bwd_wave_units = g_bwd_wave_units.load();
-  r.band_sort_min = g_band_sort_min.load();
-  r.stream_policy = g_stream_policy.load();
-  if (o != nullptr) {
-    if (o->bwd_wave_units >= 0) r.bwd_wave_units = o->bwd_wave_units != 0;
-    if (o->lazy_sort >= 0) r.lazy_sort = o->lazy_sort != 0;
-    if (o->sort_in_blend >= 0) r.sort_in_blend = o->sort_in_blend != 0;
-    if (o->bwd_piece >= 0)
-      r.bwd_piece = o->bwd_piece < GCR_PIECE_MIN ? GCR_PIECE_MIN : (o->bwd_piece > GCR_PIECE_MAX ? GCR_PIECE_MAX : o->bwd_piece);
-    if (o->deterministic_backward >= 0) r.deterministic = o->deterministic_backward != 0;
-    if (o->split_preprocess >= 0) r.split_preprocess = o->split_preprocess != 0;
-    if (o->force_radix >= 0) r.force_radix = o->force_radix != 0;
-    if (o->force_global_cursor >= 0) r.force_global_cursor = o->force_global_cursor != 0;
+  Opts r{};
+  for (const OptionRow& row : g_options) {
+    if (!row.resolved) continue;
+    int v = row.global->load();
+    if (o != nullptr && row.per_call != nullptr && o->*row.per_call >= 0)
+      v = row.normalize == opt_piece ? opt_piece(o->*row.per_call) : opt_bool(o->*row.per_call);
+    r.*row.resolved = v;
   }
   return r;
 }
@@ -93,9 +118,15 @@ int fail(gcr_status code, const std::string& msg) {
   g_err = msg;
   return (int)code;
 }
-// gcr_camera.prefiltered and a Gaussian behind the near plane (gcr_internal.h GCR_PREFILTER_MARK): the reference's words
-int fail_prefiltered() {
-  return fail(GCR_ERR_INVALID_ARGUMENT, "Point is filtered although prefiltered is set. This shouldn't happen!");
+// num_rendered as a frame word reports it (the device word, or the low half of a host word seq << 32 | R): the mark of
+// gcr_camera.prefiltered and a Gaussian behind the near plane (gcr_internal.h GCR_PREFILTER_MARK, the reference's words),
+// or a count beyond the 32-bit instance index, is an error
+int check_num_rendered(unsigned long long R) {
+  if (R == GCR_PREFILTER_MARK)
+    return fail(GCR_ERR_INVALID_ARGUMENT, "Point is filtered although prefiltered is set. This shouldn't happen!");
+  if (R > 0x7fffffffull)
+    return fail(GCR_ERR_OVERFLOW, "num_rendered exceeds 2^31-1 (32-bit instance index, as in the reference)");
+  return 0;
 }
 int fail_hip(hipError_t e, const char* where) {
   g_err = std::string(where) + ": " + hipGetErrorString(e);
@@ -181,57 +212,59 @@ int debug_sync(const gcr_camera* cam, hipStream_t s, const char* where) {
   return 0;
 }
 
-void compute_layout(int32_t P, int32_t W, int32_t H, int64_t R, gcr_layout* L) {
+gcr_layout compute_layout(int32_t P, int32_t W, int32_t H, int64_t R) {
+  gcr_layout L;
   const size_t p = (size_t)(P > 0 ? P : 0);
   const size_t nblk = (p + 255) / 256;
   size_t o = 0;
-  L->geom_rec = o;            o = align_up(o + p * sizeof(float4) * GCR_REC_QUADS);
-  L->geom_cov3D = o;          o = align_up(o + p * GCR_COV3D_FLOATS * sizeof(float));
-  L->geom_clamped = o;        o = align_up(o + p);
-  L->geom_tiles_touched = o;  o = align_up(o + p * sizeof(uint32_t));
-  L->geom_block_sums = o;     o = align_up(o + (nblk + 1) * sizeof(uint32_t));
-  L->geom_vis_list = o;       o = align_up(o + p * sizeof(uint32_t));
-  L->geom_vis_count = o;      o = align_up(o + (nblk + 1) * sizeof(uint32_t));
-  L->geom_num_rendered = o;   o = align_up(o + 16 * sizeof(uint64_t));  // frame words (gcr_internal.h: GCR_FRAME_*, nine in use)
-  L->geom_block_tiles = o;    o = align_up(o + GCR_K1_MAX_BLOCKS * sizeof(uint64_t));  // K1 blocks' shares of R
-  L->geom_vis_rec = o;        o = align_up(o + p * sizeof(uint4));  // the survivors' binning records (ABI v9)
-  L->geom_total = o;
+  L.geom_rec = o;            o = align_up(o + p * sizeof(float4) * GCR_REC_QUADS);
+  L.geom_cov3D = o;          o = align_up(o + p * GCR_COV3D_FLOATS * sizeof(float));
+  L.geom_clamped = o;        o = align_up(o + p);
+  L.geom_tiles_touched = o;  o = align_up(o + p * sizeof(uint32_t));
+  L.geom_block_sums = o;     o = align_up(o + (nblk + 1) * sizeof(uint32_t));
+  L.geom_vis_list = o;       o = align_up(o + p * sizeof(uint32_t));
+  L.geom_vis_count = o;      o = align_up(o + (nblk + 1) * sizeof(uint32_t));
+  L.geom_num_rendered = o;   o = align_up(o + 16 * sizeof(uint64_t));  // frame words (gcr_internal.h: GCR_FRAME_*, nine in use)
+  L.geom_block_tiles = o;    o = align_up(o + GCR_K1_MAX_BLOCKS * sizeof(uint64_t));  // K1 blocks' shares of R
+  L.geom_vis_rec = o;        o = align_up(o + p * sizeof(uint4));  // the survivors' binning records (ABI v9)
+  L.geom_total = o;
 
   const size_t npix = (size_t)(W > 0 ? W : 0) * (size_t)(H > 0 ? H : 0);
   const size_t gx = (size_t)(W + GCR_BLOCK_X - 1) / GCR_BLOCK_X, gy = (size_t)(H + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
   const size_t T = gx * gy;
   o = 0;
-  L->img_final_T = o;    o = align_up(o + npix * sizeof(float));
-  L->img_n_contrib = o;  o = align_up(o + npix * sizeof(uint32_t));
-  L->img_ranges = o;       o = align_up(o + T * 2 * sizeof(uint32_t));
-  L->img_tile_cursor = o;  o = align_up(o + T * GCR_CURSOR_STRIDE * sizeof(uint32_t));
+  L.img_final_T = o;    o = align_up(o + npix * sizeof(float));
+  L.img_n_contrib = o;  o = align_up(o + npix * sizeof(uint32_t));
+  L.img_ranges = o;       o = align_up(o + T * 2 * sizeof(uint32_t));
+  L.img_tile_cursor = o;  o = align_up(o + T * GCR_CURSOR_STRIDE * sizeof(uint32_t));
   {
     int G = 1;
     const int ng = gcr_tile_table_groups((int)T, GCR_K1_MAX_BLOCKS, &G);  // upper bound on groups
-    L->img_tile_table = o;   o = align_up(o + (size_t)ng * T * sizeof(uint32_t));
+    L.img_tile_table = o;   o = align_up(o + (size_t)ng * T * sizeof(uint32_t));
   }
-  L->img_tile_lazy = o;    o = align_up(o + T * 4 * sizeof(uint32_t));
-  L->img_total = o;
+  L.img_tile_lazy = o;    o = align_up(o + T * 4 * sizeof(uint32_t));
+  L.img_total = o;
 
   const size_t r = (size_t)(R > 0 ? R : 0);
   const int end_bit = 32 + (int)gcr_higher_msb((uint32_t)T);
   // The sorted instance list sits at offset 0 whatever R is, so a forward that carved the
   // buffer by *capacity* and a backward that carves it by the actual R find it in the same place.
-  L->bin_sorted = (size_t)(gcr_sort_passes(end_bit) & 1);
+  L.bin_sorted = (size_t)(gcr_sort_passes(end_bit) & 1);
   o = 0;
-  L->bin_vals[L->bin_sorted] = o;      o = align_up(o + r * sizeof(uint32_t));
-  L->bin_vals[1 - L->bin_sorted] = o;  o = align_up(o + r * sizeof(uint32_t));
-  L->bin_keys[0] = o;  o = align_up(o + r * sizeof(uint64_t));
-  L->bin_keys[1] = o;  o = align_up(o + r * sizeof(uint64_t));
-  L->bin_hist = o;     o = align_up(o + gcr_sort_hist_bytes((int64_t)r, end_bit));
+  L.bin_vals[L.bin_sorted] = o;      o = align_up(o + r * sizeof(uint32_t));
+  L.bin_vals[1 - L.bin_sorted] = o;  o = align_up(o + r * sizeof(uint32_t));
+  L.bin_keys[0] = o;  o = align_up(o + r * sizeof(uint64_t));
+  L.bin_keys[1] = o;  o = align_up(o + r * sizeof(uint64_t));
+  L.bin_hist = o;     o = align_up(o + gcr_sort_hist_bytes((int64_t)r, end_bit));
   // (tile, piece) slots of the backward blend, sized for the smallest piece the option "bwd_piece" admits
   const size_t slots = r ? (size_t)gcr_piece_slots(r, T, GCR_PIECE_MIN) : 0;
-  L->bin_lean_total = o;  // a frame that never sees gcr_backward needs nothing behind this point
-  L->bin_work = o;       o = align_up(o + slots * 16);
-  L->bin_mask = o;       o = align_up(o + r * sizeof(uint16_t));
-  L->bin_ckpt = o;       o = align_up(o + slots * (size_t)GCR_CKPT_BYTES);
-  L->bin_staged = o;     o = align_up(o + r * 48);
-  L->bin_total = o;
+  L.bin_lean_total = o;  // a frame that never sees gcr_backward needs nothing behind this point
+  L.bin_work = o;       o = align_up(o + slots * 16);
+  L.bin_mask = o;       o = align_up(o + r * sizeof(uint16_t));
+  L.bin_ckpt = o;       o = align_up(o + slots * (size_t)GCR_CKPT_BYTES);
+  L.bin_staged = o;     o = align_up(o + r * 48);
+  L.bin_total = o;
+  return L;
 }
 
 int check_inputs(const gcr_camera* cam, const gcr_gaussians* g, bool need_opacity = true) {
@@ -270,6 +303,137 @@ int check_inputs(const gcr_camera* cam, const gcr_gaussians* g, bool need_opacit
   return 0;
 }
 
+// gcr_camera.host_camera: the camera constants travel in the kernels' argument blocks
+void fill_cam(GcrCamVals& c, const gcr_camera* cam) {
+  memset(&c, 0, sizeof(c));
+  if (!cam->host_camera) return;
+  c.by_value = 1;
+  memcpy(c.view, cam->view_matrix, sizeof(c.view));
+  memcpy(c.proj, cam->proj_matrix, sizeof(c.proj));
+  memcpy(c.campos, cam->campos, sizeof(c.campos));
+  memcpy(c.bg, cam->bg, sizeof(c.bg));
+}
+inline int stride_or(int32_t s, int dense) { return s > 0 ? (int)s : dense; }
+
+// One frame's view of the caller's buffers, worked out once per entry point: the carve, the tile grid, K1's persistent
+// grid, the tile-table groups and the typed pointers the stages read.  Pointers into a null buffer are null (`binning`
+// is null while nothing can be rendered).
+struct FrameSetup {
+  gcr_layout L;
+  int64_t R_layout;  // instances the binning buffer is carved for
+  int gx, gy, T;
+  int nblocks, chunk;  // K1's persistent grid
+  int NG, G;           // LDS tile-table groups (NG == 0: global tile cursors)
+  // geometry buffer; `frame`: the frame words (gcr_internal.h GCR_FRAME_*); `banded`: the band-sorted survivors (in
+  // tiles_touched) where this T admits a band sort, else null
+  float4* rec;
+  float* cov3D;
+  uint32_t *tiles_touched, *block_sums, *vis_list, *vis_count;
+  uint4 *vis_rec, *banded;
+  unsigned long long *frame, *block_tiles;
+  // image buffer
+  float* final_T;
+  uint32_t *n_contrib, *ranges, *cursor, *table;
+  uint4* lazy;
+  // binning buffer; `list` = vals[L.bin_sorted]: the sorted instance list
+  char* bin;
+  uint64_t* keys[2];
+  uint32_t *vals[2], *list, *hist;
+};
+template <class T>
+T* at(const void* base, size_t off) {
+  return base ? (T*)((char*)base + off) : nullptr;
+}
+FrameSetup frame_setup(const Opts& op, int32_t P, const gcr_camera* cam, int64_t R_layout, const void* geom,
+                       const void* img, const void* binning) {
+  FrameSetup f;
+  f.L = compute_layout(P, cam->img_w, cam->img_h, R_layout);
+  const gcr_layout& L = f.L;
+  f.R_layout = R_layout;
+  f.gx = (cam->img_w + GCR_BLOCK_X - 1) / GCR_BLOCK_X;
+  f.gy = (cam->img_h + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
+  f.T = f.gx * f.gy;
+  gcr_preprocess_grid(P, gcr_preprocess_resident_blocks(false), &f.nblocks, &f.chunk);
+  f.G = 1;
+  f.NG = op.force_global_cursor ? 0 : gcr_tile_table_groups(f.T, f.nblocks, &f.G);
+  f.rec = at<float4>(geom, L.geom_rec);
+  f.cov3D = at<float>(geom, L.geom_cov3D);
+  f.tiles_touched = at<uint32_t>(geom, L.geom_tiles_touched);
+  f.block_sums = at<uint32_t>(geom, L.geom_block_sums);
+  f.vis_list = at<uint32_t>(geom, L.geom_vis_list);
+  f.vis_count = at<uint32_t>(geom, L.geom_vis_count);
+  f.vis_rec = at<uint4>(geom, L.geom_vis_rec);
+  f.frame = at<unsigned long long>(geom, L.geom_num_rendered);
+  f.block_tiles = at<unsigned long long>(geom, L.geom_block_tiles);
+  f.banded = gcr_band_sort_possible(f.T) ? at<uint4>(geom, L.geom_tiles_touched) : nullptr;
+  f.final_T = at<float>(img, L.img_final_T);
+  f.n_contrib = at<uint32_t>(img, L.img_n_contrib);
+  f.ranges = at<uint32_t>(img, L.img_ranges);
+  f.cursor = at<uint32_t>(img, L.img_tile_cursor);
+  f.table = at<uint32_t>(img, L.img_tile_table);
+  f.lazy = at<uint4>(img, L.img_tile_lazy);
+  f.bin = at<char>(binning, 0);
+  for (int k = 0; k < 2; k++) {
+    f.keys[k] = at<uint64_t>(binning, L.bin_keys[k]);
+    f.vals[k] = at<uint32_t>(binning, L.bin_vals[k]);
+  }
+  f.list = f.vals[L.bin_sorted];
+  f.hist = at<uint32_t>(binning, L.bin_hist);
+  return f;
+}
+
+// The caller's buffer sizes against the frame's carve; the binning buffer only when instances are carved for, lean
+// unless a backward follows (gcr_binning_bytes_lean)
+int check_buffers(const FrameSetup& f, const gcr_camera* cam, size_t geom_bytes, size_t img_bytes, const void* binning,
+                  size_t binning_bytes, const char* binning_msg) {
+  if (geom_bytes < f.L.geom_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "geometry buffer too small");
+  if (img_bytes < f.L.img_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "image buffer too small");
+  if (f.R_layout > 0 && (!binning || binning_bytes < (cam->backward == 1 ? f.L.bin_total : f.L.bin_lean_total)))
+    return fail(GCR_ERR_BUFFER_TOO_SMALL, binning_msg);
+  return 0;
+}
+
+// The Gaussian inputs that K1, K8 and the cull-cache build read, with the dense row strides
+template <class A>
+void set_gaussian_args(A& a, const gcr_gaussians* g) {
+  a.P = g->P;
+  a.means3D = g->means3D; a.scales = g->scales; a.rotations = g->rotations;
+  a.s_mean = stride_or(g->stride_means3D, 3);
+  a.s_scale = stride_or(g->stride_scales, 3);
+  a.s_rot = stride_or(g->stride_rotations, 4);
+}
+// ... and the camera: the arguments K1 (GcrPreprocessArgs) and K8 (GcrPreprocessBwdArgs) share
+template <class A>
+void set_camera_args(A& a, const gcr_camera* cam, const gcr_gaussians* g) {
+  set_gaussian_args(a, g);
+  a.D = cam->sh_degree; a.M = g->M; a.W = cam->img_w; a.H = cam->img_h;
+  a.tanfovx = cam->tanfovx; a.tanfovy = cam->tanfovy;
+  a.focal_y = cam->img_h / (2.0f * cam->tanfovy);  // cr/rasterizer_impl.cu:189-190
+  a.focal_x = cam->img_w / (2.0f * cam->tanfovx);
+  a.scale_modifier = cam->scale_modifier;
+  a.shs = g->shs;
+  a.view = cam->view_matrix; a.proj = cam->proj_matrix; a.campos = cam->campos;
+  fill_cam(a.cam, cam);
+}
+
+// The GcrBlendArgs fields every blend of a frame shares (the forward's two binning paths and the backward)
+GcrBlendArgs blend_args(const FrameSetup& f, const gcr_camera* cam, const uint32_t* list) {
+  GcrBlendArgs b;
+  memset(&b, 0, sizeof(b));
+  b.ranges = f.ranges;
+  b.list = list;
+  b.rec = f.rec;
+  b.W = cam->img_w; b.H = cam->img_h; b.gx = f.gx; b.gy = f.gy;
+  b.bg = cam->bg;
+  b.flip_x = cam->flip_x != 0; b.flip_y = cam->flip_y != 0;
+  b.win_x = cam->win_x; b.win_y = cam->win_y; b.win_w = cam->win_w; b.win_h = cam->win_h;
+  b.out_u8 = cam->out_u8 != 0 && cam->backward != 1;
+  fill_cam(b.cam, cam);
+  b.final_T = f.final_T;
+  b.n_contrib = f.n_contrib;
+  return b;
+}
+
 }  // namespace
 
 extern "C" {
@@ -286,77 +450,24 @@ int gcr_grad_record_floats_opt(const gcr_options* options) {
 }
 const char* gcr_last_error(void) { return g_err.c_str(); }
 
-size_t gcr_geometry_bytes(int32_t P) {
-  gcr_layout L;
-  compute_layout(P, 16, 16, 0, &L);
-  return L.geom_total;
-}
-size_t gcr_image_bytes(int32_t W, int32_t H) {
-  gcr_layout L;
-  compute_layout(0, W, H, 0, &L);
-  return L.img_total;
-}
-size_t gcr_binning_bytes(int64_t R, int32_t W, int32_t H) {
-  gcr_layout L;
-  compute_layout(0, W, H, R, &L);
-  return L.bin_total;
-}
-size_t gcr_binning_bytes_lean(int64_t R, int32_t W, int32_t H) {
-  gcr_layout L;
-  compute_layout(0, W, H, R, &L);
-  return L.bin_lean_total;
-}
+size_t gcr_geometry_bytes(int32_t P) { return compute_layout(P, 16, 16, 0).geom_total; }
+size_t gcr_image_bytes(int32_t W, int32_t H) { return compute_layout(0, W, H, 0).img_total; }
+size_t gcr_binning_bytes(int64_t R, int32_t W, int32_t H) { return compute_layout(0, W, H, R).bin_total; }
+size_t gcr_binning_bytes_lean(int64_t R, int32_t W, int32_t H) { return compute_layout(0, W, H, R).bin_lean_total; }
 int gcr_get_layout(int32_t P, int32_t W, int32_t H, int64_t R, gcr_layout* out) {
   if (!out) return fail(GCR_ERR_INVALID_ARGUMENT, "null layout");
-  compute_layout(P, W, H, R, out);
+  *out = compute_layout(P, W, H, R);
   return 0;
 }
 
 int gcr_set_option(const char* name, int value) {
-  if (!name) return -1;
-  if (!strcmp(name, "bwd_wave_units")) return g_bwd_wave_units.exchange(value != 0);
-  if (!strcmp(name, "rescue_hold")) return g_rescue_hold.exchange(value != 0);
-  if (!strcmp(name, "gate_polls")) return g_gate_polls.exchange(value < 1 ? 1 : value);
-  if (!strcmp(name, "timing")) return g_timing.exchange(value);
-  if (!strcmp(name, "band_sort_min")) return g_band_sort_min.exchange(value < 0 ? -1 : value);
-  if (!strcmp(name, "stream_policy")) return g_stream_policy.exchange(value < 0 ? -1 : (value != 0));
-  if (!strcmp(name, "force_radix")) return g_force_radix.exchange(value);
-  if (!strcmp(name, "force_global_cursor")) return g_force_global_cursor.exchange(value);
-#ifdef GCR_EXPERIMENTS
-  if (!strcmp(name, "k7_skip_flush")) return g_k7_skip_flush.exchange(value);
-  if (!strcmp(name, "k6_debug")) return g_k6_debug.exchange(value);
-#endif
-  if (!strcmp(name, "split_preprocess")) return g_split_preprocess.exchange(value);
-  if (!strcmp(name, "sort_in_blend")) return g_sort_in_blend.exchange(value);
-  if (!strcmp(name, "lazy_sort")) return g_lazy_sort.exchange(value != 0);
-  if (!strcmp(name, "deterministic_backward")) return g_deterministic.exchange(value != 0);
-  if (!strcmp(name, "bwd_piece")) {
-    const int v = value < GCR_PIECE_MIN ? GCR_PIECE_MIN : (value > GCR_PIECE_MAX ? GCR_PIECE_MAX : value);
-    return g_bwd_piece.exchange(v);
-  }
-  return -1;
+  const OptionRow* o = find_option(name);
+  return o ? o->global->exchange(o->normalize(value)) : -1;
 }
 
 int gcr_get_option(const char* name) {
-  if (!name) return INT32_MIN;
-  if (!strcmp(name, "bwd_wave_units")) return g_bwd_wave_units.load();
-  if (!strcmp(name, "rescue_hold")) return g_rescue_hold.load();
-  if (!strcmp(name, "gate_polls")) return g_gate_polls.load();
-  if (!strcmp(name, "timing")) return g_timing.load();
-  if (!strcmp(name, "band_sort_min")) return g_band_sort_min.load();
-  if (!strcmp(name, "stream_policy")) return g_stream_policy.load();
-  if (!strcmp(name, "force_radix")) return g_force_radix.load();
-  if (!strcmp(name, "force_global_cursor")) return g_force_global_cursor.load();
-  if (!strcmp(name, "split_preprocess")) return g_split_preprocess.load();
-  if (!strcmp(name, "sort_in_blend")) return g_sort_in_blend.load();
-  if (!strcmp(name, "lazy_sort")) return g_lazy_sort.load();
-  if (!strcmp(name, "deterministic_backward")) return g_deterministic.load();
-  if (!strcmp(name, "bwd_piece")) return g_bwd_piece.load();
-#ifdef GCR_EXPERIMENTS
-  if (!strcmp(name, "k7_skip_flush")) return g_k7_skip_flush.load();
-  if (!strcmp(name, "k6_debug")) return g_k6_debug.load();
-#endif
-  return INT32_MIN;
+  const OptionRow* o = find_option(name);
+  return o ? o->global->load() : INT32_MIN;
 }
 
 int gcr_get_stage_ms(float* ms_out, int capacity) {
@@ -371,117 +482,73 @@ int gcr_get_stage_ms(float* ms_out, int capacity) {
   return n;
 }
 
-// gcr_camera.host_camera: the camera constants travel in the kernels' argument blocks
-static void fill_cam(GcrCamVals& c, const gcr_camera* cam) {
-  memset(&c, 0, sizeof(c));
-  if (!cam->host_camera) return;
-  c.by_value = 1;
-  memcpy(c.view, cam->view_matrix, sizeof(c.view));
-  memcpy(c.proj, cam->proj_matrix, sizeof(c.proj));
-  memcpy(c.campos, cam->campos, sizeof(c.campos));
-  memcpy(c.bg, cam->bg, sizeof(c.bg));
+// May the band-sorted survivor numbering use gcr_layout.geom_tiles_touched on this frame?  (Decided where the tiles are
+// counted; the count kernel records the answer in frame[GCR_FRAME_BANDED], and the scatter follows that word.)
+static inline bool band_sort_slot_free(const Opts& op) {
+  return !op.split_preprocess && !op.force_radix && !op.force_global_cursor;
 }
-static inline int stride_or(int32_t s, int dense) { return s > 0 ? (int)s : dense; }
 
-// Enqueues K1 + tile counting + tile scan; leaves {R, longest list, go flag} in the geometry
-// buffer (*frame_dev_out).  cap_* only influence the go flag used by speculative launches.
+// Enqueues K1 + tile counting + tile scan; leaves {R, longest list, go flag} in the frame words (f.frame).
+// cap_* only influence the go flag used by speculative launches.
 // `host_R` (optional): pinned word that receives (seq << 32 | num_rendered) as soon as K1 is done.
-// May the band-sorted survivor numbering use gcr_layout.geom_tiles_touched on this frame?
-static inline bool band_sort_slot_free(const Opts& op, int T) {
-  return !op.split_preprocess && !op.force_radix && !op.force_global_cursor && gcr_band_sort_possible(T);
-}
-
-static int enqueue_preprocess(const Opts& op, const gcr_camera* cam, const gcr_gaussians* g, void* geom, size_t geom_bytes,
-                              void* img, size_t img_bytes, int32_t* radii, unsigned long long cap_instances,
-                              unsigned long long cap_list, unsigned long long** frame_dev_out, hipStream_t s,
+static int enqueue_preprocess(const Opts& op, const gcr_camera* cam, const gcr_gaussians* g, const FrameSetup& f,
+                              int32_t* radii, unsigned long long cap_instances, unsigned long long cap_list, hipStream_t s,
                               unsigned long long* host_R = nullptr, unsigned int seq = 0, bool nt_stream = false) {
-  if (!geom || !radii || !img) return fail(GCR_ERR_INVALID_ARGUMENT, "geom/img/radii must be non-null");
-  gcr_layout L;
-  compute_layout(g->P, cam->img_w, cam->img_h, 0, &L);
-  if (geom_bytes < L.geom_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "geometry buffer too small");
-  if (img_bytes < L.img_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "image buffer too small");
-  char *gb = (char*)geom, *ib = (char*)img;
-
   GcrPreprocessArgs a;
-  a.P = g->P; a.D = cam->sh_degree; a.M = g->M; a.W = cam->img_w; a.H = cam->img_h;
-  a.gx = (cam->img_w + GCR_BLOCK_X - 1) / GCR_BLOCK_X;
-  a.gy = (cam->img_h + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
-  const int T = a.gx * a.gy;
-  a.tanfovx = cam->tanfovx; a.tanfovy = cam->tanfovy;
-  a.focal_y = cam->img_h / (2.0f * cam->tanfovy);  // cr/rasterizer_impl.cu:189-190
-  a.focal_x = cam->img_w / (2.0f * cam->tanfovx);
-  a.scale_modifier = cam->scale_modifier;
-  a.means3D = g->means3D; a.scales = g->scales; a.rotations = g->rotations;
-  a.opacities = g->opacities; a.shs = g->shs; a.cov3D_precomp = g->cov3D_precomp;
-  a.colors_precomp = g->colors_precomp;
-  a.view = cam->view_matrix; a.proj = cam->proj_matrix; a.campos = cam->campos;
-  a.s_mean = stride_or(g->stride_means3D, 3);
+  set_camera_args(a, cam, g);
+  a.gx = f.gx; a.gy = f.gy;
+  a.opacities = g->opacities; a.cov3D_precomp = g->cov3D_precomp; a.colors_precomp = g->colors_precomp;
   a.s_opac = stride_or(g->stride_opacities, 1);
   a.s_col = stride_or(g->stride_colors, 3);
-  a.s_scale = stride_or(g->stride_scales, 3);
-  a.s_rot = stride_or(g->stride_rotations, 4);
   a.prefiltered = cam->prefiltered != 0;
   a.cull_cache = op.split_preprocess ? nullptr : reinterpret_cast<const float4*>(g->cull_cache);
   a.cull_shape = a.cull_cache ? reinterpret_cast<const float4*>((const char*)g->cull_cache + gcr_cull_cache_offset_b(g->P)) : nullptr;
   a.nt_stream = nt_stream ? 1 : 0;
-  fill_cam(a.cam, cam);
   a.radii = radii;
-  a.rec = (float4*)(gb + L.geom_rec);
-  a.cov3D = (float*)(gb + L.geom_cov3D);
-  a.tile_count = (uint32_t*)(ib + L.img_tile_cursor);
-  a.vis_list = (uint32_t*)(gb + L.geom_vis_list);
-  a.vis_count = (uint32_t*)(gb + L.geom_vis_count);
-  a.vis_rec = (uint4*)(gb + L.geom_vis_rec);
+  a.rec = f.rec;
+  a.cov3D = f.cov3D;
+  a.tile_count = f.cursor;
+  a.vis_list = f.vis_list;
+  a.vis_count = f.vis_count;
+  a.vis_rec = f.vis_rec;
   // candidate list / counts of K1a live in the arrays only the radix fallback needs later
-  a.cand_list = (uint32_t*)(gb + L.geom_tiles_touched);
-  a.cand_count = (uint32_t*)(gb + L.geom_block_sums);
-  gcr_preprocess_grid(g->P, gcr_preprocess_resident_blocks(op.split_preprocess != 0), &a.nblocks, &a.chunk);
-  unsigned long long* frame = (unsigned long long*)(gb + L.geom_num_rendered);
-  a.block_tiles = (unsigned long long*)(gb + L.geom_block_tiles);
-  *frame_dev_out = frame;
-  int G = 1;
-  const int NG = op.force_global_cursor ? 0 : gcr_tile_table_groups(T, a.nblocks, &G);
-  uint32_t* cursor = (uint32_t*)(ib + L.img_tile_cursor);
-  uint32_t* ranges = (uint32_t*)(ib + L.img_ranges);
-  if (NG > 0) {
-    // default: per-tile counts are built in LDS tables after K1 (no global atomics)
-    a.tile_count = nullptr;
-    {
-      StageTimer t(s, ST_PRE);
-      HIP_TRY(gcr_launch_preprocess(a, op.split_preprocess != 0, s), "preprocess");
-    }
-    if (int rc = debug_sync(cam, s, "preprocess")) return rc;
-    StageTimer t(s, ST_SCAN);
+  a.cand_list = f.tiles_touched;
+  a.cand_count = f.block_sums;
+  a.nblocks = f.nblocks; a.chunk = f.chunk;
+  a.block_tiles = f.block_tiles;
+  const int T = f.T;
+  if (f.NG > 0) a.tile_count = nullptr;  // default: per-tile counts are built in LDS tables after K1 (no global atomics)
+  {
+    StageTimer t(s, ST_PRE);
+    if (f.NG == 0)
+      HIP_TRY(hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t) * GCR_CURSOR_STRIDE * (size_t)T, s), "tile count memset");
+    HIP_TRY(gcr_launch_preprocess(a, op.split_preprocess != 0, s), "preprocess");
+  }
+  if (int rc = debug_sync(cam, s, "preprocess")) return rc;
+  StageTimer t(s, ST_SCAN);
+  if (f.NG > 0) {
     // Band sort for frames expected to hold many instances (the caller's capacity guess: ~0 = no guess, the staged entry
     // point): the renumbered survivors go where only K1a's candidates (split mode) and the radix fallback keep anything
-    const bool band = band_sort_slot_free(op, T) && op.band_sort_min >= 0 &&
+    const bool band = f.banded && band_sort_slot_free(op) && op.band_sort_min >= 0 &&
                       (op.band_sort_min == 0 || (cap_instances != ~0ull && cap_instances >= (unsigned long long)op.band_sort_min));
     // tile_total | tile_local | blk_total share the (T x 128 B) cursor region, unused on this path
-    HIP_TRY(gcr_launch_tile_count(T, a.gx, NG, G, a.nblocks, a.chunk, a.vis_rec, a.vis_count,
-                                  (uint32_t*)(ib + L.img_tile_table), cursor, cursor + (size_t)T,
-                                  cursor + 2 * (size_t)T, frame, a.block_tiles, host_R, seq,
-                                  band ? (uint4*)(gb + L.geom_tiles_touched) : nullptr, g->P / 4, s),
+    HIP_TRY(gcr_launch_tile_count(T, f.gx, f.NG, f.G, f.nblocks, f.chunk, f.vis_rec, f.vis_count, f.table, f.cursor,
+                                  f.cursor + (size_t)T, f.cursor + 2 * (size_t)T, f.frame, f.block_tiles, host_R, seq,
+                                  band ? f.banded : nullptr, g->P / 4, s),
             "tile count");
   } else {
-    {
-      StageTimer t(s, ST_PRE);
-      HIP_TRY(hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t) * GCR_CURSOR_STRIDE * (size_t)T, s), "tile count memset");
-      HIP_TRY(gcr_launch_preprocess(a, op.split_preprocess != 0, s), "preprocess");
-    }
-    if (int rc = debug_sync(cam, s, "preprocess")) return rc;
-    StageTimer t(s, ST_SCAN);
-    HIP_TRY(gcr_launch_scan_tiles(cursor, GCR_CURSOR_STRIDE, ranges, T, frame, cap_instances, cap_list, host_R, seq,
-                                  a.block_tiles, a.nblocks, s),
+    HIP_TRY(gcr_launch_scan_tiles(f.cursor, GCR_CURSOR_STRIDE, f.ranges, T, f.frame, cap_instances, cap_list, host_R, seq,
+                                  f.block_tiles, f.nblocks, s),
             "tile scan");
   }
   return 0;
 }
 
-// Where the forward blend leaves its checkpoints (gcr_internal.h "backward pieces").  `binning` may be null when
-// nothing can be rendered (R_layout == 0): the tiles are empty then and the backward never launches its blend.
-static void set_piece_args(const Opts& op, GcrBlendArgs& b, bool want_state, const gcr_layout& L, void* binning,
-                           void* geom) {
-  char* bb = want_state ? (char*)binning : nullptr;  // no state: the blend runs its instantiation without it
+// Where the forward blend leaves its checkpoints (gcr_internal.h "backward pieces").  None when nothing can be rendered
+// (R_layout == 0): the tiles are empty then and the backward never launches its blend.
+static void set_piece_args(const Opts& op, GcrBlendArgs& b, bool want_state, const FrameSetup& f) {
+  const gcr_layout& L = f.L;
+  char* bb = want_state && f.R_layout > 0 ? f.bin : nullptr;  // no state: the blend runs its instantiation without it
   // Measured (tools/k7_ab.py, round 5: one workgroup per item): 160-entry pieces, C2 backward blend 60 us against 63 at
   // 128 and 67 at 223, the forward blend 31.4 against 32.5 / 31.0 (profiles/r05_k7_ab.jsonl).  Pieces cost the
   // forward blend a few per cent (more staging rounds, more sentinel steps, the checkpoint stores), so only frames
@@ -500,7 +567,7 @@ static void set_piece_args(const Opts& op, GcrBlendArgs& b, bool want_state, con
   b.work_off = L.bin_work;
   b.mask_off = L.bin_mask;
   b.carve_bytes = L.bin_total;
-  b.frame_out = (unsigned long long*)((char*)geom + L.geom_num_rendered);
+  b.frame_out = f.frame;
 #ifdef GCR_EXPERIMENTS
   if (const char* e = getenv("GCR_K6_NOEXTRAS")) {  // A/B only: what the backward's state costs the forward blend
     if (strchr(e, 'w')) { b.ckpt = nullptr; b.work = nullptr; }
@@ -511,44 +578,25 @@ static void set_piece_args(const Opts& op, GcrBlendArgs& b, bool want_state, con
 
 // Enqueues scatter + per-tile LDS sort + forward blend (the default binning path).
 // `frame_guard` (device {R, max, go}) makes the three kernels no-ops when go == 0.
-static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_gaussians* g, void* geom, void* binning, void* img,
-                              int64_t R_layout, int64_t list_length_hint, bool speculative,
-                              unsigned long long cap_instances, unsigned long long cap_list, float* out_color,
-                              hipStream_t s, unsigned long long* host_longest = nullptr,
-                              unsigned long long* gate_words = nullptr, unsigned int gate_seq = 0, bool nt_out = false) {
-  gcr_layout L;
-  compute_layout(g->P, cam->img_w, cam->img_h, R_layout, &L);
-  char *gb = (char*)geom, *bb = (char*)binning, *ib = (char*)img;
-  const int gx = (cam->img_w + GCR_BLOCK_X - 1) / GCR_BLOCK_X;
-  const int gy = (cam->img_h + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
-  const int T = gx * gy;
-  const float4* rec = (const float4*)(gb + L.geom_rec);
-  const uint32_t* vis_list = (const uint32_t*)(gb + L.geom_vis_list);
-  const uint32_t* vis_count = (const uint32_t*)(gb + L.geom_vis_count);
-  uint32_t* ranges = (uint32_t*)(ib + L.img_ranges);
-  uint64_t* pairs = (uint64_t*)(bb + L.bin_keys[0]);
-  uint32_t* list = (uint32_t*)(bb + L.bin_vals[L.bin_sorted]);
-  unsigned long long* frame_dev = (unsigned long long*)(gb + L.geom_num_rendered);
-  const unsigned long long* frame_guard = speculative ? frame_dev : nullptr;
-  int nblocks, chunk;
-  gcr_preprocess_grid(g->P, gcr_preprocess_resident_blocks(op.split_preprocess != 0), &nblocks, &chunk);
-  int G = 1;
-  const int NG = op.force_global_cursor ? 0 : gcr_tile_table_groups(T, nblocks, &G);
+static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_gaussians* g, const FrameSetup& f,
+                              int64_t list_length_hint, bool speculative, unsigned long long cap_instances,
+                              unsigned long long cap_list, float* out_color, hipStream_t s,
+                              unsigned long long* host_longest = nullptr, unsigned long long* gate_words = nullptr,
+                              unsigned int gate_seq = 0, bool nt_out = false) {
+  const int64_t R_layout = f.R_layout;
+  uint64_t* pairs = f.keys[0];
+  const unsigned long long* frame_guard = speculative ? f.frame : nullptr;
   {
     StageTimer t(s, ST_EMIT);
-    if (NG > 0) {
+    if (f.NG > 0) {
       // also rebuilds `ranges` from the block totals, so it runs even when nothing is rendered
-      uint32_t* cursor = (uint32_t*)(ib + L.img_tile_cursor);
-      HIP_TRY(gcr_launch_tile_scatter(T, gx, NG, G, nblocks, chunk, (const uint4*)(gb + L.geom_vis_rec), vis_count,
-                                      (uint32_t*)(ib + L.img_tile_table), cursor, cursor + (size_t)T,
-                                      cursor + 2 * (size_t)T, ranges, pairs, frame_dev, cap_instances, cap_list,
-                                      host_longest,
-                                      band_sort_slot_free(op, T) ? (const uint4*)(gb + L.geom_tiles_touched) : nullptr,
-                                      g->P / 4, s),
+      HIP_TRY(gcr_launch_tile_scatter(f.T, f.gx, f.NG, f.G, f.nblocks, f.chunk, f.vis_rec, f.vis_count, f.table, f.cursor,
+                                      f.cursor + (size_t)f.T, f.cursor + 2 * (size_t)f.T, f.ranges, pairs, f.frame,
+                                      cap_instances, cap_list, host_longest, f.banded, g->P / 4, s),
               "tile scatter");
     } else if (R_layout > 0) {
-      HIP_TRY(gcr_launch_scatter_instances(nblocks, chunk, vis_list, vis_count, rec, gx,
-                                           (uint32_t*)(ib + L.img_tile_cursor), pairs, ranges, T, frame_guard, s),
+      HIP_TRY(gcr_launch_scatter_instances(f.nblocks, f.chunk, f.vis_list, f.vis_count, f.rec, f.gx, f.cursor, pairs,
+                                           f.ranges, f.T, frame_guard, s),
               "scatter instances");
     }
   }
@@ -559,35 +607,23 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
   // VALU-bound blend grows by 14 us, while the separate latency-bound sort kernel hides behind the other frame's
   // work) -- so it is off by default.
   const bool sort_in_blend = R_layout > 0 && list_length_hint <= GCR_SORT_IN_BLEND_MAX && op.sort_in_blend != 0;
-  uint4* lazy = (R_layout > 0 && !sort_in_blend && op.lazy_sort != 0) ? (uint4*)(ib + L.img_tile_lazy) : nullptr;
+  uint4* lazy = (R_layout > 0 && !sort_in_blend && op.lazy_sort != 0) ? f.lazy : nullptr;
   if (R_layout > 0 && !sort_in_blend) {
     StageTimer t(s, ST_SORT);
     // LDS of the sort sized for 1.5x the expected longest list (longer ones take its run + merge path)
-    HIP_TRY(gcr_launch_tile_sort(ranges, T, pairs, (uint64_t*)(bb + L.bin_keys[1]), list,
-                                 list_length_hint + list_length_hint / 2 + 64, frame_guard, lazy, s),
+    HIP_TRY(gcr_launch_tile_sort(f.ranges, f.T, pairs, f.keys[1], f.list, list_length_hint + list_length_hint / 2 + 64,
+                                 frame_guard, lazy, s),
             "tile sort");
   }
   if (int rc = debug_sync(cam, s, "tile sort")) return rc;
-  GcrBlendArgs b;
-  memset(&b, 0, sizeof(b));
-  b.ranges = ranges;
-  b.list = list;
-  b.rec = rec;
-  b.W = cam->img_w; b.H = cam->img_h; b.gx = gx; b.gy = gy;
-  b.bg = cam->bg;
-  b.flip_x = cam->flip_x != 0; b.flip_y = cam->flip_y != 0;
-  b.win_x = cam->win_x; b.win_y = cam->win_y; b.win_w = cam->win_w; b.win_h = cam->win_h;
-  b.out_u8 = cam->out_u8 != 0 && cam->backward != 1;
+  GcrBlendArgs b = blend_args(f, cam, f.list);
   b.nt_out = nt_out && cam->backward != 1;
-  fill_cam(b.cam, cam);
-  b.final_T = (float*)(ib + L.img_final_T);
-  b.n_contrib = (uint32_t*)(ib + L.img_n_contrib);
   b.out_color = out_color;
   b.frame = frame_guard;
   b.pairs = pairs;
-  b.list_out = list;
+  b.list_out = f.list;
   b.lazy = lazy;
-  set_piece_args(op, b, cam->backward == 1, L, R_layout > 0 ? binning : nullptr, geom);
+  set_piece_args(op, b, cam->backward == 1, f);
   b.gate_words = gate_words;  // asynchronous frames: the forward blend is the frame's last kernel and carries the gate
   b.gate_seq = gate_seq;
   b.gate_polls = (unsigned int)g_gate_polls.load();
@@ -691,28 +727,21 @@ int gcr_forward_preprocess(const gcr_camera* cam, const gcr_gaussians* g, void* 
   info_host->num_rendered = 0;
   info_host->max_tile_instances = 0;
   if (g->P == 0) return 0;  // dgr/rasterize_points.cu:71
+  if (!geom || !radii || !img) return fail(GCR_ERR_INVALID_ARGUMENT, "geom/img/radii must be non-null");
   const Opts op = resolve_options(cam->options);
+  const FrameSetup f = frame_setup(op, g->P, cam, 0, geom, img, nullptr);
+  if (int rc = check_buffers(f, cam, geom_bytes, img_bytes, nullptr, 0, nullptr)) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
-  unsigned long long* frame = nullptr;
   const SyncCullGuard sync_cull;  // (until this call returns: the copy below is the frame's host wait)
   const bool nt = op.stream_policy > 0 || (op.stream_policy < 0 && sync_cull.others == 0);
-  if (int rc = enqueue_preprocess(op, cam, g, geom, geom_bytes, img, img_bytes, radii, ~0ull, ~0ull, &frame, s, nullptr, 0, nt))
-    return rc;
+  if (int rc = enqueue_preprocess(op, cam, g, f, radii, ~0ull, ~0ull, s, nullptr, 0, nt)) return rc;
   unsigned long long r[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(r, frame, sizeof(r), hipMemcpyDeviceToHost, s), "num_rendered copy");
+  HIP_TRY(hipMemcpyAsync(r, f.frame, sizeof(r), hipMemcpyDeviceToHost, s), "num_rendered copy");
   HIP_TRY(hipStreamSynchronize(s), "num_rendered sync");  // cr/rasterizer_impl.cu:236-238
-  if (r[0] == GCR_PREFILTER_MARK) return fail_prefiltered();
-  if (r[0] > 0x7fffffffull)
-    return fail(GCR_ERR_OVERFLOW, "num_rendered exceeds 2^31-1 (32-bit instance index, as in the reference)");
+  if (int rc = check_num_rendered(r[0])) return rc;
   info_host->num_rendered = (int64_t)r[0];
   info_host->max_tile_instances = (int64_t)r[1];
   return 0;
-}
-
-// bytes a forward needs in `binning` for `capacity` instances: the lean carve for frames that never see a backward
-static size_t forward_binning_need(const gcr_camera* cam, int64_t capacity) {
-  return cam->backward != 1 ? gcr_binning_bytes_lean(capacity, cam->img_w, cam->img_h)
-                             : gcr_binning_bytes(capacity, cam->img_w, cam->img_h);
 }
 
 int gcr_forward(const gcr_camera* cam, const gcr_gaussians* g, void* geom, size_t geom_bytes, void* binning,
@@ -726,10 +755,13 @@ int gcr_forward(const gcr_camera* cam, const gcr_gaussians* g, void* geom, size_
   if (!out_color) return fail(GCR_ERR_INVALID_ARGUMENT, "out_color is null");
   if (binning_capacity < 0 || binning_capacity > 0x7fffffffll)
     return fail(GCR_ERR_INVALID_ARGUMENT, "binning_capacity out of range");
-  if (binning_capacity > 0 && (!binning || binning_bytes < forward_binning_need(cam, binning_capacity)))
-    return fail(GCR_ERR_BUFFER_TOO_SMALL, "binning buffer smaller than gcr_binning_bytes(binning_capacity)");
-  if (int rc = g_readback.ensure()) return rc;
+  if (!geom || !radii || !img) return fail(GCR_ERR_INVALID_ARGUMENT, "geom/img/radii must be non-null");
   const Opts op = resolve_options(cam->options);
+  const FrameSetup f = frame_setup(op, g->P, cam, binning_capacity, geom, img, binning);
+  if (int rc = check_buffers(f, cam, geom_bytes, img_bytes, binning, binning_bytes,
+                               "binning buffer smaller than gcr_binning_bytes(binning_capacity)"))
+    return rc;
+  if (int rc = g_readback.ensure()) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const bool speculate = binning_capacity > 0 && !op.force_radix && !cam->debug;
   // The longest-list guess only sizes the LDS of the tile sort (any length is sorted correctly), so the
@@ -737,20 +769,17 @@ int gcr_forward(const gcr_camera* cam, const gcr_gaussians* g, void* geom, size_
   const int64_t list_hint = tile_list_capacity > 0 ? tile_list_capacity : (int64_t)gcr_tile_sort_capacity();
   FrameReadback& rb = g_readback;
   const unsigned int seq = ++rb.seq ? rb.seq : ++rb.seq;  // never 0: the word starts out as 0
-  unsigned long long* frame = nullptr;
   // "stream_policy": this caller's next cull cannot start before the wait below has seen this one end
   const SyncCullGuard sync_cull;
   const bool nt = op.stream_policy > 0 || (op.stream_policy < 0 && sync_cull.others == 0);
-  if (int rc = enqueue_preprocess(op, cam, g, geom, geom_bytes, img, img_bytes, radii,
-                                  speculate ? (unsigned long long)binning_capacity : 0ull, ~0ull, &frame, s,
+  if (int rc = enqueue_preprocess(op, cam, g, f, radii, speculate ? (unsigned long long)binning_capacity : 0ull, ~0ull, s,
                                   rb.pinned, seq, nt))
     return rc;
   if (speculate) {
     // Everything else of the frame is enqueued before the host knows R: the kernels read the
     // tile ranges from device memory and are vetoed by frame[2] if the capacity guess was short.
-    if (int rc = enqueue_render_lds(op, cam, g, geom, binning, img, binning_capacity, list_hint, true,
-                                    (unsigned long long)binning_capacity, ~0ull, out_color, s, rb.pinned + 1,
-                                    nullptr, 0, nt))
+    if (int rc = enqueue_render_lds(op, cam, g, f, list_hint, true, (unsigned long long)binning_capacity, ~0ull, out_color,
+                                    s, rb.pinned + 1, nullptr, 0, nt))
       return rc;
   }
   // the one host wait of the frame: poll the pinned word until the kernel after K1 has tagged it with this frame
@@ -768,9 +797,7 @@ int gcr_forward(const gcr_camera* cam, const gcr_gaussians* g, void* geom, size_
   const unsigned long long R = v & 0xffffffffull;
   // the same decision the scatter kernel takes on the device from the same number
   const bool go = R <= (unsigned long long)binning_capacity;
-  if (R == GCR_PREFILTER_MARK) return fail_prefiltered();
-  if (R > 0x7fffffffull)
-    return fail(GCR_ERR_OVERFLOW, "num_rendered exceeds 2^31-1 (32-bit instance index, as in the reference)");
+  if (int rc = check_num_rendered(R)) return rc;
   info_host->num_rendered = (int64_t)R;
   if (speculate && go) {
     // longest list: what the most recent scatter kernel of this thread published (a hint for the next guess);
@@ -782,7 +809,7 @@ int gcr_forward(const gcr_camera* cam, const gcr_gaussians* g, void* geom, size_
   }
   // retry path: the caller needs the exact longest list of THIS frame to size the sort
   unsigned long long mx = 0;
-  HIP_TRY(hipMemcpyAsync(&mx, frame + 1, sizeof(mx), hipMemcpyDeviceToHost, s), "longest list copy");
+  HIP_TRY(hipMemcpyAsync(&mx, f.frame + 1, sizeof(mx), hipMemcpyDeviceToHost, s), "longest list copy");
   HIP_TRY(hipStreamSynchronize(s), "longest list sync");
   info_host->max_tile_instances = (int64_t)mx;
   return 1;  // GCR_RETRY_RENDER: call gcr_forward_render with a binning buffer sized for info_host
@@ -857,7 +884,7 @@ class RescueService {
     void* stale = nullptr;  // a scratch buffer that was too small: freed AFTER the gate is released (hipFree waits for
     //                         every stream of the device, the caller's -- which the gate is holding -- included)
     do {
-      if (R > 0x7fffffffull) break;
+      if (check_num_rendered(R)) break;
       if (hipSetDevice(f.device) != hipSuccess) break;
       const int d = f.device & 63;
       if (!streams_[d]) {
@@ -880,12 +907,11 @@ class RescueService {
         cam.campos = f.camvals + 32;
         cam.bg = f.camvals + 35;
       }
-      gcr_layout L;
-      compute_layout(f.g.P, cam.img_w, cam.img_h, 0, &L);
+      const FrameSetup fs = frame_setup(resolve_options(cam.options), f.g.P, &cam, 0, f.geom, f.img, nullptr);
       gcr_frame_info info;
       info.num_rendered = (int64_t)R;
       unsigned long long longest = 0;
-      if (hipMemcpyAsync(&longest, (char*)f.geom + L.geom_num_rendered + 8, 8, hipMemcpyDeviceToHost, s) != hipSuccess) break;
+      if (hipMemcpyAsync(&longest, fs.frame + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess) break;
       if (hipStreamSynchronize(s) != hipSuccess) break;
       info.max_tile_instances = (int64_t)longest;
       const size_t bytes = gcr_binning_bytes_lean((int64_t)R, cam.img_w, cam.img_h);
@@ -1030,14 +1056,16 @@ int gcr_forward_async(const gcr_camera* cam, const gcr_gaussians* g, void* geom,
   if (binning_capacity <= 0 || binning_capacity > 0x7fffffffll || op.force_radix || cam->debug)
     return fail(GCR_ERR_INVALID_ARGUMENT,
                 "gcr_forward_async needs a capacity guess > 0 and neither force_radix nor debug: use gcr_forward");
-  if (!binning || binning_bytes < forward_binning_need(cam, binning_capacity))
-    return fail(GCR_ERR_BUFFER_TOO_SMALL, "binning buffer smaller than gcr_binning_bytes(binning_capacity)");
+  if (!geom || !radii || !img) return fail(GCR_ERR_INVALID_ARGUMENT, "geom/img/radii must be non-null");
+  const FrameSetup fr = frame_setup(op, g->P, cam, binning_capacity, geom, img, binning);
+  if (int rc = check_buffers(fr, cam, geom_bytes, img_bytes, binning, binning_bytes,
+                               "binning buffer smaller than gcr_binning_bytes(binning_capacity)"))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t list_hint = tile_list_capacity > 0 ? tile_list_capacity : (int64_t)gcr_tile_sort_capacity();
-  unsigned long long* frame = nullptr;
   // (asynchronous frames are what runs side by side: their streams keep the default cache policy unless "stream_policy" is 1)
-  if (int rc = enqueue_preprocess(op, cam, g, geom, geom_bytes, img, img_bytes, radii, (unsigned long long)binning_capacity,
-                                  ~0ull, &frame, s, words_host, seq, op.stream_policy > 0))
+  if (int rc = enqueue_preprocess(op, cam, g, fr, radii, (unsigned long long)binning_capacity, ~0ull, s, words_host, seq,
+                                  op.stream_policy > 0))
     return rc;
   AsyncFrame f;
   memset((void*)&f, 0, sizeof(f));
@@ -1063,9 +1091,8 @@ int gcr_forward_async(const gcr_camera* cam, const gcr_gaussians* g, void* geom,
   f.capacity = binning_capacity;
   f.born = std::chrono::steady_clock::now();
   rescue_service().add(f);  // (before the kernel that may call for it is enqueued)
-  const int rc = enqueue_render_lds(op, cam, g, geom, binning, img, binning_capacity, list_hint, true,
-                                    (unsigned long long)binning_capacity, ~0ull, out_color, s, words_host + 1, words_host, seq,
-                                    op.stream_policy > 0);
+  const int rc = enqueue_render_lds(op, cam, g, fr, list_hint, true, (unsigned long long)binning_capacity, ~0ull, out_color, s,
+                                    words_host + 1, words_host, seq, op.stream_policy > 0);
   if (rc < 0) rescue_service().remove(words_host, seq);  // no gate was enqueued: nobody will ever call for this frame
   return rc;
 }
@@ -1075,9 +1102,7 @@ static int ticket_state(const unsigned long long* words_host, uint32_t seq, int6
   const unsigned long long v = w[0];
   if ((unsigned int)(v >> 32) != seq) return 1;
   const unsigned long long R = v & 0xffffffffull;
-  if (R == GCR_PREFILTER_MARK) return fail_prefiltered();
-  if (R > 0x7fffffffull)
-    return fail(GCR_ERR_OVERFLOW, "num_rendered exceeds 2^31-1 (32-bit instance index, as in the reference)");
+  if (int rc = check_num_rendered(R)) return rc;
   if (R > (unsigned long long)capacity) {  // the frame needed the rescue: resolved when that is complete
     if ((unsigned int)w[5] == seq) return fail(GCR_ERR_DEVICE, "the overflow rescue of an asynchronous frame failed");
     if ((unsigned int)w[2] != seq) {
@@ -1129,74 +1154,41 @@ int gcr_forward_render(const gcr_camera* cam, const gcr_gaussians* g, void* geom
   const int64_t R = info->num_rendered;
   if (R < 0 || R > 0x7fffffffll) return fail(GCR_ERR_INVALID_ARGUMENT, "R out of range");
   if (R > 0 && !binning) return fail(GCR_ERR_INVALID_ARGUMENT, "binning buffer is null");
-  gcr_layout L;
-  compute_layout(g->P, cam->img_w, cam->img_h, R, &L);
-  if (geom_bytes < L.geom_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "geometry buffer too small");
-  if (img_bytes < L.img_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "image buffer too small");
-  if (R > 0 && binning_bytes < (cam->backward == 1 ? L.bin_total : L.bin_lean_total))
-    return fail(GCR_ERR_BUFFER_TOO_SMALL, "binning buffer too small");
   const Opts op = resolve_options(cam->options);
+  const FrameSetup f = frame_setup(op, g->P, cam, R, geom, img, binning);
+  if (int rc = check_buffers(f, cam, geom_bytes, img_bytes, binning, binning_bytes, "binning buffer too small")) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   // Tile lists beyond the LDS sort capacity are sorted by the same workgroup with runs + merge passes; every
   // other tile stays on the LDS path (no whole-frame fallback for a long list).
   if (R == 0 || !op.force_radix)
-    return enqueue_render_lds(op, cam, g, geom, binning, img, R, info->max_tile_instances, false, ~0ull, ~0ull, out_color, s,
-                              nullptr, nullptr, 0, op.stream_policy > 0);
+    return enqueue_render_lds(op, cam, g, f, info->max_tile_instances, false, ~0ull, ~0ull, out_color, s, nullptr, nullptr, 0,
+                              op.stream_policy > 0);
 
   // "force_radix" (A/B and test option): the reference's own scheme -- emit tile|depth keys in index
   // order, stable global radix sort, boundary scan.
-  char *gb = (char*)geom, *bb = (char*)binning, *ib = (char*)img;
-  const int gx = (cam->img_w + GCR_BLOCK_X - 1) / GCR_BLOCK_X;
-  const int gy = (cam->img_h + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
-  const int T = gx * gy;
-  const float4* rec = (const float4*)(gb + L.geom_rec);
-  uint32_t* tiles_touched = (uint32_t*)(gb + L.geom_tiles_touched);
-  uint32_t* block_sums = (uint32_t*)(gb + L.geom_block_sums);
-  const uint32_t* vis_list = (const uint32_t*)(gb + L.geom_vis_list);
-  const uint32_t* vis_count = (const uint32_t*)(gb + L.geom_vis_count);
-  int nblocks, chunk;
-  gcr_preprocess_grid(g->P, gcr_preprocess_resident_blocks(op.split_preprocess != 0), &nblocks, &chunk);
-  uint64_t* k0 = (uint64_t*)(bb + L.bin_keys[0]);
-  uint64_t* k1 = (uint64_t*)(bb + L.bin_keys[1]);
-  uint32_t* v0 = (uint32_t*)(bb + L.bin_vals[0]);
-  uint32_t* v1 = (uint32_t*)(bb + L.bin_vals[1]);
-  uint32_t* ranges = (uint32_t*)(ib + L.img_ranges);
-  int half = (int)L.bin_sorted;
+  int half = (int)f.L.bin_sorted;
   {
     StageTimer t(s, ST_EMIT);
-    unsigned long long* scratch_total = (unsigned long long*)(bb + L.bin_hist);
-    HIP_TRY(gcr_launch_tiles_touched(g->P, nblocks, chunk, vis_list, vis_count, rec, tiles_touched, block_sums, s),
+    HIP_TRY(gcr_launch_tiles_touched(g->P, f.nblocks, f.chunk, f.vis_list, f.vis_count, f.rec, f.tiles_touched, f.block_sums, s),
             "tiles touched");
-    HIP_TRY(gcr_launch_scan_block_sums(block_sums, (g->P + 255) / 256, scratch_total, s), "scan");
-    HIP_TRY(gcr_launch_emit(g->P, tiles_touched, block_sums, rec, gx, k0, v0, s), "emit");
+    HIP_TRY(gcr_launch_scan_block_sums(f.block_sums, (g->P + 255) / 256, (unsigned long long*)f.hist, s), "scan");
+    HIP_TRY(gcr_launch_emit(g->P, f.tiles_touched, f.block_sums, f.rec, f.gx, f.keys[0], f.vals[0], s), "emit");
   }
   if (int rc = debug_sync(cam, s, "emit")) return rc;
   {
     StageTimer t(s, ST_SORT);
-    const int end_bit = 32 + (int)gcr_higher_msb((uint32_t)T);  // cr/rasterizer_impl.cu:252
-    HIP_TRY(gcr_launch_sort(k0, v0, k1, v1, R, end_bit, (uint32_t*)(bb + L.bin_hist), &half, s), "sort");
+    const int end_bit = 32 + (int)gcr_higher_msb((uint32_t)f.T);  // cr/rasterizer_impl.cu:252
+    HIP_TRY(gcr_launch_sort(f.keys[0], f.vals[0], f.keys[1], f.vals[1], R, end_bit, f.hist, &half, s), "sort");
   }
   if (int rc = debug_sync(cam, s, "sort")) return rc;
   {
     StageTimer t(s, ST_RANGES);
-    HIP_TRY(gcr_launch_tile_ranges(half ? k1 : k0, R, ranges, T, s), "tile ranges");
+    HIP_TRY(gcr_launch_tile_ranges(f.keys[half], R, f.ranges, f.T, s), "tile ranges");
   }
   if (int rc = debug_sync(cam, s, "tile ranges")) return rc;
-  GcrBlendArgs b;
-  memset(&b, 0, sizeof(b));
-  b.ranges = ranges;
-  b.list = half ? v1 : v0;
-  b.rec = rec;
-  b.W = cam->img_w; b.H = cam->img_h; b.gx = gx; b.gy = gy;
-  b.bg = cam->bg;
-  b.flip_x = cam->flip_x != 0; b.flip_y = cam->flip_y != 0;
-  b.win_x = cam->win_x; b.win_y = cam->win_y; b.win_w = cam->win_w; b.win_h = cam->win_h;
-  fill_cam(b.cam, cam);
-  b.final_T = (float*)(ib + L.img_final_T);
-  b.n_contrib = (uint32_t*)(ib + L.img_n_contrib);
+  GcrBlendArgs b = blend_args(f, cam, f.vals[half]);
   b.out_color = out_color;
-  b.out_u8 = cam->out_u8 != 0 && cam->backward != 1;
-  set_piece_args(op, b, cam->backward == 1, L, binning, geom);
+  set_piece_args(op, b, cam->backward == 1, f);
   {
     StageTimer t(s, ST_BLEND_FWD);
     HIP_TRY(gcr_launch_blend_fwd(b, false, s), "blend forward");
@@ -1232,21 +1224,12 @@ int gcr_backward(const gcr_camera* cam, const gcr_gaussians* g, const int32_t* r
     return fail(GCR_ERR_INVALID_ARGUMENT,
                 "gcr_backward needs a frame rendered with gcr_camera.backward == 1 (pass the same value here); for a frame "
                 "rendered without it call gcr_forward_render(out_color = NULL, backward = 1) first");
-  gcr_layout L;
-  compute_layout(g->P, cam->img_w, cam->img_h, R, &L);
-  if (geom_bytes < L.geom_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "geometry buffer too small");
-  if (img_bytes < L.img_total) return fail(GCR_ERR_BUFFER_TOO_SMALL, "image buffer too small");
+  const Opts op = resolve_options(cam->options);
+  const FrameSetup f = frame_setup(op, g->P, cam, R, geom, img, binning);
   // (the forward may have carved the buffer for a larger capacity: the blend kernel checks the carve the forward
   // published against binning_bytes on the device and poisons the gradients instead of reading out of bounds)
-  if (R > 0 && (!binning || binning_bytes < L.bin_total))
-    return fail(GCR_ERR_BUFFER_TOO_SMALL, "binning buffer too small");
-  const Opts op = resolve_options(cam->options);
+  if (int rc = check_buffers(f, cam, geom_bytes, img_bytes, binning, binning_bytes, "binning buffer too small")) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
-  const char *gb = (const char*)geom, *bb = (const char*)binning, *ib = (const char*)img;
-  const int gx = (cam->img_w + GCR_BLOCK_X - 1) / GCR_BLOCK_X;
-  const int gy = (cam->img_h + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
-  int nblocks_k1 = 0, chunk_k1 = 0;
-  gcr_preprocess_grid(g->P, gcr_preprocess_resident_blocks(op.split_preprocess != 0), &nblocks_k1, &chunk_k1);
 
   const int det = op.deterministic;  // the caller sized dL_dconic with gcr_grad_record_floats_opt() under the same options
 
@@ -1289,28 +1272,16 @@ int gcr_backward(const gcr_camera* cam, const gcr_gaussians* g, const int32_t* r
 
   if (R > 0) {
     StageTimer t(s, ST_BLEND_BWD);  // one slot per stage: a second timer of the same stage would halve the average
-    HIP_TRY(gcr_launch_zero_grad_records(nblocks_k1, chunk_k1, (const uint32_t*)(gb + L.geom_vis_list),
-                                         (const uint32_t*)(gb + L.geom_vis_count), (float4*)gr->dL_dconic,
+    HIP_TRY(gcr_launch_zero_grad_records(f.nblocks, f.chunk, f.vis_list, f.vis_count, (float4*)gr->dL_dconic,
                                          (det ? GCR_GRAD_REC_FLOATS_DET : GCR_GRAD_REC_FLOATS) / 4, s),
             "zero gradient records");
-    GcrBlendArgs b;
-    memset(&b, 0, sizeof(b));
+    GcrBlendArgs b = blend_args(f, cam, f.list);
     b.fill = fill;
-    b.ranges = (const uint32_t*)(ib + L.img_ranges);
-    b.list = (const uint32_t*)(bb + L.bin_vals[L.bin_sorted]);
-    b.rec = (const float4*)(gb + L.geom_rec);
-    b.W = cam->img_w; b.H = cam->img_h; b.gx = gx; b.gy = gy;
-    b.bg = cam->bg;
-    b.flip_x = cam->flip_x != 0; b.flip_y = cam->flip_y != 0;
-    b.win_x = cam->win_x; b.win_y = cam->win_y; b.win_w = cam->win_w; b.win_h = cam->win_h;
-    fill_cam(b.cam, cam);
-    b.final_T = (float*)(ib + L.img_final_T);
-    b.n_contrib = (uint32_t*)(ib + L.img_n_contrib);
     b.dL_dpix = dL_dpix;
     b.grad_rec = gr->dL_dconic;  // [P][gcr_grad_record_floats()] accumulation records (include/gcr.h)
     b.deterministic = det;
-    b.binning_base = bb;
-    b.frame_in = (const unsigned long long*)(gb + L.geom_num_rendered);
+    b.binning_base = f.bin;
+    b.frame_in = f.frame;
     b.R = (unsigned long long)R;
     b.piece = op.bwd_piece;  // sizes the grid only: the kernel takes the forward's piece size from frame_in
     b.binning_bytes = (unsigned long long)binning_bytes;
@@ -1325,39 +1296,29 @@ int gcr_backward(const gcr_camera* cam, const gcr_gaussians* g, const int32_t* r
   if (int rc = debug_sync(cam, s, "blend backward")) return rc;
 
   GcrPreprocessBwdArgs a;
-  a.P = g->P; a.D = cam->sh_degree; a.M = g->M; a.W = cam->img_w; a.H = cam->img_h;
-  a.tanfovx = cam->tanfovx; a.tanfovy = cam->tanfovy;
-  a.focal_y = cam->img_h / (2.0f * cam->tanfovy);
-  a.focal_x = cam->img_w / (2.0f * cam->tanfovx);
-  a.scale_modifier = cam->scale_modifier;
-  a.means3D = g->means3D; a.scales = g->scales; a.rotations = g->rotations; a.shs = g->shs;
+  set_camera_args(a, cam, g);
   // cr/rasterizer_impl.cu:329-330 reads the forward's stored covariance when none was supplied; K8 derives it from scales and
   // rotation again instead (gcr_preprocess.hip phase_a1_exact: the same function, the same bits) -- the pointer below is only
   // read for a supplied covariance
-  a.cov3D = g->cov3D_precomp ? g->cov3D_precomp : (const float*)(gb + L.geom_cov3D);
+  a.cov3D = g->cov3D_precomp ? g->cov3D_precomp : f.cov3D;
   a.s_cov3d = g->cov3D_precomp ? 6 : GCR_COV3D_FLOATS;
-  a.view = cam->view_matrix; a.proj = cam->proj_matrix; a.campos = cam->campos;
   a.radii = radii;
-  a.vis_list = (const uint32_t*)(gb + L.geom_vis_list);
-  a.vis_count = (const uint32_t*)(gb + L.geom_vis_count);
-  a.nblocks = nblocks_k1; a.chunk = chunk_k1;
-  a.frame = R > 0 ? (const unsigned long long*)(gb + L.geom_num_rendered) : nullptr;
+  a.vis_list = f.vis_list;
+  a.vis_count = f.vis_count;
+  a.nblocks = f.nblocks; a.chunk = f.chunk;
+  a.frame = R > 0 ? f.frame : nullptr;
   a.binning_bytes = (unsigned long long)binning_bytes;
   a.grad_rec = (const float4*)gr->dL_dconic;
-  a.rec = (const float4*)(gb + L.geom_rec);
+  a.rec = f.rec;
   a.deterministic = det;
   a.dL_dmean2D = gr->dL_dmeans2D; a.dL_dcolor = gr->dL_dcolors; a.dL_dopacity = gr->dL_dopacity;
   a.dL_dmean3D = gr->dL_dmeans3D; a.dL_dcov3D = gr->dL_dcov3D; a.dL_dsh = gr->dL_dsh;
   a.dL_dscale = gr->dL_dscales; a.dL_drot = gr->dL_drotations;
-  a.s_mean = stride_or(g->stride_means3D, 3);
-  a.s_scale = stride_or(g->stride_scales, 3);
-  a.s_rot = stride_or(g->stride_rotations, 4);
   a.g_mean = stride_or(gr->stride_means3D, 3);
   a.g_opac = stride_or(gr->stride_opacity, 1);
   a.g_col = stride_or(gr->stride_colors, 3);
   a.g_scale = stride_or(gr->stride_scales, 3);
   a.g_rot = stride_or(gr->stride_rotations, 4);
-  fill_cam(a.cam, cam);
   {
     StageTimer t(s, ST_PRE_BWD);
     HIP_TRY(gcr_launch_preprocess_bwd(a, s), "preprocess backward");
@@ -1380,13 +1341,10 @@ int gcr_build_cull_cache(const gcr_gaussians* g, float scale_modifier, void* cul
     return fail(GCR_ERR_INVALID_ARGUMENT, "cull_cache_out must be a 128-byte aligned buffer of gcr_cull_cache_bytes(P) bytes");
   GcrPreprocessArgs a;
   memset(&a, 0, sizeof(a));
-  a.P = g->P;
+  set_gaussian_args(a, g);
   a.scale_modifier = scale_modifier;
-  a.means3D = g->means3D; a.scales = g->scales; a.rotations = g->rotations; a.cov3D_precomp = g->cov3D_precomp;
+  a.cov3D_precomp = g->cov3D_precomp;
   a.opacities = g->opacities;
-  a.s_mean = stride_or(g->stride_means3D, 3);
-  a.s_scale = stride_or(g->stride_scales, 3);
-  a.s_rot = stride_or(g->stride_rotations, 4);
   a.s_opac = stride_or(g->stride_opacities, 1);
   HIP_TRY(gcr_launch_build_cull_cache(a, reinterpret_cast<float4*>(cull_cache_out),
                                       reinterpret_cast<float4*>((char*)cull_cache_out + gcr_cull_cache_offset_b(g->P)),

@@ -69,7 +69,8 @@ typedef enum gcr_status {
 /* Per-call options (ABI v6; v7: "fast_exp" is gone, "bwd_wave_units" added at the end).  Every field: -1 = the process-wide default (gcr_set_option), >= 0 = this call's value.
  * The reference's entry points are re-entrant and carry no global state (dgr/rasterize_points.cu:37-93); with this
  * record two host threads can render with different options at the same time.  The forward and the backward of one
- * frame must be given the same values (as with the process-wide knobs).  Meanings: see gcr_set_option below. */
+ * frame must be given the same values (as with the process-wide knobs), and so must the gcr_forward_preprocess and
+ * gcr_forward_render calls of one frame.  Meanings: see gcr_set_option below. */
 typedef struct gcr_options {
   int32_t lazy_sort;
   int32_t sort_in_blend;

@@ -307,3 +307,169 @@ def test_gce_library_exports_every_declared_symbol():
     assert b"C must be" in lib.gce_last_error()
     assert lib.gce_forward(None, None, None, None, 8, 3, 2, 2, 1.0, 4, 0, None, 0, 0, None) < 0   # null tensors
     assert lib.gce_backward(None, None, None, None, None, 8, 9, 2, 2, 1.0, 4, 0, None, None, 0, 0, None) < 0
+
+
+# Every process-wide option: (name, default, [(value handed to gcr_set_option, value it keeps)]).  The A/B switches
+# keep what they are given; the per-call gcr_options fields of the same names are read as != 0 (bwd_piece clamped).
+_OPTIONS = [
+    ("timing", 0, [(5, 5), (-3, -3)]),
+    ("force_radix", 0, [(5, 5), (-3, -3)]),
+    ("force_global_cursor", 0, [(5, 5)]),
+    ("split_preprocess", 0, [(5, 5)]),
+    ("sort_in_blend", 0, [(5, 5)]),
+    ("lazy_sort", 1, [(5, 1), (0, 0), (-3, 1)]),
+    ("deterministic_backward", 0, [(5, 1), (-3, 1)]),
+    ("bwd_wave_units", 0, [(5, 1)]),
+    ("rescue_hold", 0, [(5, 1)]),
+    ("gate_polls", 400000, [(0, 1), (-5, 1), (7, 7)]),
+    ("band_sort_min", 6000000, [(-7, -1), (0, 0), (12, 12)]),
+    ("bwd_piece", 160, [(10, 64), (4096, 223), (100, 100)]),
+    ("stream_policy", -1, [(5, 1), (0, 0), (-3, -1)]),
+]
+
+
+@pytest.mark.parametrize("name,default,steps", _OPTIONS, ids=[o[0] for o in _OPTIONS])
+def test_option_defaults_round_trips_and_clamps(name, default, steps):
+    """gcr_set_option returns the previous value and stores the normalised one; gcr_get_option reads it back."""
+    lib = N.lib()
+    assert lib.gcr_get_option(name.encode()) == default
+    prev = default
+    try:
+        for value, kept in steps:
+            assert lib.gcr_set_option(name.encode(), value) == prev
+            assert lib.gcr_get_option(name.encode()) == kept
+            prev = kept
+    finally:
+        assert lib.gcr_set_option(name.encode(), default) == prev
+    assert lib.gcr_get_option(name.encode()) == default
+
+
+def test_unknown_options_and_per_call_normalisation():
+    lib = N.lib()
+    for name in (b"no_such_option", b"", b"k6_debug", b"k7_skip_flush", b"fast_exp"):
+        assert lib.gcr_set_option(name, 1) == -1 and lib.gcr_get_option(name) == -2 ** 31
+    assert lib.gcr_set_option(None, 1) == -1 and lib.gcr_get_option(None) == -2 ** 31
+    # a per-call field >= 0 is read as != 0, whatever the process-wide value
+    assert lib.gcr_grad_record_floats_opt(C.byref(N.Options(deterministic_backward=7))) == 32
+    assert lib.gcr_grad_record_floats_opt(C.byref(N.Options(deterministic_backward=0))) == 16
+    assert lib.gcr_set_option(b"deterministic_backward", 9) == 0
+    try:
+        assert lib.gcr_grad_record_floats() == 32
+        assert lib.gcr_grad_record_floats_opt(C.byref(N.Options(deterministic_backward=0))) == 16
+        assert lib.gcr_grad_record_floats_opt(C.byref(N.Options())) == 32
+    finally:
+        assert lib.gcr_set_option(b"deterministic_backward", 0) == 1
+    # force_radix: the process-wide value is kept raw, a per-call 3 counts as set (no speculative form)
+    buf = (C.c_float * 256)()
+    p = (C.addressof(buf) + 63) // 64 * 64
+    words = (C.c_uint64 * N.TICKET_WORDS)()
+    cam = N.Camera(16, 16, 0.3, 0.3, 1.0, 0, 0, 0, p, p, p, p)
+    g = N.Gaussians(4, 0, p, p, None, p, p, p, None)
+    big = 1 << 30
+    opt = N.Options(force_radix=3)
+    cam.options = C.pointer(opt)
+    rc = lib.gcr_forward_async(C.byref(cam), C.byref(g), p, big, p, big, 100, 0, p, big, p, p, C.addressof(words), 1, None)
+    assert rc == -1 and b"force_radix" in lib.gcr_last_error()
+
+
+def _buffer_case(backward=0):
+    """A frame of 4 Gaussians on 16 x 16 pixels whose buffers are never reached: every call below fails a check."""
+    buf = (C.c_float * 256)()
+    p = (C.addressof(buf) + 63) // 64 * 64
+    cam = N.Camera(16, 16, 0.3, 0.3, 1.0, 0, 0, 0, p, p, p, p)
+    cam.backward = backward
+    g = N.Gaussians(4, 0, p, p, None, p, p, p, None)
+    return buf, p, cam, g
+
+
+def _sizes(R):
+    L = N.get_layout(4, 16, 16, R)
+    return L.geom_total, L.img_total, L.bin_lean_total, L.bin_total
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+def test_forward_async_reports_small_buffers(backward):
+    lib = N.lib()
+    buf, p, cam, g = _buffer_case(backward)
+    cap = 1000
+    geom, img, lean, full = _sizes(cap)
+    assert lean < full
+    need = full if backward else lean
+    words = (C.c_uint64 * N.TICKET_WORDS)()
+
+    def call(gb, bb, ib):
+        return lib.gcr_forward_async(C.byref(cam), C.byref(g), p, gb, p, bb, cap, 0, p, ib, p, p, C.addressof(words), 1, None)
+
+    for args, text in (((geom - 1, need, img), b"geometry buffer too small"), ((geom, need, img - 1), b"image buffer too small"),
+                       ((geom, need - 1, img), b"binning buffer smaller than gcr_binning_bytes(binning_capacity)")):
+        assert call(*args) == -2 and lib.gcr_last_error() == text
+    assert words[0] == 0
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+def test_forward_reports_a_small_binning_buffer(backward):
+    lib = N.lib()
+    buf, p, cam, g = _buffer_case(backward)
+    cap = 1000
+    geom, img, lean, full = _sizes(cap)
+    need = full if backward else lean
+    info = N.FrameInfo(-1, -1)
+    rc = lib.gcr_forward(C.byref(cam), C.byref(g), p, geom, p, need - 1, cap, 0, p, img, p, p, C.byref(info), None)
+    assert rc == -2 and lib.gcr_last_error() == b"binning buffer smaller than gcr_binning_bytes(binning_capacity)"
+    assert (info.num_rendered, info.max_tile_instances) == (0, 0)
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+def test_forward_reports_small_geometry_and_image_buffers_before_any_hip_call(backward):
+    """New behaviour: gcr_forward checks every buffer before it allocates its pinned read-back words, so these come back
+    as -2 on a machine without a device too (they came back as a failed hipHostMalloc there before)."""
+    lib = N.lib()
+    buf, p, cam, g = _buffer_case(backward)
+    cap = 1000
+    geom, img, lean, full = _sizes(cap)
+    need = full if backward else lean
+    info = N.FrameInfo(-1, -1)
+    for gb, ib, text in ((geom - 1, img, b"geometry buffer too small"), (geom, img - 1, b"image buffer too small")):
+        rc = lib.gcr_forward(C.byref(cam), C.byref(g), p, gb, p, need, cap, 0, p, ib, p, p, C.byref(info), None)
+        assert rc == -2 and lib.gcr_last_error() == text
+    # (no capacity guess: no binning buffer is needed)
+    rc = lib.gcr_forward(C.byref(cam), C.byref(g), p, geom - 1, None, 0, 0, 0, p, img, p, p, C.byref(info), None)
+    assert rc == -2 and lib.gcr_last_error() == b"geometry buffer too small"
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+def test_forward_render_reports_small_buffers_lean_or_full_carve(backward):
+    lib = N.lib()
+    buf, p, cam, g = _buffer_case(backward)
+    R = 700
+    geom, img, lean, full = _sizes(R)
+    need = full if backward else lean
+    info = N.FrameInfo(R, 10)
+
+    def call(gb, bb, ib):
+        return lib.gcr_forward_render(C.byref(cam), C.byref(g), p, gb, p, bb, p, ib, C.byref(info), p, None)
+
+    cases = [((geom - 1, need, img), b"geometry buffer too small"), ((geom, need, img - 1), b"image buffer too small"),
+             ((geom, need - 1, img), b"binning buffer too small")]
+    if backward:
+        cases.append(((geom, lean, img), b"binning buffer too small"))   # a frame for a backward needs the full carve
+    for args, text in cases:
+        assert call(*args) == -2 and lib.gcr_last_error() == text
+
+
+def test_backward_reports_small_buffers():
+    lib = N.lib()
+    buf, p, cam, g = _buffer_case(1)
+    g = N.Gaussians(1, 0, p, None, None, p, p, p, None)
+    gr = N.Grads(p, p, p, p, p, p, None, p, p)
+    R = 700
+    L = N.get_layout(1, 16, 16, R)
+    geom, img, lean, full = L.geom_total, L.img_total, L.bin_lean_total, L.bin_total
+
+    def call(gb, bb, ib, binning=p):
+        return lib.gcr_backward(C.byref(cam), C.byref(g), p, p, gb, binning, bb, p, ib, R, p, C.byref(gr), None)
+
+    for args, text in (((geom - 1, full, img), b"geometry buffer too small"), ((geom, full, img - 1), b"image buffer too small"),
+                       ((geom, full - 1, img), b"binning buffer too small"), ((geom, lean, img), b"binning buffer too small")):
+        assert call(*args) == -2 and lib.gcr_last_error() == text
+    assert call(geom, full, img, binning=None) == -2 and lib.gcr_last_error() == b"binning buffer too small"

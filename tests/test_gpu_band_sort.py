@@ -150,3 +150,42 @@ def test_the_default_threshold_sorts_big_frames_only(cuda_device):
     assert N.get_option("band_sort_min") == 6_000_000
     assert N.set_option("band_sort_min", -7) == 6_000_000 and N.get_option("band_sort_min") == -1
     N.set_option("band_sort_min", 6_000_000)
+
+
+@pytest.mark.parametrize("band_sort", [0], indirect=True, ids=["band_sorted"])
+def test_staged_frame_rendered_under_other_options_follows_its_count(oracle_mod, cuda_device, band_sort):
+    """The scatter follows the numbering the tiles were counted in (frame[GCR_FRAME_BANDED]), not the options of the
+    call that renders: gcr_forward_preprocess band-sorts under the default options, gcr_forward_render then runs under
+    a per-call split_preprocess = 1 (whose own count would not band-sort).  The frame stays bit-exact."""
+    import ctypes as C
+
+    from gaussiancity_amd import _native as N, ext
+    P, W, H = 60_000, 512, 288
+    sc, rs = _city(P, 302, W, H, 11)
+    fr = _frame(oracle_mod, rs, sc)
+    (bg, means3D, colors, opacity, scales, rots, scale_modifier, cov, view, proj, tfx, tfy, _, _, sh, degree, campos,
+     prefiltered, debug) = _args(rs, sc, cuda_device)
+    cam, keep_cam = ext._camera(cuda_device, bg, view, proj, campos, tfx, tfy, H, W, scale_modifier, degree, prefiltered,
+                                debug)
+    g, keep_g = ext._gaussians(cuda_device, P, means3D, opacity, sh, colors, scales, rots, cov)
+    lib, stream = N.lib(), ext._stream(cuda_device)
+    byte = dict(dtype=torch.uint8, device=cuda_device)
+    geom = torch.empty((lib.gcr_geometry_bytes(P),), **byte)
+    img = torch.empty((lib.gcr_image_bytes(W, H),), **byte)
+    radii = torch.empty((P,), dtype=torch.int32, device=cuda_device)
+    info = N.FrameInfo()
+    N.check(lib.gcr_forward_preprocess(C.byref(cam), C.byref(g), geom.data_ptr(), geom.numel(), img.data_ptr(), img.numel(),
+                                       radii.data_ptr(), C.byref(info), stream), "gcr_forward_preprocess")
+    assert info.num_rendered == fr.R
+    L = N.get_layout(P, W, H, fr.R)
+    frame_words = geom[L.geom_num_rendered:L.geom_num_rendered + 128].cpu().numpy().view(np.uint64)
+    assert frame_words[9] != 0   # GCR_FRAME_BANDED: counted over the band-sorted survivors
+    binning = torch.empty((lib.gcr_binning_bytes_lean(fr.R, W, H),), **byte)
+    out_color = torch.empty((3, H, W), dtype=torch.float32, device=cuda_device)
+    opt = N.Options(split_preprocess=1)
+    cam.options = C.pointer(opt)
+    N.check(lib.gcr_forward_render(C.byref(cam), C.byref(g), geom.data_ptr(), geom.numel(), binning.data_ptr(),
+                                   binning.numel(), img.data_ptr(), img.numel(), C.byref(info), out_color.data_ptr(), stream),
+            "gcr_forward_render")
+    torch.cuda.synchronize()
+    _check_forward(fr, G.decode(P, W, H, (fr.R, out_color, radii, geom, binning, img)), P, True)
