@@ -1,0 +1,783 @@
+// gcs_sparse.hip -- MI355X (gfx950) kernels + C ABI (include/gcs.h) of the point backbone's sparse operators:
+// submanifold 3-D convolution (spconv SubMConv3d) and segment_csr (torch_scatter).  DESIGN.md section 15.
+//
+// Rulebook (built once per indice_key, reused by every convolution of a stage):
+//   * open-addressing hash of packed (b, d0, d1, d2) keys, 64-bit atomicCAS insert, atomicMin picks the
+//     lowest row of a voxel as its representative;
+//   * neighbour map nbr [N][K] (-1 = absent) and rep [N] (the representative of the row's own voxel);
+//   * per tap, the rows that have that neighbour, in row order (pair lists for dW; deterministic scan);
+//   * when voxels hold several rows: per representative, its rows in row order (the fold of dy for dX).
+// Convolution: output-stationary gather-GEMM on the VALU.  A workgroup owns TM rows x TN output columns; per tap
+// it loads the tile's neighbour rows, skips the tap when none is present (block-uniform), and runs an LDS-tiled
+// fp32 FMA GEMM of the gathered rows against W[:, k, :].  dX is the same kernel with mirrored taps and W read
+// transposed, on dy folded onto the representatives.  dW: per tap, a GEMM over the tap's pair list, cut into a
+// fixed number of slices that are summed in slice order.  Every sum has a fixed order: no float atomics.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <climits>
+#include <cstring>
+#include <string>
+
+#include "../../include/gcs.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+#define HIP_TRY(expr, where)                                                                     \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return fail(GCS_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+constexpr uint64_t kEmpty = ~0ull;
+constexpr int kScanThreads = 256;
+constexpr int kScanPerThread = 16;
+constexpr int kScanChunk = kScanThreads * kScanPerThread;  // rows per block of the deterministic scans
+constexpr int kMaxK = 1024;                                // taps: up to 9 x 9 x 9 plus headroom
+
+size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
+
+uint64_t table_capacity(int64_t n) {
+  uint64_t cap = 64;
+  while (cap < 2 * (uint64_t)n) cap <<= 1;
+  return cap;
+}
+
+int64_t scan_blocks(int64_t n) { return (n + kScanChunk - 1) / kScanChunk; }
+
+// ---- rulebook layout (device buffer of gcs_subm_rulebook_bytes) ------------------------------------------------
+struct Rulebook {
+  int32_t* hdr;     // [4 + K]: 0 invalid rows, 1 duplicate flag, 4 + k pairs of tap k
+  int32_t* nbr;     // [N][K]
+  int32_t* rep;     // [N]
+  int32_t* prow;    // [K][N] rows that have tap k, ascending
+  int32_t* gstart;  // [N] first entry of a representative's group in glist
+  int32_t* gcnt;    // [N] rows of a representative's voxel (0 for the other rows)
+  int32_t* glist;   // [N] rows grouped by representative, ascending within a group
+  size_t bytes;
+};
+Rulebook carve_rulebook(void* base, int64_t n, int32_t k) {
+  Rulebook r;
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t b) {
+    char* q = p ? p + off : nullptr;
+    off += align_up(b);
+    return (int32_t*)q;
+  };
+  r.hdr = take(4 * (4 + (size_t)k));
+  r.nbr = take(4 * (size_t)n * k);
+  r.rep = take(4 * (size_t)n);
+  r.prow = take(4 * (size_t)n * k);
+  r.gstart = take(4 * (size_t)n);
+  r.gcnt = take(4 * (size_t)n);
+  r.glist = take(4 * (size_t)n);
+  r.bytes = off;
+  return r;
+}
+struct Scratch {
+  uint64_t* keys;   // [cap]
+  int32_t* vals;    // [cap] representative row of the slot
+  int32_t* gfill;   // [N]
+  int32_t* bsum;    // [K][blocks] scan block totals
+  size_t bytes;
+};
+Scratch carve_scratch(void* base, int64_t n) {
+  Scratch s;
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t b) {
+    char* q = p ? p + off : nullptr;
+    off += align_up(b);
+    return q;
+  };
+  const uint64_t cap = table_capacity(n);
+  s.keys = (uint64_t*)take(8 * cap);
+  s.vals = (int32_t*)take(4 * cap);
+  s.gfill = (int32_t*)take(4 * (size_t)n);
+  s.bsum = (int32_t*)take(4 * (size_t)kMaxK * scan_blocks(n));
+  s.bytes = off;
+  return s;
+}
+
+// ---- hash table --------------------------------------------------------------------------------------------------
+struct Geom {
+  int32_t batch, s0, s1, s2;
+  int32_t k0, k1, k2, dl0, dl1, dl2;
+};
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ bool row_valid(const int32_t* idx, int64_t i, const Geom& g) {
+  const int b = idx[4 * i], a = idx[4 * i + 1], c = idx[4 * i + 2], d = idx[4 * i + 3];
+  return b >= 0 && b < g.batch && a >= 0 && a < g.s0 && c >= 0 && c < g.s1 && d >= 0 && d < g.s2;
+}
+__device__ __forceinline__ uint64_t pack(int b, int a, int c, int d, const Geom& g) {
+  return (((uint64_t)b * (uint64_t)g.s0 + (uint64_t)a) * (uint64_t)g.s1 + (uint64_t)c) * (uint64_t)g.s2 + (uint64_t)d;
+}
+__device__ __forceinline__ int32_t lookup(const uint64_t* keys, const int32_t* vals, uint64_t mask, uint64_t key) {
+  uint64_t slot = mix64(key) & mask;
+  for (uint64_t probe = 0; probe <= mask; probe++) {
+    const uint64_t k = keys[slot];
+    if (k == key) return vals[slot];
+    if (k == kEmpty) return -1;
+    slot = (slot + 1) & mask;
+  }
+  return -1;
+}
+
+__global__ void k_insert(const int32_t* __restrict__ idx, int64_t n, Geom g, uint64_t* keys, int32_t* vals,
+                         uint64_t mask, int32_t* hdr) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!row_valid(idx, i, g)) {
+    atomicAdd(&hdr[0], 1);
+    return;
+  }
+  const uint64_t key = pack(idx[4 * i], idx[4 * i + 1], idx[4 * i + 2], idx[4 * i + 3], g);
+  uint64_t slot = mix64(key) & mask;
+  for (uint64_t probe = 0; probe <= mask; probe++) {
+    const unsigned long long prev =
+        atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)kEmpty, (unsigned long long)key);
+    if (prev == kEmpty || prev == key) {
+      atomicMin(&vals[slot], (int32_t)i);
+      return;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+// one thread per (row, tap); the centre tap also records the row's representative and the duplicate flag
+__global__ void k_neighbours(const int32_t* __restrict__ idx, int64_t n, Geom g, const uint64_t* __restrict__ keys,
+                             const int32_t* __restrict__ vals, uint64_t mask, int32_t* __restrict__ nbr,
+                             int32_t* __restrict__ rep, int32_t* hdr) {
+  const int K = g.k0 * g.k1 * g.k2;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * K) return;
+  const int64_t i = e / K;
+  const int k = (int)(e - i * K);
+  int32_t j = -1;
+  if (row_valid(idx, i, g)) {
+    const int ta = k / (g.k1 * g.k2), tb = (k / g.k2) % g.k1, tc = k % g.k2;
+    const int a = idx[4 * i + 1] + (ta - g.k0 / 2) * g.dl0;
+    const int b = idx[4 * i + 2] + (tb - g.k1 / 2) * g.dl1;
+    const int c = idx[4 * i + 3] + (tc - g.k2 / 2) * g.dl2;
+    if (a >= 0 && a < g.s0 && b >= 0 && b < g.s1 && c >= 0 && c < g.s2)
+      j = lookup(keys, vals, mask, pack(idx[4 * i], a, b, c, g));
+  }
+  nbr[e] = j;
+  if (k == K / 2) {
+    rep[i] = j;
+    if (j >= 0 && j != (int32_t)i) atomicOr(&hdr[1], 1);
+  }
+}
+
+// ---- deterministic block scans (pair lists per tap, duplicate groups) --------------------------------------------
+// MODE 0: value of row i in column k (= blockIdx.y) is nbr[i][k] >= 0; pass 3 writes prow[k][offset] = i.
+// MODE 1: value of row i is gcnt[i] (only when hdr[1], the duplicate flag, is set); pass 3 writes gstart[i].
+template <int MODE>
+__device__ __forceinline__ int scan_value(const int32_t* src, int64_t i, int k, int K) {
+  return MODE == 0 ? (src[i * K + k] >= 0 ? 1 : 0) : src[i];
+}
+
+__device__ int block_exclusive_scan(int v, int* sh, int* total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < kScanThreads; d <<= 1) {
+    const int add = t >= d ? sh[t - d] : 0;
+    __syncthreads();
+    sh[t] += add;
+    __syncthreads();
+  }
+  const int incl = sh[t];
+  *total = sh[kScanThreads - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kScanThreads) void k_scan_count(const int32_t* __restrict__ src, int64_t n, int K,
+                                                             const int32_t* hdr, int32_t* __restrict__ bsum) {
+  if (MODE == 1 && hdr[1] == 0) return;
+  __shared__ int sh[kScanThreads];
+  const int k = blockIdx.y;
+  const int64_t r0 = (int64_t)blockIdx.x * kScanChunk + (int64_t)threadIdx.x * kScanPerThread;
+  int v = 0;
+  for (int q = 0; q < kScanPerThread; q++)
+    if (r0 + q < n) v += scan_value<MODE>(src, r0 + q, k, K);
+  int total;
+  block_exclusive_scan(v, sh, &total);
+  if (threadIdx.x == 0) bsum[(int64_t)k * gridDim.x + blockIdx.x] = total;
+}
+
+// one thread per column: block totals -> exclusive block offsets (in place), column total into hdr[4 + k]
+template <int MODE>
+__global__ void k_scan_blocks(int32_t* bsum, int64_t nb, int K, int32_t* hdr) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K || (MODE == 1 && hdr[1] == 0)) return;
+  int run = 0;
+  for (int64_t b = 0; b < nb; b++) {
+    const int v = bsum[(int64_t)k * nb + b];
+    bsum[(int64_t)k * nb + b] = run;
+    run += v;
+  }
+  if (MODE == 0) hdr[4 + k] = run;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kScanThreads) void k_scan_write(const int32_t* __restrict__ src, int64_t n, int K,
+                                                             const int32_t* hdr, const int32_t* __restrict__ bsum,
+                                                             int32_t* __restrict__ dst) {
+  if (MODE == 1 && hdr[1] == 0) return;
+  __shared__ int sh[kScanThreads];
+  const int k = blockIdx.y;
+  const int64_t r0 = (int64_t)blockIdx.x * kScanChunk + (int64_t)threadIdx.x * kScanPerThread;
+  int v = 0;
+  for (int q = 0; q < kScanPerThread; q++)
+    if (r0 + q < n) v += scan_value<MODE>(src, r0 + q, k, K);
+  int total;
+  int off = block_exclusive_scan(v, sh, &total) + bsum[(int64_t)k * gridDim.x + blockIdx.x];
+  for (int q = 0; q < kScanPerThread; q++) {
+    const int64_t i = r0 + q;
+    if (i >= n) break;
+    const int x = scan_value<MODE>(src, i, k, K);
+    if (MODE == 0) {
+      if (x) dst[(int64_t)k * n + off] = (int32_t)i;
+    } else {
+      dst[i] = off;
+    }
+    off += x;
+  }
+}
+
+__global__ void k_group_count(const int32_t* __restrict__ rep, int64_t n, const int32_t* hdr, int32_t* gcnt) {
+  if (hdr[1] == 0) return;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && rep[i] >= 0) atomicAdd(&gcnt[rep[i]], 1);
+}
+__global__ void k_group_fill(const int32_t* __restrict__ rep, int64_t n, const int32_t* hdr,
+                             const int32_t* __restrict__ gstart, int32_t* gfill, int32_t* glist) {
+  if (hdr[1] == 0) return;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || rep[i] < 0) return;
+  const int r = rep[i];
+  glist[gstart[r] + atomicAdd(&gfill[r], 1)] = (int32_t)i;
+}
+// groups are small (rows of one voxel): insertion sort puts each in row order, the representative first
+__global__ void k_group_sort(int64_t n, const int32_t* hdr, const int32_t* __restrict__ gstart,
+                             const int32_t* __restrict__ gcnt, int32_t* glist) {
+  if (hdr[1] == 0) return;
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n || gcnt[r] < 2) return;
+  int32_t* g = glist + gstart[r];
+  for (int a = 1; a < gcnt[r]; a++) {
+    const int32_t v = g[a];
+    int b = a - 1;
+    for (; b >= 0 && g[b] > v; b--) g[b + 1] = g[b];
+    g[b + 1] = v;
+  }
+}
+
+// ---- convolution ---------------------------------------------------------------------------------------------
+// y[row][o] = bias[o] + sum_k sum_c W(k, o, c) * x[nbr[row][tap(k)]][c],  W(k, o, c) = w[k*sk + o*sn + c*sc],
+// tap(k) = k, or K-1-k (mirror, for dX).  rowmask: rows with rowmask[row] != row are written 0 (dX of duplicates).
+// 256 threads; a thread owns MR rows x MC columns; TRANS picks the coalesced order of the weight tile load.
+constexpr int KC = 16;
+template <int TM, int TN, int MR, int MC, bool TRANS>
+__global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, int cin, const float* __restrict__ w,
+                                                   int64_t sk, int64_t sn, int64_t sc, const float* __restrict__ bias,
+                                                   const int32_t* __restrict__ nbr, int K, int mirror,
+                                                   const int32_t* __restrict__ rowmask, float* __restrict__ y, int nout,
+                                                   int64_t n) {
+  constexpr int TCX = TN / MC, TCY = 256 / TCX;
+  static_assert(TCY * MR == TM, "tile shape");
+  __shared__ float As[KC][TM];
+  __shared__ float Bs[KC][TN];
+  __shared__ int32_t sN[TM];
+  const int tid = threadIdx.x, tx = tid % TCX, ty = tid / TCX;
+  const int64_t row0 = (int64_t)blockIdx.x * TM;
+  const int n0 = blockIdx.y * TN;
+  float acc[MR][MC];
+#pragma unroll
+  for (int i = 0; i < MR; i++)
+#pragma unroll
+    for (int j = 0; j < MC; j++) acc[i][j] = 0.0f;
+
+  for (int k = 0; k < K; k++) {
+    const int kn = mirror ? K - 1 - k : k;
+    int any = 0;
+    for (int r = tid; r < TM; r += 256) {
+      const int64_t row = row0 + r;
+      const int32_t j = row < n ? nbr[row * K + kn] : -1;
+      sN[r] = j;
+      any |= j >= 0;
+    }
+    if (!__syncthreads_or(any)) continue;
+    for (int c0 = 0; c0 < cin; c0 += KC) {
+      for (int e = tid; e < TM * KC; e += 256) {
+        const int r = e / KC, cc = e % KC, c = c0 + cc;
+        const int32_t j = sN[r];
+        As[cc][r] = (j >= 0 && c < cin) ? x[(int64_t)j * cin + c] : 0.0f;
+      }
+      for (int e = tid; e < TN * KC; e += 256) {
+        const int cc = TRANS ? e / TN : e % KC, nn = TRANS ? e % TN : e / KC;
+        const int c = c0 + cc, o = n0 + nn;
+        Bs[cc][nn] = (c < cin && o < nout) ? w[(int64_t)k * sk + (int64_t)o * sn + (int64_t)c * sc] : 0.0f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int cc = 0; cc < KC; cc++) {
+        float a[MR], b[MC];
+#pragma unroll
+        for (int i = 0; i < MR; i++) a[i] = As[cc][ty * MR + i];
+#pragma unroll
+        for (int j = 0; j < MC; j++) b[j] = Bs[cc][tx * MC + j];
+#pragma unroll
+        for (int i = 0; i < MR; i++)
+#pragma unroll
+          for (int j = 0; j < MC; j++) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+      }
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MR; i++) {
+    const int64_t row = row0 + ty * MR + i;
+    if (row >= n) continue;
+    const bool zero = rowmask && rowmask[row] != (int32_t)row;
+#pragma unroll
+    for (int j = 0; j < MC; j++) {
+      const int o = n0 + tx * MC + j;
+      if (o < nout) y[row * nout + o] = zero ? 0.0f : (bias ? acc[i][j] + bias[o] : acc[i][j]);
+    }
+  }
+}
+
+// dw partial of slice s: part[s][o][k][c] = sum over the slice's pairs p of tap k: dy[i_p][o] * x[nbr[i_p][k]][c]
+constexpr int KR = 16;
+template <int TO, int TC, int MR, int MC>
+__global__ __launch_bounds__(256) void k_subm_dw(const float* __restrict__ dy, int cout, const float* __restrict__ x,
+                                                 int cin, const int32_t* __restrict__ nbr, int K,
+                                                 const int32_t* __restrict__ prow, const int32_t* __restrict__ hdr,
+                                                 int64_t n, int nslice, float* __restrict__ part) {
+  constexpr int TCX = TC / MC, TCY = 256 / TCX;
+  static_assert(TCY * MR == TO, "tile shape");
+  __shared__ float Ds[KR][TO];
+  __shared__ float Xs[KR][TC];
+  __shared__ int32_t sI[KR], sJ[KR];
+  const int tid = threadIdx.x, tx = tid % TCX, ty = tid / TCX;
+  const int tiles_c = (cin + TC - 1) / TC;
+  const int o0 = (blockIdx.x / tiles_c) * TO, c0 = (blockIdx.x % tiles_c) * TC;
+  const int k = blockIdx.y, s = blockIdx.z;
+  const int64_t cnt = hdr[4 + k];
+  const int64_t per = (cnt + nslice - 1) / nslice;
+  const int64_t p0 = s * per, p1 = p0 + per < cnt ? p0 + per : cnt;
+  float acc[MR][MC];
+#pragma unroll
+  for (int i = 0; i < MR; i++)
+#pragma unroll
+    for (int j = 0; j < MC; j++) acc[i][j] = 0.0f;
+  for (int64_t p = p0; p < p1; p += KR) {
+    if (tid < KR) {
+      const int64_t q = p + tid;
+      const int32_t i = q < p1 ? prow[(int64_t)k * n + q] : -1;
+      sI[tid] = i;
+      sJ[tid] = i >= 0 ? nbr[(int64_t)i * K + k] : -1;
+    }
+    __syncthreads();
+    for (int e = tid; e < KR * TO; e += 256) {
+      const int r = e / TO, o = o0 + e % TO;
+      const int32_t i = sI[r];
+      Ds[r][e % TO] = (i >= 0 && o < cout) ? dy[(int64_t)i * cout + o] : 0.0f;
+    }
+    for (int e = tid; e < KR * TC; e += 256) {
+      const int r = e / TC, c = c0 + e % TC;
+      const int32_t j = sJ[r];
+      Xs[r][e % TC] = (j >= 0 && c < cin) ? x[(int64_t)j * cin + c] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < KR; r++) {
+      float a[MR], b[MC];
+#pragma unroll
+      for (int i = 0; i < MR; i++) a[i] = Ds[r][ty * MR + i];
+#pragma unroll
+      for (int j = 0; j < MC; j++) b[j] = Xs[r][tx * MC + j];
+#pragma unroll
+      for (int i = 0; i < MR; i++)
+#pragma unroll
+        for (int j = 0; j < MC; j++) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+  float* out = part + (int64_t)s * cout * K * cin;
+#pragma unroll
+  for (int i = 0; i < MR; i++) {
+    const int o = o0 + ty * MR + i;
+    if (o >= cout) continue;
+#pragma unroll
+    for (int j = 0; j < MC; j++) {
+      const int c = c0 + tx * MC + j;
+      if (c < cin) out[((int64_t)o * K + k) * cin + c] = acc[i][j];
+    }
+  }
+}
+
+// out[e] = sum_s part[s][e], s ascending
+__global__ void k_sum_slices(const float* __restrict__ part, int nslice, int64_t len, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= len) return;
+  float v = part[e];
+  for (int s = 1; s < nslice; s++) v += part[(int64_t)s * len + e];
+  out[e] = v;
+}
+
+// column sums of dy over a slice of rows: 64 columns x 4 row phases per block, phases combined in order
+__global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ dy, int64_t n, int cout, int nslice,
+                                                float* __restrict__ part) {
+  __shared__ float red[4][64];
+  const int col = blockIdx.x * 64 + threadIdx.x % 64, ph = threadIdx.x / 64, s = blockIdx.y;
+  const int64_t per = (n + nslice - 1) / nslice, r0 = s * per, r1 = r0 + per < n ? r0 + per : n;
+  float v = 0.0f;
+  if (col < cout)
+    for (int64_t r = r0 + ph; r < r1; r += 4) v += dy[r * cout + col];
+  red[ph][threadIdx.x % 64] = v;
+  __syncthreads();
+  if (ph == 0 && col < cout) part[(int64_t)s * cout + col] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// dyf[r] = sum of dy over the rows of representative r's voxel, row order; other rows are never read
+__global__ void k_fold(const float* __restrict__ dy, int64_t n, int cout, const int32_t* __restrict__ rep,
+                       const int32_t* __restrict__ gstart, const int32_t* __restrict__ gcnt,
+                       const int32_t* __restrict__ glist, float* __restrict__ dyf) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * cout) return;
+  const int64_t r = e / cout;
+  const int o = (int)(e - r * cout);
+  if (rep[r] != (int32_t)r) return;
+  const int cnt = gcnt[r];
+  if (cnt < 2) {  // a voxel of one row (or groups never built: the rulebook had no duplicates)
+    dyf[e] = dy[e];
+    return;
+  }
+  const int32_t* g = glist + gstart[r];
+  float v = dy[(int64_t)g[0] * cout + o];
+  for (int q = 1; q < cnt; q++) v += dy[(int64_t)g[q] * cout + o];
+  dyf[e] = v;
+}
+
+// ---- segment_csr -------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void seg_bounds(const int64_t* indptr, int64_t s, int64_t m, int64_t* lo, int64_t* hi) {
+  int64_t a = indptr[s], b = indptr[s + 1];
+  a = a < 0 ? 0 : (a > m ? m : a);
+  b = b < a ? a : (b > m ? m : b);
+  *lo = a;
+  *hi = b;
+}
+
+// one wave per (segment, block of 64 columns), rows summed in index order
+__global__ __launch_bounds__(64) void k_seg_fwd(const float* __restrict__ src, int64_t m, int64_t f,
+                                                const int64_t* __restrict__ indptr, int64_t nfb, int reduce,
+                                                float* __restrict__ out, int64_t* __restrict__ arg) {
+  const int64_t s = blockIdx.x / nfb, col = (blockIdx.x % nfb) * 64 + threadIdx.x;
+  if (col >= f) return;
+  int64_t lo, hi;
+  seg_bounds(indptr, s, m, &lo, &hi);
+  float v = 0.0f;
+  int64_t best = -1;
+  if (reduce == GCS_SUM || reduce == GCS_MEAN) {
+    for (int64_t r = lo; r < hi; r++) v += src[r * f + col];
+    if (reduce == GCS_MEAN && hi > lo) v = v / (float)(hi - lo);
+  } else if (hi > lo) {
+    v = src[lo * f + col];
+    best = lo;
+    for (int64_t r = lo + 1; r < hi; r++) {
+      const float u = src[r * f + col];
+      if (reduce == GCS_MAX ? u > v : u < v) {
+        v = u;
+        best = r;
+      }
+    }
+  }
+  out[s * f + col] = v;
+  if (arg) arg[s * f + col] = best;
+}
+
+__global__ __launch_bounds__(64) void k_seg_bwd(const float* __restrict__ dout, int64_t m, int64_t f,
+                                                const int64_t* __restrict__ indptr, int64_t nfb, int reduce,
+                                                const int64_t* __restrict__ arg, float* __restrict__ dsrc) {
+  const int64_t s = blockIdx.x / nfb, col = (blockIdx.x % nfb) * 64 + threadIdx.x;
+  if (col >= f) return;
+  int64_t lo, hi;
+  seg_bounds(indptr, s, m, &lo, &hi);
+  float g = dout[s * f + col];
+  if (reduce == GCS_MEAN && hi > lo) g = g / (float)(hi - lo);
+  const int64_t a = (reduce == GCS_MIN || reduce == GCS_MAX) ? arg[s * f + col] : -1;
+  for (int64_t r = lo; r < hi; r++)
+    dsrc[r * f + col] = (reduce == GCS_SUM || reduce == GCS_MEAN) ? g : (r == a ? g : 0.0f);
+}
+
+// ---- host helpers ----------------------------------------------------------------------------------------------
+int check_conv_dims(const char* who, int64_t n, int32_t K, int32_t cin, int32_t cout) {
+  if (n < 0 || n > (int64_t)INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": n out of range");
+  if (K < 1 || K > kMaxK || n * (int64_t)K > (int64_t)INT32_MAX)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": kernel volume out of range");
+  if (cin < 1 || cout < 1 || cin > 65536 || cout > 65536)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": channel count out of range");
+  return 0;
+}
+
+// slices of the dW reduction: enough workgroups to fill the GPU, a function of the shape only
+int dw_slices(int64_t n, int32_t cin, int32_t cout, int32_t K) {
+  const int t = (cin >= 64 && cout >= 64) ? 64 : 32;
+  const int64_t wgs = (int64_t)((cout + t - 1) / t) * ((cin + t - 1) / t) * K;
+  int64_t s = (2048 + wgs - 1) / wgs;
+  const int64_t by_rows = n / 256 > 1 ? n / 256 : 1;  // at least ~256 rows per slice
+  s = s < by_rows ? s : by_rows;
+  return (int)(s < 1 ? 1 : (s > 32 ? 32 : s));
+}
+int colsum_slices(int64_t n) {
+  const int64_t s = n / 2048;
+  return (int)(s < 1 ? 1 : (s > 64 ? 64 : s));
+}
+
+struct BwdWs {
+  float* dyf;    // [N][Cout] when dups
+  float* dwp;    // [S][Cout][K][Cin] when S > 1
+  float* dbp;    // [Sb][Cout]
+  size_t bytes;
+};
+BwdWs carve_bwd(void* base, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups) {
+  BwdWs w;
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t b) {
+    char* q = (p && b) ? p + off : nullptr;
+    off += align_up(b);
+    return (float*)q;
+  };
+  const int S = dw_slices(n, cin, cout, K);
+  w.dyf = take(dups ? 4 * (size_t)n * cout : 0);
+  w.dwp = take(S > 1 ? 4 * (size_t)S * cout * K * cin : 0);
+  w.dbp = take(4 * (size_t)colsum_slices(n) * cout);
+  w.bytes = off;
+  return w;
+}
+
+template <bool TRANS>
+void launch_gemm(const float* x, int cin, const float* w, int64_t sk, int64_t sn, int64_t sc, const float* bias,
+                 const int32_t* nbr, int K, int mirror, const int32_t* rowmask, float* y, int nout, int64_t n,
+                 hipStream_t st) {
+  const int64_t wide = ((n + 63) / 64) * ((nout + 63) / 64), tall = (n + 127) / 128;
+  if (nout > 32 && wide >= 256) {
+    dim3 grid((unsigned)((n + 63) / 64), (unsigned)((nout + 63) / 64));
+    k_subm_gemm<64, 64, 4, 4, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
+  } else if (nout > 16 && nout <= 32 && tall >= 256) {
+    dim3 grid((unsigned)tall, 1);
+    k_subm_gemm<128, 32, 4, 4, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
+  } else {
+    dim3 grid((unsigned)((n + 31) / 32), (unsigned)((nout + 31) / 32));
+    k_subm_gemm<32, 32, 2, 2, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
+  }
+}
+
+unsigned blocks_for(int64_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
+
+}  // namespace
+
+extern "C" {
+
+int gcs_abi_version(void) { return GCS_ABI_VERSION; }
+const char* gcs_last_error(void) { return g_err.c_str(); }
+
+size_t gcs_subm_rulebook_bytes(int64_t n, int32_t kvol) {
+  if (check_conv_dims("gcs_subm_rulebook_bytes", n, kvol, 1, 1)) return 0;
+  return carve_rulebook(nullptr, n, kvol).bytes;
+}
+size_t gcs_subm_rulebook_scratch_bytes(int64_t n) {
+  if (check_conv_dims("gcs_subm_rulebook_scratch_bytes", n, 1, 1, 1)) return 0;
+  return carve_scratch(nullptr, n).bytes;
+}
+size_t gcs_subm_backward_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups) {
+  if (check_conv_dims("gcs_subm_backward_workspace_bytes", n, kvol, cin, cout)) return 0;
+  return carve_bwd(nullptr, n, cin, cout, kvol, dups).bytes;
+}
+
+int gcs_subm_rulebook(const int32_t* indices, int64_t n, int32_t batch_size, const int32_t* spatial_shape,
+                      const int32_t* ksize, const int32_t* dilation, void* rulebook, size_t rulebook_bytes,
+                      void* scratch, size_t scratch_bytes, int32_t* host_info, void* hip_stream) {
+  if (!spatial_shape || !ksize || !dilation) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: null shape argument");
+  Geom g{batch_size, spatial_shape[0], spatial_shape[1], spatial_shape[2], ksize[0], ksize[1], ksize[2],
+         dilation[0], dilation[1], dilation[2]};
+  for (int d = 0; d < 3; d++) {
+    if (ksize[d] < 1 || ksize[d] % 2 == 0)
+      return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: kernel sizes must be odd and positive");
+    if (dilation[d] < 1) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: dilations must be positive");
+    if (spatial_shape[d] < 1) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: spatial_shape must be positive");
+  }
+  if (batch_size < 1) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: batch_size must be positive");
+  const int32_t K = ksize[0] * ksize[1] * ksize[2];
+  if (int rc = check_conv_dims("gcs_subm_rulebook", n, K, 1, 1)) return rc;
+  // every packed key must stay below the empty marker: batch_size * prod(spatial_shape) <= 2^63
+  unsigned __int128 vol = (unsigned __int128)(uint32_t)batch_size * (uint32_t)g.s0 * (uint32_t)g.s1 * (uint32_t)g.s2;
+  if (vol > ((unsigned __int128)1 << 63))
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: batch_size * spatial_shape does not fit the 64-bit key");
+  const Rulebook rb = carve_rulebook(rulebook, n, K);
+  const Scratch sc = carve_scratch(scratch, n);
+  if (!rulebook || rulebook_bytes < rb.bytes)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: rulebook buffer missing or smaller than gcs_subm_rulebook_bytes");
+  if (!scratch || scratch_bytes < sc.bytes)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: scratch buffer missing or smaller than gcs_subm_rulebook_scratch_bytes");
+  if (n > 0 && !indices) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_rulebook: null indices");
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipMemsetAsync(rb.hdr, 0, 4 * (4 + (size_t)K), st), "rulebook header clear");
+  if (n > 0) {
+    const uint64_t cap = table_capacity(n), mask = cap - 1;
+    const int64_t nb = scan_blocks(n);
+    HIP_TRY(hipMemsetAsync(sc.keys, 0xFF, 8 * cap, st), "hash key clear");
+    HIP_TRY(hipMemsetAsync(sc.vals, 0x7F, 4 * cap, st), "hash value clear");
+    HIP_TRY(hipMemsetAsync(rb.gcnt, 0, 4 * (size_t)n, st), "group count clear");
+    HIP_TRY(hipMemsetAsync(sc.gfill, 0, 4 * (size_t)n, st), "group fill clear");
+    k_insert<<<blocks_for(n, 256), 256, 0, st>>>(indices, n, g, sc.keys, sc.vals, mask, rb.hdr);
+    k_neighbours<<<blocks_for(n * K, 256), 256, 0, st>>>(indices, n, g, sc.keys, sc.vals, mask, rb.nbr, rb.rep, rb.hdr);
+    const dim3 gp((unsigned)nb, (unsigned)K);
+    k_scan_count<0><<<gp, kScanThreads, 0, st>>>(rb.nbr, n, K, rb.hdr, sc.bsum);
+    k_scan_blocks<0><<<blocks_for(K, 64), 64, 0, st>>>(sc.bsum, nb, K, rb.hdr);
+    k_scan_write<0><<<gp, kScanThreads, 0, st>>>(rb.nbr, n, K, rb.hdr, sc.bsum, rb.prow);
+    // duplicate groups: every kernel below returns at once when the centre taps found no duplicate
+    k_group_count<<<blocks_for(n, 256), 256, 0, st>>>(rb.rep, n, rb.hdr, rb.gcnt);
+    const dim3 g1((unsigned)nb, 1);
+    k_scan_count<1><<<g1, kScanThreads, 0, st>>>(rb.gcnt, n, 1, rb.hdr, sc.bsum);
+    k_scan_blocks<1><<<1, 64, 0, st>>>(sc.bsum, nb, 1, rb.hdr);
+    k_scan_write<1><<<g1, kScanThreads, 0, st>>>(rb.gcnt, n, 1, rb.hdr, sc.bsum, rb.gstart);
+    k_group_fill<<<blocks_for(n, 256), 256, 0, st>>>(rb.rep, n, rb.hdr, rb.gstart, sc.gfill, rb.glist);
+    k_group_sort<<<blocks_for(n, 256), 256, 0, st>>>(n, rb.hdr, rb.gstart, rb.gcnt, rb.glist);
+    HIP_TRY(hipGetLastError(), "rulebook launch");
+  }
+  if (host_info) {
+    int32_t h[4 + kMaxK];
+    HIP_TRY(hipMemcpyAsync(h, rb.hdr, 4 * (4 + (size_t)K), hipMemcpyDeviceToHost, st), "rulebook header read-back");
+    HIP_TRY(hipStreamSynchronize(st), "rulebook wait");
+    host_info[0] = h[0];
+    host_info[1] = h[1];
+    for (int k = 0; k < K; k++) host_info[GCS_HOST_INFO_HEADER + k] = h[4 + k];
+  }
+  return 0;
+}
+
+int gcs_subm_forward(const void* rulebook, int64_t n, int32_t kvol, const float* features, int32_t cin,
+                     const float* weight, const float* bias, int32_t cout, float* out, void* hip_stream) {
+  if (int rc = check_conv_dims("gcs_subm_forward", n, kvol, cin, cout)) return rc;
+  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_forward: null rulebook or weight");
+  if (n == 0) return 0;
+  if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_forward: null features or output");
+  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  hipStream_t st = (hipStream_t)hip_stream;
+  launch_gemm<false>(features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0, nullptr, out, cout, n, st);
+  HIP_TRY(hipGetLastError(), "forward launch");
+  return 0;
+}
+
+int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const float* features,
+                      int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx, float* dw,
+                      float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rc = check_conv_dims("gcs_subm_backward", n, kvol, cin, cout)) return rc;
+  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: null rulebook or weight");
+  const BwdWs ws = carve_bwd(workspace, n, cin, cout, kvol, dups);
+  if (!workspace || workspace_bytes < ws.bytes)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: workspace missing or smaller than gcs_subm_backward_workspace_bytes");
+  if (n > 0 && (!dout || ((dx || dw) && !features)))
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: null features or output gradient");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  if (n == 0) {
+    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 4 * (size_t)cout * kvol * cin, st), "dw clear");
+    if (db) HIP_TRY(hipMemsetAsync(db, 0, 4 * (size_t)cout, st), "db clear");
+    return 0;
+  }
+  if (dx) {
+    const float* g = dout;
+    if (dups) {
+      k_fold<<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
+      g = ws.dyf;
+    }
+    // dX[j][c] = sum_k sum_o W[o][k][c] * g[nbr[j][K-1-k]][o]: reduction over o (stride K*Cin), output c (stride 1)
+    launch_gemm<true>(g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1, dups ? rb.rep : nullptr,
+                      dx, cin, n, st);
+  }
+  if (dw) {
+    const int S = dw_slices(n, cin, cout, kvol);
+    float* dst = S > 1 ? ws.dwp : dw;
+    if (cin >= 64 && cout >= 64) {
+      dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)kvol, (unsigned)S);
+      k_subm_dw<64, 64, 4, 4><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
+    } else {
+      dim3 grid((unsigned)(((cout + 31) / 32) * ((cin + 31) / 32)), (unsigned)kvol, (unsigned)S);
+      k_subm_dw<32, 32, 2, 2><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
+    }
+    if (S > 1) {
+      const int64_t len = (int64_t)cout * kvol * cin;
+      k_sum_slices<<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
+    }
+  }
+  if (db) {
+    const int S = colsum_slices(n);
+    k_colsum<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
+    k_sum_slices<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
+  }
+  HIP_TRY(hipGetLastError(), "backward launch");
+  return 0;
+}
+
+static int check_segment(const char* who, const void* a, const void* b, const int64_t* indptr, int64_t m, int64_t f,
+                         int64_t s, int32_t reduce, const int64_t* arg, bool arg_read) {
+  if (m < 0 || f < 1 || s < 0 || f > (int64_t)INT32_MAX)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": sizes out of range");
+  if (reduce < GCS_SUM || reduce > GCS_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown reduce");
+  const bool needs_arg = reduce == GCS_MIN || reduce == GCS_MAX;
+  if (s > 0 && (!b || !indptr)) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (m > 0 && !a) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (s > 0 && needs_arg && !arg && arg_read)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": min and max need the arg buffer");
+  const int64_t nfb = (f + 63) / 64;
+  if (s * nfb > (int64_t)INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many segments");
+  return 0;
+}
+
+int gcs_segment_csr_forward(const float* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s, int32_t reduce,
+                            float* out, int64_t* arg, void* hip_stream) {
+  if (int rc = check_segment("gcs_segment_csr_forward", src, out, indptr, m, f, s, reduce, arg, true)) return rc;
+  if (s == 0) return 0;
+  const int64_t nfb = (f + 63) / 64;
+  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
+  k_seg_fwd<<<(unsigned)(s * nfb), 64, 0, (hipStream_t)hip_stream>>>(src, m, f, indptr, nfb, reduce, out,
+                                                                     minmax ? arg : nullptr);
+  HIP_TRY(hipGetLastError(), "segment_csr forward launch");
+  return 0;
+}
+
+int gcs_segment_csr_backward(const float* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
+                             int32_t reduce, const int64_t* arg, float* dsrc, void* hip_stream) {
+  if (int rc = check_segment("gcs_segment_csr_backward", dsrc, dout, indptr, m, f, s, reduce, arg, true)) return rc;
+  if (m == 0) return 0;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipMemsetAsync(dsrc, 0, 4 * (size_t)m * f, st), "dsrc clear");
+  if (s > 0) {
+    const int64_t nfb = (f + 63) / 64;
+    k_seg_bwd<<<(unsigned)(s * nfb), 64, 0, st>>>(dout, m, f, indptr, nfb, reduce, arg, dsrc);
+  }
+  HIP_TRY(hipGetLastError(), "segment_csr backward launch");
+  return 0;
+}
+
+}  // extern "C"

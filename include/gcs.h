@@ -1,0 +1,80 @@
+/*
+ * gcs.h -- C ABI of the MI355X-native sparse operators of the point backbone (libgcs_hip.so).
+ *
+ * The PTv3 backbone of GaussianCity's generators (models/pt_v3.py) needs three things from two CUDA-only
+ * packages: spconv's submanifold convolution SubMConv3d (with its SparseConvTensor container) and
+ * torch_scatter's segment_csr.  This library holds their kernels; gaussiancity_amd/sparse.py is the autograd
+ * layer and spconv/, torch_scatter/ at the repository root are the drop-in modules.
+ *
+ * Conventions as gce.h: raw DEVICE pointers, a HIP stream appended, 0 or a negative gcs_status returned,
+ * gcs_last_error() has the text.  Arguments are checked before anything is queued on the device.
+ *
+ * Submanifold convolution
+ *   indices   int32 [N][4]  (b, d0, d1, d2); a row is valid when 0 <= b < batch_size and 0 <= d < spatial_shape.
+ *   ksize     three odd kernel sizes, K = ksize[0] * ksize[1] * ksize[2] taps, tap k = (a * ksize[1] + b) * ksize[2] + c.
+ *   dilation  three positive dilations.  Tap k of row i is the row at (b_i, p_i + (tap - ksize / 2) * dilation).
+ *   Several rows may share one voxel: the voxel's representative is its LOWEST row index, and only
+ *   representatives are ever neighbours.  Rows of one voxel therefore get identical outputs.
+ *   weight    float [Cout][K][Cin] (spconv 2.x KRSC), bias float [Cout] or NULL.
+ *   features  float [N][Cin] row-major, output float [N][Cout].
+ *
+ * The rulebook is one device buffer of gcs_subm_rulebook_bytes(N, K) bytes that the caller keeps for as long as
+ * convolutions reuse it; gcs_subm_rulebook fills it from the indices, using gcs_subm_rulebook_scratch_bytes(N)
+ * bytes of scratch that are free again when the stream reaches the end of the call.  With host_info != NULL the
+ * call waits once for the stream and writes host_info[0] = number of invalid rows (they have no neighbours and
+ * are nobody's neighbour), host_info[1] = 1 if any voxel holds several rows, host_info[2 + k] = rows that have
+ * tap k.  gcs_subm_forward / gcs_subm_backward never wait.
+ *
+ * gcs_subm_backward: dx [N][Cin], dw [Cout][K][Cin], db [Cout] are WRITTEN (not accumulated); any may be NULL.
+ * `dups` is host_info[1] of the rulebook (it selects the fold of dy onto the representatives and the
+ * gcs_subm_backward_workspace_bytes size).  No float atomics: results are bit-identical run to run.
+ *
+ * segment_csr (torch_scatter semantics, reduction along dim 0)
+ *   src float [M][F], indptr int64 [S + 1] (non-decreasing; entries are clamped to [0, M]), out float [S][F].
+ *   reduce GCS_SUM / GCS_MEAN / GCS_MIN / GCS_MAX; an empty segment gives 0.  For min and max `arg` int64 [S][F]
+ *   receives the FIRST row that attains the value (-1 for an empty segment), and the backward pass routes the
+ *   gradient to it; for sum and mean `arg` is unused.  The backward pass writes all of dsrc [M][F].
+ */
+#ifndef GCS_H
+#define GCS_H
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define GCS_ABI_VERSION 1
+#define GCS_HOST_INFO_HEADER 2 /* host_info words before the per-tap pair counts */
+
+enum gcs_status { GCS_OK = 0, GCS_ERR_INVALID_ARGUMENT = -1, GCS_ERR_HIP = -2 };
+enum gcs_reduce { GCS_SUM = 0, GCS_MEAN = 1, GCS_MIN = 2, GCS_MAX = 3 };
+
+int gcs_abi_version(void);
+const char* gcs_last_error(void);
+
+/* workspace queries; 0 means the arguments are out of range (gcs_last_error says why) */
+size_t gcs_subm_rulebook_bytes(int64_t n, int32_t kvol);
+size_t gcs_subm_rulebook_scratch_bytes(int64_t n);
+size_t gcs_subm_backward_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups);
+
+int gcs_subm_rulebook(const int32_t* indices, int64_t n, int32_t batch_size, const int32_t* spatial_shape,
+                      const int32_t* ksize, const int32_t* dilation, void* rulebook, size_t rulebook_bytes,
+                      void* scratch, size_t scratch_bytes, int32_t* host_info, void* hip_stream);
+
+int gcs_subm_forward(const void* rulebook, int64_t n, int32_t kvol, const float* features, int32_t cin,
+                     const float* weight, const float* bias, int32_t cout, float* out, void* hip_stream);
+
+int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const float* features,
+                      int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx, float* dw,
+                      float* db, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+int gcs_segment_csr_forward(const float* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s, int32_t reduce,
+                            float* out, int64_t* arg, void* hip_stream);
+int gcs_segment_csr_backward(const float* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
+                             int32_t reduce, const int64_t* arg, float* dsrc, void* hip_stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,160 @@
+"""Timing of the HIP submanifold convolution (gaussiancity_amd.sparse) on PTv3's distinct convolution shapes, against
+a yardstick of torch ops on the same neighbour map (per tap: index_select + mm + index_add_, torch's own BLAS).
+
+  python tools/sparse_bench.py [--reps 7] [--iters 10] [--inference-n 262144] [--out FILE]
+
+Clouds: a 16 384-point building shell (tests/sparse_ref.shell_cloud) pooled stage by stage (coords >> 1) gives the
+N of every stage; the stage-0 shapes also run on an inference-sized shell of --inference-n points.  One JSON line per
+shape: rulebook build, forward and forward + backward in ms (median over --reps blocks of --iters calls, device
+events), the present pairs, the FLOP and byte floors of those pairs, and the yardstick's forward and forward +
+backward.  Needs a GPU; there is no CPU path."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import sparse_ref as R  # noqa: E402
+from gaussiancity_amd import sparse as SP  # noqa: E402
+
+
+def timed(fn, reps, iters):
+    """Median ms per call over `reps` blocks of `iters` calls, device events around each block."""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / iters)
+    return statistics.median(out)
+
+
+def yardstick(x, w, bias, taps, dy):
+    """Forward and forward + backward closures of the torch-ops version on the same neighbour map."""
+    cout, K, cin = w.shape[0], taps["K"], x.shape[1]
+    W = w.reshape(cout, K, cin)
+    Wt = [W[:, k, :].t().contiguous() for k in range(K)]
+    Wk = [W[:, k, :].contiguous() for k in range(K)]
+    present = [k for k in range(K) if len(taps["rows"][k])]
+
+    def fwd():
+        y = bias.expand(x.shape[0], cout).clone() if bias is not None else x.new_zeros((x.shape[0], cout))
+        for k in present:
+            y.index_add_(0, taps["rows"][k], torch.mm(x.index_select(0, taps["cols"][k]), Wt[k]))
+        return y
+
+    def fwdbwd():
+        fwd()
+        dx = torch.zeros_like(x)
+        dw = torch.zeros_like(W)
+        for k in present:
+            g = dy.index_select(0, taps["rows"][k])
+            dx.index_add_(0, taps["cols"][k], torch.mm(g, Wk[k]))
+            dw[:, k, :] = torch.mm(g.t(), x.index_select(0, taps["cols"][k]))
+        return dx, dw, dy.sum(0)
+
+    return fwd, fwdbwd
+
+
+def bench_shape(dev, coords, cin, cout, k, bias, reps, iters, label):
+    import spconv.pytorch as spconv
+    n = len(coords)
+    idx = torch.from_numpy(R.with_batch(coords, np.zeros(n))).to(dev)
+    shape = (coords.max(0) + 3).tolist()
+    g = torch.Generator(device="cpu").manual_seed(cin * 7 + k)
+    x = torch.randn(n, cin, generator=g).to(dev)
+    dy = torch.randn(n, cout, generator=g).to(dev)
+    conv = spconv.SubMConv3d(cin, cout, k, bias=bias).to(dev)
+    t = spconv.SparseConvTensor(x, idx, shape, 1)
+
+    builds = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rb = SP.Rulebook(idx, shape, 1, conv.kernel_size, conv.dilation)
+        torch.cuda.synchronize()
+        builds.append((time.perf_counter() - t0) * 1e3)
+    pairs = sum(rb.pairs)
+    xg = x.clone().requires_grad_(True)
+
+    def fwd():
+        with torch.no_grad():
+            return SP.SubMConvFunction.apply(x, conv.weight, conv.bias, rb)
+
+    def fwdbwd():
+        y = SP.SubMConvFunction.apply(xg, conv.weight, conv.bias, rb)
+        xg.grad = None
+        conv.weight.grad = None
+        if conv.bias is not None:
+            conv.bias.grad = None
+        y.backward(dy)
+
+    fwd_ms, fb_ms = timed(fwd, reps, iters), timed(fwdbwd, reps, iters)
+
+    nbr = R.neighbours(R.with_batch(coords, np.zeros(n)), shape, conv.kernel_size, conv.dilation)
+    taps = {"K": nbr.shape[1], "rows": [], "cols": []}
+    for q in range(nbr.shape[1]):
+        rows = np.nonzero(nbr[:, q] >= 0)[0]
+        taps["rows"].append(torch.from_numpy(rows).to(dev))
+        taps["cols"].append(torch.from_numpy(nbr[rows, q]).to(dev))
+    assert sum(len(r) for r in taps["rows"]) == pairs
+    with torch.no_grad():
+        yf, yb = yardstick(x, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(), taps, dy)
+        y_ref = yf()
+        y_got = fwd()
+        agree = float((y_got - y_ref).abs().max()) / max(1e-30, float(y_ref.abs().max()))
+        tf_ms, tfb_ms = timed(yf, reps, iters), timed(yb, reps, iters)
+    K = nbr.shape[1]
+    flop_f = 2.0 * pairs * cin * cout
+    bytes_f = 4.0 * (n * cin + n * cout + K * cin * cout) + 4.0 * n * K
+    return {"shape": label, "cin": cin, "cout": cout, "k": k, "n": n, "pairs": pairs,
+            "rulebook_ms": round(statistics.median(builds), 4), "fwd_ms": round(fwd_ms, 4), "fwdbwd_ms": round(fb_ms, 4),
+            "torch_fwd_ms": round(tf_ms, 4), "torch_fwdbwd_ms": round(tfb_ms, 4),
+            "fwd_speedup": round(tf_ms / fwd_ms, 2), "fwdbwd_speedup": round(tfb_ms / fb_ms, 2),
+            "flop_fwd": flop_f, "flop_fwdbwd": 3 * flop_f, "bytes_floor_fwd": bytes_f,
+            "fwd_tflops": round(flop_f / fwd_ms / 1e9, 3), "fwdbwd_tflops": round(3 * flop_f / fb_ms / 1e9, 3),
+            "max_rel_diff_vs_yardstick": agree}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--inference-n", type=int, default=262144)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sparse_bench needs a GPU")
+    dev = torch.device("cuda:0")
+    stages = R.pool_stages(R.shell_cloud(16384, 2024), 4)
+    cases = [(stages[st], cin, cout, k, k == 3, "%d->%d k%d stage%d" % (cin, cout, k, st)) for cin, cout, k, st in R.PTV3_SHAPES]
+    if a.inference_n:
+        big = R.shell_cloud(a.inference_n, 99, extent=640, size=(8, 96))
+        cases += [(big, 128, 32, 5, False, "128->32 k5 inference"), (big, 32, 32, 3, True, "32->32 k3 inference")]
+    lines = []
+    for coords, cin, cout, k, bias, label in cases:
+        rec = bench_shape(dev, coords, cin, cout, k, bias, a.reps, a.iters, label)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    if a.out:
+        with open(a.out, "w") as f:
+            for rec in lines:
+                f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()
