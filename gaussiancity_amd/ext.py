@@ -334,18 +334,19 @@ class _on_device:
 
 _size_cache = {}  # (P,) / (W, H) -> gcr_geometry_bytes / gcr_image_bytes: pure functions, two ctypes calls saved per frame
 
-# What the backward must know about the frame it is handed and the reference's signature has no room for: was the
-# forward rendered WITH the backward's state (gcr_camera.backward), and did it fit its binning buffer?  Keyed by the
-# geometry buffer's address -- the buffer is alive from the forward to the backward of a frame, so its entry is this
-# frame's; a later forward that gets the same block overwrites it.  Bounded, locked.
+# What the backward must know about the frame it is handed and the reference's signature has no room for: the frame's
+# FrameTicket (resolved on return for a synchronous frame) -- was the forward rendered WITH the backward's state
+# (gcr_camera.backward), did it fit its binning buffer, how long was its longest tile list?  Keyed by the geometry
+# buffer's address -- the buffer is alive from the forward to the backward of a frame, so its entry is this frame's; a
+# later forward that gets the same block overwrites it.  Bounded, locked.
 _FRAME_META_MAX = 512
 _frame_meta = collections.OrderedDict()
 _meta_lock = threading.Lock()
 
 
-def _meta_put(geom, stateful, ticket_or_R, longest):
+def _meta_put(geom, ticket):
     with _meta_lock:
-        _frame_meta[geom.data_ptr()] = (stateful, ticket_or_R, longest)
+        _frame_meta[geom.data_ptr()] = ticket
         _frame_meta.move_to_end(geom.data_ptr())
         while len(_frame_meta) > _FRAME_META_MAX:
             _frame_meta.popitem(last=False)
@@ -356,14 +357,28 @@ def _meta_get(geom):
         return _frame_meta.get(geom.data_ptr())
 
 
-def _forward(L, device, cam, g, P, H, W, ticket=False):
-    """One frame with torch-owned buffers; returns the reference's six-tuple.
+def _force_radix():
+    opt = _current_options()
+    return opt.force_radix if (opt is not None and opt.force_radix >= 0) else N.get_option("force_radix")
 
-    ticket=False: gcr_forward (+ the staged retry) -- the first element is num_rendered as an int, which costs the one
-    host wait of the frame (the reference's contract).  ticket=True: gcr_forward_async -- the first element is a
-    FrameTicket and the call returns as soon as the frame is enqueued; the first frames of a (device, P, W, H) key, whose
-    num_rendered cannot be guessed yet, and the debug / force_radix modes take the synchronous path and come back with
-    a resolved ticket."""
+
+def _a512(n):
+    return (int(n) + 511) & ~511
+
+
+# What a forward hands back (_forward's `mode`):
+_INT = 0     # the reference's six-tuple, num_rendered as an int: the frame's one host wait (rasterize_gaussians)
+_TICKET = 1  # the six-tuple with a FrameTicket in num_rendered's place (rasterize_gaussians_ticket)
+_IMAGE = 2   # (out_color, radii) of an inference frame: its state never leaves the call (rasterize_gaussians_frame)
+
+
+def _forward(L, device, cam, g, P, H, W, mode):
+    """One frame with torch-owned buffers on the current stream; `mode` says what comes back.
+
+    _TICKET and _IMAGE frames go through gcr_forward_async and return as soon as the frame is enqueued.  The first frames
+    of a (device, P, W, H) key, whose num_rendered cannot be guessed yet, the debug and force_radix modes and _SYNC_ONLY
+    take the synchronous path of every _INT frame -- gcr_forward, and gcr_forward_render when the guess was too small --
+    and come back with a resolved ticket.  Every frame but an _IMAGE one leaves its ticket in _frame_meta."""
     byte = dict(dtype=torch.uint8, device=device)
     stateful = cam.backward == 1
     # every pixel / every radius is written by the kernels, so no zero-fill launches are needed
@@ -382,75 +397,75 @@ def _forward(L, device, cam, g, P, H, W, ticket=False):
         ibytes = _size_cache[(W, H)] = L.gcr_image_bytes(W, H)
     if len(_size_cache) > 256:
         _size_cache.clear()
-    geom = torch.empty((gbytes,), **byte)
-    img = torch.empty((ibytes,), **byte)
     key = (device.index, P, W, H)
     ring = None
-    if ticket and _SYNC_ONLY:
-        ticket = None  # A/B switch: every frame through the synchronous entry point, tickets resolved on return
-    if ticket:
+    if mode != _INT and not _SYNC_ONLY:
         ring = _ring(L)
         ring.harvest()
     R_seen, list_cap = _hint_get(key)
     nbytes = L.gcr_binning_bytes if stateful else L.gcr_binning_bytes_lean
-    opt = _current_options()
-    radix = opt.force_radix if (opt is not None and opt.force_radix >= 0) else N.get_option("force_radix")
-    if ticket and R_seen > 0 and not cam.debug and not radix:
+    if ring is not None and R_seen > 0 and not cam.debug and not _force_radix():
         # The guess is made from a frame that may be several frames old (the host runs ahead of the device): twice its
         # num_rendered.  A frame that still does not fit is rendered correctly by the library's rescue (include/gcr.h).
         capacity = _ASYNC_FACTOR * R_seen + _ASYNC_MARGIN
         if _guess_hook is not None:
             capacity = max(1, int(_guess_hook(key, capacity)))
-        binning = torch.empty((nbytes(capacity, W, H),), **byte)
+        bbytes = nbytes(capacity, W, H)
+        if mode == _IMAGE:  # nobody will read the state: geometry, image and binning carved from ONE allocation
+            off_i = _a512(gbytes)
+            off_b = off_i + _a512(ibytes)
+            scratch = torch.empty((off_b + bbytes,), **byte)
+            gp = scratch.data_ptr()
+            ip, bp = gp + off_i, gp + off_b
+        else:
+            geom, img, binning = (torch.empty((n,), **byte) for n in (gbytes, ibytes, bbytes))
+            gp, ip, bp = geom.data_ptr(), img.data_ptr(), binning.data_ptr()
         slot, words, addr, seq = ring.take()
-        N.check(L.gcr_forward_async(C.byref(cam), C.byref(g), geom.data_ptr(), gbytes, binning.data_ptr(), binning.numel(),
-                                    capacity, list_cap, img.data_ptr(), ibytes, radii.data_ptr(), out_color.data_ptr(),
-                                    addr, seq, stream),
+        N.check(L.gcr_forward_async(C.byref(cam), C.byref(g), gp, gbytes, bp, bbytes, capacity, list_cap, ip, ibytes,
+                                    radii.data_ptr(), out_color.data_ptr(), addr, seq, stream),
                 "gcr_forward_async")
-        t = FrameTicket(L, words, addr, seq, capacity, stream, key, stateful)
-        ring.tickets[slot] = t
+        t = ring.tickets[slot] = FrameTicket(L, words, addr, seq, capacity, stream, key, stateful)
         ring.pending.append(t)
-        _meta_put(geom, stateful, t, list_cap)
-        return t, out_color, radii, geom, binning, img
-    info = N.FrameInfo()
-    capacity = R_seen + R_seen // 2 + 4096 if R_seen > 0 else 0
-    binning = torch.empty((nbytes(capacity, W, H) if capacity else 0,), **byte)
-    rc = N.check(L.gcr_forward(C.byref(cam), C.byref(g), geom.data_ptr(), gbytes,
-                               binning.data_ptr() if capacity else None, binning.numel(), capacity,
-                               list_cap, img.data_ptr(), ibytes, radii.data_ptr(), out_color.data_ptr(),
-                               C.byref(info), stream),
-                 "gcr_forward")
-    R = int(info.num_rendered)
-    if rc == 1:  # GCR_RETRY_RENDER: no/too small a guess, or a tile list beyond the LDS sort
-        capacity = R
-        binning = torch.empty((nbytes(R, W, H),), **byte)
-        N.check(L.gcr_forward_render(C.byref(cam), C.byref(g), geom.data_ptr(), gbytes,
-                                     binning.data_ptr(), binning.numel(), img.data_ptr(),
-                                     ibytes, C.byref(info), out_color.data_ptr(), stream),
-                "gcr_forward_render")
-    longest = int(info.max_tile_instances)
-    _hint_put(key, (R, longest))  # the library adds its own margin to the longest list
-    _meta_put(geom, stateful, R, longest)
-    if ticket is not False:
-        R = FrameTicket(L, None, None, 0, max(capacity, R), stream, None, stateful, R=R, longest=longest)
-    return R, out_color, radii, geom, binning, img
+    else:
+        geom, img = torch.empty((gbytes,), **byte), torch.empty((ibytes,), **byte)
+        info = N.FrameInfo()
+        capacity = R_seen + R_seen // 2 + 4096 if R_seen > 0 else 0
+        binning = torch.empty((nbytes(capacity, W, H) if capacity else 0,), **byte)
+        rc = N.check(L.gcr_forward(C.byref(cam), C.byref(g), geom.data_ptr(), gbytes,
+                                   binning.data_ptr() if capacity else None, binning.numel(), capacity,
+                                   list_cap, img.data_ptr(), ibytes, radii.data_ptr(), out_color.data_ptr(),
+                                   C.byref(info), stream),
+                     "gcr_forward")
+        R = int(info.num_rendered)
+        if rc == 1:  # GCR_RETRY_RENDER: no/too small a guess, or a tile list beyond the LDS sort
+            capacity = R
+            binning = torch.empty((nbytes(R, W, H),), **byte)
+            N.check(L.gcr_forward_render(C.byref(cam), C.byref(g), geom.data_ptr(), gbytes,
+                                         binning.data_ptr(), binning.numel(), img.data_ptr(),
+                                         ibytes, C.byref(info), out_color.data_ptr(), stream),
+                    "gcr_forward_render")
+        longest = int(info.max_tile_instances)
+        _hint_put(key, (R, longest))  # the library adds its own margin to the longest list
+        t = FrameTicket(L, None, None, 0, max(capacity, R), stream, None, stateful, R=R, longest=longest)
+    if mode == _IMAGE:
+        return out_color, radii
+    _meta_put(geom, t)
+    return (t._R if mode == _INT else t), out_color, radii, geom, binning, img
 
 
 def _state_for_backward(L, device, cam, g, geom, binning, img, R, W, H):
     """What gcr_backward needs besides the arguments of the reference: num_rendered as an int, and a binning buffer that
-    holds the forward blend's per-piece state.  A frame that was rendered as an inference frame (gcr_camera.backward
-    == 0) or that overflowed its capacity guess (FrameTicket.rescued) is binned again, state only, into an exactly
-    sized buffer -- rare paths, both pinned by tests.  Returns (R, binning)."""
-    meta = _meta_get(geom)
-    stateful, longest = True, 0
-    if isinstance(R, FrameTicket):
-        t, R = R, R.wait()
-        stateful, longest = t.stateful and not t.rescued, t._longest
-    elif meta is not None and not isinstance(meta[1], FrameTicket) and int(meta[1]) == int(R):
-        stateful, longest = meta[0], meta[2]
-    elif meta is not None and isinstance(meta[1], FrameTicket) and meta[1].wait() == int(R):
-        stateful, longest = meta[0] and not meta[1].rescued, meta[1]._longest
+    holds the forward blend's per-piece state.  The frame's ticket tells: the one handed in as `R`, else the one its
+    forward left under the geometry buffer's address if it has the same num_rendered (a later frame that got the same
+    block does not) -- without either, the frame is taken to hold its state (the C ABI's own guards speak if it does
+    not).  A frame that was rendered as an inference frame (gcr_camera.backward == 0) or that overflowed its capacity
+    guess (FrameTicket.rescued) is binned again, state only, into an exactly sized buffer -- rare paths, both pinned by
+    tests.  Returns (R, binning)."""
+    t = R if isinstance(R, FrameTicket) else _meta_get(geom)
     R = int(R)
+    stateful, longest = True, 0
+    if t is not None and t.wait() == R:
+        stateful, longest = t.stateful and not t.rescued, t._longest
     if stateful or R == 0:
         return R, binning
     binning = torch.empty((L.gcr_binning_bytes(R, W, H),), dtype=torch.uint8, device=device)
@@ -461,11 +476,51 @@ def _state_for_backward(L, device, cam, g, geom, binning, img, R, W, H):
     return R, binning
 
 
+def _num_points(t, name, cols):
+    """P of the [P, cols] tensor of Gaussians an entry point is handed (means3D; GaussianCity's [N,14] points)."""
+    if t.dim() != 2 or t.size(1) != cols:
+        raise RuntimeError("%s must have dimensions (num_points, %d)" % (name, cols))
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a GPU tensor: this rasterizer has no CPU path" % name)
+    return int(t.size(0))
 
-def _empty_frame(device, H, W):
-    e = torch.empty((0,), dtype=torch.uint8, device=device)  # dgr/rasterize_points.cu:71: zero image, nothing rendered
-    return (0, torch.zeros((NUM_CHANNELS, H, W), dtype=torch.float32, device=device),
-            torch.zeros((0,), dtype=torch.int32, device=device), e, e.clone(), e.clone())
+
+def _empty_frame(device, H, W, mode):
+    """What a forward of P == 0 Gaussians returns: a zero image, nothing rendered (dgr/rasterize_points.cu:71)."""
+    color = torch.zeros((NUM_CHANNELS, H, W), dtype=torch.float32, device=device)
+    radii = torch.zeros((0,), dtype=torch.int32, device=device)
+    if mode == _IMAGE:
+        return color, radii
+    e = torch.empty((0,), dtype=torch.uint8, device=device)
+    R = FrameTicket(None, None, None, 0, 0, None, None, False, R=0) if mode == _TICKET else 0
+    return R, color, radii, e, e.clone(), e.clone()
+
+
+def _rasterize(mode, for_backward, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+               viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+               debug):
+    """A frame of the reference's call shape: its checks, the gcr_camera / gcr_gaussians records, _forward."""
+    P = _num_points(means3D, "means3D", 3)
+    L = N.lib()
+    device = means3D.device
+    H, W = int(image_height), int(image_width)
+    if P == 0:
+        return _empty_frame(device, H, W, mode)
+    with _on_device(device):
+        if _cull.enabled() and not for_backward:  # a static scene's cull cache: same bits, fewer bytes (cull_cache.py)
+            cam, keep_c = _camera(device, background, viewmatrix, projmatrix, campos, tan_fovx,
+                                  tan_fovy, H, W, scale_modifier, degree, prefiltered, debug, for_backward)
+            g, keep_g = _gaussians(device, P, means3D, opacity, sh, colors, scales, rotations,
+                                   cov3D_precomp)
+            keep = (keep_c, keep_g, _cull.attach(g, scale_modifier, (means3D, scales, rotations, cov3D_precomp, opacity),
+                                                 device, _stream(device)))
+        else:
+            cam, g, keep = _records(device, P, H, W, background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                                    cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, sh, degree, campos,
+                                    bool(prefiltered), bool(debug), bool(for_backward), _current_options())
+        out = _forward(L, device, cam, g, P, H, W, mode)
+        del keep
+    return out
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier,
@@ -486,31 +541,9 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     if _for_backward is None:  # the reference's contract: whoever calls this may call the backward next
         _for_backward = getattr(_tls, "backward", None)
         _for_backward = True if _for_backward is None else _for_backward
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    if not means3D.is_cuda:
-        raise RuntimeError("means3D must be a GPU tensor: this rasterizer has no CPU path")
-    L = N.lib()
-    device = means3D.device
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    if P == 0:
-        e = _empty_frame(device, H, W)
-        return ((FrameTicket(L, None, None, 0, 0, None, None, False, R=0),) + e[1:]) if _ticket else e
-    with _on_device(device):
-        if _cull.enabled() and not _for_backward:  # a static scene's cull cache: same bits, fewer bytes (cull_cache.py)
-            cam, keep_c = _camera(device, background, viewmatrix, projmatrix, campos, tan_fovx,
-                                  tan_fovy, H, W, scale_modifier, degree, prefiltered, debug, _for_backward)
-            g, keep_g = _gaussians(device, P, means3D, opacity, sh, colors, scales, rotations,
-                                   cov3D_precomp)
-            keep = (keep_c, keep_g, _cull.attach(g, scale_modifier, (means3D, scales, rotations, cov3D_precomp, opacity),
-                                                 device, _stream(device)))
-        else:
-            cam, g, keep = _records(device, P, H, W, background, means3D, colors, opacity, scales, rotations, scale_modifier,
-                                    cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, sh, degree, campos,
-                                    bool(prefiltered), bool(debug), bool(_for_backward), _current_options())
-        out = _forward(L, device, cam, g, P, H, W, _ticket)
-        del keep
-    return out
+    return _rasterize(_TICKET if _ticket else _INT, _for_backward, background, means3D, colors, opacity, scales, rotations,
+                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
+                      sh, degree, campos, prefiltered, debug)
 
 
 def rasterize_gaussians_ticket(*args, _for_backward=False):
@@ -527,9 +560,9 @@ def rasterize_gaussians_ticket(*args, _for_backward=False):
 # the calling thread needs ~63 us to get a C3 frame from the module call to the six launches (tools/host_profile_api.py),
 # a third of the frame's period, and the first frames behind every synchronize are spaced by exactly that -- so this
 # entry point does what rasterize_gaussians_ticket does with less of it:
-#   * the gcr_camera / gcr_gaussians records are kept per thread while a call's tensors are THE SAME OBJECTS at the same
-#     addresses as the previous call's with that key (weak references: nothing is kept alive; a copy made by
-#     .contiguous() is never cached -- it would be a snapshot);
+#   * the gcr_camera / gcr_gaussians records are kept per thread while a call's tensors are THE SAME OBJECTS with the same
+#     shapes at the same addresses as the previous call's with that key (weak references: nothing is kept alive; a copy
+#     made by .contiguous() is never cached -- it would be a snapshot);
 #   * geometry, image and binning state are carved from ONE allocation;
 #   * no autograd node (rasterizer.GaussianRasterizer.forward decides that), no frame-meta entry for a backward that
 #     cannot come.
@@ -538,7 +571,7 @@ _PREP_MAX = 64
 
 
 class _Prepared:
-    __slots__ = ("refs", "ptrs", "cam", "g", "device", "P")
+    __slots__ = ("refs", "ptrs", "cam", "g")
 
 
 def _prep_cache():
@@ -548,20 +581,18 @@ def _prep_cache():
     return c
 
 
-def _a512(n):
-    return (int(n) + 511) & ~511
-
-
 def _records(device, P, H, W, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
              viewmatrix, projmatrix, tan_fovx, tan_fovy, sh, degree, campos, prefiltered, debug, for_backward, opt):
     """(gcr_camera, gcr_gaussians, what must stay alive during the call) of a frame -- from this thread's cache when every
-    tensor of the call is the same object at the same address as when the records were built."""
+    tensor of the call is the same object with the same shape at the same address as when the records were built."""
     tensors = (background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, campos)
-    key = (tuple(0 if (t is None or t.numel() == 0) else id(t) for t in tensors), scale_modifier, tan_fovx, tan_fovy, H, W,
-           degree, prefiltered, debug, for_backward, id(opt))
+    # a tensor is keyed by identity and shape (an in-place resize_ keeps both object and address); absent = None or
+    # numel() == 0, i.e. a 0 in the shape
+    key = (tuple([0 if t is None or 0 in (s := t.shape) else (id(t), s) for t in tensors]), scale_modifier, tan_fovx,
+           tan_fovy, H, W, degree, prefiltered, debug, for_backward, id(opt))
     cache = _prep_cache()
     ent = cache.get(key)
-    if ent is not None and ent.P == P:
+    if ent is not None:
         for r, p, t in zip(ent.refs, ent.ptrs, tensors):
             if r is not None and (r() is not t or t.data_ptr() != p):
                 break
@@ -576,7 +607,7 @@ def _records(device, P, H, W, background, means3D, colors, opacity, scales, rota
         ent = _Prepared()
         ent.refs = tuple(None if (t is None or t.numel() == 0) else weakref.ref(t) for t in tensors)
         ent.ptrs = tuple(0 if (t is None or t.numel() == 0) else t.data_ptr() for t in tensors)
-        ent.cam, ent.g, ent.device, ent.P = cam, g, device, P
+        ent.cam, ent.g = cam, g
         cache[key] = ent
         while len(cache) > _PREP_MAX:
             cache.popitem(last=False)
@@ -588,59 +619,9 @@ def rasterize_gaussians_frame(background, means3D, colors, opacity, scales, rota
                               prefiltered):
     """One inference frame: rasterize_gaussians_ticket()'s image and radii -- (out_color[3,H,W], radii[P]) -- without
     the host wait, the state buffers, or a backward.  Absent optional inputs are None (or empty tensors)."""
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    if not means3D.is_cuda:
-        raise RuntimeError("means3D must be a GPU tensor: this rasterizer has no CPU path")
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    opt = _current_options()
-    if P == 0 or _cull.enabled() or _SYNC_ONLY or _guess_hook is not None:
-        return rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                                   viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered,
-                                   False, _for_backward=False, _ticket=True)[1:3]
-    L = N.lib()
-    device = means3D.device
-    with _on_device(device):
-        cam, g, keep = _records(device, P, H, W, background, means3D, colors, opacity, scales, rotations, scale_modifier,
-                                cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, sh, degree, campos, prefiltered,
-                                False, False, opt)
-        out = _forward_lean(L, device, cam, g, P, H, W, opt)
-        del keep
-    return out
-
-
-def _forward_lean(L, device, cam, g, P, H, W, opt):
-    """_forward(ticket=True) for a frame whose state nobody will ask for: one scratch allocation, (out_color, radii)."""
-    key = (device.index, P, W, H)
-    R_seen, list_cap = _hint_get(key)
-    radix = opt.force_radix if (opt is not None and opt.force_radix >= 0) else N.get_option("force_radix")
-    if R_seen <= 0 or radix:  # the first frames of a key (no guess yet) and the radix mode take the synchronous path
-        return _forward(L, device, cam, g, P, H, W, True)[1:3]
-    out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=device)
-    radii = torch.empty((P,), dtype=torch.int32, device=device)
-    gbytes = _size_cache.get(P)
-    if gbytes is None:
-        gbytes = _size_cache[P] = L.gcr_geometry_bytes(P)
-    ibytes = _size_cache.get((W, H))
-    if ibytes is None:
-        ibytes = _size_cache[(W, H)] = L.gcr_image_bytes(W, H)
-    ring = _ring(L)
-    ring.harvest()
-    capacity = _ASYNC_FACTOR * R_seen + _ASYNC_MARGIN
-    bbytes = L.gcr_binning_bytes_lean(capacity, W, H)
-    off_i = _a512(gbytes)
-    off_b = off_i + _a512(ibytes)
-    scratch = torch.empty((off_b + bbytes,), dtype=torch.uint8, device=device)
-    base = scratch.data_ptr()
-    stream = _stream(device)
-    slot, words, addr, seq = ring.take()
-    N.check(L.gcr_forward_async(C.byref(cam), C.byref(g), base, gbytes, base + off_b, bbytes, capacity, list_cap,
-                                base + off_i, ibytes, radii.data_ptr(), out_color.data_ptr(), addr, seq, stream),
-            "gcr_forward_async")
-    t = FrameTicket(L, words, addr, seq, capacity, stream, key, False)
-    ring.tickets[slot] = t
-    ring.pending.append(t)
-    return out_color, radii
+    return _rasterize(_IMAGE, False, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                      viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                      prefiltered, False)
 
 
 # ---- GaussianCity's own call shape: points [N,14] = xyz(3) opacity(1) scale(3) rotation(4) rgb(3) ---------------------
@@ -652,10 +633,7 @@ _POINT_COLUMNS = dict(means3D=0, opacities=3, scales=4, rotations=7, colors=11)
 
 
 def _points14_gaussians(points):
-    if points.dim() != 2 or points.size(1) != 14:
-        raise RuntimeError("points must have dimensions (num_points, 14)")
-    if not points.is_cuda:
-        raise RuntimeError("points must be a GPU tensor: this rasterizer has no CPU path")
+    _num_points(points, "points", 14)
     if points.dtype != torch.float32:
         raise RuntimeError("points must be float32 (got %s)" % points.dtype)
     if points.stride(1) != 1:
@@ -678,22 +656,52 @@ def rasterize_points14(points, background, scale_modifier, viewmatrix, projmatri
     instead of the float [3,h,w] image -- the same bytes its five elementwise kernels produce, stored by the blend."""
     if out_uint8 and for_backward:
         raise RuntimeError("out_uint8 renders video frames: there is no backward through them")
-    L = N.lib()
     g, pts = _points14_gaussians(points)
+    L = N.lib()
     device = pts.device
     P, H, W = int(pts.size(0)), int(image_height), int(image_width)
+    mode = _TICKET if ticket else _INT
     if P == 0:
-        e = _empty_frame(device, *((window[3], window[2]) if window is not None else (H, W)))
-        return ((FrameTicket(L, None, None, 0, 0, None, None, False, R=0),) + e[1:]) if ticket else e
+        return _empty_frame(device, *((window[3], window[2]) if window is not None else (H, W)), mode)
     with _on_device(device):
         cam, keep_c = _camera(device, background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W,
                               scale_modifier, 0, False, False, for_backward, flip_x, flip_y, window, out_uint8)
         keep_cc = None
-        if _cull.enabled() and not for_backward:  # (see rasterize_gaussians)
+        if _cull.enabled() and not for_backward:  # (see _rasterize)
             keep_cc = _cull.attach(g, scale_modifier, (points,), device, _stream(device))
-        out = _forward(L, device, cam, g, P, H, W, ticket)
+        out = _forward(L, device, cam, g, P, H, W, mode)
         del keep_c, pts, keep_cc
     return out
+
+
+# ---- the backward: both call shapes ----------------------------------------------------------------------------------
+def _grad_record_floats(L):
+    """Floats of gcr_backward's accumulation record per Gaussian under this thread's options: 16, or 32 in the
+    deterministic mode."""
+    opt = _current_options()
+    return int(L.gcr_grad_record_floats_opt(C.byref(opt) if opt is not None else None))
+
+
+def _grad_empty(shape, device):
+    """An output or scratch tensor of gcr_backward: uninitialised -- the library writes every element of every output
+    itself (include/gcr.h) -- or, under poison_outputs, NaN-filled."""
+    t = torch.empty(shape, dtype=torch.float32, device=device)
+    if poison_outputs and t.numel():
+        t.fill_(float("nan"))
+    return t
+
+
+def _backward(L, device, cam, g, radii, geom, binning, img, R, W, H, dL_dout_color, grads):
+    """gcr_backward of one frame into `grads` (the two call shapes differ in that record only)."""
+    dpix, dpix_ptr = _dev_f32(dL_dout_color, "dL_dout_color", device)
+    if radii.dtype != torch.int32:
+        raise RuntimeError("radii must be int32")
+    radii, geom, binning, img = radii.contiguous(), geom.contiguous(), binning.contiguous(), img.contiguous()
+    R, binning = _state_for_backward(L, device, cam, g, geom, binning, img, R, W, H)
+    N.check(L.gcr_backward(C.byref(cam), C.byref(g), radii.data_ptr(), geom.data_ptr(), geom.numel(),
+                           binning.data_ptr() if binning.numel() else None, binning.numel(), img.data_ptr(),
+                           img.numel(), R, dpix_ptr, C.byref(grads), _stream(device)),
+            "gcr_backward")
 
 
 def rasterize_points14_backward(points, radii, background, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -701,33 +709,26 @@ def rasterize_points14_backward(points, radii, background, scale_modifier, viewm
                                 image_width, flip_x=False, flip_y=False, window=None):
     """Gradient of rasterize_points14 with respect to `points`, as ONE [N,14] tensor the library fills completely
     (`dL_dout_color` has the shape of the image that was handed out: the window's, if there was one)."""
-    L = N.lib()
     g, pts = _points14_gaussians(points)
+    L = N.lib()
     device = pts.device
     P = int(pts.size(0))
     H, W = int(image_height), int(image_width)
     want = (NUM_CHANNELS, window[3], window[2]) if window is not None else (NUM_CHANNELS, H, W)
     if tuple(dL_dout_color.shape) != want:
         raise RuntimeError("dL_dout_color has shape %s, expected %s" % (tuple(dL_dout_color.shape), want))
-    grad = torch.empty((P, 14), dtype=torch.float32, device=device)
+    grad = _grad_empty((P, 14), device)
     if P == 0:
         return grad
-    if poison_outputs:
-        grad.fill_(float("nan"))
-    # scratch the API wants besides: accumulation records [P,16] (64-byte aligned), dL_dmeans2D [P,3], dL_dcov3D [P,6]
-    opt = _current_options()
-    nrec = int(L.gcr_grad_record_floats_opt(C.byref(opt) if opt is not None else None))  # 16, or 32 in the deterministic mode
-    flat = torch.empty((P * (nrec + 3 + 6) + 64,), dtype=torch.float32, device=device)
-    if poison_outputs:
-        flat.fill_(float("nan"))
+    # scratch the API wants besides: accumulation records [P,nrec] (64-byte aligned), dL_dmeans2D [P,3], dL_dcov3D [P,6]
+    nrec = _grad_record_floats(L)
+    flat = _grad_empty((P * (nrec + 3 + 6) + 64,), device)
     rec = flat[:P * nrec]
     m2d = flat[P * nrec:P * (nrec + 3)]
     c3d = flat[P * (nrec + 3):P * (nrec + 9)]
     with _on_device(device):
         cam, keep_c = _camera(device, background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W,
                               scale_modifier, 0, False, False, True, flip_x, flip_y, window)
-        dpix, dpix_ptr = _dev_f32(dL_dout_color, "dL_dout_color", device)
-        R, binningBuffer = _state_for_backward(L, device, cam, g, geomBuffer, binningBuffer, imageBuffer, R, W, H)
         gb = grad.data_ptr()
         col = {k: gb + 4 * v for k, v in _POINT_COLUMNS.items()}
         grads = N.Grads(m2d.data_ptr(), rec.data_ptr(), col["opacities"], col["colors"], col["means3D"], c3d.data_ptr(),
@@ -736,12 +737,8 @@ def rasterize_points14_backward(points, radii, background, scale_modifier, viewm
             grads.stride_rotations = 14
         grads.packed = gb
         grads.packed_floats = P * 14
-        N.check(L.gcr_backward(C.byref(cam), C.byref(g), radii.data_ptr(), geomBuffer.data_ptr(), geomBuffer.numel(),
-                               binningBuffer.data_ptr() if binningBuffer.numel() else None, binningBuffer.numel(),
-                               imageBuffer.data_ptr(), imageBuffer.numel(), int(R), dpix_ptr, C.byref(grads),
-                               _stream(device)),
-                "gcr_backward")
-        del keep_c, dpix, pts
+        _backward(L, device, cam, g, radii, geomBuffer, binningBuffer, imageBuffer, R, W, H, dL_dout_color, grads)
+        del keep_c, pts
     return grad
 
 
@@ -750,17 +747,14 @@ def _gradient_buffers(P, M, device):
     of ONE uninitialised buffer: gcr_backward writes every element of every output itself (include/gcr.h).
     dL_dconic is the native side's accumulation scratch: one 64-byte record per Gaussian.
     Order: dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dconic, dL_dopacity, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations."""
-    opt = _current_options()
-    nrec = int(N.lib().gcr_grad_record_floats_opt(C.byref(opt) if opt is not None else None))  # 16, or 32 (deterministic)
+    nrec = _grad_record_floats(N.lib())
     shapes = ((P, 3), (P, 3), (P, NUM_CHANNELS), (P, nrec), (P, 1), (P, 6), (P, M, 3), (P, 3), (P, 4))
     sizes = [int(torch.Size(sh).numel()) for sh in shapes]
     starts, off = [], 0
     for n in sizes:  # every view starts 256-byte aligned (dL_dconic and dL_drotations are accessed as float4)
         starts.append(off)
         off += (n + 63) // 64 * 64
-    flat = (torch.empty if P != 0 else torch.zeros)((off,), dtype=torch.float32, device=device)
-    if poison_outputs and P != 0:
-        flat.fill_(float("nan"))
+    flat = _grad_empty((off,), device)
     return [flat[st:st + n].view(sh) for st, n, sh in zip(starts, sizes, shapes)]
 
 
@@ -788,22 +782,12 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             # opacity is not an input of the backward (it is read from the geometry state)
             g, keep_g = _gaussians(device, P, means3D, None, sh, colors, scales, rotations,
                                    cov3D_precomp)
-            dpix, dpix_ptr = _dev_f32(dL_dout_color, "dL_dout_color", device)
-            if radii.dtype != torch.int32:
-                raise RuntimeError("radii must be int32")
-            radii_c = radii.contiguous()
             grads = N.Grads(dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
                             dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
                             dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(),
                             dL_drotations.data_ptr())
-            gb, bb, ib = geomBuffer.contiguous(), binningBuffer.contiguous(), imageBuffer.contiguous()
-            R, bb = _state_for_backward(L, device, cam, g, gb, bb, ib, R, W, H)
-            N.check(L.gcr_backward(C.byref(cam), C.byref(g), radii_c.data_ptr(), gb.data_ptr(),
-                                   gb.numel(), bb.data_ptr() if bb.numel() else None, bb.numel(),
-                                   ib.data_ptr(), ib.numel(), int(R), dpix_ptr, C.byref(grads),
-                                   _stream(device)),
-                    "gcr_backward")
-            del keep_c, keep_g, dpix
+            _backward(L, device, cam, g, radii, geomBuffer, binningBuffer, imageBuffer, R, W, H, dL_dout_color, grads)
+            del keep_c, keep_g
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
             dL_drotations)
 

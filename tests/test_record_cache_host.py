@@ -58,6 +58,19 @@ def test_records_are_reused_for_the_same_objects_only():
     assert g4.scales == t["scales"].data_ptr() and cam4 is not cam
 
 
+def test_an_in_place_resize_that_keeps_the_address_is_a_miss():
+    """resize_ to a smaller shape keeps the object and the address: a hit would hand the kernels the old M."""
+    ext._prep_cache().clear()
+    t = _scene()
+    cam, g, _ = _call(t)
+    assert g.M == 4
+    ptr = t["sh"].data_ptr()
+    t["sh"].resize_(10, 1, 3)
+    assert t["sh"].data_ptr() == ptr
+    cam2, g2, keep = _call(t)
+    assert cam2 is not cam and keep is not None and g2.M == 1
+
+
 def test_a_call_that_needed_a_copy_is_never_cached_and_nothing_is_kept_alive():
     ext._prep_cache().clear()
     t = _scene()
