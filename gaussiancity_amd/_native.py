@@ -1,26 +1,14 @@
-"""ctypes binding of libgcr_hip.so (C ABI in include/gcr.h).
+"""ctypes binding of libgcr_hip.so (C ABI in include/gcr.h): the declarations; gaussiancity_amd/_loader.py loads it.
 
 The library is the product: there is NO Python/CPU fallback.  If it is missing or a call
 fails, a RuntimeError is raised (the reference surfaces native failures the same way:
 C++ exceptions -> RuntimeError, dgr/rasterize_points.cu:46-48, cr/auxiliary.h:158-167).
 """
 import ctypes as C
-import os
 import subprocess
 
-_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-# GCR_LIB_PATH: tools/ point it at the experiment build (make -C csrc experiments); nothing else sets it
-LIB_PATH = os.environ.get("GCR_LIB_PATH") or os.path.join(_CSRC, "libgcr_hip.so")
+from . import _loader
 
-# Every symbol include/gcr.h declares; tests check that the built library exports all of them.
-EXPORTED_SYMBOLS = (
-    "gcr_abi_version", "gcr_last_error", "gcr_geometry_bytes", "gcr_image_bytes",
-    "gcr_binning_bytes", "gcr_get_layout", "gcr_forward", "gcr_forward_preprocess", "gcr_forward_render",
-    "gcr_backward", "gcr_build_cull_cache", "gcr_cull_cache_bytes", "gcr_mark_visible", "gcr_rasterize_forward", "gcr_set_option",
-    "gcr_get_stage_ms", "gcr_grad_record_floats", "gcr_grad_record_floats_opt", "gcr_binning_bytes_lean",
-    "gcr_forward_async", "gcr_ticket_poll", "gcr_ticket_wait", "gcr_host_words_alloc", "gcr_host_words_free", "gcr_rescue_count",
-    "gcr_get_option", "gcr_rescue_dropped_count",
-)
 GRAD_REC_FLOATS = 16  # gcr_grad_record_floats() by default (32 under option "deterministic_backward": ext asks per call)
 
 STAGE_NAMES = ("preprocess", "scan", "emit", "sort", "ranges", "blend_fwd", "blend_bwd",
@@ -104,113 +92,66 @@ ABI_VERSION = 9
 TICKET_WORDS = 8  # 64-bit pinned host words per asynchronous frame (include/gcr.h, gcr_forward_async)
 RESIZE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
-_lib = None
+_vp, _sz, _i32, _i64, _u32, _int = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_uint32, C.c_int
+_cam, _gs, _info, _opts = C.POINTER(Camera), C.POINTER(Gaussians), C.POINTER(FrameInfo), C.POINTER(Options)
+# Every function include/gcr.h declares: name -> (restype, argtypes).  Tests hold this table to the header and to the
+# symbols the built library exports.
+_SIGNATURES = {
+    "gcr_abi_version": (_int, []),
+    "gcr_last_error": (C.c_char_p, []),
+    "gcr_geometry_bytes": (_sz, [_i32]),
+    "gcr_image_bytes": (_sz, [_i32, _i32]),
+    "gcr_binning_bytes": (_sz, [_i64, _i32, _i32]),
+    "gcr_binning_bytes_lean": (_sz, [_i64, _i32, _i32]),
+    "gcr_get_layout": (_int, [_i32, _i32, _i32, _i64, C.POINTER(Layout)]),
+    "gcr_forward": (_int, [_cam, _gs, _vp, _sz, _vp, _sz, _i64, _i64, _vp, _sz, _vp, _vp, _info, _vp]),
+    "gcr_forward_preprocess": (_int, [_cam, _gs, _vp, _sz, _vp, _sz, _vp, _info, _vp]),
+    "gcr_forward_render": (_int, [_cam, _gs, _vp, _sz, _vp, _sz, _vp, _sz, _info, _vp, _vp]),
+    "gcr_backward": (_int, [_cam, _gs, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _i64, _vp, C.POINTER(Grads), _vp]),
+    "gcr_build_cull_cache": (_int, [_gs, C.c_float, _vp, _vp]),
+    "gcr_cull_cache_bytes": (_sz, [_i32]),
+    "gcr_mark_visible": (_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    "gcr_rasterize_forward": (_i64, [RESIZE_FN, _vp, RESIZE_FN, _vp, RESIZE_FN, _vp, _cam, _gs, _vp, _vp, _vp]),
+    "gcr_set_option": (_int, [C.c_char_p, _int]),
+    "gcr_get_option": (_int, [C.c_char_p]),
+    "gcr_get_stage_ms": (_int, [C.POINTER(C.c_float), _int]),
+    "gcr_grad_record_floats": (_int, []),
+    "gcr_grad_record_floats_opt": (_int, [_opts]),
+    "gcr_forward_async": (_int, [_cam, _gs, _vp, _sz, _vp, _sz, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _u32, _vp]),
+    "gcr_ticket_poll": (_int, [_vp, _u32, _i64, _info]),
+    "gcr_ticket_wait": (_int, [_vp, _u32, _i64, _vp, _info]),
+    "gcr_host_words_alloc": (_vp, [_sz]),
+    "gcr_host_words_free": (None, [_vp]),
+    "gcr_rescue_count": (C.c_long, []),
+    "gcr_rescue_dropped_count": (C.c_long, []),
+}
+
+
+def _check_grad_record(L):
+    if L.gcr_grad_record_floats() not in (GRAD_REC_FLOATS, 2 * GRAD_REC_FLOATS):
+        raise RuntimeError("libgcr_hip.so gradient record size mismatch")
+
+
+# GCR_LIB_PATH: tools/ point it at the experiment build (make -C csrc experiments); nothing else sets it
+_L = _loader.Library("gcr", "libgcr_hip.so", ABI_VERSION, _SIGNATURES, STAGE_NAMES, path_env="GCR_LIB_PATH",
+                     after_load=_check_grad_record)
+LIB_PATH, EXPORTED_SYMBOLS = _L.path, _L.exported_symbols
+lib, check, set_option, stage_ms = _L.lib, _L.check, _L.set_option, _L.stage_ms
 
 
 def build(force=False):
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    cmd = ["make", "-C", _CSRC, "-s", "-j4"]
+    cmd = ["make", "-C", _loader.CSRC, "-s", "-j4"]
     if force:
-        subprocess.check_call(["make", "-C", _CSRC, "-s", "clean"])
+        subprocess.check_call(["make", "-C", _loader.CSRC, "-s", "clean"])
     subprocess.check_call(cmd)
     return LIB_PATH
-
-
-def lib():
-    """Load libgcr_hip.so; fail loudly if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "libgcr_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; "
-            "g.build()'` or `make -C gaussiancity_amd/csrc`. There is no CPU fallback." % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    L.gcr_abi_version.restype = C.c_int
-    L.gcr_last_error.restype = C.c_char_p
-    L.gcr_geometry_bytes.restype = C.c_size_t
-    L.gcr_geometry_bytes.argtypes = [C.c_int32]
-    L.gcr_image_bytes.restype = C.c_size_t
-    L.gcr_image_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.gcr_binning_bytes.restype = C.c_size_t
-    L.gcr_binning_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    L.gcr_get_layout.restype = C.c_int
-    L.gcr_get_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(Layout)]
-    L.gcr_forward_preprocess.restype = C.c_int
-    L.gcr_forward_preprocess.argtypes = [C.POINTER(Camera), C.POINTER(Gaussians), C.c_void_p,
-                                         C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
-                                         C.POINTER(FrameInfo), C.c_void_p]
-    L.gcr_forward.restype = C.c_int
-    L.gcr_forward.argtypes = [C.POINTER(Camera), C.POINTER(Gaussians), C.c_void_p, C.c_size_t,
-                              C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
-                              C.c_void_p, C.c_void_p, C.POINTER(FrameInfo), C.c_void_p]
-    L.gcr_binning_bytes_lean.restype = C.c_size_t
-    L.gcr_binning_bytes_lean.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    L.gcr_host_words_alloc.restype = C.c_void_p
-    L.gcr_host_words_alloc.argtypes = [C.c_size_t]
-    L.gcr_host_words_free.restype = None
-    L.gcr_host_words_free.argtypes = [C.c_void_p]
-    L.gcr_forward_async.restype = C.c_int
-    L.gcr_forward_async.argtypes = [C.POINTER(Camera), C.POINTER(Gaussians), C.c_void_p, C.c_size_t,
-                                    C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    L.gcr_ticket_poll.restype = C.c_int
-    L.gcr_ticket_poll.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(FrameInfo)]
-    L.gcr_ticket_wait.restype = C.c_int
-    L.gcr_ticket_wait.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.POINTER(FrameInfo)]
-    L.gcr_rescue_count.restype = C.c_long
-    L.gcr_rescue_dropped_count.restype = C.c_long
-    L.gcr_grad_record_floats_opt.restype = C.c_int
-    L.gcr_grad_record_floats_opt.argtypes = [C.POINTER(Options)]
-    L.gcr_forward_render.restype = C.c_int
-    L.gcr_forward_render.argtypes = [C.POINTER(Camera), C.POINTER(Gaussians), C.c_void_p,
-                                     C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                     C.POINTER(FrameInfo), C.c_void_p, C.c_void_p]
-    L.gcr_backward.restype = C.c_int
-    L.gcr_backward.argtypes = [C.POINTER(Camera), C.POINTER(Gaussians), C.c_void_p, C.c_void_p,
-                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                               C.c_int64, C.c_void_p, C.POINTER(Grads), C.c_void_p]
-    L.gcr_cull_cache_bytes.restype = C.c_size_t
-    L.gcr_cull_cache_bytes.argtypes = [C.c_int32]
-    L.gcr_build_cull_cache.restype = C.c_int
-    L.gcr_build_cull_cache.argtypes = [C.POINTER(Gaussians), C.c_float, C.c_void_p, C.c_void_p]
-    L.gcr_mark_visible.restype = C.c_int
-    L.gcr_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]
-    L.gcr_rasterize_forward.restype = C.c_int64
-    L.gcr_rasterize_forward.argtypes = [RESIZE_FN, C.c_void_p, RESIZE_FN, C.c_void_p, RESIZE_FN,
-                                        C.c_void_p, C.POINTER(Camera), C.POINTER(Gaussians),
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-    L.gcr_set_option.restype = C.c_int
-    L.gcr_set_option.argtypes = [C.c_char_p, C.c_int]
-    L.gcr_get_option.restype = C.c_int
-    L.gcr_get_option.argtypes = [C.c_char_p]
-    L.gcr_get_stage_ms.restype = C.c_int
-    L.gcr_get_stage_ms.argtypes = [C.POINTER(C.c_float), C.c_int]
-    L.gcr_grad_record_floats.restype = C.c_int
-    if L.gcr_grad_record_floats() not in (GRAD_REC_FLOATS, 2 * GRAD_REC_FLOATS):
-        raise RuntimeError("libgcr_hip.so gradient record size mismatch")
-    if L.gcr_abi_version() != ABI_VERSION:
-        raise RuntimeError("libgcr_hip.so ABI version mismatch")
-    _lib = L
-    return L
-
-
-def check(rc, what):
-    if rc < 0:
-        msg = lib().gcr_last_error().decode("utf-8", "replace")
-        raise RuntimeError("%s failed (gcr_status %d): %s" % (what, rc, msg))
-    return rc
 
 
 def get_layout(P, W, H, R):
     out = Layout()
     check(lib().gcr_get_layout(int(P), int(W), int(H), int(R), C.byref(out)), "gcr_get_layout")
     return out
-
-
-def set_option(name, value):
-    return lib().gcr_set_option(name.encode(), int(value))
 
 
 def get_option(name):
@@ -220,9 +161,3 @@ def get_option(name):
     if v == -2 ** 31:
         raise KeyError("unknown rasterizer option %r" % name)
     return v
-
-
-def stage_ms():
-    buf = (C.c_float * len(STAGE_NAMES))()
-    n = lib().gcr_get_stage_ms(buf, len(STAGE_NAMES))
-    return {STAGE_NAMES[i]: float(buf[i]) for i in range(n)}

@@ -1,20 +1,13 @@
-"""ctypes binding of libgcv_hip.so (C ABI in include/gcv.h): point generation / visibility path.
+"""ctypes binding of libgcv_hip.so (C ABI in include/gcv.h): point generation / visibility path.  The declarations;
+gaussiancity_amd/_loader.py loads it.
 
 The library is the product: there is NO Python/CPU fallback -- a missing library or a failing call
 raises RuntimeError.
 """
 import ctypes as C
-import os
 
-_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-LIB_PATH = os.path.join(_CSRC, "libgcv_hip.so")
+from . import _loader
 
-EXPORTED_SYMBOLS = (
-    "gcv_abi_version", "gcv_last_error", "gcv_extrude_scratch_bytes", "gcv_extrude_count", "gcv_extrude_emit",
-    "gcv_maps_to_volume", "gcv_occupancy_bytes", "gcv_points_to_volume", "gcv_build_occupancy", "gcv_bounds_scratch_bytes", "gcv_points_bounds", "gcv_rows_to_volume", "gcv_rows_erase_volume",
-    "gcv_ray_voxel_intersection",
-    "gcv_set_option", "gcv_get_stage_ms",
-)
 STAGE_NAMES = ("extrude_count", "extrude_emit", "volume_clear", "volume_scatter", "occupancy", "traversal")
 ABI_VERSION = 4
 
@@ -25,67 +18,28 @@ class SegIns(C.Structure):
                                          "bldg_facade_semantic_id", "roof_ins_offset")]
 
 
-_lib = None
+_vp, _i32, _i64, _sz, _f32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_int
+_pi32, _pf32, _seg = C.POINTER(_i32), C.POINTER(_f32), C.POINTER(SegIns)
+_SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argtypes)
+    "gcv_abi_version": (_int, []),
+    "gcv_last_error": (C.c_char_p, []),
+    "gcv_extrude_scratch_bytes": (_sz, [_i32, _i32]),
+    "gcv_extrude_count": (_int, [_i32, _vp, _seg, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_i64), _vp]),
+    "gcv_extrude_emit": (_int, [_i32, _vp, _seg, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i64, _vp]),
+    "gcv_maps_to_volume": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "gcv_occupancy_bytes": (_sz, [_i32, _i32, _i32]),
+    "gcv_points_to_volume": (_int, [_i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "gcv_build_occupancy": (_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "gcv_bounds_scratch_bytes": (_sz, []),
+    "gcv_points_bounds": (_int, [_i64, _vp, _i32, _vp, _pi32, _pi32, _vp]),
+    "gcv_rows_to_volume": (_int, [_i64, _vp, _pi32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "gcv_rows_erase_volume": (_int, [_i64, _vp, _pi32, _i32, _i32, _i32, _vp, _vp]),
+    "gcv_ray_voxel_intersection": (_int, [_vp, _pi32, C.POINTER(_i64), _vp, _pf32, _pf32, _pf32, _f32, _pf32, _pi32, _i32,
+                                          _vp, _vp, _vp, _vp]),
+    "gcv_set_option": (_int, [C.c_char_p, _int]),
+    "gcv_get_stage_ms": (_int, [_pf32, _int]),
+}
 
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("libgcv_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C gaussiancity_amd/csrc`. There is no CPU fallback." % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
-    L.gcv_abi_version.restype = C.c_int
-    L.gcv_last_error.restype = C.c_char_p
-    L.gcv_extrude_scratch_bytes.restype = sz
-    L.gcv_extrude_scratch_bytes.argtypes = [i32, i32]
-    L.gcv_extrude_count.restype = C.c_int
-    L.gcv_extrude_count.argtypes = [i32, vp, C.POINTER(SegIns), i32, i32, vp, vp, vp, vp, vp, sz, C.POINTER(i64), vp]
-    L.gcv_extrude_emit.restype = C.c_int
-    L.gcv_extrude_emit.argtypes = [i32, vp, C.POINTER(SegIns), i32, i32, vp, vp, vp, vp, vp, sz, vp, i64, vp]
-    L.gcv_maps_to_volume.restype = C.c_int
-    L.gcv_maps_to_volume.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    L.gcv_occupancy_bytes.restype = sz
-    L.gcv_occupancy_bytes.argtypes = [i32, i32, i32]
-    L.gcv_points_to_volume.restype = C.c_int
-    L.gcv_points_to_volume.argtypes = [i64, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    L.gcv_bounds_scratch_bytes.restype = sz
-    L.gcv_bounds_scratch_bytes.argtypes = []
-    L.gcv_points_bounds.restype = C.c_int
-    L.gcv_points_bounds.argtypes = [i64, vp, i32, vp, C.POINTER(i32), C.POINTER(i32), vp]
-    L.gcv_rows_to_volume.restype = C.c_int
-    L.gcv_rows_to_volume.argtypes = [i64, vp, C.POINTER(i32), i32, i32, i32, vp, vp, i32, vp]
-    L.gcv_rows_erase_volume.restype = C.c_int
-    L.gcv_rows_erase_volume.argtypes = [i64, vp, C.POINTER(i32), i32, i32, i32, vp, vp]
-    L.gcv_build_occupancy.restype = C.c_int
-    L.gcv_build_occupancy.argtypes = [vp, i32, i32, i32, vp, vp]
-    L.gcv_ray_voxel_intersection.restype = C.c_int
-    L.gcv_ray_voxel_intersection.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp, C.POINTER(C.c_float),
-                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
-                                             C.POINTER(C.c_float), C.POINTER(i32), i32, vp, vp, vp, vp]
-    L.gcv_set_option.restype = C.c_int
-    L.gcv_set_option.argtypes = [C.c_char_p, C.c_int]
-    L.gcv_get_stage_ms.restype = C.c_int
-    L.gcv_get_stage_ms.argtypes = [C.POINTER(C.c_float), C.c_int]
-    if L.gcv_abi_version() != ABI_VERSION:
-        raise RuntimeError("libgcv_hip.so ABI version mismatch")
-    _lib = L
-    return L
-
-
-def check(rc, what):
-    if rc < 0:
-        raise RuntimeError("%s failed (gcv_status %d): %s" % (what, rc, lib().gcv_last_error().decode("utf-8", "replace")))
-    return rc
-
-
-def set_option(name, value):
-    return lib().gcv_set_option(name.encode(), int(value))
-
-
-def stage_ms():
-    buf = (C.c_float * len(STAGE_NAMES))()
-    n = lib().gcv_get_stage_ms(buf, len(STAGE_NAMES))
-    return {STAGE_NAMES[i]: float(buf[i]) for i in range(n)}
+_L = _loader.Library("gcv", "libgcv_hip.so", ABI_VERSION, _SIGNATURES, STAGE_NAMES)
+LIB_PATH, EXPORTED_SYMBOLS = _L.path, _L.exported_symbols
+lib, check, set_option, stage_ms = _L.lib, _L.check, _L.set_option, _L.stage_ms

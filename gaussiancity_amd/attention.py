@@ -6,17 +6,13 @@ torch supplies device memory (the caching allocator), autograd plumbing and the 
 is in the HIP library, and nothing here waits for the device or reads cu_seqlens on the host.  The flash_attn
 module at the repository root is the drop-in that models/pt_v3.py imports.
 """
-import ctypes as C
 
 import torch
 
 from . import _native_a as A
+from ._loader import current_stream as _stream
 
 SUPPORTED_HEAD_DIMS = A.HEAD_DIMS
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _kernel_ready(t):

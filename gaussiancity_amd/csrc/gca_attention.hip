@@ -26,20 +26,10 @@
 #include <string>
 
 #include "../../include/gca.h"
+#define GC_ERR_HIP GCA_ERR_HIP
+#include "gc_host.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr, where)                                                                           \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(GCA_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 typedef _Float16 half_t;
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));

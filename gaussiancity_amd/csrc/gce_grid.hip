@@ -22,64 +22,16 @@
 #include <string>
 
 #include "../../include/gce.h"
+#define GC_ERR_HIP GCE_ERR_HIP
+#include "gc_host.h"
 
 namespace {
 
-thread_local std::string g_err;
 std::atomic<int> g_timing{0};
 
-int fail(int code, const char* msg) {
-  g_err = msg;
-  return code;
-}
-int fail_hip(hipError_t e, const char* where) {
-  g_err = std::string(where) + ": " + hipGetErrorString(e);
-  return GCE_ERR_HIP;
-}
-#define HIP_TRY(expr, where)                          \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return fail_hip(e_, where); \
-  } while (0)
-
 enum Stage { ST_FWD = 0, ST_BWD_EMB, ST_BWD_IN, ST_N };
-struct StageSlot {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool pending = false;
-  double ms = 0.0;
-  int n = 0;
-};
-StageSlot g_slots[ST_N];
-void stage_resolve(StageSlot& s) {
-  if (!s.pending) return;
-  if (hipEventSynchronize(s.b) == hipSuccess) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) {
-      s.ms += ms;
-      s.n++;
-    }
-  }
-  s.pending = false;
-}
-struct StageTimer {
-  hipStream_t s;
-  StageSlot* sl = nullptr;
-  StageTimer(hipStream_t s_, int stage) : s(s_) {
-    if (g_timing.load() == 0) return;
-    sl = &g_slots[stage];
-    if (!sl->a) {
-      (void)hipEventCreate(&sl->a);
-      (void)hipEventCreate(&sl->b);
-    }
-    stage_resolve(*sl);
-    (void)hipEventRecord(sl->a, s);
-  }
-  ~StageTimer() {
-    if (!sl) return;
-    (void)hipEventRecord(sl->b, s);
-    sl->pending = true;
-  }
-};
+StageSlot g_slots[ST_N];  // process-wide: the stages of every thread (gc_host.h)
+StageSlot* stage_slot(int stage) { return g_timing.load() ? &g_slots[stage] : nullptr; }
 
 struct LevelScales {
   float v[GCE_MAX_LEVELS];
@@ -535,7 +487,7 @@ static int forward_typed(const float* inputs, const void* embeddings, const int3
                          uint32_t D, uint32_t C, uint32_t L, const LevelScales& sc, int calc_grad_inputs, void* dy_dx,
                          uint32_t gridtype, int align_corners, hipStream_t s) {
   const dim3 grid((B + 255) / 256, L, 1);
-  StageTimer t(s, ST_FWD);
+  StageTimer t(s, stage_slot(ST_FWD));
   GCE_DISPATCH_DC(D, C, (k_grid_fwd_t<T, D, C><<<grid, 256, 0, s>>>(inputs, (const T*)embeddings, offsets, (T*)outputs, B, L, sc,
                                                                   calc_grad_inputs != 0, (T*)dy_dx, gridtype, align_corners != 0)))
   return 0;
@@ -546,12 +498,12 @@ static int backward_typed(const void* grad, const float* inputs, const int32_t* 
                           void* grad_inputs, uint32_t gridtype, int align_corners, hipStream_t s) {
   const dim3 grid((unsigned)(((uint64_t)B * C + 255) / 256), L, 1);
   {
-    StageTimer t(s, ST_BWD_EMB);
+    StageTimer t(s, stage_slot(ST_BWD_EMB));
     GCE_DISPATCH_DC(D, C, (k_grid_bwd_t<T, D, C><<<grid, 256, 0, s>>>((const T*)grad, inputs, offsets, (T*)grad_embeddings, B, L, sc,
                                                                     gridtype, align_corners != 0)))
   }
   if (calc_grad_inputs) {
-    StageTimer t(s, ST_BWD_IN);
+    StageTimer t(s, stage_slot(ST_BWD_IN));
     GCE_DISPATCH_DC(D, C, (k_input_bwd_t<T, D, C><<<(B * D + 255) / 256, 256, 0, s>>>((const T*)grad, (const T*)dy_dx,
                                                                                     (T*)grad_inputs, B, L)))
   }
@@ -568,17 +520,7 @@ int gce_set_option(const char* name, int value) {
   if (!strcmp(name, "timing")) return g_timing.exchange(value);
   return -1;
 }
-int gce_get_stage_ms(float* out, int n) {
-  if (!out) return 0;
-  int k = 0;
-  for (; k < n && k < ST_N; k++) {
-    stage_resolve(g_slots[k]);
-    out[k] = g_slots[k].n ? (float)(g_slots[k].ms / g_slots[k].n) : 0.0f;
-    g_slots[k].ms = 0.0;
-    g_slots[k].n = 0;
-  }
-  return k;
-}
+int gce_get_stage_ms(float* out, int n) { return stage_report(g_slots, ST_N, out, n); }
 
 int gce_level_scales(uint32_t L, float S, uint32_t H, float* scales_host) {
   if (!scales_host || L > GCE_MAX_LEVELS) return fail(GCE_ERR_INVALID_ARGUMENT, "gce_level_scales: bad arguments");
@@ -598,7 +540,7 @@ int gce_forward(const float* inputs, const float* embeddings, const int32_t* off
   hipStream_t s = (hipStream_t)hip_stream;
   const dim3 grid((B + 255) / 256, L, 1);
   {
-    StageTimer t(s, ST_FWD);
+    StageTimer t(s, stage_slot(ST_FWD));
     GCE_DISPATCH_DC(D, C, (k_grid_fwd<D, C><<<grid, 256, 0, s>>>(inputs, embeddings, offsets, outputs, B, L, sc,
                                                                calc_grad_inputs != 0, dy_dx, gridtype, align_corners != 0)))
   }
@@ -621,13 +563,13 @@ int gce_backward(const float* grad, const float* inputs, const float* embeddings
   hipStream_t s = (hipStream_t)hip_stream;
   const dim3 grid((unsigned)(((uint64_t)B * C + 255) / 256), L, 1);
   {
-    StageTimer t(s, ST_BWD_EMB);
+    StageTimer t(s, stage_slot(ST_BWD_EMB));
     GCE_DISPATCH_DC(D, C, (k_grid_bwd<D, C><<<grid, 256, 0, s>>>(grad, inputs, offsets, grad_embeddings, B, L, sc, gridtype,
                                                                align_corners != 0)))
   }
   HIP_TRY(hipGetLastError(), "grid backward launch");
   if (calc_grad_inputs) {
-    StageTimer t(s, ST_BWD_IN);
+    StageTimer t(s, stage_slot(ST_BWD_IN));
     GCE_DISPATCH_DC(D, C, (k_input_bwd<D, C><<<(B * D + 255) / 256, 256, 0, s>>>(grad, dy_dx, grad_inputs, B, L)))
     HIP_TRY(hipGetLastError(), "input backward launch");
   }

@@ -15,10 +15,11 @@
 #include <pthread.h>
 
 #include "gcr_internal.h"
+#define GC_ERR_HIP GCR_ERR_DEVICE
+#include "gc_host.h"
 
 namespace {
 
-thread_local std::string g_err;
 std::atomic<int> g_timing{0};
 std::atomic<int> g_force_radix{0};
 std::atomic<int> g_force_global_cursor{0};
@@ -114,10 +115,6 @@ Opts resolve_options(const gcr_options* o) {
 
 enum Stage { ST_PRE = 0, ST_SCAN, ST_EMIT, ST_SORT, ST_RANGES, ST_BLEND_FWD, ST_BLEND_BWD, ST_PRE_BWD, ST_COUNT };
 
-int fail(gcr_status code, const std::string& msg) {
-  g_err = msg;
-  return (int)code;
-}
 // num_rendered as a frame word reports it (the device word, or the low half of a host word seq << 32 | R): the mark of
 // gcr_camera.prefiltered and a Gaussian behind the near plane (gcr_internal.h GCR_PREFILTER_MARK, the reference's words),
 // or a count beyond the 32-bit instance index, is an error
@@ -128,15 +125,6 @@ int check_num_rendered(unsigned long long R) {
     return fail(GCR_ERR_OVERFLOW, "num_rendered exceeds 2^31-1 (32-bit instance index, as in the reference)");
   return 0;
 }
-int fail_hip(hipError_t e, const char* where) {
-  g_err = std::string(where) + ": " + hipGetErrorString(e);
-  return (int)GCR_ERR_DEVICE;
-}
-#define HIP_TRY(expr, where)                      \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail_hip(_e, where); \
-  } while (0)
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
@@ -155,54 +143,9 @@ inline void gcr_cpu_relax() {
 // threshold leaves room for the longest list to grow from one frame to the next.
 constexpr int64_t GCR_SORT_IN_BLEND_MAX = 384;
 
-// Stage timer: pairs of hipEvents per stage recorded on the caller's stream, a ring of STAGE_RING pairs per stage.
-// Non-blocking in practice: a pair is resolved when its ring slot comes round again, STAGE_RING frames later, and no
-// caller keeps that many frames in flight (one pair per stage made the host wait for the PREVIOUS frame's stage
-// before it could enqueue this frame's -- with three frames in flight that wait thinned out the overlap and the
-// timed kernels looked a third shorter than a rocprofv3 trace of the uninstrumented loop shows them).
-// gcr_get_stage_ms() resolves what is pending and reports the average per stage since the last call.
-constexpr int STAGE_RING = 8;
-struct StageSlot {
-  hipEvent_t a[STAGE_RING] = {}, b[STAGE_RING] = {};
-  bool pending[STAGE_RING] = {};
-  int next = 0;
-  double sum_ms = 0.0;
-  long count = 0;
-};
+// Stage timer (gc_host.h); the slots are this thread's: gcr_get_stage_ms() reports the stages this thread enqueued.
 thread_local StageSlot g_slots[ST_COUNT];
-
-void stage_resolve(StageSlot& sl, int i) {
-  if (!sl.pending[i]) return;
-  float ms = 0;
-  if (hipEventSynchronize(sl.b[i]) == hipSuccess && hipEventElapsedTime(&ms, sl.a[i], sl.b[i]) == hipSuccess) {
-    sl.sum_ms += ms;
-    sl.count += 1;
-  }
-  sl.pending[i] = false;
-}
-
-struct StageTimer {
-  hipStream_t s;
-  StageSlot* sl = nullptr;
-  int i = 0;
-  StageTimer(hipStream_t s_, int stage) : s(s_) {
-    if (g_timing.load() == 0) return;
-    sl = &g_slots[stage];
-    i = sl->next;
-    sl->next = (i + 1) % STAGE_RING;
-    if (!sl->a[i]) {
-      (void)hipEventCreate(&sl->a[i]);
-      (void)hipEventCreate(&sl->b[i]);
-    }
-    stage_resolve(*sl, i);
-    (void)hipEventRecord(sl->a[i], s);
-  }
-  ~StageTimer() {
-    if (!sl) return;
-    (void)hipEventRecord(sl->b[i], s);
-    sl->pending[i] = true;
-  }
-};
+StageSlot* stage_slot(int stage) { return g_timing.load() ? &g_slots[stage] : nullptr; }
 
 int debug_sync(const gcr_camera* cam, hipStream_t s, const char* where) {
   if (cam->debug) {  // cr/auxiliary.h:158-167
@@ -470,17 +413,7 @@ int gcr_get_option(const char* name) {
   return o ? o->global->load() : INT32_MIN;
 }
 
-int gcr_get_stage_ms(float* ms_out, int capacity) {
-  int n = capacity < (int)ST_COUNT ? capacity : (int)ST_COUNT;
-  for (int i = 0; i < n; i++) {
-    StageSlot& sl = g_slots[i];
-    for (int k = 0; k < STAGE_RING; k++) stage_resolve(sl, k);
-    ms_out[i] = sl.count ? (float)(sl.sum_ms / (double)sl.count) : 0.0f;
-    sl.sum_ms = 0.0;
-    sl.count = 0;
-  }
-  return n;
-}
+int gcr_get_stage_ms(float* ms_out, int capacity) { return stage_report(g_slots, ST_COUNT, ms_out, capacity); }
 
 // May the band-sorted survivor numbering use gcr_layout.geom_tiles_touched on this frame?  (Decided where the tiles are
 // counted; the count kernel records the answer in frame[GCR_FRAME_BANDED], and the scatter follows that word.)
@@ -519,13 +452,13 @@ static int enqueue_preprocess(const Opts& op, const gcr_camera* cam, const gcr_g
   const int T = f.T;
   if (f.NG > 0) a.tile_count = nullptr;  // default: per-tile counts are built in LDS tables after K1 (no global atomics)
   {
-    StageTimer t(s, ST_PRE);
+    StageTimer t(s, stage_slot(ST_PRE));
     if (f.NG == 0)
       HIP_TRY(hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t) * GCR_CURSOR_STRIDE * (size_t)T, s), "tile count memset");
     HIP_TRY(gcr_launch_preprocess(a, op.split_preprocess != 0, s), "preprocess");
   }
   if (int rc = debug_sync(cam, s, "preprocess")) return rc;
-  StageTimer t(s, ST_SCAN);
+  StageTimer t(s, stage_slot(ST_SCAN));
   if (f.NG > 0) {
     // Band sort for frames expected to hold many instances (the caller's capacity guess: ~0 = no guess, the staged entry
     // point): the renumbered survivors go where only K1a's candidates (split mode) and the radix fallback keep anything
@@ -587,7 +520,7 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
   uint64_t* pairs = f.keys[0];
   const unsigned long long* frame_guard = speculative ? f.frame : nullptr;
   {
-    StageTimer t(s, ST_EMIT);
+    StageTimer t(s, stage_slot(ST_EMIT));
     if (f.NG > 0) {
       // also rebuilds `ranges` from the block totals, so it runs even when nothing is rendered
       HIP_TRY(gcr_launch_tile_scatter(f.T, f.gx, f.NG, f.G, f.nblocks, f.chunk, f.vis_rec, f.vis_count, f.table, f.cursor,
@@ -609,7 +542,7 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
   const bool sort_in_blend = R_layout > 0 && list_length_hint <= GCR_SORT_IN_BLEND_MAX && op.sort_in_blend != 0;
   uint4* lazy = (R_layout > 0 && !sort_in_blend && op.lazy_sort != 0) ? f.lazy : nullptr;
   if (R_layout > 0 && !sort_in_blend) {
-    StageTimer t(s, ST_SORT);
+    StageTimer t(s, stage_slot(ST_SORT));
     // LDS of the sort sized for 1.5x the expected longest list (longer ones take its run + merge path)
     HIP_TRY(gcr_launch_tile_sort(f.ranges, f.T, pairs, f.keys[1], f.list, list_length_hint + list_length_hint / 2 + 64,
                                  frame_guard, lazy, s),
@@ -644,7 +577,7 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
   }
 #endif
   {
-    StageTimer t(s, ST_BLEND_FWD);
+    StageTimer t(s, stage_slot(ST_BLEND_FWD));
     HIP_TRY(gcr_launch_blend_fwd(b, sort_in_blend, s), "blend forward");
   }
 #ifdef GCR_EXPERIMENTS
@@ -1168,7 +1101,7 @@ int gcr_forward_render(const gcr_camera* cam, const gcr_gaussians* g, void* geom
   // order, stable global radix sort, boundary scan.
   int half = (int)f.L.bin_sorted;
   {
-    StageTimer t(s, ST_EMIT);
+    StageTimer t(s, stage_slot(ST_EMIT));
     HIP_TRY(gcr_launch_tiles_touched(g->P, f.nblocks, f.chunk, f.vis_list, f.vis_count, f.rec, f.tiles_touched, f.block_sums, s),
             "tiles touched");
     HIP_TRY(gcr_launch_scan_block_sums(f.block_sums, (g->P + 255) / 256, (unsigned long long*)f.hist, s), "scan");
@@ -1176,13 +1109,13 @@ int gcr_forward_render(const gcr_camera* cam, const gcr_gaussians* g, void* geom
   }
   if (int rc = debug_sync(cam, s, "emit")) return rc;
   {
-    StageTimer t(s, ST_SORT);
+    StageTimer t(s, stage_slot(ST_SORT));
     const int end_bit = 32 + (int)gcr_higher_msb((uint32_t)f.T);  // cr/rasterizer_impl.cu:252
     HIP_TRY(gcr_launch_sort(f.keys[0], f.vals[0], f.keys[1], f.vals[1], R, end_bit, f.hist, &half, s), "sort");
   }
   if (int rc = debug_sync(cam, s, "sort")) return rc;
   {
-    StageTimer t(s, ST_RANGES);
+    StageTimer t(s, stage_slot(ST_RANGES));
     HIP_TRY(gcr_launch_tile_ranges(f.keys[half], R, f.ranges, f.T, s), "tile ranges");
   }
   if (int rc = debug_sync(cam, s, "tile ranges")) return rc;
@@ -1190,7 +1123,7 @@ int gcr_forward_render(const gcr_camera* cam, const gcr_gaussians* g, void* geom
   b.out_color = out_color;
   set_piece_args(op, b, cam->backward == 1, f);
   {
-    StageTimer t(s, ST_BLEND_FWD);
+    StageTimer t(s, stage_slot(ST_BLEND_FWD));
     HIP_TRY(gcr_launch_blend_fwd(b, false, s), "blend forward");
   }
   return debug_sync(cam, s, "blend forward");
@@ -1271,7 +1204,7 @@ int gcr_backward(const gcr_camera* cam, const gcr_gaussians* g, const int32_t* r
   }
 
   if (R > 0) {
-    StageTimer t(s, ST_BLEND_BWD);  // one slot per stage: a second timer of the same stage would halve the average
+    StageTimer t(s, stage_slot(ST_BLEND_BWD));  // one slot per stage: a second timer of the same stage would halve the average
     HIP_TRY(gcr_launch_zero_grad_records(f.nblocks, f.chunk, f.vis_list, f.vis_count, (float4*)gr->dL_dconic,
                                          (det ? GCR_GRAD_REC_FLOATS_DET : GCR_GRAD_REC_FLOATS) / 4, s),
             "zero gradient records");
@@ -1320,7 +1253,7 @@ int gcr_backward(const gcr_camera* cam, const gcr_gaussians* g, const int32_t* r
   a.g_scale = stride_or(gr->stride_scales, 3);
   a.g_rot = stride_or(gr->stride_rotations, 4);
   {
-    StageTimer t(s, ST_PRE_BWD);
+    StageTimer t(s, stage_slot(ST_PRE_BWD));
     HIP_TRY(gcr_launch_preprocess_bwd(a, s), "preprocess backward");
   }
   return debug_sync(cam, s, "preprocess backward");

@@ -20,20 +20,10 @@
 #include <string>
 
 #include "../../include/gcs.h"
+#define GC_ERR_HIP GCS_ERR_HIP
+#include "gc_host.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr, where)                                                                     \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(GCS_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr uint64_t kEmpty = ~0ull;
 constexpr int kScanThreads = 256;

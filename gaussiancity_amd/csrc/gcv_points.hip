@@ -18,66 +18,18 @@
 #include <string>
 
 #include "../../include/gcv.h"
+#define GC_ERR_HIP GCV_ERR_HIP
+#include "gc_host.h"
 
 namespace {
 
-thread_local std::string g_err;
 std::atomic<int> g_timing{0};
 std::atomic<int> g_entry_jump{1};  // option "entry_jump": closed-form walk from the camera to the grid (A/B knob)
 
-int fail(int code, const char* msg) {
-  g_err = msg;
-  return code;
-}
-int fail_hip(hipError_t e, const char* where) {
-  g_err = std::string(where) + ": " + hipGetErrorString(e);
-  return GCV_ERR_HIP;
-}
-#define HIP_TRY(expr, where)                          \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return fail_hip(e_, where); \
-  } while (0)
-
 // ---- stage timers (non-blocking; resolved lazily) ---------------------------------------------
 enum Stage { ST_COUNT = 0, ST_EMIT, ST_CLEAR, ST_SCATTER, ST_OCC, ST_TRAVERSE, ST_N };
-struct StageSlot {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool pending = false;
-  double ms = 0.0;
-  int n = 0;
-};
-StageSlot g_slots[ST_N];
-void stage_resolve(StageSlot& s) {
-  if (!s.pending) return;
-  if (hipEventSynchronize(s.b) == hipSuccess) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) {
-      s.ms += ms;
-      s.n++;
-    }
-  }
-  s.pending = false;
-}
-struct StageTimer {
-  hipStream_t s;
-  StageSlot* sl = nullptr;
-  StageTimer(hipStream_t s_, int stage) : s(s_) {
-    if (g_timing.load() == 0) return;
-    sl = &g_slots[stage];
-    if (!sl->a) {
-      (void)hipEventCreate(&sl->a);
-      (void)hipEventCreate(&sl->b);
-    }
-    stage_resolve(*sl);
-    (void)hipEventRecord(sl->a, s);
-  }
-  ~StageTimer() {
-    if (!sl) return;
-    (void)hipEventRecord(sl->b, s);
-    sl->pending = true;
-  }
-};
+StageSlot g_slots[ST_N];  // process-wide: the stages of every thread (gc_host.h)
+StageSlot* stage_slot(int stage) { return g_timing.load() ? &g_slots[stage] : nullptr; }
 
 // =============================================================================================== K15
 // fe/:143-213 is a serial triple loop on the host.  Here:
@@ -820,17 +772,7 @@ int gcv_set_option(const char* name, int value) {
   return -1;
 }
 
-int gcv_get_stage_ms(float* out, int n) {
-  if (!out) return 0;
-  int k = 0;
-  for (; k < n && k < ST_N; k++) {
-    stage_resolve(g_slots[k]);
-    out[k] = g_slots[k].n ? (float)(g_slots[k].ms / g_slots[k].n) : 0.0f;
-    g_slots[k].ms = 0.0;
-    g_slots[k].n = 0;
-  }
-  return k;
-}
+int gcv_get_stage_ms(float* out, int n) { return stage_report(g_slots, ST_N, out, n); }
 
 size_t gcv_extrude_scratch_bytes(int32_t height, int32_t width) {
   const size_t npix = (size_t)(height > 0 ? height : 0) * (size_t)(width > 0 ? width : 0);
@@ -849,7 +791,7 @@ int gcv_extrude_count(int32_t inc_btm, const int16_t* lut, const gcv_seg_ins* m,
   const unsigned long long init[2] = {0ull, ~0ull};
   HIP_TRY(hipMemcpyAsync(sc, init, sizeof(init), hipMemcpyHostToDevice, s), "extrude scratch init");
   {
-    StageTimer t(s, ST_COUNT);
+    StageTimer t(s, stage_slot(ST_COUNT));
     k_extrude_count<<<nblocks, EX_BLOCK, 0, s>>>(a, sc);
     k_extrude_scan<<<1, 1024, 0, s>>>(sc, nblocks);
   }
@@ -878,7 +820,7 @@ int gcv_extrude_emit(int32_t inc_btm, const int16_t* lut, const gcv_seg_ins* m, 
   hipStream_t s = (hipStream_t)hip_stream;
   const int nblocks = (int)(((size_t)H * W + EX_BLOCK - 1) / EX_BLOCK);
   {
-    StageTimer t(s, ST_EMIT);
+    StageTimer t(s, stage_slot(ST_EMIT));
     k_extrude_emit<<<nblocks, EX_BLOCK, 0, s>>>(a, (const unsigned long long*)scratch, points_out, (long long)n_points);
   }
   HIP_TRY(hipGetLastError(), "extrude emit launch");
@@ -924,12 +866,12 @@ int gcv_points_to_volume(int64_t n, const int16_t* points, const int32_t* pt_ids
   if (n < 0 || (n > 0 && (!points || !pt_ids || !scales))) return fail(GCV_ERR_INVALID_ARGUMENT, "null point arrays");
   hipStream_t s = (hipStream_t)hip_stream;
   {
-    StageTimer t(s, ST_CLEAR);
+    StageTimer t(s, stage_slot(ST_CLEAR));
     HIP_TRY(hipMemsetAsync(volume, 0, sizeof(int32_t) * (size_t)h * w * d, s), "volume clear");
     if (occupancy) HIP_TRY(hipMemsetAsync(occupancy, 0, gcv_occupancy_bytes(h, w, d), s), "occupancy clear");
   }
   if (n > 0) {
-    StageTimer t(s, ST_SCATTER);
+    StageTimer t(s, stage_slot(ST_SCATTER));
     k_points_to_volume<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)n, h, w, d, points, pt_ids, scales, volume,
                                                                   occupancy);
     HIP_TRY(hipGetLastError(), "points_to_volume launch");
@@ -965,7 +907,7 @@ int gcv_rows_erase_volume(int64_t n, const int16_t* rows, const int32_t offset[3
   if (n < 0 || (n > 0 && !rows)) return fail(GCV_ERR_INVALID_ARGUMENT, "null rows");
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)hip_stream;
-  StageTimer t(s, ST_CLEAR);
+  StageTimer t(s, stage_slot(ST_CLEAR));
   k_rows_to_volume<true><<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)n, h, w, d, rows, offset[0], offset[1],
                                                                     offset[2], volume, nullptr);
   HIP_TRY(hipGetLastError(), "rows_erase_volume launch");
@@ -980,12 +922,12 @@ int gcv_rows_to_volume(int64_t n, const int16_t* rows, const int32_t offset[3], 
   if (n >= 2147483647ll) return fail(GCV_ERR_INVALID_ARGUMENT, "more than 2^31-2 points (ids are int32, dataset_generator.py:1381)");
   hipStream_t s = (hipStream_t)hip_stream;
   if (!volume_is_zero) {
-    StageTimer t(s, ST_CLEAR);
+    StageTimer t(s, stage_slot(ST_CLEAR));
     HIP_TRY(hipMemsetAsync(volume, 0, sizeof(int32_t) * (size_t)h * w * d, s), "volume clear");
   }
   if (occupancy) HIP_TRY(hipMemsetAsync(occupancy, 0, gcv_occupancy_bytes(h, w, d), s), "occupancy clear");
   if (n > 0) {
-    StageTimer t(s, ST_SCATTER);
+    StageTimer t(s, stage_slot(ST_SCATTER));
     k_rows_to_volume<false><<<(unsigned)((n + 255) / 256), 256, 0, s>>>((long long)n, h, w, d, rows, offset[0], offset[1],
                                                                 offset[2], volume, occupancy);
     HIP_TRY(hipGetLastError(), "rows_to_volume launch");
@@ -997,7 +939,7 @@ int gcv_build_occupancy(const int32_t* volume, int32_t h, int32_t w, int32_t d, 
   if (h <= 0 || w <= 0 || d <= 0) return fail(GCV_ERR_INVALID_ARGUMENT, "volume dimensions must be positive");
   if (!volume || !occupancy) return fail(GCV_ERR_INVALID_ARGUMENT, "null volume / occupancy");
   hipStream_t s = (hipStream_t)hip_stream;
-  StageTimer t(s, ST_OCC);
+  StageTimer t(s, stage_slot(ST_OCC));
   HIP_TRY(hipMemsetAsync(occupancy, 0, gcv_occupancy_bytes(h, w, d), s), "occupancy clear");
   const long long threads = (long long)h * w * ((d + 15) >> 4);
   k_build_occ<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(volume, h, w, d, occupancy);
@@ -1041,7 +983,7 @@ int gcv_ray_voxel_intersection(const int32_t* volume, const int32_t dims[3], con
   hipStream_t s = (hipStream_t)hip_stream;
   const dim3 grid((img_dims[1] + 7) / 8, (img_dims[0] + 7) / 8, 1);
   {
-    StageTimer t(s, ST_TRAVERSE);
+    StageTimer t(s, stage_slot(ST_TRAVERSE));
     const bool entry = g_entry_jump.load() != 0;
     if (occupancy && entry)
       k_rvip<true, true><<<grid, 64, 0, s>>>(out_voxel_id, out_depth, out_raydirs, volume, occupancy, p);

@@ -10,16 +10,12 @@ torch supplies device memory, autograd plumbing and the current stream; the comp
 library.  The embeddings' dtype selects the kernels as upstream's AT_DISPATCH_FLOATING_TYPES_AND_HALF does
 (grid_encoder_ext.cu:555,597): float32 (GaussianCity's own; the tuned kernels), float16, float64.  `inputs` are float32.
 """
-import ctypes as C
 import math
 
 import torch
 
 from . import _native_e as E
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._loader import current_stream as _stream
 
 
 _DTYPES = {torch.float32: E.DTYPE_F32, torch.float16: E.DTYPE_F16, torch.float64: E.DTYPE_F64}

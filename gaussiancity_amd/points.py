@@ -18,10 +18,7 @@ import scipy.spatial.transform
 import torch
 
 from . import _native_v as V
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._loader import current_stream as _stream
 
 
 def _need_gpu(dev=None):

@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import _native_s as S
+from ._loader import current_stream as _stream
 
 _STATS = {"rulebook_builds": 0}
 
@@ -28,10 +29,6 @@ def stats():
 def reset_stats():
     for k in _STATS:
         _STATS[k] = 0
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _triple(v, name):

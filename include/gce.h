@@ -65,7 +65,8 @@ int gce_backward_t(int dtype, const void* grad, const float* inputs, const void*
                    int calc_grad_inputs, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
                    void* hip_stream);
 
-/* avg device ms per stage since the last call (option "timing"): 0 forward, 1 backward_embeddings, 2 backward_inputs */
+/* avg device ms per stage since the last call (option "timing"; hipEvent pairs on the caller's stream, a ring of 8
+ * pairs per stage): 0 forward, 1 backward_embeddings, 2 backward_inputs */
 int gce_set_option(const char* name, int value);
 int gce_get_stage_ms(float* out, int n);
 

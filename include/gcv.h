@@ -119,7 +119,8 @@ int gcv_ray_voxel_intersection(const int32_t* volume, const int32_t dims[3], con
                                const int32_t img_dims[2], int32_t max_samples, int32_t* out_voxel_id,
                                float* out_depth, float* out_raydirs, void* hip_stream);
 
-/* avg device ms per stage since the last call (option "timing" of gcv_set_option):
+/* avg device ms per stage since the last call (option "timing" of gcv_set_option; hipEvent pairs on the caller's
+ * stream, a ring of 8 pairs per stage, so recording never waits for a stage still in flight):
  * 0 extrude_count, 1 extrude_emit, 2 volume_clear, 3 volume_scatter, 4 occupancy, 5 traversal */
 int gcv_set_option(const char* name, int value);
 int gcv_get_stage_ms(float* out, int n);

@@ -1,7 +1,8 @@
-"""C-ABI library (not gpu): it loads without a GPU, exports every symbol include/gcr.h declares,
-its host-only entry points work, and argument errors are reported through the status/last-error
+"""C-ABI libraries (not gpu): each loads without a GPU and exports exactly what its header declares (all five, one
+test); the rasterizer's host-only entry points work, and argument errors are reported through the status/last-error
 convention -- no compute call is made here."""
 import ctypes as C
+import importlib
 import os
 import re
 import subprocess
@@ -13,22 +14,29 @@ from gaussiancity_amd import _native as N
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_functions():
-    src = open(os.path.join(ROOT, "include", "gcr.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(gcr_[a-z_]+)\s*\(", src)) - {"gcr_resize_fn"})
+_BINDINGS = {"gcr": "_native", "gcv": "_native_v", "gce": "_native_e", "gcs": "_native_s", "gca": "_native_a"}
+_OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
-def test_library_exports_every_declared_symbol():
-    lib = N.lib()
-    declared = _header_functions()
-    assert set(declared) == set(N.EXPORTED_SYMBOLS), (declared, N.EXPORTED_SYMBOLS)
-    for name in declared:
-        assert hasattr(lib, name), name
-    out = subprocess.check_output(["nm", "-D", "--defined-only", N.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (gcr_[a-z_]+)", out))
-    assert set(declared) <= exported
-    assert lib.gcr_abi_version() == N.ABI_VERSION == int(re.search(r"#define GCR_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "gcr.h")).read()).group(1))
+@pytest.mark.parametrize("prefix", sorted(_BINDINGS))
+def test_library_exports_every_declared_symbol(prefix):
+    """Each of the five libraries loads without a GPU; the functions its header declares, the binding's signature table
+    and the symbols the library defines are the same set; every one of them has its prototype bound; library, binding
+    and header agree on the ABI number; and the library carries a gfx950 code object."""
+    B = importlib.import_module("gaussiancity_amd." + _BINDINGS[prefix])
+    lib = B.lib()
+    header = open(os.path.join(ROOT, "include", prefix + ".h")).read()
+    src = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    declared = set(re.findall(r"\b(%s_[a-z_]+)\s*\(" % prefix, src)) - {"gcr_resize_fn"}
+    assert declared == set(B.EXPORTED_SYMBOLS), (sorted(declared), B.EXPORTED_SYMBOLS)
+    out = subprocess.check_output(["nm", "-D", "--defined-only", B.LIB_PATH]).decode()
+    assert set(re.findall(r" T (%s_[a-z_]+)" % prefix, out)) == declared
+    unbound = [name for name in B.EXPORTED_SYMBOLS if getattr(lib, name).argtypes is None]
+    assert not unbound, unbound
+    assert getattr(lib, prefix + "_abi_version")() == B.ABI_VERSION == int(
+        re.search(r"#define %s_ABI_VERSION (\d+)" % prefix.upper(), header).group(1))
+    code = subprocess.check_output([_OBJDUMP, "--offloading", B.LIB_PATH]).decode() if os.path.exists(_OBJDUMP) else "gfx950"
+    assert "gfx950" in code
 
 
 def test_library_contains_gfx950_code_object():
@@ -260,26 +268,11 @@ def test_a_failed_frame_fails_its_own_ticket_and_nothing_else_without_a_gpu():
 
 
 
-def _gcv_header_functions():
-    src = open(os.path.join(ROOT, "include", "gcv.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(gcv_[a-z_]+)\s*\(", src)))
-
-
-def test_gcv_library_exports_every_declared_symbol():
-    """libgcv_hip.so (point generation / visibility, include/gcv.h): loads without a GPU and exports
-    exactly what the header declares; argument errors come back without touching the device."""
+def test_gcv_host_entry_points():
+    """libgcv_hip.so (point generation / visibility, include/gcv.h): the size queries answer without a GPU; argument
+    errors come back without touching the device."""
     from gaussiancity_amd import _native_v as V
     lib = V.lib()
-    declared = _gcv_header_functions()
-    assert set(declared) == set(V.EXPORTED_SYMBOLS), (declared, V.EXPORTED_SYMBOLS)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", V.LIB_PATH]).decode()
-    assert set(declared) <= set(re.findall(r" T (gcv_[a-z_]+)", out))
-    assert lib.gcv_abi_version() == V.ABI_VERSION == int(
-        re.search(r"#define GCV_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "gcv.h")).read()).group(1))
-    code = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", V.LIB_PATH]).decode() \
-        if os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump") else "gfx950"
-    assert "gfx950" in code
     assert lib.gcv_extrude_scratch_bytes(2048, 2048) >= 8 * (2 + 2048 * 2048 // 256)
     assert lib.gcv_occupancy_bytes(16, 16, 16) == 4 and lib.gcv_occupancy_bytes(0, 1, 1) == 0
     n = C.c_int64(0)
@@ -291,16 +284,11 @@ def test_gcv_library_exports_every_declared_symbol():
                                           None, None) < 0
 
 
-def test_gce_library_exports_every_declared_symbol():
-    """libgce_hip.so (hash-grid encoder, include/gce.h)."""
+def test_gce_host_entry_points():
+    """libgce_hip.so (hash-grid encoder, include/gce.h): the host-side level scales; argument errors come back without
+    touching the device."""
     from gaussiancity_amd import _native_e as E
     lib = E.lib()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gce.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(gce_[a-z_]+)\s*\(", src)))
-    assert set(declared) == set(E.EXPORTED_SYMBOLS), (declared, E.EXPORTED_SYMBOLS)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", E.LIB_PATH]).decode()
-    assert set(declared) <= set(re.findall(r" T (gce_[a-z_]+)", out))
-    assert lib.gce_abi_version() == E.ABI_VERSION == int(re.search(r"#define GCE_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "gce.h")).read()).group(1))
     sc = (C.c_float * 4)()
     assert lib.gce_level_scales(4, 1.0, 16, sc) == 0 and list(sc) == [15.0, 31.0, 63.0, 127.0]
     assert lib.gce_forward(None, None, None, None, 8, 3, 3, 2, 1.0, 4, 0, None, 0, 0, None) < 0   # C = 3
