@@ -296,7 +296,7 @@ FrameSetup frame_setup(const Opts& op, int32_t P, const gcr_camera* cam, int64_t
   f.gx = (cam->img_w + GCR_BLOCK_X - 1) / GCR_BLOCK_X;
   f.gy = (cam->img_h + GCR_BLOCK_Y - 1) / GCR_BLOCK_Y;
   f.T = f.gx * f.gy;
-  gcr_preprocess_grid(P, gcr_preprocess_resident_blocks(false), &f.nblocks, &f.chunk);
+  gcr_preprocess_grid(P, gcr_preprocess_resident_blocks(), &f.nblocks, &f.chunk);
   f.G = 1;
   f.NG = op.force_global_cursor ? 0 : gcr_tile_table_groups(f.T, f.nblocks, &f.G);
   f.rec = at<float4>(geom, L.geom_rec);

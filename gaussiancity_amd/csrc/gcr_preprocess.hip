@@ -102,6 +102,13 @@ GCR_DEV void compute_cov3d(const V3 scale, float mod, const float4 rot, float (&
 #undef GCR_SIG
 }
 
+// The view depth exactly as transformPoint4x3 computes it, and in_frustum's only test on it (cr/auxiliary.h:145): K0, the
+// cull's phase A0 and gcr_camera.prefiltered all ask this one question.
+GCR_DEV float gcr_view_depth(const float* __restrict__ vm, const V3 p) {
+  return vm[2] * p.x + vm[6] * p.y + vm[10] * p.z + vm[14];
+}
+GCR_DEV bool gcr_behind_near_plane(const float* __restrict__ vm, const V3 p) { return gcr_view_depth(vm, p) <= 0.2f; }
+
 // ------------------------------------------------------------------------------------- K0
 // cr/rasterizer_impl.cu:52-62 with in_frustum of cr/auxiliary.h:135-156 (near plane only).
 __global__ __launch_bounds__(256) void k_mark_visible(int P, const float* __restrict__ means3D,
@@ -110,26 +117,27 @@ __global__ __launch_bounds__(256) void k_mark_visible(int P, const float* __rest
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= P) return;
   const V3 p = {means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]};
-  const V3 pv = transform_point_4x3(p, view);
-  present[idx] = !(pv.z <= 0.2f);
+  present[idx] = !gcr_behind_near_plane(view, p);
 }
 
 // ------------------------------------------------------------------------------------- K1
-// cr/forward.cu:147-233, split in two for wave64 lane efficiency.  In city-scale frames only a few
-// percent of the Gaussians survive culling, and the exact per-Gaussian math (~460 VALU ops: IEEE
-// divisions, sqrt, double-precision ndc2Pix) plus the SH gather are latency-heavy.  Measured on 5M
-// Gaussians: inputs alone stream in 35 us (6.2 TB/s); doing the exact math in the streaming loop
-// cost 92 us; queueing candidates in LDS and draining them inside the same kernel still cost
-// 101 us because every wave fills its queue only at the end of its chunk, so all the gathers pile up
-// where nothing is left to overlap them.  Hence:
-//   K1a k_preprocess_cull (persistent grid, prefetch one iteration ahead): phase A0 -- the exact
-//       near-plane test plus a CONSERVATIVE fast-math screen test -- writes radii = 0 for certain
-//       culls and appends everything else to the block's candidate list.  39 us.
-//   K1b k_preprocess_project (one candidate per thread, dense): phase A1 -- the reference's exact
-//       arithmetic (gcr-fp32-v1) takes EVERY decision (det == 0, radius, tile rect, area == 0) --
-//       then phase B: SH -> RGB, the 64-byte record (clamp mask in its fourth quad), and the compacted visible list
-//       that the binning kernels and the backward preprocess iterate.
+// cr/forward.cu:147-233 in phases, for wave64 lane efficiency.  In city-scale frames only a few percent of the Gaussians
+// survive culling, and the exact per-Gaussian math (~460 VALU ops: IEEE divisions, sqrt, double-precision ndc2Pix) plus the
+// SH gather are latency-heavy.  So every Gaussian goes through
+//   phase A0, the streaming cull: the exact near-plane test plus a CONSERVATIVE fast-math screen test -- radii = 0 for
+//       certain culls, everything else is a candidate;
+// and only the candidates, one per lane, through
+//   phase A1: the reference's exact arithmetic (gcr-fp32-v1) takes EVERY decision (det == 0, radius, tile rect, area == 0),
+//   phase B: SH -> RGB, the 64-byte record (clamp mask in its fourth quad), and the compacted visible list that the
+//       binning kernels and the backward preprocess iterate.
 // A0 only ever skips Gaussians whose exact result is radius 0 / no tiles, so outputs are unchanged.
+// What ships is ONE kernel, k_preprocess_fused (k_preprocess_fused_cached over a static scene's cull cache): candidates wait
+// in LDS and a pass of A1 + B runs whenever 256 of them do.  Option split_preprocess keeps the first form, k_preprocess_cull
+// then k_preprocess_project with the candidate list in memory between them; the cull cache is not used under it
+// (gcr_api.hip).  All four are the pieces K1Frame ... k1_publish below around their own streaming loop.  Measured on 5M
+// Gaussians when the split was introduced (commit 4e518f4): inputs alone stream in 35 us (6.2 TB/s); the exact math in the
+// streaming loop cost 92 us; queueing candidates in LDS and draining them at the end of the chunk still cost 101 us, all
+// the gathers piling up where nothing is left to overlap them; the cull kernel alone, inputs prefetched, 39 us.
 struct PhaseAIn {
   V3 p;
   float c0, c1, c2, c3, c4, c5, c6;  // scale.xyz + rot.rxyz, or cov3D[0..5] (scalars: stay in VGPRs)
@@ -213,8 +221,8 @@ GCR_DEV float cull_rho(float scale_modifier, const PhaseAIn& in) {
 template <bool PRECOMP_COV>
 GCR_DEV bool phase_a0_certainly_culled(const GcrPreprocessArgs& a, const float (&vm)[16], const float (&pm)[16],
                                        float wf2, const PhaseAIn& in, float rho) {
-  const float tz = vm[2] * in.p.x + vm[6] * in.p.y + vm[10] * in.p.z + vm[14];  // exact, as transformPoint4x3
-  if (tz <= 0.2f) return true;  // in_frustum, cr/auxiliary.h:145
+  if (gcr_behind_near_plane(vm, in.p)) return true;
+  const float tz = gcr_view_depth(vm, in.p);
   const float tx = __builtin_fmaf(vm[0], in.p.x, __builtin_fmaf(vm[4], in.p.y, __builtin_fmaf(vm[8], in.p.z, vm[12])));
   const float ty = __builtin_fmaf(vm[1], in.p.x, __builtin_fmaf(vm[5], in.p.y, __builtin_fmaf(vm[9], in.p.z, vm[13])));
   const float hx = __builtin_fmaf(pm[0], in.p.x, __builtin_fmaf(pm[4], in.p.y, __builtin_fmaf(pm[8], in.p.z, pm[12])));
@@ -237,12 +245,6 @@ GCR_DEV bool phase_a0_certainly_culled(const GcrPreprocessArgs& a, const float (
   // area == 0 upstream  <=>  px + r < 1  or  px - r >= 16*grid_x  (same in y), cr/auxiliary.h:36-46
   return px + rb < -slack || px - rb > 16.0f * (float)a.gx + slack || py + rb < -slack ||
          py - rb > 16.0f * (float)a.gy + slack;
-}
-
-// gcr_camera.prefiltered: does this Gaussian fail the near-plane test (the only test of in_frustum, cr/auxiliary.h:145)?
-GCR_DEV bool near_plane_violation(const float (&vm)[16], const PhaseAIn& in) {
-  const float tz = vm[2] * in.p.x + vm[6] * in.p.y + vm[10] * in.p.z + vm[14];  // exact, as transformPoint4x3
-  return tz <= 0.2f;
 }
 
 // Phase A1: the reference's exact per-Gaussian arithmetic.  Returns whether the Gaussian is
@@ -436,39 +438,196 @@ GCR_DEV void preprocess_phase_b(const GcrPreprocessArgs& a, int idx, const V3 me
   }
 }
 
-// K1a: streaming cull.  Persistent grid, inputs prefetched one iteration ahead; writes radii = 0
-// for everything phase A0 rules out and appends the rest to the block's candidate list
-// (wave-level ballot compaction, one LDS atomic per wave and iteration).
+// What a K1 workgroup knows before it looks at a Gaussian: the camera matrices as wave-uniform values (SGPRs), the cull's
+// bound on the view matrix, its chunk of the Gaussians with its visible list, the thread's place in its wave.
+struct K1Frame {
+  float vm[16], pm[16];
+  float wf2;  // >= |W|_2^2 for the 3x3 block W the covariance projection uses: Gershgorin row sums of W^T W
+  long long chunk_begin, chunk_end, last;  // last = chunk_end - 1 (every block owns a Gaussian: gcr_preprocess_grid)
+  uint32_t* __restrict__ my_list;  // the block's visible list
+  int tid, lane;
+  uint64_t lt_mask;  // the lanes of the wave below this one
+};
+
+GCR_DEV void k1_camera(const float* __restrict__ view, const float* __restrict__ proj, K1Frame& f) {
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    f.vm[i] = gcr_uniform(view[i]);
+    f.pm[i] = gcr_uniform(proj[i]);
+  }
+}
+
+GCR_DEV void k1_frame(const GcrPreprocessArgs& a, K1Frame& f) {
+  // ONE branch around the 32 reads, each side a batch of scalar loads behind one wait.  (GCR_CAM per element, as K8 has it,
+  // selects between two ADDRESSES per element when written in a kernel's body -- 7 flat loads + 25 v_readfirstlane -- and
+  // out of a helper turns into a branch per element around serialised scalar loads: +85 to +120 instructions per kernel.)
+  if (a.cam.by_value) k1_camera(a.cam.view, a.cam.proj, f);
+  else k1_camera(a.view, a.proj, f);
+  f.wf2 = 0.0f;
+  const float wc[3][3] = {{f.vm[0], f.vm[1], f.vm[2]}, {f.vm[4], f.vm[5], f.vm[6]}, {f.vm[8], f.vm[9], f.vm[10]}};
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    float row = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+      row += __builtin_fabsf(wc[0][i] * wc[0][j] + wc[1][i] * wc[1][j] + wc[2][i] * wc[2][j]);
+    f.wf2 = __builtin_fmaxf(f.wf2, row);
+  }
+  f.wf2 *= 1.001f;
+  f.chunk_begin = (long long)blockIdx.x * a.chunk;
+  f.chunk_end = f.chunk_begin + a.chunk < a.P ? f.chunk_begin + a.chunk : a.P;
+  f.last = f.chunk_end - 1;
+  f.my_list = a.vis_list + f.chunk_begin;
+  f.tid = threadIdx.x;
+  f.lane = f.tid & 63;
+  f.lt_mask = (1ull << f.lane) - 1ull;
+}
+
+// Where a stream's prefetch of Gaussian i goes.  It never leaves the block's own chunk: lanes that would read past it
+// re-read the chunk's last Gaussian (an L2-hot line).  Until round 5 they read on into the next block's chunk -- 20 KB x
+// 2 048 blocks = 42 MB of the 313 MB the kernel fetched at C3.  K1 alone: C3 82.3 -> 83.2 us, C5 355 -> 347 us, C2 18.3
+// -> 17.1 us (profiles/r05_k1_ab_stateless_clamp_touch.jsonl, one process, alternating).
+GCR_DEV long long k1_in_chunk(const K1Frame& f, long long i) { return i < f.last ? i : f.last; }
+
+// Wave-level ballot compaction: the lanes whose `pred` holds are appended to the list whose length is *tail (LDS) with ONE
+// atomic per wave.  Returns this lane's position in the list (of use where pred holds); *wave_count (LDS) = the wave's count.
+GCR_DEV uint32_t k1_wave_append(const K1Frame& f, uint32_t* tail, bool pred, uint32_t* wave_count = nullptr) {
+  const uint64_t m = __ballot(pred);
+  if (wave_count != nullptr && f.lane == 0) *wave_count = (uint32_t)__popcll(m);
+  uint32_t base = 0;
+  if (m != 0ull) {
+    if (f.lane == 0) base = atomicAdd(tail, (uint32_t)__popcll(m));
+    base = __shfl(base, 0, 64);
+  }
+  return base + (uint32_t)__popcll(m & f.lt_mask);
+}
+
+// Phase A0 for the stream's Gaussian idx64 (a lane past the chunk's end has none): a certain cull gets its radii = 0 here,
+// everything else is a candidate (returned).  viol: gcr_camera.prefiltered and a Gaussian behind the near plane.
+template <bool PRECOMP_COV, bool NT = false>
+GCR_DEV bool k1_cull_lane(const GcrPreprocessArgs& a, const K1Frame& f, long long idx64, const PhaseAIn& in, float rho,
+                          bool& viol) {
+  if (idx64 >= f.chunk_end) return false;
+  const bool candidate = !phase_a0_certainly_culled<PRECOMP_COV>(a, f.vm, f.pm, f.wf2, in, rho);
+  if (!candidate) {  // (nobody reads a culled Gaussian's zero again in this frame)
+    if (NT) __builtin_nontemporal_store(0, a.radii + idx64);
+    else a.radii[idx64] = 0;
+  }
+  if (a.prefiltered) viol |= gcr_behind_near_plane(f.vm, in.p);
+  return candidate;
+}
+
+// The exact pass for one candidate per lane: the reference's exact arithmetic takes every decision, survivors get colour +
+// record and are compacted into the block's visible list (length *vis_tail, LDS); my_tiles collects the (Gaussian, tile)
+// instances of this thread's survivors.  fetch(idx, in, opac) produces the candidate inside the single `if` of the lanes
+// that have one: handed over in registers, filled under the caller's own `if`, its ten floats stay live across the join
+// (+5 to +7 VGPRs).
+template <bool PRECOMP_COV, bool HAVE_OPACITY, typename Fetch>
+GCR_DEV void k1_exact_lane(const GcrPreprocessArgs& a, const K1Frame& f, bool have, uint32_t* vis_tail, uint32_t& my_tiles,
+                           Fetch fetch) {
+  bool keep = false;
+  int idx = 0, radius = 0;
+  float opac = 0.0f;
+  PhaseAIn in;
+  Projected pr;
+  if (have) {
+    fetch(idx, in, opac);
+    keep = phase_a1_exact<PRECOMP_COV>(a, f.vm, f.pm, idx, in, pr, radius);
+    a.radii[idx] = radius;
+  }
+  const uint32_t list_pos = k1_wave_append(f, vis_tail, keep);
+  if (keep) {
+    my_tiles += ((pr.rect_x >> 16) - (pr.rect_x & 0xffffu)) * ((pr.rect_y >> 16) - (pr.rect_y & 0xffffu));
+    preprocess_phase_b<HAVE_OPACITY>(a, idx, in.p, pr, list_pos, f.my_list, opac);
+  }
+}
+
+// The fused kernels' candidates wait here, in LDS: index, mean (f[0..2]) and whatever else of the stream the exact pass
+// needs, so they never go back to HBM for it.
+template <int NF, int CAP>
+struct K1Queue {
+  uint32_t idx[CAP];
+  float f[NF][CAP];
+  uint32_t tail;
+};
+
+// Processing passes over the `waiting` candidates of the queue: full 256-lane passes, plus the remainder when `last`.
+// shape(it, idx, in, opac) completes candidate `it`, whose index and mean have been read from the queue.  The (< 256)
+// candidates that did not fill a pass move to the front and wait for the next one; returns how many those are (= q.tail).
+// The caller's next barrier makes the compacted queue visible.
+template <bool PRECOMP_COV, bool HAVE_OPACITY, int NF, int CAP, typename Shape>
+GCR_DEV uint32_t k1_process_waiting(const GcrPreprocessArgs& a, const K1Frame& f, K1Queue<NF, CAP>& q, uint32_t waiting,
+                                    bool last, uint32_t* vis_tail, uint32_t& my_tiles, Shape shape) {
+  uint32_t done = 0;
+  while (done + 256u <= waiting || (last && done < waiting)) {
+    const uint32_t it = done + (uint32_t)f.tid;
+    auto fetch = [&](int& idx, PhaseAIn& in, float& opac) {
+      idx = (int)q.idx[it];
+      in.p = {q.f[0][it], q.f[1][it], q.f[2][it]};
+      shape(it, idx, in, opac);
+    };
+    k1_exact_lane<PRECOMP_COV, HAVE_OPACITY>(a, f, it < waiting, vis_tail, my_tiles, fetch);
+    done += 256u;
+  }
+  if (done > waiting) done = waiting;
+  const uint32_t left = waiting - done;
+  __syncthreads();  // every lane has read its candidate
+  uint32_t mv_idx = 0;
+  float mv[NF];
+  if ((uint32_t)f.tid < left) {
+    mv_idx = q.idx[done + f.tid];
+#pragma unroll
+    for (int k = 0; k < NF; k++) mv[k] = q.f[k][done + f.tid];
+  }
+  __syncthreads();
+  if ((uint32_t)f.tid < left) {
+    q.idx[f.tid] = mv_idx;
+#pragma unroll
+    for (int k = 0; k < NF; k++) q.f[k][f.tid] = mv[k];
+  }
+  if (f.tid == 0) q.tail = left;
+  return left;
+}
+
+// The block's LDS counters start at zero, behind a barrier.
+GCR_DEV void k1_reset(uint32_t* vis_tail, unsigned long long* blk_tiles, uint32_t* queue_tail = nullptr) {
+  if (threadIdx.x == 0) {
+    *vis_tail = 0;
+    *blk_tiles = 0ull;
+    if (queue_tail != nullptr) *queue_tail = 0;
+  }
+  __syncthreads();
+}
+
+// Epilogue: the block's visible-list length and its share of num_rendered = the sum of its survivors' tile counts (what the
+// reference obtains from its inclusive scan, cr/rasterizer_impl.cu:228-238), accumulated per block here so that the host
+// can have R right after K1 instead of after the tile-count kernels.  The first workgroup of the kernel that follows sums
+// the blocks' shares and publishes the total to the host (no atomics, nothing to zero beforehand); bit 63: a prefilter
+// violation.  REDUCE_VIOL: `viol` is per thread; otherwise it is block-uniform already.
+template <bool REDUCE_VIOL>
+GCR_DEV void k1_publish(const GcrPreprocessArgs& a, const K1Frame& f, uint32_t my_tiles, unsigned long long* blk_tiles,
+                        const uint32_t* vis_tail, bool viol) {
+  const uint32_t wsum = gcr_wave_sum_u32(my_tiles);
+  if (f.lane == 0 && wsum) atomicAdd(blk_tiles, (unsigned long long)wsum);
+  int any_viol = viol ? 1 : 0;
+  if (REDUCE_VIOL) any_viol = __syncthreads_or(any_viol);
+  else __syncthreads();
+  if (f.tid == 0) {
+    a.vis_count[blockIdx.x] = *vis_tail;
+    a.block_tiles[blockIdx.x] = *blk_tiles | (any_viol ? GCR_PREFILTER_FLAG : 0ull);
+  }
+}
+
+// Option split_preprocess, K1a: streaming cull.  Persistent grid; writes radii = 0 for everything phase A0 rules out and
+// appends the rest to the block's candidate list.
 template <bool PRECOMP_COV>
 __global__ __launch_bounds__(256) void k_preprocess_cull(const GcrPreprocessArgs a) {
   __shared__ uint32_t list_tail;  // length of this block's candidate list
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) list_tail = 0;
+  if (threadIdx.x == 0) list_tail = 0;
   __syncthreads();
-  float vm[16], pm[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    vm[i] = gcr_uniform(GCR_CAM(a, view, a.view, i));
-    pm[i] = gcr_uniform(GCR_CAM(a, proj, a.proj, i));
-  }
-  // wf2 >= |W|_2^2 for the 3x3 block W the covariance projection uses: Gershgorin row sums of W^T W
-  float wf2 = 0.0f;
-  {
-    const float wc[3][3] = {{vm[0], vm[1], vm[2]}, {vm[4], vm[5], vm[6]}, {vm[8], vm[9], vm[10]}};
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      float row = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-        row += __builtin_fabsf(wc[0][i] * wc[0][j] + wc[1][i] * wc[1][j] + wc[2][i] * wc[2][j]);
-      wf2 = __builtin_fmaxf(wf2, row);
-    }
-    wf2 *= 1.001f;
-  }
-  const long long chunk_begin = (long long)blockIdx.x * a.chunk;
-  const long long chunk_end = chunk_begin + a.chunk < a.P ? chunk_begin + a.chunk : a.P;
-  uint32_t* __restrict__ my_cand = a.cand_list + chunk_begin;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  K1Frame f;
+  k1_frame(a, f);
+  uint32_t* __restrict__ my_cand = a.cand_list + f.chunk_begin;
 
   // inputs are requested two iterations ahead (when the kernel shares the GPU with another frame's blend it gets a
   // fraction of the wave slots, and bytes in flight per wave are what keeps the stream at HBM speed).  What the hardware
@@ -476,257 +635,112 @@ __global__ __launch_bounds__(256) void k_preprocess_cull(const GcrPreprocessArgs
   // the loop waits for all but the newest loads -- see k_preprocess_fused_cached for the copy-free form and why this
   // 40-byte stream does not gain from it
   PhaseAIn cur, nxt, nx2;
-  bool viol = false;  // gcr_camera.prefiltered and a Gaussian behind the near plane
-  long long idx64 = chunk_begin + tid;
-  const long long last = chunk_end - 1;  // the prefetch stays inside the block's own chunk (see k_preprocess_fused)
-  phase_a_load<PRECOMP_COV>(a, idx64 < last ? idx64 : last, cur);
-  phase_a_load<PRECOMP_COV>(a, idx64 + 256 < last ? idx64 + 256 : last, nxt);
-  for (long long base = chunk_begin; base < chunk_end; base += 256) {
-    idx64 = base + tid;
-    phase_a_load<PRECOMP_COV>(a, idx64 + 512 < last ? idx64 + 512 : last, nx2);  // prefetch, two iterations ahead
-    bool candidate = false;
-    if (idx64 < chunk_end) {
-      candidate = !phase_a0_certainly_culled<PRECOMP_COV>(a, vm, pm, wf2, cur, cull_rho<PRECOMP_COV>(a.scale_modifier, cur));
-      if (!candidate) a.radii[idx64] = 0;
-      if (a.prefiltered) viol |= near_plane_violation(vm, cur);
-    }
-    const uint64_t m = __ballot(candidate);
-    if (m != 0ull) {
-      uint32_t wbase = 0;
-      if (lane == 0) wbase = atomicAdd(&list_tail, (uint32_t)__popcll(m));
-      wbase = __shfl(wbase, 0, 64);
-      if (candidate) my_cand[wbase + (uint32_t)__popcll(m & lt_mask)] = (uint32_t)idx64;
-    }
+  bool viol = false;
+  long long idx64 = f.chunk_begin + f.tid;
+  phase_a_load<PRECOMP_COV>(a, k1_in_chunk(f, idx64), cur);
+  phase_a_load<PRECOMP_COV>(a, k1_in_chunk(f, idx64 + 256), nxt);
+  for (long long base = f.chunk_begin; base < f.chunk_end; base += 256) {
+    idx64 = base + f.tid;
+    phase_a_load<PRECOMP_COV>(a, k1_in_chunk(f, idx64 + 512), nx2);  // prefetch, two iterations ahead
+    const float rho = cull_rho<PRECOMP_COV>(a.scale_modifier, cur);
+    const bool candidate = k1_cull_lane<PRECOMP_COV>(a, f, idx64, cur, rho, viol);
+    const uint32_t slot = k1_wave_append(f, &list_tail, candidate);
+    if (candidate) my_cand[slot] = (uint32_t)idx64;
     cur = nxt;
     nxt = nx2;
   }
   const int any_viol = __syncthreads_or(viol ? 1 : 0);
-  if (tid == 0) a.cand_count[blockIdx.x] = list_tail | (any_viol ? 0x80000000u : 0u);  // (a block holds < 2^31 candidates)
+  if (f.tid == 0) a.cand_count[blockIdx.x] = list_tail | (any_viol ? 0x80000000u : 0u);  // (a block holds < 2^31 of them)
 }
 
-// K1b: dense pass over the candidates of K1a block `blockIdx.x`, one candidate per thread: the
-// reference's exact arithmetic takes every decision, survivors get colour + record and are
-// compacted into the block's visible list.  Gather latency is hidden by occupancy here instead of
-// stalling the streaming kernel.  (Tried and measured slower: one-wave workgroups with a global
-// atomic per wave, 115 us; prefetching the SH coefficients before the exact math, no gain.)
+// K1b: dense exact pass over the candidates of K1a block `blockIdx.x`, one candidate per thread.  Gather latency is hidden
+// by occupancy here instead of stalling the streaming kernel.  (Tried and measured slower: one-wave workgroups with a
+// global atomic per wave, 115 us; prefetching the SH coefficients before the exact math, no gain.)
 template <bool PRECOMP_COV>
 __global__ __launch_bounds__(256) void k_preprocess_project(const GcrPreprocessArgs a) {
-  __shared__ uint32_t list_tail;
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) list_tail = 0;
-  __syncthreads();
-  float vm[16], pm[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    vm[i] = gcr_uniform(GCR_CAM(a, view, a.view, i));
-    pm[i] = gcr_uniform(GCR_CAM(a, proj, a.proj, i));
-  }
-  const size_t chunk_begin = (size_t)blockIdx.x * a.chunk;
-  const uint32_t* __restrict__ my_cand = a.cand_list + chunk_begin;
-  uint32_t* __restrict__ my_list = a.vis_list + chunk_begin;
+  __shared__ uint32_t vis_tail;
+  __shared__ unsigned long long blk_tiles;
+  k1_reset(&vis_tail, &blk_tiles);
+  K1Frame f;
+  k1_frame(a, f);
+  const uint32_t* __restrict__ my_cand = a.cand_list + f.chunk_begin;
   const uint32_t ncand_word = a.cand_count[blockIdx.x];
   const uint32_t ncand = ncand_word & 0x7fffffffu;  // (bit 31: the cull kernel met a prefilter violation)
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  uint32_t my_tiles = 0;  // (Gaussian, tile) instances of this thread's survivors
+  uint32_t my_tiles = 0;
   for (uint32_t it0 = 0; it0 < ncand; it0 += 256) {  // block-uniform trip count
-    const uint32_t it = it0 + tid;
-    bool keep = false;
-    int idx = 0, radius = 0;
-    PhaseAIn in;
-    Projected pr;
-    if (it < ncand) {
+    const uint32_t it = it0 + (uint32_t)f.tid;
+    k1_exact_lane<PRECOMP_COV, false>(a, f, it < ncand, &vis_tail, my_tiles, [&](int& idx, PhaseAIn& in, float&) {
       idx = (int)my_cand[it];
       phase_a_load<PRECOMP_COV>(a, idx, in);
-      keep = phase_a1_exact<PRECOMP_COV>(a, vm, pm, idx, in, pr, radius);
-      a.radii[idx] = radius;
-    }
-    const uint64_t m = __ballot(keep);
-    if (m != 0ull) {
-      uint32_t lbase = 0;
-      if (lane == 0) lbase = atomicAdd(&list_tail, (uint32_t)__popcll(m));
-      lbase = __shfl(lbase, 0, 64);
-      if (keep) {
-        my_tiles += ((pr.rect_x >> 16) - (pr.rect_x & 0xffffu)) * ((pr.rect_y >> 16) - (pr.rect_y & 0xffffu));
-        preprocess_phase_b(a, idx, in.p, pr, lbase + (uint32_t)__popcll(m & lt_mask), my_list);
-      }
-    }
+    });
   }
-  // num_rendered = sum of the survivors' tile counts (what the reference obtains from its inclusive scan,
-  // cr/rasterizer_impl.cu:228-238), accumulated per block here so that the host can have R right after K1
-  // instead of after the tile-count kernels.
-  __shared__ unsigned long long blk_tiles;
-  if (tid == 0) blk_tiles = 0ull;
-  __syncthreads();
-  const uint32_t wsum = gcr_wave_sum_u32(my_tiles);
-  if (lane == 0 && wsum) atomicAdd(&blk_tiles, (unsigned long long)wsum);
-  __syncthreads();
-  if (tid == 0) {
-    a.vis_count[blockIdx.x] = list_tail;
-    // this block's share of num_rendered; the first workgroup of the kernel that follows sums the blocks' shares
-    // and publishes the total to the host (no atomics, nothing to zero beforehand)
-    a.block_tiles[blockIdx.x] = blk_tiles | ((ncand_word & 0x80000000u) ? GCR_PREFILTER_FLAG : 0ull);
-  }
+  k1_publish<false>(a, f, my_tiles, &blk_tiles, &vis_tail, (ncand_word & 0x80000000u) != 0u);
 }
 
-// K1 fused (default): ONE kernel whose workgroups alternate between STREAMING their chunk through the cull
-// (K1a's loop) and PROCESSING the candidates they have collected -- exact projection, colour, record (K1b's body).
+// K1 fused (default): ONE kernel whose workgroups alternate between STREAMING their chunk through the cull (K1a's loop) and
+// PROCESSING the candidates they have collected -- exact projection, colour, record (K1b's body).
 // The candidates' inputs (index + 10 floats) wait in LDS, so they never go back to HBM and K1b's re-gather of three
 // 128-byte lines per candidate disappears; and while one workgroup is in its latency-bound processing pass the
 // other workgroups of the CU keep the HBM stream going, so the pass is hidden instead of being a second kernel
 // that starts only when the slowest streaming block has finished.  A processing pass runs whenever 256 candidates
 // are waiting (all lanes busy) and once more at the end of the chunk.
+//
+// How many candidates are `waiting` must be block-uniform (it decides whether the workgroup enters a processing pass with
+// its barriers), and here the two fused kernels differ for a reason.  The stateless kernel has ONE barrier per iteration:
+// on an iteration without a pass nothing separates a read of q.tail from the next iteration's atomicAdd of a faster wave
+// (ADVICE r02), so it keeps the count in a register -- every wave publishes how many candidates it appended (slot parity
+// = iteration parity, so the next iteration's writes cannot overtake a slow reader; the one after that is behind the next
+// barrier) and every thread adds up the four counts after the barrier.  The cached kernel has a barrier PAIR per group of
+// iterations, nobody appends between the two, and it reads q.tail there.
 constexpr int FUSED_CAP = 512;  // <= 255 left over + <= 256 new candidates per iteration
 
 template <bool PRECOMP_COV, bool NT>
 __global__ __launch_bounds__(256) void k_preprocess_fused(const GcrPreprocessArgs a) {
-  __shared__ uint32_t sIdx[FUSED_CAP];
-  __shared__ float sIn[10][FUSED_CAP];
-  __shared__ uint32_t cand_tail, vis_tail;
+  __shared__ K1Queue<10, FUSED_CAP> q;  // a candidate waits with everything the stream has read of it
+  __shared__ uint32_t vis_tail;
   __shared__ uint32_t wave_new[2][4];  // candidates each wave found in this iteration, double-buffered by parity
   __shared__ unsigned long long blk_tiles;
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) {
-    cand_tail = 0;
-    vis_tail = 0;
-    blk_tiles = 0ull;
-  }
-  __syncthreads();
-  float vm[16], pm[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    vm[i] = gcr_uniform(GCR_CAM(a, view, a.view, i));
-    pm[i] = gcr_uniform(GCR_CAM(a, proj, a.proj, i));
-  }
-  float wf2 = 0.0f;
-  {
-    const float wc[3][3] = {{vm[0], vm[1], vm[2]}, {vm[4], vm[5], vm[6]}, {vm[8], vm[9], vm[10]}};
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      float row = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-        row += __builtin_fabsf(wc[0][i] * wc[0][j] + wc[1][i] * wc[1][j] + wc[2][i] * wc[2][j]);
-      wf2 = __builtin_fmaxf(wf2, row);
-    }
-    wf2 *= 1.001f;
-  }
-  const long long chunk_begin = (long long)blockIdx.x * a.chunk;
-  const long long chunk_end = chunk_begin + a.chunk < a.P ? chunk_begin + a.chunk : a.P;
-  uint32_t* __restrict__ my_list = a.vis_list + chunk_begin;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  k1_reset(&vis_tail, &blk_tiles, &q.tail);
+  K1Frame f;
+  k1_frame(a, f);
   uint32_t my_tiles = 0;
-
-  // `waiting` = candidates in the LDS queue.  It must be block-uniform (it decides whether the workgroup enters a
-  // processing pass with its barriers), so it is NOT read back from cand_tail -- on an iteration without a pass no
-  // barrier separates that read from the next iteration's atomicAdd of a faster wave -- but kept in a
-  // register: every wave publishes how many candidates it appended (slot parity = iteration parity, so the next
-  // iteration's writes cannot overtake a slow reader; the one after that is behind the next barrier) and every
-  // thread adds up the four counts after the barrier.
-  uint32_t waiting = 0;
+  uint32_t waiting = 0;  // (in a register, see above)
   uint32_t parity = 0;
 
   PhaseAIn cur, nxt, nx2;  // (requested two iterations ahead; what the rotation below leaves of that: see k_preprocess_cull)
-  bool viol = false;  // gcr_camera.prefiltered and a Gaussian behind the near plane
-  long long idx64 = chunk_begin + tid;
-  // The prefetch never leaves the block's own chunk: lanes that would read past it re-read the chunk's last Gaussian (an
-  // L2-hot line).  Until round 5 they read on into the next block's chunk -- 20 KB x 2 048 blocks = 42 MB of the 313 MB the
-  // kernel fetched at C3.  K1 alone: C3 82.3 -> 83.2 us, C5 355 -> 347 us, C2 18.3 -> 17.1 us
-  // (profiles/r05_k1_ab_stateless_clamp_touch.jsonl, one process, alternating).
-  const long long last = chunk_end - 1;
-  phase_a_load<PRECOMP_COV, NT>(a, idx64 < last ? idx64 : last, cur);
-  phase_a_load<PRECOMP_COV, NT>(a, idx64 + 256 < last ? idx64 + 256 : last, nxt);
-  for (long long base = chunk_begin; base < chunk_end; base += 256, parity ^= 1u) {
-    idx64 = base + tid;
-    phase_a_load<PRECOMP_COV, NT>(a, idx64 + 512 < last ? idx64 + 512 : last, nx2);  // prefetch, two iterations ahead
-    bool candidate = false;
-    if (idx64 < chunk_end) {
-      candidate = !phase_a0_certainly_culled<PRECOMP_COV>(a, vm, pm, wf2, cur, cull_rho<PRECOMP_COV>(a.scale_modifier, cur));
-      if (!candidate) {  // (nobody reads a culled Gaussian's zero again in this frame)
-        if (NT) __builtin_nontemporal_store(0, a.radii + idx64);
-        else a.radii[idx64] = 0;
-      }
-      if (a.prefiltered) viol |= near_plane_violation(vm, cur);
-    }
-    const uint64_t m = __ballot(candidate);
-    if (lane == 0) wave_new[parity][tid >> 6] = (uint32_t)__popcll(m);
-    if (m != 0ull) {
-      uint32_t wbase = 0;
-      if (lane == 0) wbase = atomicAdd(&cand_tail, (uint32_t)__popcll(m));
-      wbase = __shfl(wbase, 0, 64);
-      if (candidate) {
-        const uint32_t slot = wbase + (uint32_t)__popcll(m & lt_mask);
-        sIdx[slot] = (uint32_t)idx64;
-        sIn[0][slot] = cur.p.x; sIn[1][slot] = cur.p.y; sIn[2][slot] = cur.p.z;
-        sIn[3][slot] = cur.c0; sIn[4][slot] = cur.c1; sIn[5][slot] = cur.c2;
-        sIn[6][slot] = cur.c3; sIn[7][slot] = cur.c4; sIn[8][slot] = cur.c5;
-        sIn[9][slot] = cur.c6;
-      }
+  bool viol = false;
+  long long idx64 = f.chunk_begin + f.tid;
+  phase_a_load<PRECOMP_COV, NT>(a, k1_in_chunk(f, idx64), cur);
+  phase_a_load<PRECOMP_COV, NT>(a, k1_in_chunk(f, idx64 + 256), nxt);
+  for (long long base = f.chunk_begin; base < f.chunk_end; base += 256, parity ^= 1u) {
+    idx64 = base + f.tid;
+    phase_a_load<PRECOMP_COV, NT>(a, k1_in_chunk(f, idx64 + 512), nx2);  // prefetch, two iterations ahead
+    const float rho = cull_rho<PRECOMP_COV>(a.scale_modifier, cur);
+    const bool candidate = k1_cull_lane<PRECOMP_COV, NT>(a, f, idx64, cur, rho, viol);
+    const uint32_t slot = k1_wave_append(f, &q.tail, candidate, &wave_new[parity][f.tid >> 6]);
+    if (candidate) {
+      q.idx[slot] = (uint32_t)idx64;
+      q.f[0][slot] = cur.p.x; q.f[1][slot] = cur.p.y; q.f[2][slot] = cur.p.z;
+      q.f[3][slot] = cur.c0; q.f[4][slot] = cur.c1; q.f[5][slot] = cur.c2;
+      q.f[6][slot] = cur.c3; q.f[7][slot] = cur.c4; q.f[8][slot] = cur.c5;
+      q.f[9][slot] = cur.c6;
     }
     cur = nxt;
     nxt = nx2;
     __syncthreads();
     waiting += wave_new[parity][0] + wave_new[parity][1] + wave_new[parity][2] + wave_new[parity][3];
-    const bool last_iter = base + 256 >= chunk_end;
+    const bool last_iter = base + 256 >= f.chunk_end;
     if (waiting >= 256u || (last_iter && waiting > 0u)) {
-      // ---- processing passes over the waiting candidates: full 256-lane passes, plus the remainder at the end
-      uint32_t done = 0;
-      while (done + 256u <= waiting || (last_iter && done < waiting)) {
-        const uint32_t it = done + (uint32_t)tid;
-        bool keep = false;
-        int idx = 0, radius = 0;
-        PhaseAIn in;
-        Projected pr;
-        if (it < waiting) {
-          idx = (int)sIdx[it];
-          in.p = {sIn[0][it], sIn[1][it], sIn[2][it]};
-          in.c0 = sIn[3][it]; in.c1 = sIn[4][it]; in.c2 = sIn[5][it];
-          in.c3 = sIn[6][it]; in.c4 = sIn[7][it]; in.c5 = sIn[8][it];
-          in.c6 = sIn[9][it];
-          keep = phase_a1_exact<PRECOMP_COV>(a, vm, pm, idx, in, pr, radius);
-          a.radii[idx] = radius;
-        }
-        const uint64_t mk = __ballot(keep);
-        if (mk != 0ull) {
-          uint32_t lbase = 0;
-          if (lane == 0) lbase = atomicAdd(&vis_tail, (uint32_t)__popcll(mk));
-          lbase = __shfl(lbase, 0, 64);
-          if (keep) {
-            my_tiles += ((pr.rect_x >> 16) - (pr.rect_x & 0xffffu)) * ((pr.rect_y >> 16) - (pr.rect_y & 0xffffu));
-            preprocess_phase_b(a, idx, in.p, pr, lbase + (uint32_t)__popcll(mk & lt_mask), my_list);
-          }
-        }
-        done += 256u;
-      }
-      if (done > waiting) done = waiting;
-      // the (< 256) candidates that did not fill a pass move to the front and wait for the next one
-      const uint32_t left = waiting - done;
-      __syncthreads();  // every lane has read its candidate
-      uint32_t mv_idx = 0;
-      float mv[10];
-      if ((uint32_t)tid < left) {
-        mv_idx = sIdx[done + tid];
-#pragma unroll
-        for (int k = 0; k < 10; k++) mv[k] = sIn[k][done + tid];
-      }
-      __syncthreads();
-      if ((uint32_t)tid < left) {
-        sIdx[tid] = mv_idx;
-#pragma unroll
-        for (int k = 0; k < 10; k++) sIn[k][tid] = mv[k];
-      }
-      if (tid == 0) cand_tail = left;
-      waiting = left;
+      waiting = k1_process_waiting<PRECOMP_COV, false>(a, f, q, waiting, last_iter, &vis_tail, my_tiles,
+                                                       [&](uint32_t it, int, PhaseAIn& in, float&) {
+        in.c0 = q.f[3][it]; in.c1 = q.f[4][it]; in.c2 = q.f[5][it];
+        in.c3 = q.f[6][it]; in.c4 = q.f[7][it]; in.c5 = q.f[8][it];
+        in.c6 = q.f[9][it];
+      });
       __syncthreads();
     }
   }
-  const uint32_t wsum = gcr_wave_sum_u32(my_tiles);
-  if (lane == 0 && wsum) atomicAdd(&blk_tiles, (unsigned long long)wsum);
-  const int any_viol = __syncthreads_or(viol ? 1 : 0);
-  if (tid == 0) {
-    a.vis_count[blockIdx.x] = vis_tail;
-    // summed (= num_rendered) by the first workgroup of the next kernel; bit 63: a prefilter violation
-    a.block_tiles[blockIdx.x] = blk_tiles | (any_viol ? GCR_PREFILTER_FLAG : 0ull);
-  }
+  k1_publish<true>(a, f, my_tiles, &blk_tiles, &vis_tail, viol);
 }
 
 // K1 fused, a static scene's variant (gcr_gaussians.cull_cache -- a second line, never the headline).  The stream is part A
@@ -753,151 +767,54 @@ __global__ __launch_bounds__(256) void k_preprocess_fused(const GcrPreprocessArg
 template <bool PRECOMP_COV>
 __global__ __launch_bounds__(256) void k_preprocess_fused_cached(const GcrPreprocessArgs a) {
   constexpr int NS = GCR_K1_STAGES_CACHED;
-  constexpr int CAP = 256 * (NS + 1);  // <= 255 left over + <= 256 NS new candidates per group
-  __shared__ uint32_t sIdx[CAP];
-  __shared__ float sP[3][CAP];
-  __shared__ uint32_t cand_tail, vis_tail;
+  __shared__ K1Queue<3, 256 * (NS + 1)> q;  // <= 255 left over + <= 256 NS new candidates per group
+  __shared__ uint32_t vis_tail;
   __shared__ unsigned long long blk_tiles;
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) {
-    cand_tail = 0;
-    vis_tail = 0;
-    blk_tiles = 0ull;
-  }
-  __syncthreads();
-  float vm[16], pm[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    vm[i] = gcr_uniform(GCR_CAM(a, view, a.view, i));
-    pm[i] = gcr_uniform(GCR_CAM(a, proj, a.proj, i));
-  }
-  float wf2 = 0.0f;
-  {
-    const float wc[3][3] = {{vm[0], vm[1], vm[2]}, {vm[4], vm[5], vm[6]}, {vm[8], vm[9], vm[10]}};
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      float row = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-        row += __builtin_fabsf(wc[0][i] * wc[0][j] + wc[1][i] * wc[1][j] + wc[2][i] * wc[2][j]);
-      wf2 = __builtin_fmaxf(wf2, row);
-    }
-    wf2 *= 1.001f;
-  }
-  const long long chunk_begin = (long long)blockIdx.x * a.chunk;
-  const long long chunk_end = chunk_begin + a.chunk < a.P ? chunk_begin + a.chunk : a.P;
-  const long long clast = chunk_end - 1;  // (every block owns at least one Gaussian: gcr_preprocess_grid)
-  uint32_t* __restrict__ my_list = a.vis_list + chunk_begin;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  k1_reset(&vis_tail, &blk_tiles, &q.tail);
+  K1Frame f;
+  k1_frame(a, f);
   uint32_t my_tiles = 0;
-  bool viol = false;  // gcr_camera.prefiltered and a Gaussian behind the near plane
+  bool viol = false;
 
-  float4 q[NS];  // (mean, rho) of this thread's Gaussian in iteration k of the group
+  float4 rec[NS];  // (mean, rho) of this thread's Gaussian in iteration k of the group
 #pragma unroll
-  for (int k = 0; k < NS; k++) {
-    const long long i = chunk_begin + 256 * k + tid;
-    q[k] = a.cull_cache[i < clast ? i : clast];
-  }
-  for (long long gbase = chunk_begin; gbase < chunk_end; gbase += 256 * NS) {
+  for (int k = 0; k < NS; k++) rec[k] = a.cull_cache[k1_in_chunk(f, f.chunk_begin + 256 * k + f.tid)];
+  for (long long gbase = f.chunk_begin; gbase < f.chunk_end; gbase += 256 * NS) {
 #pragma unroll
     for (int k = 0; k < NS; k++) {
-      const long long idx64 = gbase + 256 * k + tid;
-      bool candidate = false;
-      if (idx64 < chunk_end) {
-        PhaseAIn in;
-        in.p = {q[k].x, q[k].y, q[k].z};
-        in.c0 = in.c1 = in.c2 = in.c3 = in.c4 = in.c5 = in.c6 = 0.0f;  // (the cull reads the mean and rho only)
-        candidate = !phase_a0_certainly_culled<PRECOMP_COV>(a, vm, pm, wf2, in, q[k].w);
-        if (!candidate) a.radii[idx64] = 0;
-        if (a.prefiltered) viol |= near_plane_violation(vm, in);
-      }
-      const uint64_t m = __ballot(candidate);
-      if (m != 0ull) {
-        uint32_t wbase = 0;
-        if (lane == 0) wbase = atomicAdd(&cand_tail, (uint32_t)__popcll(m));
-        wbase = __shfl(wbase, 0, 64);
-        if (candidate) {
-          const uint32_t slot = wbase + (uint32_t)__popcll(m & lt_mask);
-          sIdx[slot] = (uint32_t)idx64;
-          sP[0][slot] = q[k].x; sP[1][slot] = q[k].y; sP[2][slot] = q[k].z;
-        }
+      const long long idx64 = gbase + 256 * k + f.tid;
+      PhaseAIn in = {};  // (the cull reads the mean and rho only)
+      in.p = {rec[k].x, rec[k].y, rec[k].z};
+      const bool candidate = k1_cull_lane<PRECOMP_COV>(a, f, idx64, in, rec[k].w, viol);
+      const uint32_t slot = k1_wave_append(f, &q.tail, candidate);
+      if (candidate) {
+        q.idx[slot] = (uint32_t)idx64;
+        q.f[0][slot] = rec[k].x; q.f[1][slot] = rec[k].y; q.f[2][slot] = rec[k].z;
       }
       // stage k's registers are free now: the same iteration of the NEXT group goes into them (the compiler must not
       // hoist the load above the uses -- it would need a second register set and copy it at the back-edge)
       asm volatile("" ::: "memory");
-      const long long inext = idx64 + 256 * NS;
-      q[k] = a.cull_cache[inext < clast ? inext : clast];
+      rec[k] = a.cull_cache[k1_in_chunk(f, idx64 + 256 * NS)];
     }
     __syncthreads();
-    const uint32_t waiting = cand_tail;  // block-uniform: nobody appends again before the barrier(s) below
-    const bool last_group = gbase + 256 * NS >= chunk_end;
-    if (waiting >= 256u || (last_group && waiting > 0u)) {
-      // ---- processing passes over the waiting candidates: full 256-lane passes, plus the remainder at the end
-      uint32_t done = 0;
-      while (done + 256u <= waiting || (last_group && done < waiting)) {
-        const uint32_t it = done + (uint32_t)tid;
-        bool keep = false;
-        int idx = 0, radius = 0;
-        float opac = 0.0f;
-        PhaseAIn in;
-        Projected pr;
-        if (it < waiting) {
-          idx = (int)sIdx[it];
-          in.p = {sP[0][it], sP[1][it], sP[2][it]};
-          {  // ONE 32-byte record: scales (or covariance), opacity, rotation
-            const float4 b0 = a.cull_shape[2 * (size_t)idx], b1 = a.cull_shape[2 * (size_t)idx + 1];
-            if (PRECOMP_COV) {
-              in.c0 = b0.x; in.c1 = b0.y; in.c2 = b0.z; in.c3 = b0.w; in.c4 = b1.x; in.c5 = b1.y; in.c6 = 0.0f;
-              opac = b1.z;
-            } else {
-              in.c0 = b0.x; in.c1 = b0.y; in.c2 = b0.z; opac = b0.w;
-              in.c3 = b1.x; in.c4 = b1.y; in.c5 = b1.z; in.c6 = b1.w;
-            }
-          }
-          keep = phase_a1_exact<PRECOMP_COV>(a, vm, pm, idx, in, pr, radius);
-          a.radii[idx] = radius;
+    const uint32_t waiting = q.tail;  // block-uniform: nobody appends again before the barrier(s) below
+    const bool last_group = gbase + 256 * NS >= f.chunk_end;
+    if (waiting >= 256u || (last_group && waiting > 0u))
+      k1_process_waiting<PRECOMP_COV, true>(a, f, q, waiting, last_group, &vis_tail, my_tiles,
+                                            [&](uint32_t, int idx, PhaseAIn& in, float& opac) {
+        // ONE 32-byte record: scales (or covariance), opacity, rotation
+        const float4 b0 = a.cull_shape[2 * (size_t)idx], b1 = a.cull_shape[2 * (size_t)idx + 1];
+        if (PRECOMP_COV) {
+          in.c0 = b0.x; in.c1 = b0.y; in.c2 = b0.z; in.c3 = b0.w; in.c4 = b1.x; in.c5 = b1.y; in.c6 = 0.0f;
+          opac = b1.z;
+        } else {
+          in.c0 = b0.x; in.c1 = b0.y; in.c2 = b0.z; opac = b0.w;
+          in.c3 = b1.x; in.c4 = b1.y; in.c5 = b1.z; in.c6 = b1.w;
         }
-        const uint64_t mk = __ballot(keep);
-        if (mk != 0ull) {
-          uint32_t lbase = 0;
-          if (lane == 0) lbase = atomicAdd(&vis_tail, (uint32_t)__popcll(mk));
-          lbase = __shfl(lbase, 0, 64);
-          if (keep) {
-            my_tiles += ((pr.rect_x >> 16) - (pr.rect_x & 0xffffu)) * ((pr.rect_y >> 16) - (pr.rect_y & 0xffffu));
-            preprocess_phase_b<true>(a, idx, in.p, pr, lbase + (uint32_t)__popcll(mk & lt_mask), my_list, opac);
-          }
-        }
-        done += 256u;
-      }
-      if (done > waiting) done = waiting;
-      // the (< 256) candidates that did not fill a pass move to the front and wait for the next one
-      const uint32_t left = waiting - done;
-      __syncthreads();  // every lane has read its candidate
-      uint32_t mv_idx = 0;
-      float mv[3];
-      if ((uint32_t)tid < left) {
-        mv_idx = sIdx[done + tid];
-#pragma unroll
-        for (int k = 0; k < 3; k++) mv[k] = sP[k][done + tid];
-      }
-      __syncthreads();
-      if ((uint32_t)tid < left) {
-        sIdx[tid] = mv_idx;
-#pragma unroll
-        for (int k = 0; k < 3; k++) sP[k][tid] = mv[k];
-      }
-      if (tid == 0) cand_tail = left;
-    }
-    __syncthreads();  // everybody has read cand_tail (and sees the compacted queue) before the next group appends
+      });
+    __syncthreads();  // everybody has read q.tail (and sees the compacted queue) before the next group appends
   }
-  const uint32_t wsum = gcr_wave_sum_u32(my_tiles);
-  if (lane == 0 && wsum) atomicAdd(&blk_tiles, (unsigned long long)wsum);
-  const int any_viol = __syncthreads_or(viol ? 1 : 0);
-  if (tid == 0) {
-    a.vis_count[blockIdx.x] = vis_tail;
-    // summed (= num_rendered) by the first workgroup of the next kernel; bit 63: a prefilter violation
-    a.block_tiles[blockIdx.x] = blk_tiles | (any_viol ? GCR_PREFILTER_FLAG : 0ull);
-  }
+  k1_publish<true>(a, f, my_tiles, &blk_tiles, &vis_tail, viol);
 }
 
 // ------------------------------------------------------------------------------------- K2
@@ -1332,13 +1249,12 @@ hipError_t gcr_launch_mark_visible(int P, const float* means3D, const float* vie
 
 // Grid of the persistent K1 kernels (and of every kernel that walks K1's per-block survivor lists).
 // A MEASURED constant, not an occupancy premise: 8 workgroups per CU, at most GCR_K1_MAX_BLOCKS.  That is one
-// resident round of the register-light streaming cull (split mode) and TWO rounds of the fused kernel (119 VGPRs,
-// 22.5 KB LDS: four workgroups per CU) -- for the fused kernel many short blocks measured better than one resident
+// resident round of the register-light streaming cull (split mode) and TWO rounds of the fused kernel (103-107 VGPRs,
+// 22 832 B LDS: four workgroups per CU) -- for the fused kernel many short blocks measured better than one resident
 // round (4 660 vs 4 470 frames/s at C3: short blocks co-schedule with the other frames' blend workgroups, and a
 // block's latency-bound processing pass is covered by its neighbours' streaming).  Both modes use the same grid so
 // that the survivor-list layout in the geometry buffer does not depend on the mode (the backward re-derives it).
-int gcr_preprocess_resident_blocks(bool split) {
-  (void)split;
+int gcr_preprocess_resident_blocks() {
   static int cached = [] {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) {

@@ -28,7 +28,7 @@ def analyse(rows):
     d = sorted((b - a) / 1e3 for a, b in zip(bl[skip:-1], bl[skip + 1:]))
     if d:
         out["blend_start_period_us"] = {"median": d[len(d) // 2], "mean": sum(d) / len(d), "n": len(d)}
-    k1 = [(r[2], r[3]) for r in rows if "k_preprocess_fused" in r[0] or "k_preprocess_exact" in r[0]]
+    k1 = [(r[2], r[3]) for r in rows if "k_preprocess_fused" in r[0]]
     k1 = k1[skip:]
     gaps, overlaps = [], 0
     for (s0, e0), (s1, e1) in zip(k1[:-1], k1[1:]):
