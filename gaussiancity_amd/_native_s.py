@@ -6,8 +6,9 @@ import ctypes as C
 from . import _loader
 
 REDUCE = {"sum": 0, "add": 0, "mean": 1, "min": 2, "max": 3}  # enum gcs_reduce
+TILE_32X32, TILE_64X64, TILE_128X32 = 0, 1, 2  # enum gcs_tile
 HOST_INFO_HEADER = 2  # GCS_HOST_INFO_HEADER: invalid rows, duplicate flag, then pairs per tap
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 _vp, _sz, _i32, _i64, _int = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int
 _pi32 = C.POINTER(_i32)
@@ -17,6 +18,7 @@ _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argt
     "gcs_subm_rulebook_bytes": (_sz, [_i64, _i32]),
     "gcs_subm_rulebook_scratch_bytes": (_sz, [_i64]),
     "gcs_subm_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "gcs_subm_plan": (_int, [_i64, _i32, _i32, _i32, _pi32]),
     "gcs_subm_rulebook": (_int, [_vp, _i64, _i32, _pi32, _pi32, _pi32, _vp, _sz, _vp, _sz, _pi32, _vp]),
     "gcs_subm_forward": (_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "gcs_subm_backward": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -32,3 +34,10 @@ lib, check = _L.lib, _L.check
 def triple(values):
     """Three int32 values for the shape arguments of gcs_subm_rulebook."""
     return (C.c_int32 * 3)(*[int(v) for v in values])
+
+
+def subm_plan(n, cin, cout, kvol):
+    """(forward tile, dX tile, dW tile, dW slices, dB slices) of gcs_subm_plan: what the library launches for the shape."""
+    out = (C.c_int32 * 5)()
+    check(lib().gcs_subm_plan(n, cin, cout, kvol, out), "gcs_subm_plan")
+    return tuple(out)

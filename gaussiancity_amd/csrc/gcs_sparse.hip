@@ -527,9 +527,18 @@ int check_conv_dims(const char* who, int64_t n, int32_t K, int32_t cin, int32_t 
   return 0;
 }
 
+// ---- the plan: every shape-dependent choice of the convolution, made here and nowhere else ---------------------
+// Tile of k_subm_gemm for n rows x nout output columns: 64 x 64 or 128 x 32 (4 x 4 per thread) once they give the
+// GPU 256 workgroups, 32 x 32 (2 x 2 per thread) for the small grids below that.
+int gemm_tile(int64_t n, int32_t nout) {
+  const int64_t wide = ((n + 63) / 64) * ((nout + 63) / 64), tall = (n + 127) / 128;
+  if (nout > 32 && wide >= 256) return GCS_TILE_64X64;
+  if (nout > 16 && nout <= 32 && tall >= 256) return GCS_TILE_128X32;
+  return GCS_TILE_32X32;
+}
 // slices of the dW reduction: enough workgroups to fill the GPU, a function of the shape only
-int dw_slices(int64_t n, int32_t cin, int32_t cout, int32_t K) {
-  const int t = (cin >= 64 && cout >= 64) ? 64 : 32;
+int dw_slices(int64_t n, int32_t cin, int32_t cout, int32_t K, int tile) {
+  const int t = tile == GCS_TILE_64X64 ? 64 : 32;
   const int64_t wgs = (int64_t)((cout + t - 1) / t) * ((cin + t - 1) / t) * K;
   int64_t s = (2048 + wgs - 1) / wgs;
   const int64_t by_rows = n / 256 > 1 ? n / 256 : 1;  // at least ~256 rows per slice
@@ -539,6 +548,18 @@ int dw_slices(int64_t n, int32_t cin, int32_t cout, int32_t K) {
 int colsum_slices(int64_t n) {
   const int64_t s = n / 2048;
   return (int)(s < 1 ? 1 : (s > 64 ? 64 : s));
+}
+struct Plan {
+  int32_t fwd, dx, dw, dw_slices, db_slices;  // the order of gcs_subm_plan's output
+};
+Plan plan_of(int64_t n, int32_t cin, int32_t cout, int32_t K) {
+  Plan p;
+  p.fwd = gemm_tile(n, cout);
+  p.dx = gemm_tile(n, cin);
+  p.dw = (cin >= 64 && cout >= 64) ? GCS_TILE_64X64 : GCS_TILE_32X32;
+  p.dw_slices = dw_slices(n, cin, cout, K, p.dw);
+  p.db_slices = colsum_slices(n);
+  return p;
 }
 
 struct BwdWs {
@@ -556,24 +577,23 @@ BwdWs carve_bwd(void* base, int64_t n, int32_t cin, int32_t cout, int32_t K, int
     off += align_up(b);
     return (float*)q;
   };
-  const int S = dw_slices(n, cin, cout, K);
+  const Plan pl = plan_of(n, cin, cout, K);
   w.dyf = take(dups ? 4 * (size_t)n * cout : 0);
-  w.dwp = take(S > 1 ? 4 * (size_t)S * cout * K * cin : 0);
-  w.dbp = take(4 * (size_t)colsum_slices(n) * cout);
+  w.dwp = take(pl.dw_slices > 1 ? 4 * (size_t)pl.dw_slices * cout * K * cin : 0);
+  w.dbp = take(4 * (size_t)pl.db_slices * cout);
   w.bytes = off;
   return w;
 }
 
 template <bool TRANS>
-void launch_gemm(const float* x, int cin, const float* w, int64_t sk, int64_t sn, int64_t sc, const float* bias,
+void launch_gemm(int tile, const float* x, int cin, const float* w, int64_t sk, int64_t sn, int64_t sc, const float* bias,
                  const int32_t* nbr, int K, int mirror, const int32_t* rowmask, float* y, int nout, int64_t n,
                  hipStream_t st) {
-  const int64_t wide = ((n + 63) / 64) * ((nout + 63) / 64), tall = (n + 127) / 128;
-  if (nout > 32 && wide >= 256) {
+  if (tile == GCS_TILE_64X64) {
     dim3 grid((unsigned)((n + 63) / 64), (unsigned)((nout + 63) / 64));
     k_subm_gemm<64, 64, 4, 4, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
-  } else if (nout > 16 && nout <= 32 && tall >= 256) {
-    dim3 grid((unsigned)tall, 1);
+  } else if (tile == GCS_TILE_128X32) {
+    dim3 grid((unsigned)((n + 127) / 128), 1);  // nout <= 32: one column tile
     k_subm_gemm<128, 32, 4, 4, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
   } else {
     dim3 grid((unsigned)((n + 31) / 32), (unsigned)((nout + 31) / 32));
@@ -601,6 +621,18 @@ size_t gcs_subm_rulebook_scratch_bytes(int64_t n) {
 size_t gcs_subm_backward_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups) {
   if (check_conv_dims("gcs_subm_backward_workspace_bytes", n, kvol, cin, cout)) return 0;
   return carve_bwd(nullptr, n, cin, cout, kvol, dups).bytes;
+}
+
+int gcs_subm_plan(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t plan[5]) {
+  if (int rc = check_conv_dims("gcs_subm_plan", n, kvol, cin, cout)) return rc;
+  if (!plan) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_plan: null plan");
+  const Plan p = plan_of(n, cin, cout, kvol);
+  plan[0] = p.fwd;
+  plan[1] = p.dx;
+  plan[2] = p.dw;
+  plan[3] = p.dw_slices;
+  plan[4] = p.db_slices;
+  return 0;
 }
 
 int gcs_subm_rulebook(const int32_t* indices, int64_t n, int32_t batch_size, const int32_t* spatial_shape,
@@ -673,7 +705,8 @@ int gcs_subm_forward(const void* rulebook, int64_t n, int32_t kvol, const float*
   if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_forward: null features or output");
   const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
   hipStream_t st = (hipStream_t)hip_stream;
-  launch_gemm<false>(features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0, nullptr, out, cout, n, st);
+  launch_gemm<false>(plan_of(n, cin, cout, kvol).fwd, features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr,
+                     kvol, 0, nullptr, out, cout, n, st);
   HIP_TRY(hipGetLastError(), "forward launch");
   return 0;
 }
@@ -690,6 +723,7 @@ int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dup
     return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: null features or output gradient");
   hipStream_t st = (hipStream_t)hip_stream;
   const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  const Plan pl = plan_of(n, cin, cout, kvol);
   if (n == 0) {
     if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 4 * (size_t)cout * kvol * cin, st), "dw clear");
     if (db) HIP_TRY(hipMemsetAsync(db, 0, 4 * (size_t)cout, st), "db clear");
@@ -702,13 +736,13 @@ int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dup
       g = ws.dyf;
     }
     // dX[j][c] = sum_k sum_o W[o][k][c] * g[nbr[j][K-1-k]][o]: reduction over o (stride K*Cin), output c (stride 1)
-    launch_gemm<true>(g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1, dups ? rb.rep : nullptr,
-                      dx, cin, n, st);
+    launch_gemm<true>(pl.dx, g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1,
+                      dups ? rb.rep : nullptr, dx, cin, n, st);
   }
   if (dw) {
-    const int S = dw_slices(n, cin, cout, kvol);
+    const int S = pl.dw_slices;
     float* dst = S > 1 ? ws.dwp : dw;
-    if (cin >= 64 && cout >= 64) {
+    if (pl.dw == GCS_TILE_64X64) {
       dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)kvol, (unsigned)S);
       k_subm_dw<64, 64, 4, 4><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
     } else {
@@ -721,7 +755,7 @@ int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dup
     }
   }
   if (db) {
-    const int S = colsum_slices(n);
+    const int S = pl.db_slices;
     k_colsum<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
     k_sum_slices<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
   }

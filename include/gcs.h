@@ -44,11 +44,13 @@
 extern "C" {
 #endif
 
-#define GCS_ABI_VERSION 1
+#define GCS_ABI_VERSION 2
 #define GCS_HOST_INFO_HEADER 2 /* host_info words before the per-tap pair counts */
 
 enum gcs_status { GCS_OK = 0, GCS_ERR_INVALID_ARGUMENT = -1, GCS_ERR_HIP = -2 };
 enum gcs_reduce { GCS_SUM = 0, GCS_MEAN = 1, GCS_MIN = 2, GCS_MAX = 3 };
+/* workgroup tiles (rows x columns) of the convolution kernels, as gcs_subm_plan reports them */
+enum gcs_tile { GCS_TILE_32X32 = 0, GCS_TILE_64X64 = 1, GCS_TILE_128X32 = 2 };
 
 int gcs_abi_version(void);
 const char* gcs_last_error(void);
@@ -57,6 +59,12 @@ const char* gcs_last_error(void);
 size_t gcs_subm_rulebook_bytes(int64_t n, int32_t kvol);
 size_t gcs_subm_rulebook_scratch_bytes(int64_t n);
 size_t gcs_subm_backward_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups);
+
+/* Host only, no device work: the kernel variants that gcs_subm_forward / gcs_subm_backward launch for this shape, the
+ * one choice they dispatch from.  plan[0] = gcs_tile of the forward (n x cout), plan[1] = gcs_tile of dX (n x cin),
+ * plan[2] = gcs_tile of dW, plan[3] = slices of the dW sum, plan[4] = slices of the dB sum.  Tests ask it to make
+ * sure that a shape still reaches the variant it was chosen for. */
+int gcs_subm_plan(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t plan[5]);
 
 int gcs_subm_rulebook(const int32_t* indices, int64_t n, int32_t batch_size, const int32_t* spatial_shape,
                       const int32_t* ksize, const int32_t* dilation, void* rulebook, size_t rulebook_bytes,

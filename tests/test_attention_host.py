@@ -154,8 +154,8 @@ def test_reference_leaves_uncovered_rows_zero():
     assert not ref2["out"][16:].any() and ref2["out"][:16].any()
 
 
-def _emulated_worst(qkv, cu, dout, scale):
-    return R.errors_in_units(R.emulate(qkv, cu, dout, scale), R.reference(qkv, cu, dout, scale))
+def _emulated_worst(qkv, cu, dout, scale, max_seqlen=None):
+    return R.errors_in_units(R.emulate(qkv, cu, dout, scale, max_seqlen), R.reference(qkv, cu, dout, scale, max_seqlen))
 
 
 def test_emulated_contract_within_two_units_ragged():
@@ -173,3 +173,66 @@ def test_emulated_contract_within_two_units_amplitude(v_amp, do_amp):
         worst = _emulated_worst(qkv, cu, dout, 0.25)
         print("amplitude", amp, v_amp, do_amp, worst)
         assert max(worst.values()) <= 2.0, (amp, worst)
+
+
+# ---- the twins of the cases that tests/test_varlen_attention_gpu.py adds at head dimensions 32 and 64: the same seeds,
+# lengths, scales and cuts; the rounding contract alone must leave the GPU bar (4 units) half of its room
+SWEEP_LENS = R.RAGGED_LENS + [127, 128, 129, 191, 192, 193, 257]
+
+
+@pytest.mark.parametrize("d,scale", [(d, s) for d in (16, 32, 64) for s in (None, 0.25)] + [(64, -0.25), (64, 0.0)])
+def test_emulated_contract_within_two_units_length_sweep(d, scale):
+    qkv, cu, dout = R.random_case(200 + d, SWEEP_LENS, heads=3, d=d)
+    got = R.emulate(qkv, cu, dout, scale)
+    worst = R.errors_in_units(got, R.reference(qkv, cu, dout, scale))
+    print("length sweep", d, scale, worst)
+    assert max(worst.values()) <= 2.0, (d, scale, worst)
+    if scale == 0.0:
+        assert not got["dq"].any() and not got["dk"].any()
+
+
+@pytest.mark.parametrize("amp", [1.0, 3.0, 6.0])
+@pytest.mark.parametrize("d", [32, 64])
+def test_emulated_contract_within_two_units_amplitude_other_head_dims(d, amp):
+    qkv, cu, dout = R.random_case(300 + d + int(amp), [300], heads=1, d=d, qk_amp=amp)
+    worst = _emulated_worst(qkv, cu, dout, None)
+    print("amplitude", d, amp, worst)
+    assert max(worst.values()) <= 2.0, (d, amp, worst)
+
+
+@pytest.mark.parametrize("d,cut", [(32, 100), (64, 65)])
+def test_emulated_contract_within_two_units_cut_by_max_seqlen(d, cut):
+    qkv, cu, dout = R.random_case(400 + d, [300, 70], heads=2, d=d)
+    worst = _emulated_worst(qkv, cu, dout, None, cut)
+    print("cut", d, cut, worst)
+    assert max(worst.values()) <= 2.0, (d, cut, worst)
+    ref = R.reference(qkv, cu, dout, None, cut)
+    assert not ref["u_out"][cut:300].any() and ref["u_out"][:cut].all() and not ref["out"][300 + min(cut, 70):].any()
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_emulated_contract_within_two_units_strided_twin(d):
+    qkv, cu, dout = R.random_case(500 + d, [200, 56, 300], heads=3, d=d)
+    worst = _emulated_worst(qkv, cu, dout, None)
+    print("strided twin", d, worst)
+    assert max(worst.values()) <= 2.0, (d, worst)
+
+
+@pytest.mark.parametrize("d", [16, 32, 64])
+def test_emulated_contract_within_two_units_dout_layouts(d):
+    """The random dout of the layout cases, its float32 variant rounded to binary16, and dout = 1 (out.sum().backward())."""
+    qkv, cu, dout = R.random_case(600 + d, [130, 1, 0, 77, 200], heads=3, d=d)
+    d32 = np.random.default_rng(d).normal(size=dout.shape).astype(np.float32)
+    for what, g in (("random", dout), ("rounded float32", d32.astype(np.float16)), ("ones", np.ones_like(dout))):
+        worst = _emulated_worst(qkv, cu, g, None, 256)
+        print("dout", what, d, worst)
+        assert max(worst.values()) <= 2.0, (d, what, worst)
+
+
+@pytest.mark.parametrize("d", [16, 32, 64])
+def test_emulated_contract_within_two_units_lse_case(d):
+    lens = [1, 2, 63, 64, 65, 129, 300, 0, 5]
+    qkv, cu, dout = R.random_case(700 + d, lens, heads=2, d=d, total=sum(lens) + 9)
+    worst = _emulated_worst(qkv, cu, dout, None, 1024)
+    print("lse case", d, worst)
+    assert max(worst.values()) <= 2.0, (d, worst)

@@ -27,6 +27,45 @@ def test_workspace_queries(lib):
     assert lib.gcs_subm_rulebook_bytes(10, 0) == 0
 
 
+def test_plan_names_the_kernels_of_ptv3s_own_sizes(lib):
+    """gcs_subm_plan is the chooser the launches dispatch from; the GPU tests assert it before they run a variant."""
+    from gaussiancity_amd import _native_s as S
+    # stage 0 of the inference loop, 518 k points: the stem forward, the 32 -> 32 layers forward and their dX take
+    # the 128 x 32 tile; the stem's dX has 128 output columns and takes the 64 x 64 one
+    fwd, dx, dw, dws, dbs = S.subm_plan(518000, 128, 32, 125)
+    assert (fwd, dx, dw) == (S.TILE_128X32, S.TILE_64X64, S.TILE_32X32) and 1 < dws <= 32 and dbs == 64
+    assert S.subm_plan(518000, 32, 32, 27)[:3] == (S.TILE_128X32, S.TILE_128X32, S.TILE_32X32)
+    # the thresholds: 256 workgroups of 128 rows, or of 64 x 64; at most 16 or more than 32 columns leave the tall tile
+    assert S.subm_plan(32640, 32, 32, 27)[:2] == (S.TILE_32X32, S.TILE_32X32)
+    assert S.subm_plan(32641, 32, 17, 27)[:2] == (S.TILE_128X32, S.TILE_128X32)
+    assert S.subm_plan(32641, 16, 33, 27)[:2] == (S.TILE_64X64, S.TILE_32X32)
+    assert S.subm_plan(16320, 64, 64, 27)[:2] == (S.TILE_32X32, S.TILE_32X32)
+    assert S.subm_plan(16321, 64, 64, 27)[:3] == (S.TILE_64X64, S.TILE_64X64, S.TILE_64X64)
+    assert S.subm_plan(4033, 256, 200, 27)[:3] == (S.TILE_64X64, S.TILE_64X64, S.TILE_64X64)
+    # dW: 64 x 64 only when both channel counts reach 64; slices: ceil(2048 / workgroups), at least 256 rows each, 32 at most
+    assert S.subm_plan(5000, 64, 63, 27)[2] == S.TILE_32X32 and S.subm_plan(5000, 64, 64, 27)[2] == S.TILE_64X64
+    assert S.subm_plan(511, 64, 64, 27)[3] == 1 and S.subm_plan(5000, 64, 64, 27)[3] == 19
+    assert S.subm_plan(16384, 512, 512, 27)[3] == 2 and S.subm_plan(10 ** 6, 4, 4, 27)[3] == 32
+    # dB: one slice per 2048 rows, 64 at most
+    assert [S.subm_plan(n, 4, 4, 27)[4] for n in (0, 4095, 4096, 10 ** 6)] == [1, 1, 2, 64]
+    # the workspace follows the same plan: the dW slices and the dB slices are in it
+    n, cin, cout, k = 5000, 64, 64, 27
+    assert lib.gcs_subm_backward_workspace_bytes(n, cin, cout, k, 0) >= 19 * cout * k * cin * 4 + 2 * cout * 4
+
+
+def test_plan_rejects_bad_arguments(lib):
+    out = (C.c_int32 * 5)()
+    assert lib.gcs_subm_plan(-1, 4, 4, 27, out) < 0 and b"n out of range" in lib.gcs_last_error()
+    assert lib.gcs_subm_plan(2 ** 31, 4, 4, 27, out) < 0
+    assert lib.gcs_subm_plan(10, 0, 4, 27, out) < 0 and b"channel" in lib.gcs_last_error()
+    assert lib.gcs_subm_plan(10, 4, 65537, 27, out) < 0 and b"channel" in lib.gcs_last_error()
+    assert lib.gcs_subm_plan(10, 4, 4, 0, out) < 0 and b"kernel volume" in lib.gcs_last_error()
+    assert lib.gcs_subm_plan(10, 4, 4, 1025, out) < 0
+    assert lib.gcs_subm_plan(2 ** 30, 4, 4, 27, out) < 0 and b"kernel volume" in lib.gcs_last_error()   # n * K beyond int32
+    assert lib.gcs_subm_plan(10, 4, 4, 27, None) < 0 and b"null plan" in lib.gcs_last_error()
+    assert lib.gcs_subm_plan(0, 1, 1, 1, out) == 0 and list(out) == [0, 0, 0, 1, 1]
+
+
 def _rulebook(lib, ksize=(3, 3, 3), dilation=(1, 1, 1), shape=(8, 8, 8), batch=1, n=4, buf=1, scratch=1, size=1 << 20):
     from gaussiancity_amd import _native_s as S
     info = (C.c_int32 * 200)()

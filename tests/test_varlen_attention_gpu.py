@@ -33,13 +33,17 @@ def dev():
 
 
 def _run(dev, qkv, cu, dout, max_seqlen, scale=None):
-    """Forward + backward through the drop-in; out, dq, dk, dv as numpy binary16."""
+    """Forward + backward through the drop-in; out, dq, dk, dv as numpy binary16.  `dout` is a numpy array (copied to the
+    device, contiguous), a tensor that is handed to backward() as it is, or None for out.sum().backward()."""
     import flash_attn
     x = (qkv if isinstance(qkv, torch.Tensor) else torch.from_numpy(qkv).to(dev)).requires_grad_(True)
     out = flash_attn.flash_attn_varlen_qkvpacked_func(x, torch.from_numpy(np.asarray(cu, np.int32)).to(dev), max_seqlen,
                                                       softmax_scale=scale)
     assert out.dtype == torch.float16 and tuple(out.shape) == (x.shape[0], x.shape[2], x.shape[3])
-    out.backward(torch.from_numpy(dout).to(dev))
+    if dout is None:
+        out.sum().backward()
+    else:
+        out.backward(dout if isinstance(dout, torch.Tensor) else torch.from_numpy(dout).to(dev))
     assert x.grad.dtype == torch.float16 and x.grad.shape == x.shape
     g = x.grad.cpu().numpy()
     return {"out": out.detach().cpu().numpy(), "dq": g[:, 0], "dk": g[:, 1], "dv": g[:, 2]}
@@ -91,6 +95,49 @@ def test_other_head_dims(dev, d):
     assert d in SUPPORTED_HEAD_DIMS
     qkv, cu, dout = R.random_case(50 + d, [1, 17, 64, 130, 300, 0, 77], heads=2, d=d)
     _check(dev, qkv, cu, dout, 300, None, "head dimension %d" % d)
+
+
+SWEEP_LENS = R.RAGGED_LENS + [127, 128, 129, 191, 192, 193, 257]
+
+
+@pytest.mark.parametrize("d,scale", [(d, s) for d in (16, 32, 64) for s in (None, 0.25)] + [(64, -0.25), (64, 0.0)])
+def test_length_sweep_at_every_head_dim(dev, d, scale):
+    """Every staged-block boundary (64-key steps, 128-row blocks, the 64-row blocks of the dK/dV pass at d = 64) at every
+    head dimension: the LDS pitches differ with d."""
+    qkv, cu, dout = R.random_case(200 + d, SWEEP_LENS, heads=3, d=d)
+    got = _check(dev, qkv, cu, dout, 1024, scale, "length sweep d = %d, scale %r" % (d, scale))
+    if scale == 0.0:
+        # uniform attention: the reference that _check compared with IS the segment's mean of V, and scale * dS is exactly zero
+        assert not got["dq"].any() and not got["dk"].any()
+        ref = R.reference(qkv, cu, dout, scale)["out"]
+        v = qkv[:, 2].astype(np.float64)
+        for b, n in R.segments(cu, qkv.shape[0]):
+            if n:
+                assert np.abs(ref[b:b + n] - v[b:b + n].mean(axis=0)).max() <= 1e-12
+
+
+@pytest.mark.parametrize("amp", [1.0, 3.0, 6.0])
+@pytest.mark.parametrize("d", [32, 64])
+def test_amplitude_at_other_head_dims(dev, d, amp):
+    qkv, cu, dout = R.random_case(300 + d + int(amp), [300], heads=1, d=d, qk_amp=amp)
+    _check(dev, qkv, cu, dout, 300, None, "d = %d, amplitude %g" % (d, amp))
+
+
+@pytest.mark.parametrize("d,cut", [(32, 100), (64, 65)])
+def test_cut_by_max_seqlen_against_the_reference(dev, d, cut):
+    """A segment longer than max_seqlen is its first max_seqlen rows: those match the reference of the cut segment, the
+    rows beyond have unit 0 and must be exact zeros (errors_in_units counts anything else as infinitely wrong)."""
+    qkv, cu, dout = R.random_case(400 + d, [300, 70], heads=2, d=d)
+    got = _run(dev, qkv, cu, dout, cut, None)
+    ref = R.reference(qkv, cu, dout, None, max_seqlen=cut)
+    worst = R.errors_in_units(got, ref)
+    print("cut at %d, d = %d: worst error in units %s" % (cut, d, {k: round(v, 3) for k, v in worst.items()}))
+    assert all(v <= BAR for v in worst.values()), worst
+    kept = min(cut, 70)                                     # of the second segment, rows 300 .. 369
+    for n in R.NAMES:
+        assert ref["u_" + n][:cut].all() and not ref["u_" + n][cut:300].any() and not ref["u_" + n][300 + kept:].any()
+        assert got[n][:cut].any() and not got[n][cut:300].any(), n
+        assert got[n][300:300 + kept].any() and not got[n][300 + kept:].any(), n
 
 
 def test_orientation_one_hot_is_a_copy(dev):
@@ -179,6 +226,102 @@ def test_strided_qkv_gives_the_same_bits(dev):
         c = _run(dev, perm, cu, dout, 1024, 0.25)
         for n in R.NAMES:
             assert _same_bits(c[n], b[n]), (dims, n)
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_strided_qkv_gives_the_same_bits_at_other_head_dims(dev, d):
+    heads = 3
+    qkv, cu, dout = R.random_case(500 + d, [200, 56, 300], heads=heads, d=d)
+    total, width = qkv.shape[0], 3 * heads * d
+    wide = torch.zeros(total, width + 64, dtype=torch.float16, device=dev)
+    wide[:, 8:8 + width] = torch.from_numpy(qkv).to(dev).reshape(total, width)
+    view = wide[:, 8:8 + width].view(total, 3, heads, d).detach()
+    assert not view.is_contiguous() and view.stride() == (width + 64, heads * d, d, 1)
+    a = _run(dev, view, cu, dout, 300, None)
+    b = _check(dev, qkv, cu, dout, 300, None, "contiguous twin of the strided view, d = %d" % d)
+    for n in R.NAMES:
+        assert _same_bits(a[n], b[n]), n
+
+
+@pytest.mark.parametrize("d", [16, 32, 64])
+def test_strided_and_converted_dout(dev, d):
+    """dout_row_stride and dout_head_stride reach three kernels (delta, dK/dV, dQ); every layout that the autograd
+    layer passes through as it is, and every one it converts, gives the bits of the contiguous binary16 dout."""
+    heads = 3
+    qkv, cu, dout = R.random_case(600 + d, [130, 1, 0, 77, 200], heads=heads, d=d)
+    total = qkv.shape[0]
+    base = _check(dev, qkv, cu, dout, 256, None, "contiguous dout, d = %d" % d)
+    t = torch.from_numpy(dout).to(dev)
+    # a slice of a wider row: the head stride is d, the row stride is not H * d
+    wide = torch.full((total, heads * d + 64), 7.0, dtype=torch.float16, device=dev)
+    wide[:, 8:8 + heads * d] = t.reshape(total, heads * d)
+    row_view = wide[:, 8:8 + heads * d].view(total, heads, d)
+    assert row_view.stride() == (heads * d + 64, d, 1)
+    # the middle of a [total, H, 2 d] buffer: the head stride is larger than d
+    deep = torch.full((total, heads, 2 * d), 7.0, dtype=torch.float16, device=dev)
+    deep[:, :, 8:8 + d] = t
+    head_view = deep[:, :, 8:8 + d]
+    assert head_view.stride() == (2 * heads * d, 2 * d, 1)
+    for what, g in (("row-strided", row_view), ("head-strided", head_view), ("float32", t.float())):
+        got = _run(dev, qkv, cu, g, 256, None)
+        for n in R.NAMES:
+            assert _same_bits(got[n], base[n]), (what, n)
+    # float32 values that are no binary16 numbers: the bits of their binary16 rounding
+    rng = np.random.default_rng(d)
+    d32 = rng.normal(size=dout.shape).astype(np.float32)
+    got = _run(dev, qkv, cu, torch.from_numpy(d32).to(dev), 256, None)
+    want = _run(dev, qkv, cu, d32.astype(np.float16), 256, None)
+    for n in R.NAMES:
+        assert _same_bits(got[n], want[n]), ("float32 rounding", n)
+    # out.sum().backward(): an expanded dout (every stride 0) over real segments
+    got = _run(dev, qkv, cu, None, 256, None)
+    worst = R.errors_in_units(got, R.reference(qkv, cu, np.ones_like(dout), None, 256))
+    print("expanded dout = 1, d = %d: worst error in units %s" % (d, {k: round(v, 3) for k, v in worst.items()}))
+    assert all(v <= BAR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("d", [16, 32, 64])
+def test_log_sum_exp(dev, d):
+    """lse [heads][total] of gca_varlen_forward, called directly: the float64 log-sum-exp on covered rows, exactly 0 on
+    the others.
+
+    Tolerance, from what the kernel does.  lse = (m + log2f(l)) * ln 2, m the fp32 maximum of the scores in units of
+    log2, l the fp32 sum of v_exp_f32(s - m).  An error ds_j of score j moves lse by p_j ds_j, so the scores count
+    with their softmax weight: at most max |ds_j| over the keys that matter, whose scores are near the maximum and so
+    no larger than |lse| + log(n).  A score is d exact products summed in fp32 (d - 1 roundings of partial sums that
+    are of the size of the score times a few: about sqrt(d) / 2 half-ulps as a random walk, 2 ulp at d = 64) and one
+    product with scale * log2(e) (1/2 ulp).  Then 1 ulp for every v_exp_f32, the sum of up to 300 terms of one sign as 4
+    partial sums per lane and two lane exchanges (about sqrt(300 / 16) half-ulps relative to l, i.e. 2 * 2^-24
+    absolute on lse), 1 ulp for log2f, 1/2 each for the sum and the product with ln 2.  Together below 6 ulp; the
+    bound is 8 ulp of max(|lse|, 1), ulp = 2^-23, and the worst ratio is printed."""
+    from gaussiancity_amd import _native_a as A
+    heads, lens = 2, [1, 2, 63, 64, 65, 129, 300, 0, 5]
+    qkv, cu, _ = R.random_case(700 + d, lens, heads=heads, d=d, total=sum(lens) + 9)     # nine rows that no segment covers
+    total = qkv.shape[0]
+    scale = d ** -0.5
+    x = torch.from_numpy(qkv).to(dev)
+    cut = torch.from_numpy(cu).to(dev)
+    out = torch.empty(total, heads, d, dtype=torch.float16, device=dev)
+    lse = torch.full((heads, total), 7.0, dtype=torch.float32, device=dev)
+    A.check(A.lib().gca_varlen_forward(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), cut.data_ptr(), len(lens), total,
+                                       heads, d, 1024, scale, out.data_ptr(), lse.data_ptr(), None), "gca_varlen_forward")
+    torch.cuda.synchronize()
+    got = lse.cpu().numpy().astype(np.float64)
+    want = np.zeros((heads, total))
+    f = qkv.astype(np.float64)
+    for b, n in R.segments(cu, total):
+        for h in range(heads):
+            if n:
+                s = scale * (f[b:b + n, 0, h] @ f[b:b + n, 1, h].T)
+                m = s.max(axis=1)
+                want[h, b:b + n] = m + np.log(np.exp(s - m[:, None]).sum(axis=1))
+    covered = np.zeros(total, bool)
+    covered[:sum(lens)] = True
+    assert not got[:, ~covered].any() and (~covered).sum() == 9
+    tol = 8 * 2.0 ** -23 * np.maximum(np.abs(want), 1.0)
+    err = np.abs(got - want)
+    print("lse d = %d: worst error %.3g of the tolerance" % (d, float((err / tol)[:, covered].max())))
+    assert (err <= tol)[:, covered].all()
 
 
 def test_two_runs_are_bit_identical(dev):
