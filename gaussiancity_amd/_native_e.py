@@ -7,7 +7,7 @@ from . import _loader
 
 DTYPE_F32, DTYPE_F16, DTYPE_F64 = 0, 1, 2  # enum gce_dtype
 STAGE_NAMES = ("forward", "backward_embeddings", "backward_inputs")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _vp, _u32, _f32, _int = C.c_void_p, C.c_uint32, C.c_float, C.c_int
 _SIGNATURES = {  # every function include/gce.h declares: name -> (restype, argtypes)
@@ -21,6 +21,9 @@ _SIGNATURES = {  # every function include/gce.h declares: name -> (restype, argt
     "gce_forward_t": (_int, [_int, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _int, _vp, _u32, _int, _vp]),
     "gce_backward_t": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _int, _vp, _vp, _u32, _int,
                               _vp]),
+    "gce_backward_det_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32, _u32]),
+    "gce_backward_det": (_int, [_int, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _f32, _u32, _int, _vp, _vp, _u32, _int,
+                                _vp, C.c_size_t, _vp]),
 }
 
 _L = _loader.Library("gce", "libgce_hip.so", ABI_VERSION, _SIGNATURES, STAGE_NAMES)

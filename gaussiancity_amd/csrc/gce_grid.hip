@@ -9,7 +9,8 @@
 //   * a row of C = 8 floats is 32 B = two dwordx4 loads; the 2^D corner indices are computed once and
 //     kept in registers, so the input-gradient pass (D * 2^(D-1) left/right pairs) re-reads rows that
 //     are L1/L2 hits instead of re-hashing (upstream hashes them again);
-//   * backward uses hardware global_atomic_add_f32 (the library is built with -munsafe-fp-atomics).
+//   * backward uses hardware global_atomic_add_f32 (the library is built with -munsafe-fp-atomics); gce_backward_det
+//     (gce_det.h) forms the same table gradient without float atomics, bit-identical from run to run.
 // Arithmetic follows the reference's association order without contraction (gce-fp32-v1), so forward
 // and dy_dx are bit-comparable with oracle/gce_oracle.c.
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/gce.h"
 #define GC_ERR_HIP GCE_ERR_HIP
@@ -288,6 +290,10 @@ __global__ __launch_bounds__(256) void k_input_bwd(const float* __restrict__ gra
 template <typename T>
 struct GceOps;
 template <>
+struct GceOps<float> {  // the float kernels above spell their arithmetic out; gce_det.h needs the one product
+  static __device__ __forceinline__ float mulw(float w, float g) { return w * g; }
+};
+template <>
 struct GceOps<double> {
   static __device__ __forceinline__ double mulw(float w, double g) { return (double)w * g; }  // float * double -> double
   static __device__ __forceinline__ double add(double a, double b) { return a + b; }
@@ -481,6 +487,8 @@ int check_dims(uint32_t B, uint32_t D, uint32_t C, uint32_t L) {
 
 }  // namespace
 
+#include "gce_det.h"  // deterministic table gradient (ABI v3): keys, sort, reduce
+
 // ---- typed entry points (ABI v2): dtype of embeddings / outputs / dy_dx / grad / grad_embeddings / grad_inputs
 template <typename T>
 static int forward_typed(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs, uint32_t B,
@@ -506,6 +514,42 @@ static int backward_typed(const void* grad, const float* inputs, const int32_t* 
     StageTimer t(s, stage_slot(ST_BWD_IN));
     GCE_DISPATCH_DC(D, C, (k_input_bwd_t<T, D, C><<<(B * D + 255) / 256, 256, 0, s>>>((const T*)grad, (const T*)dy_dx,
                                                                                     (T*)grad_inputs, B, L)))
+  }
+  return 0;
+}
+
+// ---- deterministic table gradient (ABI v3).  The checks every entry point of it shares: the check_dims limits, and what
+// keeps ids and keys in 31 bits.
+static int det_check(uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t total_rows) {
+  if (int rc = check_dims(B, D, C, L)) return rc;
+  if ((((uint64_t)L * B) << D) >= (1ull << 31))
+    return fail(GCE_ERR_UNSUPPORTED, "gce_backward_det: L * B * 2^D contributions must stay below 2^31");
+  if (total_rows > 0x7FFFFFFFu) return fail(GCE_ERR_UNSUPPORTED, "gce_backward_det: total_rows must fit an int32 offset");
+  return 0;
+}
+
+template <typename T>
+static int backward_det_typed(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings,
+                              uint32_t total_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L, const LevelScales& sc,
+                              int calc_grad_inputs, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
+                              char* ws, const DetLayout& lay, hipStream_t s) {
+  {
+    StageTimer t(s, stage_slot(ST_BWD_EMB));
+    hipError_t e = hipSuccess;
+    GCE_DISPATCH_DC(D, C, (e = det_launch<T, D, C>((const T*)grad, inputs, offsets, (T*)grad_embeddings, total_rows, B, L, sc,
+                                                   gridtype, align_corners != 0, ws, lay, s)))
+    HIP_TRY(e, "deterministic grid backward launch");
+  }
+  if (calc_grad_inputs) {
+    StageTimer t(s, stage_slot(ST_BWD_IN));
+    if constexpr (std::is_same<T, float>::value) {
+      GCE_DISPATCH_DC(D, C, (k_input_bwd<D, C><<<(B * D + 255) / 256, 256, 0, s>>>((const float*)grad, (const float*)dy_dx,
+                                                                                 (float*)grad_inputs, B, L)))
+    } else {
+      GCE_DISPATCH_DC(D, C, (k_input_bwd_t<T, D, C><<<(B * D + 255) / 256, 256, 0, s>>>((const T*)grad, (const T*)dy_dx,
+                                                                                      (T*)grad_inputs, B, L)))
+    }
+    HIP_TRY(hipGetLastError(), "input backward launch");
   }
   return 0;
 }
@@ -623,6 +667,43 @@ int gce_backward_t(int dtype, const void* grad, const float* inputs, const void*
   if (rc) return rc;
   HIP_TRY(hipGetLastError(), "grid backward launch");
   return 0;
+}
+
+size_t gce_backward_det_workspace_bytes(uint32_t B, uint32_t D, uint32_t L, uint32_t total_rows) {
+  if (det_check(B, D, 1, L, total_rows)) return 0;
+  g_err.clear();
+  if (B == 0) return 0;
+  return det_layout((L * B) << D, total_rows).total;
+}
+
+int gce_backward_det(int dtype, const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings,
+                     uint32_t total_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                     int calc_grad_inputs, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
+                     void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rc = det_check(B, D, C, L, total_rows)) return rc;
+  if (dtype != GCE_F32 && dtype != GCE_F16 && dtype != GCE_F64)
+    return fail(GCE_ERR_UNSUPPORTED, "gce_backward_det: dtype must be GCE_F32, GCE_F16 or GCE_F64");
+  if (B == 0) return 0;
+  const DetLayout lay = det_layout((L * B) << D, total_rows);
+  if (!workspace || workspace_bytes < lay.total)
+    return fail(GCE_ERR_INVALID_ARGUMENT, "gce_backward_det: workspace is null or smaller than gce_backward_det_workspace_bytes (" +
+                                              std::to_string(lay.total) + " bytes)");
+  if ((uintptr_t)workspace & 15u) return fail(GCE_ERR_INVALID_ARGUMENT, "gce_backward_det: workspace must be 16-byte aligned");
+  if (!grad || !inputs || !offsets || !grad_embeddings) return fail(GCE_ERR_INVALID_ARGUMENT, "gce_backward_det: null tensor");
+  if (calc_grad_inputs && (!dy_dx || !grad_inputs))
+    return fail(GCE_ERR_INVALID_ARGUMENT, "gce_backward_det: calc_grad_inputs needs dy_dx and grad_inputs");
+  LevelScales sc;
+  gce_level_scales(L, S, H, sc.v);
+  hipStream_t s = (hipStream_t)hip_stream;
+  char* ws = (char*)workspace;
+  if (dtype == GCE_F16)
+    return backward_det_typed<_Float16>(grad, inputs, offsets, grad_embeddings, total_rows, B, D, C, L, sc, calc_grad_inputs, dy_dx,
+                                        grad_inputs, gridtype, align_corners, ws, lay, s);
+  if (dtype == GCE_F64)
+    return backward_det_typed<double>(grad, inputs, offsets, grad_embeddings, total_rows, B, D, C, L, sc, calc_grad_inputs, dy_dx,
+                                      grad_inputs, gridtype, align_corners, ws, lay, s);
+  return backward_det_typed<float>(grad, inputs, offsets, grad_embeddings, total_rows, B, D, C, L, sc, calc_grad_inputs, dy_dx,
+                                   grad_inputs, gridtype, align_corners, ws, lay, s);
 }
 
 }  // extern "C"

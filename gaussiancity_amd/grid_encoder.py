@@ -2,6 +2,9 @@
 
   ext_forward / ext_backward   the native module's two functions, positional signatures of
                                extensions/grid_encoder/bindings.cpp:19-40 (re-exported by grid_encoder_ext.py)
+  ext_backward_deterministic   ext_backward with the table gradient summed in a fixed order (gce_backward_det: no float
+                               atomics, bit-identical from run to run); set_deterministic / GCE_DETERMINISTIC /
+                               torch.use_deterministic_algorithms make ext_backward route to it.  Off by default.
   GridEncoderFunction          extensions/grid_encoder/__init__.py:18-124
   GridEncoder                  extensions/grid_encoder/__init__.py:127-193 (same constructor arguments, buffers,
                                parameter name `embeddings`, init range, output layout)
@@ -11,6 +14,7 @@ library.  The embeddings' dtype selects the kernels as upstream's AT_DISPATCH_FL
 (grid_encoder_ext.cu:555,597): float32 (GaussianCity's own; the tuned kernels), float16, float64.  `inputs` are float32.
 """
 import math
+import os
 
 import torch
 
@@ -19,6 +23,48 @@ from ._loader import current_stream as _stream
 
 
 _DTYPES = {torch.float32: E.DTYPE_F32, torch.float16: E.DTYPE_F16, torch.float64: E.DTYPE_F64}
+
+_STATS = {"atomic_backward_calls": 0, "deterministic_backward_calls": 0}
+
+
+def stats():
+    """Counters of this process: which table-gradient path the backward calls took."""
+    return dict(_STATS)
+
+
+def reset_stats():
+    for k in _STATS:
+        _STATS[k] = 0
+
+
+def _env_flag(name):
+    v = os.environ.get(name, "").strip()
+    if v == "":
+        return None
+    if v not in ("0", "1"):
+        raise RuntimeError("%s must be 0 or 1 (got %r)" % (name, v))
+    return v == "1"
+
+
+_ENV_DETERMINISTIC = _env_flag("GCE_DETERMINISTIC")  # read once, at import
+_deterministic = None                                # set_deterministic's explicit setting
+
+
+def set_deterministic(mode):
+    """True / False: every backward takes the deterministic / the atomic table gradient.  None: no explicit setting --
+    GCE_DETERMINISTIC decides, and without it torch.are_deterministic_algorithms_enabled()."""
+    global _deterministic
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError("set_deterministic takes True, False or None (got %r)" % (mode,))
+    _deterministic = mode
+
+
+def deterministic_enabled():
+    if _deterministic is not None:
+        return _deterministic
+    if _ENV_DETERMINISTIC is not None:
+        return _ENV_DETERMINISTIC
+    return bool(torch.are_deterministic_algorithms_enabled())
 
 
 def _chk(t, name, dtype=None):
@@ -57,7 +103,11 @@ def ext_forward(inputs, embeddings, offsets, outputs, B, D, C_, L, S, H, calc_gr
 
 def ext_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C_, L, S, H, calc_grad_inputs, dy_dx,
                  grad_inputs, gridtype, align_corners):
-    """grid_encoder_ext.backward (bindings.cpp:25-33): accumulates into grad_embeddings, fills grad_inputs."""
+    """grid_encoder_ext.backward (bindings.cpp:25-33): accumulates into grad_embeddings, fills grad_inputs.  With
+    deterministic_enabled() the call goes to ext_backward_deterministic."""
+    if deterministic_enabled():
+        return ext_backward_deterministic(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C_, L, S, H,
+                                          calc_grad_inputs, dy_dx, grad_inputs, gridtype, align_corners)
     code = _scalar_type(embeddings)
     _chk(inputs, "inputs", torch.float32)
     for t, n in ((grad, "grad"), (embeddings, "embeddings"), (grad_embeddings, "grad_embeddings"), (dy_dx, "dy_dx"),
@@ -69,6 +119,33 @@ def ext_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C_, L
                                        grad_embeddings.data_ptr(), int(B), int(D), int(C_), int(L), float(S), int(H),
                                        int(bool(calc_grad_inputs)), dy_dx.data_ptr(), grad_inputs.data_ptr(),
                                        int(gridtype), int(bool(align_corners)), _stream()), "gce_backward")
+    _STATS["atomic_backward_calls"] += 1
+
+
+def ext_backward_deterministic(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C_, L, S, H, calc_grad_inputs, dy_dx,
+                               grad_inputs, gridtype, align_corners, workspace=None):
+    """ext_backward through gce_backward_det (include/gce.h): the same terms, every table row summed in one fixed order
+    and added once into grad_embeddings; grad_inputs as ext_backward.  `workspace`: a CUDA uint8 tensor of at least
+    gce_backward_det_workspace_bytes; by default one from the caching allocator (its contents never matter)."""
+    code = _scalar_type(embeddings)
+    _chk(inputs, "inputs", torch.float32)
+    for t, n in ((grad, "grad"), (embeddings, "embeddings"), (grad_embeddings, "grad_embeddings"), (dy_dx, "dy_dx"),
+                 (grad_inputs, "grad_inputs")):
+        _chk(t, n, embeddings.dtype)
+    _chk(offsets, "offsets")
+    lib = E.lib()
+    rows = int(grad_embeddings.shape[0])
+    need = int(lib.gce_backward_det_workspace_bytes(int(B), int(D), int(L), rows))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=inputs.device)
+    else:
+        _chk(workspace, "workspace", torch.uint8)
+    with torch.cuda.device(inputs.device):
+        E.check(lib.gce_backward_det(code, grad.data_ptr(), inputs.data_ptr(), offsets.data_ptr(), grad_embeddings.data_ptr(),
+                                     rows, int(B), int(D), int(C_), int(L), float(S), int(H), int(bool(calc_grad_inputs)),
+                                     dy_dx.data_ptr(), grad_inputs.data_ptr(), int(gridtype), int(bool(align_corners)),
+                                     workspace.data_ptr(), int(workspace.numel()), _stream()), "gce_backward_det")
+    _STATS["deterministic_backward_calls"] += 1
 
 
 class _Geometry:
@@ -120,7 +197,7 @@ class GridEncoderFunction(torch.autograd.Function):
         B, D, Cc, L, S, H, gridtype = ctx.dims
         wants_inputs = ctx.calc_grad_inputs
         upstream = grad.reshape(B, L, Cc).transpose(0, 1).contiguous()      # back to level-major
-        d_table = torch.zeros_like(table)                                   # the kernel accumulates with atomics
+        d_table = torch.zeros_like(table)                                   # the kernels add into it
         d_points = table.new_zeros(points.shape if wants_inputs else (1,))
         ext_backward(upstream, points, table, level_rows, d_table, B, D, Cc, L, S, H, wants_inputs, jacobian, d_points,
                      gridtype, ctx.align_corners)

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define GCE_ABI_VERSION 2
+#define GCE_ABI_VERSION 3
 #define GCE_MAX_LEVELS 32
 
 enum gce_status { GCE_OK = 0, GCE_ERR_INVALID_ARGUMENT = -1, GCE_ERR_HIP = -2, GCE_ERR_UNSUPPORTED = -3 };
@@ -64,6 +64,34 @@ int gce_backward_t(int dtype, const void* grad, const float* inputs, const void*
                    void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                    int calc_grad_inputs, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
                    void* hip_stream);
+
+/* Deterministic table gradient (ABI v3): gce_backward_t's result without float atomics.  Arguments as gce_backward_t
+ * (minus `embeddings`, which no kernel reads), plus
+ *   total_rows   offsets[L] = rows of the table.  From the host, because offsets lives on the device and the width of the
+ *                sort keys must be known without waiting for it.
+ *   workspace    device memory of at least gce_backward_det_workspace_bytes(B, D, L, total_rows) bytes (about 16.8 bytes
+ *                per contribution, n = L * B * 2^D of them), 16-byte aligned.  Its contents before the call do not matter.
+ * The n contributions are keyed by table row, stable-sorted by key, and every row's run is summed in an order fixed by
+ * the sorted positions.  Contract:
+ *   - same terms as the atomic path: the w * gc products k_grid_bwd / k_grid_bwd_t add, with the same rounding (binary16:
+ *     float * half -> float, then rounded to half).  Only the summation differs.
+ *   - a row's sum is formed in float for GCE_F32 and GCE_F16 tables, in double for GCE_F64.
+ *   - one add into the table: grad_embeddings[row] = old + sum, rounded once to the table's type.  Rows that nothing
+ *     contributes to are not written.  A point outside [0,1], and a row >= total_rows (bad offsets), contribute nothing.
+ *   - a pure function of the arguments: not of the number of resident workgroups, the stream, what the workspace held,
+ *     or calc_grad_inputs.  No float atomics (integer atomics build the sort's histograms).
+ *   - everything is enqueued on hip_stream; nothing waits for the host; the library allocates no device memory.
+ *   - grad_inputs comes from the same kernel as in gce_backward_t.
+ * gce_backward_det_workspace_bytes returns 0 with a message in gce_last_error() for arguments out of range (D, L as
+ * above; n >= 2^31; total_rows >= 2^31), and 0 with the message cleared for the valid empty problem B == 0.
+ * gce_backward_det checks, in this order and before any HIP call: dims, dtype, B == 0 (returns 0), workspace null /
+ * short / misaligned (GCE_ERR_INVALID_ARGUMENT, "workspace" in the message), null tensors.  Its time is reported under
+ * stage 1. */
+size_t gce_backward_det_workspace_bytes(uint32_t B, uint32_t D, uint32_t L, uint32_t total_rows);
+int gce_backward_det(int dtype, const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings,
+                     uint32_t total_rows, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                     int calc_grad_inputs, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
+                     void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* avg device ms per stage since the last call (option "timing"; hipEvent pairs on the caller's stream, a ring of 8
  * pairs per stage): 0 forward, 1 backward_embeddings, 2 backward_inputs */
