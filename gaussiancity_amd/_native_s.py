@@ -8,10 +8,13 @@ from . import _loader
 REDUCE = {"sum": 0, "add": 0, "mean": 1, "min": 2, "max": 3}  # enum gcs_reduce
 TILE_32X32, TILE_64X64, TILE_128X32 = 0, 1, 2  # enum gcs_tile
 HOST_INFO_HEADER = 2  # GCS_HOST_INFO_HEADER: invalid rows, duplicate flag, then pairs per tap
-ABI_VERSION = 2
+ENGINE_VALU, ENGINE_MFMA = 0, 1  # enum gcs_engine
+ENGINES = {"valu": ENGINE_VALU, "mfma": ENGINE_MFMA}
+ABI_VERSION = 3
 
 _vp, _sz, _i32, _i64, _int = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int
 _pi32 = C.POINTER(_i32)
+_psz = C.POINTER(_sz)
 _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argtypes)
     "gcs_abi_version": (_int, []),
     "gcs_last_error": (C.c_char_p, []),
@@ -22,6 +25,11 @@ _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argt
     "gcs_subm_rulebook": (_int, [_vp, _i64, _i32, _pi32, _pi32, _pi32, _vp, _sz, _vp, _sz, _pi32, _vp]),
     "gcs_subm_forward": (_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "gcs_subm_backward": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcs_subm_engine_plan": (_int, [_i32, _i64, _i32, _i32, _i32, _pi32]),
+    "gcs_subm_engine_workspace_bytes": (_int, [_i32, _i64, _i32, _i32, _i32, _i32, _psz, _psz]),
+    "gcs_subm_forward_engine": (_int, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "gcs_subm_backward_engine": (_int, [_i32, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
+                                        _vp]),
     "gcs_segment_csr_forward": (_int, [_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "gcs_segment_csr_backward": (_int, [_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
@@ -41,3 +49,18 @@ def subm_plan(n, cin, cout, kvol):
     out = (C.c_int32 * 5)()
     check(lib().gcs_subm_plan(n, cin, cout, kvol, out), "gcs_subm_plan")
     return tuple(out)
+
+
+def subm_engine_plan(engine, n, cin, cout, kvol):
+    """gcs_subm_engine_plan: subm_plan's five values, then the tap slices of the forward and of dX (1, 1 for VALU)."""
+    out = (C.c_int32 * 7)()
+    check(lib().gcs_subm_engine_plan(engine, n, cin, cout, kvol, out), "gcs_subm_engine_plan")
+    return tuple(out)
+
+
+def subm_engine_workspace_bytes(engine, n, cin, cout, kvol, dups):
+    """(forward bytes, backward bytes) of gcs_subm_engine_workspace_bytes; the forward's are 0 with one tap slice."""
+    f, b = _sz(0), _sz(0)
+    check(lib().gcs_subm_engine_workspace_bytes(engine, n, cin, cout, kvol, dups, C.byref(f), C.byref(b)),
+          "gcs_subm_engine_workspace_bytes")
+    return int(f.value), int(b.value)

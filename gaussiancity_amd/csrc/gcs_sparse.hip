@@ -12,6 +12,8 @@
 // fp32 FMA GEMM of the gathered rows against W[:, k, :].  dX is the same kernel with mirrored taps and W read
 // transposed, on dy folded onto the representatives.  dW: per tap, a GEMM over the tap's pair list, cut into a
 // fixed number of slices that are summed in slice order.  Every sum has a fixed order: no float atomics.
+// Opt-in second engine (GCS_ENGINE_MFMA, gcs_mfma.h): the same gather-GEMM on the f32 matrix cores, in tap slices where
+// the tile grid cannot fill the GPU; the entry points without `_engine` in their names are the VALU engine.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -353,6 +355,8 @@ __global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, 
   }
 }
 
+#include "gcs_mfma.h"
+
 // dw partial of slice s: part[s][o][k][c] = sum over the slice's pairs p of tap k: dy[i_p][o] * x[nbr[i_p][k]][c]
 constexpr int KR = 16;
 template <int TO, int TC, int MR, int MC>
@@ -562,13 +566,51 @@ Plan plan_of(int64_t n, int32_t cin, int32_t cout, int32_t K) {
   return p;
 }
 
+// Tap slices of the matrix-core engine for an n x nout gemm over K taps under `tile`: 1 once the tile grid has 256
+// workgroups (a shape that fills the GPU keeps the VALU engine's values), below that enough slices for about
+// GCS_SLICE_TARGET workgroups, normalised so that no slice is empty.  A function of (n, nout, K) only.
+#ifndef GCS_SLICE_TARGET
+#define GCS_SLICE_TARGET 512
+#endif
+int tap_slices(int64_t n, int32_t nout, int32_t K, int tile) {
+  const int tm = tile == GCS_TILE_64X64 ? 64 : tile == GCS_TILE_128X32 ? 128 : 32;
+  const int tn = tile == GCS_TILE_64X64 ? 64 : 32;
+  const int64_t wgs = ((n + tm - 1) / tm) * ((nout + tn - 1) / tn);
+  if (wgs == 0 || wgs >= 256) return 1;
+  int64_t s = ((int64_t)GCS_SLICE_TARGET + wgs - 1) / wgs;
+  s = s < 1 ? 1 : (s > K ? K : s);
+  const int64_t per = (K + s - 1) / s;
+  return (int)((K + per - 1) / per);
+}
+struct EnginePlan {
+  Plan p;
+  int32_t fwd_slices, dx_slices;  // tap slices of the forward and of dX: 1, 1 for the VALU engine
+};
+EnginePlan engine_plan_of(int32_t engine, int64_t n, int32_t cin, int32_t cout, int32_t K) {
+  EnginePlan e;
+  e.p = plan_of(n, cin, cout, K);
+  const bool mfma = engine == GCS_ENGINE_MFMA;
+  e.fwd_slices = mfma ? tap_slices(n, cout, K, e.p.fwd) : 1;
+  e.dx_slices = mfma ? tap_slices(n, cin, K, e.p.dx) : 1;
+  return e;
+}
+int check_engine(const char* who, int32_t engine) {
+  if (engine != GCS_ENGINE_VALU && engine != GCS_ENGINE_MFMA)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown engine (GCS_ENGINE_VALU or GCS_ENGINE_MFMA)");
+  return 0;
+}
+size_t forward_ws_bytes(const EnginePlan& e, int64_t n, int32_t cout) {
+  return e.fwd_slices > 1 ? align_up(4 * (size_t)e.fwd_slices * n * cout) : 0;
+}
+
 struct BwdWs {
   float* dyf;    // [N][Cout] when dups
   float* dwp;    // [S][Cout][K][Cin] when S > 1
   float* dbp;    // [Sb][Cout]
+  float* dxp;    // [Sx][N][Cin] when dX runs in Sx > 1 tap slices (matrix-core engine)
   size_t bytes;
 };
-BwdWs carve_bwd(void* base, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups) {
+BwdWs carve_bwd(void* base, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups, int dx_slices = 1) {
   BwdWs w;
   char* p = (char*)base;
   size_t off = 0;
@@ -581,6 +623,7 @@ BwdWs carve_bwd(void* base, int64_t n, int32_t cin, int32_t cout, int32_t K, int
   w.dyf = take(dups ? 4 * (size_t)n * cout : 0);
   w.dwp = take(pl.dw_slices > 1 ? 4 * (size_t)pl.dw_slices * cout * K * cin : 0);
   w.dbp = take(4 * (size_t)pl.db_slices * cout);
+  w.dxp = take(dx_slices > 1 ? 4 * (size_t)dx_slices * n * cin : 0);
   w.bytes = off;
   return w;
 }
@@ -602,6 +645,91 @@ void launch_gemm(int tile, const float* x, int cin, const float* w, int64_t sk, 
 }
 
 unsigned blocks_for(int64_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
+
+// the forward and the backward of both engines; `who` names the entry point in the error texts
+int subm_forward(const char* who, int32_t engine, const void* rulebook, int64_t n, int32_t kvol, const float* features,
+                 int32_t cin, const float* weight, const float* bias, int32_t cout, float* out, void* workspace,
+                 size_t workspace_bytes, void* hip_stream) {
+  const std::string me(who);
+  if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
+  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
+  if (n == 0) return 0;
+  if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output");
+  const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
+  const size_t need = forward_ws_bytes(e, n, cout);
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than gcs_subm_engine_workspace_bytes");
+  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (engine == GCS_ENGINE_MFMA)
+    launch_gemm_mfma<false>(e.p.fwd, e.fwd_slices, features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0,
+                            nullptr, out, cout, n, (float*)workspace, st);
+  else
+    launch_gemm<false>(e.p.fwd, features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0, nullptr, out,
+                       cout, n, st);
+  HIP_TRY(hipGetLastError(), "forward launch");
+  return 0;
+}
+
+int subm_backward(const char* who, int32_t engine, const void* rulebook, int64_t n, int32_t kvol, int32_t dups,
+                  const float* features, int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx,
+                  float* dw, float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const std::string me(who);
+  if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
+  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
+  const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
+  const Plan& pl = e.p;
+  const BwdWs ws = carve_bwd(workspace, n, cin, cout, kvol, dups, e.dx_slices);
+  if (!workspace || workspace_bytes < ws.bytes)
+    return fail(GCS_ERR_INVALID_ARGUMENT,
+                me + (engine == GCS_ENGINE_VALU ? ": workspace missing or smaller than gcs_subm_backward_workspace_bytes"
+                                                : ": workspace missing or smaller than gcs_subm_engine_workspace_bytes"));
+  if (n > 0 && (!dout || ((dx || dw) && !features)))
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output gradient");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  if (n == 0) {
+    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 4 * (size_t)cout * kvol * cin, st), "dw clear");
+    if (db) HIP_TRY(hipMemsetAsync(db, 0, 4 * (size_t)cout, st), "db clear");
+    return 0;
+  }
+  if (dx) {
+    const float* g = dout;
+    if (dups) {
+      k_fold<<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
+      g = ws.dyf;
+    }
+    // dX[j][c] = sum_k sum_o W[o][k][c] * g[nbr[j][K-1-k]][o]: reduction over o (stride K*Cin), output c (stride 1)
+    if (engine == GCS_ENGINE_MFMA)
+      launch_gemm_mfma<true>(pl.dx, e.dx_slices, g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1,
+                             dups ? rb.rep : nullptr, dx, cin, n, ws.dxp, st);
+    else
+      launch_gemm<true>(pl.dx, g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1,
+                        dups ? rb.rep : nullptr, dx, cin, n, st);
+  }
+  if (dw) {
+    const int S = pl.dw_slices;
+    float* dst = S > 1 ? ws.dwp : dw;
+    if (pl.dw == GCS_TILE_64X64) {
+      dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)kvol, (unsigned)S);
+      k_subm_dw<64, 64, 4, 4><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
+    } else {
+      dim3 grid((unsigned)(((cout + 31) / 32) * ((cin + 31) / 32)), (unsigned)kvol, (unsigned)S);
+      k_subm_dw<32, 32, 2, 2><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
+    }
+    if (S > 1) {
+      const int64_t len = (int64_t)cout * kvol * cin;
+      k_sum_slices<<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
+    }
+  }
+  if (db) {
+    const int S = pl.db_slices;
+    k_colsum<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
+    k_sum_slices<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
+  }
+  HIP_TRY(hipGetLastError(), "backward launch");
+  return 0;
+}
 
 }  // namespace
 
@@ -699,67 +827,54 @@ int gcs_subm_rulebook(const int32_t* indices, int64_t n, int32_t batch_size, con
 
 int gcs_subm_forward(const void* rulebook, int64_t n, int32_t kvol, const float* features, int32_t cin,
                      const float* weight, const float* bias, int32_t cout, float* out, void* hip_stream) {
-  if (int rc = check_conv_dims("gcs_subm_forward", n, kvol, cin, cout)) return rc;
-  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_forward: null rulebook or weight");
-  if (n == 0) return 0;
-  if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_forward: null features or output");
-  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
-  hipStream_t st = (hipStream_t)hip_stream;
-  launch_gemm<false>(plan_of(n, cin, cout, kvol).fwd, features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr,
-                     kvol, 0, nullptr, out, cout, n, st);
-  HIP_TRY(hipGetLastError(), "forward launch");
-  return 0;
+  return subm_forward("gcs_subm_forward", GCS_ENGINE_VALU, rulebook, n, kvol, features, cin, weight, bias, cout, out, nullptr,
+                      0, hip_stream);
+}
+int gcs_subm_forward_engine(int32_t engine, const void* rulebook, int64_t n, int32_t kvol, const float* features,
+                            int32_t cin, const float* weight, const float* bias, int32_t cout, float* out,
+                            void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rc = check_engine("gcs_subm_forward_engine", engine)) return rc;
+  return subm_forward("gcs_subm_forward_engine", engine, rulebook, n, kvol, features, cin, weight, bias, cout, out, workspace,
+                      workspace_bytes, hip_stream);
 }
 
 int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const float* features,
                       int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx, float* dw,
                       float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (int rc = check_conv_dims("gcs_subm_backward", n, kvol, cin, cout)) return rc;
-  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: null rulebook or weight");
-  const BwdWs ws = carve_bwd(workspace, n, cin, cout, kvol, dups);
-  if (!workspace || workspace_bytes < ws.bytes)
-    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: workspace missing or smaller than gcs_subm_backward_workspace_bytes");
-  if (n > 0 && (!dout || ((dx || dw) && !features)))
-    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_backward: null features or output gradient");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
-  const Plan pl = plan_of(n, cin, cout, kvol);
-  if (n == 0) {
-    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 4 * (size_t)cout * kvol * cin, st), "dw clear");
-    if (db) HIP_TRY(hipMemsetAsync(db, 0, 4 * (size_t)cout, st), "db clear");
-    return 0;
-  }
-  if (dx) {
-    const float* g = dout;
-    if (dups) {
-      k_fold<<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
-      g = ws.dyf;
-    }
-    // dX[j][c] = sum_k sum_o W[o][k][c] * g[nbr[j][K-1-k]][o]: reduction over o (stride K*Cin), output c (stride 1)
-    launch_gemm<true>(pl.dx, g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1,
-                      dups ? rb.rep : nullptr, dx, cin, n, st);
-  }
-  if (dw) {
-    const int S = pl.dw_slices;
-    float* dst = S > 1 ? ws.dwp : dw;
-    if (pl.dw == GCS_TILE_64X64) {
-      dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)kvol, (unsigned)S);
-      k_subm_dw<64, 64, 4, 4><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
-    } else {
-      dim3 grid((unsigned)(((cout + 31) / 32) * ((cin + 31) / 32)), (unsigned)kvol, (unsigned)S);
-      k_subm_dw<32, 32, 2, 2><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
-    }
-    if (S > 1) {
-      const int64_t len = (int64_t)cout * kvol * cin;
-      k_sum_slices<<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
-    }
-  }
-  if (db) {
-    const int S = pl.db_slices;
-    k_colsum<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
-    k_sum_slices<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
-  }
-  HIP_TRY(hipGetLastError(), "backward launch");
+  return subm_backward("gcs_subm_backward", GCS_ENGINE_VALU, rulebook, n, kvol, dups, features, cin, weight, cout, dout, dx, dw,
+                       db, workspace, workspace_bytes, hip_stream);
+}
+int gcs_subm_backward_engine(int32_t engine, const void* rulebook, int64_t n, int32_t kvol, int32_t dups,
+                             const float* features, int32_t cin, const float* weight, int32_t cout, const float* dout,
+                             float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rc = check_engine("gcs_subm_backward_engine", engine)) return rc;
+  return subm_backward("gcs_subm_backward_engine", engine, rulebook, n, kvol, dups, features, cin, weight, cout, dout, dx, dw,
+                       db, workspace, workspace_bytes, hip_stream);
+}
+
+int gcs_subm_engine_plan(int32_t engine, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t plan[7]) {
+  if (int rc = check_engine("gcs_subm_engine_plan", engine)) return rc;
+  if (int rc = check_conv_dims("gcs_subm_engine_plan", n, kvol, cin, cout)) return rc;
+  if (!plan) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_engine_plan: null plan");
+  const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
+  plan[0] = e.p.fwd;
+  plan[1] = e.p.dx;
+  plan[2] = e.p.dw;
+  plan[3] = e.p.dw_slices;
+  plan[4] = e.p.db_slices;
+  plan[5] = e.fwd_slices;
+  plan[6] = e.dx_slices;
+  return 0;
+}
+int gcs_subm_engine_workspace_bytes(int32_t engine, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups,
+                                    size_t* forward_bytes, size_t* backward_bytes) {
+  if (int rc = check_engine("gcs_subm_engine_workspace_bytes", engine)) return rc;
+  if (int rc = check_conv_dims("gcs_subm_engine_workspace_bytes", n, kvol, cin, cout)) return rc;
+  if (!forward_bytes || !backward_bytes)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_engine_workspace_bytes: null output");
+  const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
+  *forward_bytes = forward_ws_bytes(e, n, cout);
+  *backward_bytes = carve_bwd(nullptr, n, cin, cout, kvol, dups, e.dx_slices).bytes;
   return 0;
 }
 

@@ -9,26 +9,59 @@ is in the HIP library.  fp32 only.  Semantics that spconv leaves open are fixed 
   * several rows on one voxel: the lowest row is the voxel's representative, every row of the voxel gets the same
     output, and only representatives are read as neighbours;
   * min / max of segment_csr: the gradient goes to the first row that attains the value.
+
+Two engines run the forward and dX of the convolution (include/gcs.h, ABI v3): "valu", the default, and "mfma", the same
+gather-GEMM on the f32 matrix cores, cut over the taps where the grid is small.  set_engine() / get_engine() choose for
+the convolutions that start afterwards; the environment variable GCS_ENGINE gives the initial value.
 """
 import ctypes as C
+import functools
 import math
+import os
 
 import torch
 
 from . import _native_s as S
 from ._loader import current_stream as _stream
 
-_STATS = {"rulebook_builds": 0}
+_STATS = {"rulebook_builds": 0, "conv_forward_calls_valu": 0, "conv_forward_calls_mfma": 0}
 
 
 def stats():
-    """Counters of this process: `rulebook_builds` counts rulebooks built (a reused indice_key does not build)."""
+    """Counters of this process: `rulebook_builds` counts rulebooks built (a reused indice_key does not build),
+    `conv_forward_calls_valu` / `conv_forward_calls_mfma` the convolution forwards each engine ran."""
     return dict(_STATS)
 
 
 def reset_stats():
     for k in _STATS:
         _STATS[k] = 0
+
+
+def _engine_name(name, where):
+    if name not in S.ENGINES:
+        raise ValueError("%s: the engine must be \"valu\" or \"mfma\", got %r" % (where, name))
+    return name
+
+
+_ENGINE = _engine_name(os.environ.get("GCS_ENGINE", "valu"), "GCS_ENGINE")
+
+
+def get_engine():
+    """The engine that the next SubMConv3d forward will run (and with it that layer's backward): "valu" or "mfma"."""
+    return _ENGINE
+
+
+def set_engine(name):
+    """Choose "valu" or "mfma" for the convolutions whose forward starts from now on; returns the previous name."""
+    global _ENGINE
+    prev, _ENGINE = _ENGINE, _engine_name(name, "set_engine")
+    return prev
+
+
+@functools.lru_cache(maxsize=256)
+def _engine_workspace_bytes(engine, n, cin, cout, kvol, dups):
+    return S.subm_engine_workspace_bytes(engine, n, cin, cout, kvol, dups)
 
 
 def _triple(v, name):
@@ -126,12 +159,25 @@ class SubMConvFunction(torch.autograd.Function):
         w = weight.contiguous()
         n, cin, cout = x.shape[0], x.shape[1], w.shape[0]
         out = x.new_empty((n, cout))
+        engine = _ENGINE  # read once: the backward of this call runs the same engine, whatever is set by then
+        b_ptr = bias.contiguous().data_ptr() if bias is not None else None
         with torch.cuda.device(x.device):
-            S.check(S.lib().gcs_subm_forward(rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None, cin,
-                                             w.data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-                                             cout, out.data_ptr() if n else None, _stream()), "gcs_subm_forward")
+            if engine == "valu":
+                S.check(S.lib().gcs_subm_forward(rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None, cin,
+                                                 w.data_ptr(), b_ptr, cout, out.data_ptr() if n else None, _stream()),
+                        "gcs_subm_forward")
+            else:
+                ws_bytes = _engine_workspace_bytes(S.ENGINES[engine], n, cin, cout, rb.kvol, rb.dups)[0]
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+                S.check(S.lib().gcs_subm_forward_engine(S.ENGINES[engine], rb.buf.data_ptr(), n, rb.kvol,
+                                                        x.data_ptr() if n else None, cin, w.data_ptr(), b_ptr, cout,
+                                                        out.data_ptr() if n else None,
+                                                        ws.data_ptr() if ws is not None else None, ws_bytes, _stream()),
+                        "gcs_subm_forward_engine")
+        _STATS["conv_forward_calls_" + engine] += 1
         ctx.save_for_backward(x, w)
         ctx.rb = rb
+        ctx.engine = engine
         ctx.has_bias = bias is not None
         return out
 
@@ -146,13 +192,21 @@ class SubMConvFunction(torch.autograd.Function):
         dw = w.new_empty(w.shape) if want_w else None
         db = w.new_empty((cout,)) if want_b else None
         L = S.lib()
-        ws_bytes = L.gcs_subm_backward_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
         ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
-        with torch.cuda.device(x.device):
-            S.check(L.gcs_subm_backward(rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x), cin, w.data_ptr(), cout,
-                                        ptr(dy), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(), ws_bytes, _stream()),
-                    "gcs_subm_backward")
+        if ctx.engine == "valu":
+            ws_bytes = L.gcs_subm_backward_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+            with torch.cuda.device(x.device):
+                S.check(L.gcs_subm_backward(rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x), cin, w.data_ptr(), cout,
+                                            ptr(dy), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(), ws_bytes, _stream()),
+                        "gcs_subm_backward")
+        else:
+            ws_bytes = _engine_workspace_bytes(S.ENGINES[ctx.engine], n, cin, cout, rb.kvol, rb.dups)[1]
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+            with torch.cuda.device(x.device):
+                S.check(L.gcs_subm_backward_engine(S.ENGINES[ctx.engine], rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x),
+                                                   cin, w.data_ptr(), cout, ptr(dy), ptr(dx), ptr(dw), ptr(db),
+                                                   ws.data_ptr(), ws_bytes, _stream()), "gcs_subm_backward_engine")
         return dx, dw, db, None
 
 

@@ -1,13 +1,16 @@
 """Timing of the HIP submanifold convolution (gaussiancity_amd.sparse) on PTv3's distinct convolution shapes, against
 a yardstick of torch ops on the same neighbour map (per tap: index_select + mm + index_add_, torch's own BLAS).
 
-  python tools/sparse_bench.py [--reps 7] [--iters 10] [--inference-n 262144] [--out FILE]
+  python tools/sparse_bench.py [--reps 7] [--iters 10] [--inference-n 262144] [--out FILE] [--engine valu|mfma|both]
 
 Clouds: a 16 384-point building shell (tests/sparse_ref.shell_cloud) pooled stage by stage (coords >> 1) gives the
 N of every stage; the stage-0 shapes also run on an inference-sized shell of --inference-n points.  One JSON line per
 shape: rulebook build, forward and forward + backward in ms (median over --reps blocks of --iters calls, device
 events), the present pairs, the FLOP and byte floors of those pairs, and the yardstick's forward and forward +
-backward.  Needs a GPU; there is no CPU path."""
+backward.  --engine picks the engine of the forward and dX gemms (gaussiancity_amd.sparse.set_engine); `both` runs the
+two engines one after the other shape by shape in this one process and writes one line per shape and engine to
+profiles/sparse_bench_engines.jsonl (or --out).  Every timing comes with the spread of its block medians
+((max - min) / median over the --reps blocks).  Needs a GPU; there is no CPU path."""
 import argparse
 import json
 import os
@@ -27,6 +30,11 @@ import sparse_ref as R  # noqa: E402
 from gaussiancity_amd import sparse as SP  # noqa: E402
 
 
+class Timing(float):
+    """Median ms per call; `.spread` is (max - min) / median of the blocks it is the median of."""
+    spread = 0.0
+
+
 def timed(fn, reps, iters):
     """Median ms per call over `reps` blocks of `iters` calls, device events around each block."""
     fn()
@@ -40,7 +48,9 @@ def timed(fn, reps, iters):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out)
+    t = Timing(statistics.median(out))
+    t.spread = (max(out) - min(out)) / t if t > 0 else 0.0
+    return t
 
 
 def yardstick(x, w, bias, taps, dy):
@@ -70,8 +80,16 @@ def yardstick(x, w, bias, taps, dy):
     return fwd, fwdbwd
 
 
-def bench_shape(dev, coords, cin, cout, k, bias, reps, iters, label):
+def bench_shape(dev, coords, cin, cout, k, bias, reps, iters, label, engine="valu"):
     import spconv.pytorch as spconv
+    previous = SP.set_engine(engine)
+    try:
+        return _bench_shape(spconv, dev, coords, cin, cout, k, bias, reps, iters, label, engine)
+    finally:
+        SP.set_engine(previous)
+
+
+def _bench_shape(spconv, dev, coords, cin, cout, k, bias, reps, iters, label, engine):
     n = len(coords)
     idx = torch.from_numpy(R.with_batch(coords, np.zeros(n))).to(dev)
     shape = (coords.max(0) + 3).tolist()
@@ -121,7 +139,9 @@ def bench_shape(dev, coords, cin, cout, k, bias, reps, iters, label):
     K = nbr.shape[1]
     flop_f = 2.0 * pairs * cin * cout
     bytes_f = 4.0 * (n * cin + n * cout + K * cin * cout) + 4.0 * n * K
-    return {"shape": label, "cin": cin, "cout": cout, "k": k, "n": n, "pairs": pairs,
+    plan = SP.S.subm_engine_plan(SP.S.ENGINES[engine], n, cin, cout, K)
+    return {"shape": label, "engine": engine, "fwd_slices": plan[5], "dx_slices": plan[6],
+            "fwd_spread": round(fwd_ms.spread, 4), "fwdbwd_spread": round(fb_ms.spread, 4), "cin": cin, "cout": cout, "k": k, "n": n, "pairs": pairs,
             "rulebook_ms": round(statistics.median(builds), 4), "fwd_ms": round(fwd_ms, 4), "fwdbwd_ms": round(fb_ms, 4),
             "torch_fwd_ms": round(tf_ms, 4), "torch_fwdbwd_ms": round(tfb_ms, 4),
             "fwd_speedup": round(tf_ms / fwd_ms, 2), "fwdbwd_speedup": round(tfb_ms / fb_ms, 2),
@@ -136,6 +156,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--inference-n", type=int, default=262144)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--engine", choices=["valu", "mfma", "both"], default="valu")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sparse_bench needs a GPU")
@@ -147,11 +168,13 @@ def main():
         cases += [(big, 128, 32, 5, False, "128->32 k5 inference"), (big, 32, 32, 3, True, "32->32 k3 inference")]
     lines = []
     for coords, cin, cout, k, bias, label in cases:
-        rec = bench_shape(dev, coords, cin, cout, k, bias, a.reps, a.iters, label)
-        print(json.dumps(rec), flush=True)
-        lines.append(rec)
-    if a.out:
-        with open(a.out, "w") as f:
+        for engine in (("valu", "mfma") if a.engine == "both" else (a.engine,)):
+            rec = bench_shape(dev, coords, cin, cout, k, bias, a.reps, a.iters, label, engine)
+            print(json.dumps(rec), flush=True)
+            lines.append(rec)
+    out = a.out or (os.path.join(ROOT, "profiles", "sparse_bench_engines.jsonl") if a.engine == "both" else None)
+    if out:
+        with open(out, "w") as f:
             for rec in lines:
                 f.write(json.dumps(rec) + "\n")
 
