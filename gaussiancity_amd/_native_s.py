@@ -10,7 +10,8 @@ TILE_32X32, TILE_64X64, TILE_128X32 = 0, 1, 2  # enum gcs_tile
 HOST_INFO_HEADER = 2  # GCS_HOST_INFO_HEADER: invalid rows, duplicate flag, then pairs per tap
 ENGINE_VALU, ENGINE_MFMA = 0, 1  # enum gcs_engine
 ENGINES = {"valu": ENGINE_VALU, "mfma": ENGINE_MFMA}
-ABI_VERSION = 3
+PRODUCT_FORWARD, PRODUCT_DX, PRODUCT_DW = 1, 2, 4  # GCS_PRODUCT_*: the bits of gcs_engine_products
+ABI_VERSION = 4
 
 _vp, _sz, _i32, _i64, _int = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int
 _pi32 = C.POINTER(_i32)
@@ -25,6 +26,7 @@ _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argt
     "gcs_subm_rulebook": (_int, [_vp, _i64, _i32, _pi32, _pi32, _pi32, _vp, _sz, _vp, _sz, _pi32, _vp]),
     "gcs_subm_forward": (_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "gcs_subm_backward": (_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcs_engine_products": (_int, [_i32]),
     "gcs_subm_engine_plan": (_int, [_i32, _i64, _i32, _i32, _i32, _pi32]),
     "gcs_subm_engine_workspace_bytes": (_int, [_i32, _i64, _i32, _i32, _i32, _i32, _psz, _psz]),
     "gcs_subm_forward_engine": (_int, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
@@ -49,6 +51,11 @@ def subm_plan(n, cin, cout, kvol):
     out = (C.c_int32 * 5)()
     check(lib().gcs_subm_plan(n, cin, cout, kvol, out), "gcs_subm_plan")
     return tuple(out)
+
+
+def engine_products(engine):
+    """gcs_engine_products: the PRODUCT_* bits of what `engine` runs on the matrix cores (0 for VALU, 7 for MFMA)."""
+    return check(lib().gcs_engine_products(engine), "gcs_engine_products")
 
 
 def subm_engine_plan(engine, n, cin, cout, kvol):

@@ -1,8 +1,10 @@
-// gcs_mfma.h -- the matrix-core engine of the submanifold convolution (GCS_ENGINE_MFMA, include/gcs.h): the gather-GEMM
-// of k_subm_gemm on v_mfma_f32_16x16x4_f32, and the tap slices for grids too small to fill the GPU.  Included by
-// gcs_sparse.hip after k_subm_gemm (it uses KC); device code and launch helpers only, the C ABI stays in gcs_sparse.hip.
+// gcs_mfma.h -- the matrix-core engine of the submanifold convolution (GCS_ENGINE_MFMA, include/gcs.h): its three products
+// on v_mfma_f32_16x16x4_f32.  The gather-GEMM of k_subm_gemm (forward and dX) with the tap slices for grids too small to
+// fill the GPU comes first, the weight gradient of k_subm_dw (k_subm_dw_mfma, with its own comment) last.  Included by
+// gcs_sparse.hip after k_subm_gemm (it uses KC and KR); device code and launch helpers only, the C ABI stays in
+// gcs_sparse.hip.
 //
-// Contract, the same as k_subm_gemm's: every output element is ONE chain from 0.0f over (tap in loop order, channel
+// Forward and dX.  Contract, the same as k_subm_gemm's: every output element is ONE chain from 0.0f over (tap in loop order, channel
 // ascending), the bias added after the chain.  The f32-input MFMA is a k-ordered fmaf chain (one rounding per product,
 // nothing wider inside), so with the same workgroup tile (gemm_tile), the same block-uniform tap skip and the same
 // 16-channel zero-padded slices this kernel gives k_subm_gemm's values; tests/test_sparse_engine_gpu.py holds it to that.
@@ -165,6 +167,122 @@ void launch_gemm_mfma(int tile, int S, const float* x, int cin, const float* w, 
   if (S > 1) {
     const int64_t len = n * nout;
     k_slice_epilogue<<<(unsigned)((len + 255) / 256), 256, 0, st>>>(part, S, n, nout, bias, rowmask, y);
+  }
+}
+
+// ---- dW -------------------------------------------------------------------------------------------------------------
+// k_subm_dw on the matrix cores: part[s][o][k][c] = sum over the pairs p of slice s of tap k: dy[i_p][o] * x[nbr[i_p][k]][c].
+// The grid, the slices [p0, p1) and the zero-filled last chunk are k_subm_dw's; every element is one chain from 0.0f over
+// the slice's pairs in list order, KR pairs per chunk = four chained MFMAs per accumulator.  Square tiles, T = 64 or 32.
+// Both operands are pair-major LDS images at a pitch of T + 16 words, Ds[pair][o] and Xs[pair][c]: the 64 lanes of a
+// fragment read (4 pairs x 16 columns) fall on 64 banks (pitch mod 64 = 16 or 48), a staging write is contiguous.
+// Three loads run ahead of the MFMAs of chunk c, none depending on another: the rows of x / dy of chunk c + 1, the nbr
+// entries of chunk c + 2, the prow entries of chunk c + 3.  A thread stages NQ = T / 16 elements of each image, in the
+// pairs r = tid / T + (256 / T) q, and keeps the indices of those pairs itself (a wave asks for one or two addresses).
+template <int TO, int TC>
+__global__ __launch_bounds__(256) void k_subm_dw_mfma(const float* __restrict__ dy, int cout, const float* __restrict__ x,
+                                                      int cin, const int32_t* __restrict__ nbr, int K,
+                                                      const int32_t* __restrict__ prow, const int32_t* __restrict__ hdr,
+                                                      int64_t n, int nslice, float* __restrict__ part) {
+  static_assert(TO == TC && (TO == 32 || TO == 64), "tile shape: one staging map serves both images");
+  constexpr int T = TO;
+  constexpr int WT = T / 2, FR = WT / 16;  // waves 2 x 2, a wave's outputs WT x WT
+  constexpr int NQ = KR * T / 256, RSTEP = 256 / T;
+  constexpr int PITCH = T + 16;
+  __shared__ float Ds[KR * PITCH];
+  __shared__ float Xs[KR * PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = (wave >> 1) * WT, wc = (wave & 1) * WT;
+  const int fl = lane & 15, fk = lane >> 4;
+  const int sr = tid / T, scol = tid % T;  // staging: pair sr + RSTEP * q, column scol
+  const int tiles_c = (cin + T - 1) / T;
+  const int o0 = (blockIdx.x / tiles_c) * T, c0 = (blockIdx.x % tiles_c) * T;
+  const int k = blockIdx.y, s = blockIdx.z;
+  const int64_t cnt = hdr[4 + k];
+  const int64_t per = (cnt + nslice - 1) / nslice;
+  const int64_t p0 = s * per, p1 = p0 + per < cnt ? p0 + per : cnt;
+  mfma_f32x4 acc[FR][FR];
+#pragma unroll
+  for (int i = 0; i < FR; i++)
+#pragma unroll
+    for (int j = 0; j < FR; j++) acc[i][j] = mfma_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  int32_t ia[NQ], ja[NQ], ib[NQ];  // (row, neighbour) of the chunk after this one; rows of the one after that
+  float rd[NQ], rx[NQ];
+  auto rows = [&](int64_t p, int32_t (&ii)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      const int64_t e = p + sr + RSTEP * q;
+      ii[q] = e < p1 ? prow[(int64_t)k * n + e] : -1;
+    }
+  };
+  auto nbrs = [&](const int32_t (&ii)[NQ], int32_t (&jj)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; q++) jj[q] = ii[q] >= 0 ? nbr[(int64_t)ii[q] * K + k] : -1;
+  };
+  auto fetch = [&]() {
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      rd[q] = (ia[q] >= 0 && o0 + scol < cout) ? dy[(int64_t)ia[q] * cout + o0 + scol] : 0.0f;
+      rx[q] = (ja[q] >= 0 && c0 + scol < cin) ? x[(int64_t)ja[q] * cin + c0 + scol] : 0.0f;
+    }
+  };
+  rows(p0, ia);
+  nbrs(ia, ja);
+  fetch();
+  rows(p0 + KR, ia);
+  nbrs(ia, ja);
+  rows(p0 + 2 * KR, ib);
+  for (int64_t p = p0; p < p1; p += KR) {
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      Ds[(sr + RSTEP * q) * PITCH + scol] = rd[q];
+      Xs[(sr + RSTEP * q) * PITCH + scol] = rx[q];
+    }
+    __syncthreads();
+    fetch();
+    nbrs(ib, ja);
+#pragma unroll
+    for (int q = 0; q < NQ; q++) ia[q] = ib[q];
+    rows(p + 3 * KR, ib);
+#pragma unroll
+    for (int kk = 0; kk < KR; kk += 4) {
+      float a[FR], b[FR];
+#pragma unroll
+      for (int i = 0; i < FR; i++) a[i] = Ds[(kk + fk) * PITCH + wr + 16 * i + fl];
+#pragma unroll
+      for (int j = 0; j < FR; j++) b[j] = Xs[(kk + fk) * PITCH + wc + 16 * j + fl];
+#pragma unroll
+      for (int i = 0; i < FR; i++)
+#pragma unroll
+        for (int j = 0; j < FR; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  float* out = part + (int64_t)s * cout * K * cin;
+#pragma unroll
+  for (int i = 0; i < FR; i++)
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const int o = o0 + wr + 16 * i + 4 * fk + v;
+      if (o >= cout) continue;
+#pragma unroll
+      for (int j = 0; j < FR; j++) {
+        const int c = c0 + wc + 16 * j + fl;
+        if (c < cin) out[((int64_t)o * K + k) * cin + c] = acc[i][j][v];
+      }
+    }
+}
+
+// the launch of k_subm_dw on the matrix cores: the same grid, slices and destination
+void launch_dw_mfma(int tile, int S, const float* dy, int cout, const float* x, int cin, const int32_t* nbr, int K,
+                    const int32_t* prow, const int32_t* hdr, int64_t n, float* dst, hipStream_t st) {
+  if (tile == GCS_TILE_64X64) {
+    dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)K, (unsigned)S);
+    k_subm_dw_mfma<64, 64><<<grid, 256, 0, st>>>(dy, cout, x, cin, nbr, K, prow, hdr, n, S, dst);
+  } else {
+    dim3 grid((unsigned)(((cout + 31) / 32) * ((cin + 31) / 32)), (unsigned)K, (unsigned)S);
+    k_subm_dw_mfma<32, 32><<<grid, 256, 0, st>>>(dy, cout, x, cin, nbr, K, prow, hdr, n, S, dst);
   }
 }
 

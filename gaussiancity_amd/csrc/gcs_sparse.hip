@@ -12,8 +12,9 @@
 // fp32 FMA GEMM of the gathered rows against W[:, k, :].  dX is the same kernel with mirrored taps and W read
 // transposed, on dy folded onto the representatives.  dW: per tap, a GEMM over the tap's pair list, cut into a
 // fixed number of slices that are summed in slice order.  Every sum has a fixed order: no float atomics.
-// Opt-in second engine (GCS_ENGINE_MFMA, gcs_mfma.h): the same gather-GEMM on the f32 matrix cores, in tap slices where
-// the tile grid cannot fill the GPU; the entry points without `_engine` in their names are the VALU engine.
+// Opt-in second engine (GCS_ENGINE_MFMA, gcs_mfma.h): the same three products (forward, dX, dW) on the f32 matrix cores,
+// the gather-GEMM in tap slices where the tile grid cannot fill the GPU; the entry points without `_engine` in their
+// names are the VALU engine.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -285,6 +286,7 @@ __global__ void k_group_sort(int64_t n, const int32_t* hdr, const int32_t* __res
 // tap(k) = k, or K-1-k (mirror, for dX).  rowmask: rows with rowmask[row] != row are written 0 (dX of duplicates).
 // 256 threads; a thread owns MR rows x MC columns; TRANS picks the coalesced order of the weight tile load.
 constexpr int KC = 16;
+constexpr int KR = 16;  // pairs per LDS chunk of the dW kernels (k_subm_dw below, k_subm_dw_mfma in gcs_mfma.h)
 template <int TM, int TN, int MR, int MC, bool TRANS>
 __global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, int cin, const float* __restrict__ w,
                                                    int64_t sk, int64_t sn, int64_t sc, const float* __restrict__ bias,
@@ -358,7 +360,6 @@ __global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, 
 #include "gcs_mfma.h"
 
 // dw partial of slice s: part[s][o][k][c] = sum over the slice's pairs p of tap k: dy[i_p][o] * x[nbr[i_p][k]][c]
-constexpr int KR = 16;
 template <int TO, int TC, int MR, int MC>
 __global__ __launch_bounds__(256) void k_subm_dw(const float* __restrict__ dy, int cout, const float* __restrict__ x,
                                                  int cin, const int32_t* __restrict__ nbr, int K,
@@ -710,7 +711,9 @@ int subm_backward(const char* who, int32_t engine, const void* rulebook, int64_t
   if (dw) {
     const int S = pl.dw_slices;
     float* dst = S > 1 ? ws.dwp : dw;
-    if (pl.dw == GCS_TILE_64X64) {
+    if (engine == GCS_ENGINE_MFMA) {
+      launch_dw_mfma(pl.dw, S, dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, dst, st);
+    } else if (pl.dw == GCS_TILE_64X64) {
       dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)kvol, (unsigned)S);
       k_subm_dw<64, 64, 4, 4><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
     } else {
@@ -865,6 +868,10 @@ int gcs_subm_engine_plan(int32_t engine, int64_t n, int32_t cin, int32_t cout, i
   plan[5] = e.fwd_slices;
   plan[6] = e.dx_slices;
   return 0;
+}
+int gcs_engine_products(int32_t engine) {
+  if (int rc = check_engine("gcs_engine_products", engine)) return rc;
+  return engine == GCS_ENGINE_MFMA ? GCS_PRODUCT_FORWARD | GCS_PRODUCT_DX | GCS_PRODUCT_DW : 0;
 }
 int gcs_subm_engine_workspace_bytes(int32_t engine, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups,
                                     size_t* forward_bytes, size_t* backward_bytes) {

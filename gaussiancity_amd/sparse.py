@@ -10,9 +10,10 @@ is in the HIP library.  fp32 only.  Semantics that spconv leaves open are fixed 
     output, and only representatives are read as neighbours;
   * min / max of segment_csr: the gradient goes to the first row that attains the value.
 
-Two engines run the forward and dX of the convolution (include/gcs.h, ABI v3): "valu", the default, and "mfma", the same
-gather-GEMM on the f32 matrix cores, cut over the taps where the grid is small.  set_engine() / get_engine() choose for
-the convolutions that start afterwards; the environment variable GCS_ENGINE gives the initial value.
+Two engines run the three products of the convolution, the forward, dX and dW (include/gcs.h, ABI v4): "valu", the
+default, and "mfma", the same products on the f32 matrix cores, the forward and dX cut over the taps where the grid is
+small.  set_engine() / get_engine() choose for the convolutions that start afterwards; the environment variable
+GCS_ENGINE gives the initial value; engine_products() says which products an engine runs on the matrix cores.
 """
 import ctypes as C
 import functools
@@ -24,12 +25,15 @@ import torch
 from . import _native_s as S
 from ._loader import current_stream as _stream
 
-_STATS = {"rulebook_builds": 0, "conv_forward_calls_valu": 0, "conv_forward_calls_mfma": 0}
+_STATS = {"rulebook_builds": 0, "conv_forward_calls_valu": 0, "conv_forward_calls_mfma": 0, "conv_dw_calls_valu": 0,
+          "conv_dw_calls_mfma": 0}
 
 
 def stats():
     """Counters of this process: `rulebook_builds` counts rulebooks built (a reused indice_key does not build),
-    `conv_forward_calls_valu` / `conv_forward_calls_mfma` the convolution forwards each engine ran."""
+    `conv_forward_calls_valu` / `conv_forward_calls_mfma` the convolution forwards each engine ran,
+    `conv_dw_calls_valu` / `conv_dw_calls_mfma` the weight gradients each engine ran (a backward that is not asked
+    for the weight gradient counts nothing)."""
     return dict(_STATS)
 
 
@@ -57,6 +61,16 @@ def set_engine(name):
     global _ENGINE
     prev, _ENGINE = _ENGINE, _engine_name(name, "set_engine")
     return prev
+
+
+_PRODUCTS = (("forward", S.PRODUCT_FORWARD), ("dx", S.PRODUCT_DX), ("dw", S.PRODUCT_DW))
+
+
+def engine_products(name=None):
+    """The products that engine `name` (the current engine when None) runs on the matrix cores, a tuple of names out of
+    ("forward", "dx", "dw"): () for "valu", all three for "mfma" (gcs_engine_products)."""
+    bits = S.engine_products(S.ENGINES[_engine_name(_ENGINE if name is None else name, "engine_products")])
+    return tuple(product for product, bit in _PRODUCTS if bits & bit)
 
 
 @functools.lru_cache(maxsize=256)
@@ -207,6 +221,8 @@ class SubMConvFunction(torch.autograd.Function):
                 S.check(L.gcs_subm_backward_engine(S.ENGINES[ctx.engine], rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x),
                                                    cin, w.data_ptr(), cout, ptr(dy), ptr(dx), ptr(dw), ptr(db),
                                                    ws.data_ptr(), ws_bytes, _stream()), "gcs_subm_backward_engine")
+        if want_w:
+            _STATS["conv_dw_calls_" + ctx.engine] += 1
         return dx, dw, db, None
 
 

@@ -44,15 +44,20 @@
 extern "C" {
 #endif
 
-#define GCS_ABI_VERSION 3
+#define GCS_ABI_VERSION 4
 #define GCS_HOST_INFO_HEADER 2 /* host_info words before the per-tap pair counts */
 
 enum gcs_status { GCS_OK = 0, GCS_ERR_INVALID_ARGUMENT = -1, GCS_ERR_HIP = -2 };
 enum gcs_reduce { GCS_SUM = 0, GCS_MEAN = 1, GCS_MIN = 2, GCS_MAX = 3 };
 /* workgroup tiles (rows x columns) of the convolution kernels, as gcs_subm_plan reports them */
 enum gcs_tile { GCS_TILE_32X32 = 0, GCS_TILE_64X64 = 1, GCS_TILE_128X32 = 2 };
-/* what runs the forward and dX gemms (ABI v3): the VALU kernels, or the same gather-GEMM on the f32 matrix cores */
+/* what runs the convolution's three products, the forward, dX and dW (ABI v3; dW since v4): the VALU kernels, or the
+ * same products on the f32 matrix cores */
 enum gcs_engine { GCS_ENGINE_VALU = 0, GCS_ENGINE_MFMA = 1 };
+/* bits of gcs_engine_products (ABI v4) */
+#define GCS_PRODUCT_FORWARD 1
+#define GCS_PRODUCT_DX 2
+#define GCS_PRODUCT_DW 4
 
 int gcs_abi_version(void);
 const char* gcs_last_error(void);
@@ -79,18 +84,25 @@ int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dup
                       int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx, float* dw,
                       float* db, void* workspace, size_t workspace_bytes, void* hip_stream);
 
-/* Engines (ABI v3).  The entry points above are GCS_ENGINE_VALU; the `_engine` calls take the engine as their first
- * argument and are, with GCS_ENGINE_VALU, the calls above: the same launches, the same backward workspace.  With
- * GCS_ENGINE_MFMA the forward and dX run on v_mfma_f32_16x16x4_f32 under the same tiles, with the same summation
+/* Engines (ABI v3; v4 moved dW to the engine and added gcs_engine_products).  The entry points above are
+ * GCS_ENGINE_VALU; the `_engine` calls take the engine as their first argument and are, with GCS_ENGINE_VALU, the
+ * calls above: the same launches, the same backward workspace.  With GCS_ENGINE_MFMA the forward and dX run on v_mfma_f32_16x16x4_f32 under the same tiles, with the same summation
  * order per output element (taps in loop order, channels ascending, the bias last): where the plan has one tap slice
  * the values are those of the VALU engine.  A tile grid below 256 workgroups is cut over the taps into S slices whose
  * partial tiles [S][N][columns] go to the workspace and are summed in slice order; the workspace's previous contents
- * never matter.  dW, dB, the rulebook and segment_csr are the same kernels under both engines.
+ * never matter.  dW runs on the same instruction under the VALU plan's tile and slice count (plan[2], plan[3]): every
+ * element of a slice's partial is one chain from 0 over the slice's pairs in list order under both engines, so dW is
+ * the VALU engine's dW bit for bit at every shape, and its share of the workspace is the same.  The sum of the dW
+ * slices, dB, the fold of dY, the rulebook and segment_csr are the same kernels under both engines.
+ *
+ * gcs_engine_products: host only; the products that `engine` runs on the matrix cores, a set of GCS_PRODUCT_* bits:
+ * 0 for GCS_ENGINE_VALU, 7 for GCS_ENGINE_MFMA; -1 (GCS_ERR_INVALID_ARGUMENT) for an unknown engine.
  *
  * gcs_subm_engine_plan: plan[0..4] as gcs_subm_plan, plan[5] = tap slices of the forward, plan[6] = tap slices of dX
  * (1, 1 for GCS_ENGINE_VALU).  gcs_subm_engine_workspace_bytes returns a status, so that 0 bytes is a valid answer (a
  * forward with one slice needs none and accepts NULL).  An unknown engine, and a workspace that is missing or too small
  * when the plan needs one, are GCS_ERR_INVALID_ARGUMENT before anything is queued. */
+int gcs_engine_products(int32_t engine);
 int gcs_subm_engine_plan(int32_t engine, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t plan[7]);
 int gcs_subm_engine_workspace_bytes(int32_t engine, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups,
                                     size_t* forward_bytes, size_t* backward_bytes);

@@ -6,10 +6,13 @@ a yardstick of torch ops on the same neighbour map (per tap: index_select + mm +
 Clouds: a 16 384-point building shell (tests/sparse_ref.shell_cloud) pooled stage by stage (coords >> 1) gives the
 N of every stage; the stage-0 shapes also run on an inference-sized shell of --inference-n points.  One JSON line per
 shape: rulebook build, forward and forward + backward in ms (median over --reps blocks of --iters calls, device
-events), the present pairs, the FLOP and byte floors of those pairs, and the yardstick's forward and forward +
-backward.  --engine picks the engine of the forward and dX gemms (gaussiancity_amd.sparse.set_engine); `both` runs the
-two engines one after the other shape by shape in this one process and writes one line per shape and engine to
-profiles/sparse_bench_engines.jsonl (or --out).  Every timing comes with the spread of its block medians
+events), the backward split (a backward asked for dX only and one asked for dW only, through the C ABI on buffers
+allocated once, so that the figure is the device work and not the autograd layer around it), the present pairs, the FLOP and byte
+floors of those pairs, the yardstick's forward and forward + backward, the dW slices of the plan and the products the
+engine runs on the matrix cores.  --engine picks the engine of the convolution's three products
+(gaussiancity_amd.sparse.set_engine); `both` runs the two engines one after the other shape by shape in this one
+process and writes one line per shape and engine to profiles/sparse_bench_engines.jsonl (or --out): VALU against MFMA
+is compared within that one process.  Every timing comes with the spread of its block medians
 ((max - min) / median over the --reps blocks).  Needs a GPU; there is no CPU path."""
 import argparse
 import json
@@ -123,6 +126,28 @@ def _bench_shape(spconv, dev, coords, cin, cout, k, bias, reps, iters, label, en
 
     fwd_ms, fb_ms = timed(fwd, reps, iters), timed(fwdbwd, reps, iters)
 
+    def backward_only(want_x, want_w):
+        """A backward asked for one gradient, through the C ABI on buffers allocated once: the device work, without the
+        autograd layer's allocations around it."""
+        eng, K = SP.S.ENGINES[engine], rb.kvol
+        ws_bytes = SP.S.subm_engine_workspace_bytes(eng, n, cin, cout, K, rb.dups)[1]
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        w = conv.weight.detach()
+        dx = torch.empty_like(x) if want_x else None
+        dw = torch.empty_like(w) if want_w else None
+        args = (eng, rb.buf.data_ptr(), n, K, rb.dups, x.data_ptr(), cin, w.data_ptr(), cout, dy.data_ptr(),
+                dx.data_ptr() if want_x else None, dw.data_ptr() if want_w else None, None, ws.data_ptr(), ws_bytes,
+                SP._stream())
+        call = SP.S.lib().gcs_subm_backward_engine
+
+        def run():
+            SP.S.check(call(*args), "gcs_subm_backward_engine")
+
+        run.buffers = (ws, dx, dw)  # the pointers in `args` stay valid as long as the closure lives
+        return run
+
+    dx_ms, dw_ms = timed(backward_only(True, False), reps, iters), timed(backward_only(False, True), reps, iters)
+
     nbr = R.neighbours(R.with_batch(coords, np.zeros(n)), shape, conv.kernel_size, conv.dilation)
     taps = {"K": nbr.shape[1], "rows": [], "cols": []}
     for q in range(nbr.shape[1]):
@@ -140,7 +165,10 @@ def _bench_shape(spconv, dev, coords, cin, cout, k, bias, reps, iters, label, en
     flop_f = 2.0 * pairs * cin * cout
     bytes_f = 4.0 * (n * cin + n * cout + K * cin * cout) + 4.0 * n * K
     plan = SP.S.subm_engine_plan(SP.S.ENGINES[engine], n, cin, cout, K)
-    return {"shape": label, "engine": engine, "fwd_slices": plan[5], "dx_slices": plan[6],
+    return {"shape": label, "engine": engine, "engine_products": list(SP.engine_products(engine)),
+            "fwd_slices": plan[5], "dx_slices": plan[6], "dw_slices": plan[3],
+            "dx_ms": round(dx_ms, 4), "dx_spread": round(dx_ms.spread, 4),
+            "dw_ms": round(dw_ms, 4), "dw_spread": round(dw_ms.spread, 4),
             "fwd_spread": round(fwd_ms.spread, 4), "fwdbwd_spread": round(fb_ms.spread, 4), "cin": cin, "cout": cout, "k": k, "n": n, "pairs": pairs,
             "rulebook_ms": round(statistics.median(builds), 4), "fwd_ms": round(fwd_ms, 4), "fwdbwd_ms": round(fb_ms, 4),
             "torch_fwd_ms": round(tf_ms, 4), "torch_fwdbwd_ms": round(tfb_ms, 4),
