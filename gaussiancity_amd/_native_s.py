@@ -11,6 +11,8 @@ HOST_INFO_HEADER = 2  # GCS_HOST_INFO_HEADER: invalid rows, duplicate flag, then
 ENGINE_VALU, ENGINE_MFMA = 0, 1  # enum gcs_engine
 ENGINES = {"valu": ENGINE_VALU, "mfma": ENGINE_MFMA}
 PRODUCT_FORWARD, PRODUCT_DX, PRODUCT_DW = 1, 2, 4  # GCS_PRODUCT_*: the bits of gcs_engine_products
+DTYPE_F32, DTYPE_F16 = 0, 1  # enum gcs_dtype
+DTYPES = {"float32": DTYPE_F32, "float16": DTYPE_F16}  # the `_t` entry points; gcs_dtypes() says which the library runs
 ABI_VERSION = 4
 
 _vp, _sz, _i32, _i64, _int = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int
@@ -34,6 +36,12 @@ _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argt
                                         _vp]),
     "gcs_segment_csr_forward": (_int, [_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "gcs_segment_csr_backward": (_int, [_vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "gcs_dtypes": (_int, []),
+    "gcs_subm_workspace_bytes_t": (_int, [_i32, _i64, _i32, _i32, _i32, _i32, _psz, _psz]),
+    "gcs_subm_forward_t": (_int, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "gcs_subm_backward_t": (_int, [_i32, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcs_segment_csr_forward_t": (_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "gcs_segment_csr_backward_t": (_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
 
 _L = _loader.Library("gcs", "libgcs_hip.so", ABI_VERSION, _SIGNATURES)
@@ -70,4 +78,18 @@ def subm_engine_workspace_bytes(engine, n, cin, cout, kvol, dups):
     f, b = _sz(0), _sz(0)
     check(lib().gcs_subm_engine_workspace_bytes(engine, n, cin, cout, kvol, dups, C.byref(f), C.byref(b)),
           "gcs_subm_engine_workspace_bytes")
+    return int(f.value), int(b.value)
+
+
+def dtypes():
+    """gcs_dtypes: the names out of DTYPES that the library runs, in enum order."""
+    bits = lib().gcs_dtypes()
+    return tuple(name for name, code in DTYPES.items() if bits >> code & 1)
+
+
+def subm_workspace_bytes_t(dtype, n, cin, cout, kvol, dups):
+    """(forward bytes, backward bytes) of gcs_subm_workspace_bytes_t for the DTYPE_* code `dtype`."""
+    f, b = _sz(0), _sz(0)
+    check(lib().gcs_subm_workspace_bytes_t(dtype, n, cin, cout, kvol, dups, C.byref(f), C.byref(b)),
+          "gcs_subm_workspace_bytes_t")
     return int(f.value), int(b.value)

@@ -15,11 +15,14 @@
 // Opt-in second engine (GCS_ENGINE_MFMA, gcs_mfma.h): the same three products (forward, dX, dW) on the f32 matrix cores,
 // the gather-GEMM in tap slices where the tile grid cannot fill the GPU; the entry points without `_engine` in their
 // names are the VALU engine.
+// Binary16 (GCS_F16 of the `_t` entry points, gcs_half.h): the same products on v_mfma_f32_16x16x16_f16, fp32 sums, one
+// rounding on store, under the matrix-core engine's plan; binary16 segment_csr.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <climits>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/gcs.h"
@@ -522,6 +525,8 @@ __global__ __launch_bounds__(64) void k_seg_bwd(const float* __restrict__ dout, 
     dsrc[r * f + col] = (reduce == GCS_SUM || reduce == GCS_MEAN) ? g : (r == a ? g : 0.0f);
 }
 
+#include "gcs_half.h"
+
 // ---- host helpers ----------------------------------------------------------------------------------------------
 int check_conv_dims(const char* who, int64_t n, int32_t K, int32_t cin, int32_t cout) {
   if (n < 0 || n > (int64_t)INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": n out of range");
@@ -734,6 +739,112 @@ int subm_backward(const char* who, int32_t engine, const void* rulebook, int64_t
   return 0;
 }
 
+
+// ---- binary16 (GCS_F16 of the `_t` entry points): one engine, the matrix cores, under engine_plan_of(GCS_ENGINE_MFMA) -----
+int check_dtype(const char* who, int32_t dtype) {
+  if (dtype != GCS_F32 && dtype != GCS_F16)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown dtype (GCS_F32 or GCS_F16)");
+  return 0;
+}
+int check_half_pointers(const char* who, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 1) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": a binary16 pointer is not 2-byte aligned");
+  return 0;
+}
+
+struct BwdWsH {
+  half_t* dyf;  // [N][Cout] binary16 when dups
+  float* dwp;   // [S][Cout][K][Cin] when S > 1
+  float* dbp;   // [Sb][Cout]
+  float* dxp;   // [Sx][N][Cin] when dX runs in Sx > 1 tap slices
+  size_t bytes;
+};
+BwdWsH carve_bwd_h(void* base, const EnginePlan& e, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups) {
+  BwdWsH w;
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t b) {
+    char* q = (p && b) ? p + off : nullptr;
+    off += align_up(b);
+    return (void*)q;
+  };
+  w.dyf = (half_t*)take(dups ? 2 * (size_t)n * cout : 0);
+  w.dwp = (float*)take(e.p.dw_slices > 1 ? 4 * (size_t)e.p.dw_slices * cout * K * cin : 0);
+  w.dbp = (float*)take(4 * (size_t)e.p.db_slices * cout);
+  w.dxp = (float*)take(e.dx_slices > 1 ? 4 * (size_t)e.dx_slices * n * cin : 0);
+  w.bytes = off;
+  return w;
+}
+
+int subm_forward_h(const char* who, const void* rulebook, int64_t n, int32_t kvol, const half_t* features, int32_t cin,
+                   const half_t* weight, const half_t* bias, int32_t cout, half_t* out, void* workspace,
+                   size_t workspace_bytes, void* hip_stream) {
+  const std::string me(who);
+  if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
+  if (int rc = check_half_pointers(who, {features, weight, bias, out})) return rc;
+  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
+  if (n == 0) return 0;
+  if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output");
+  const EnginePlan e = engine_plan_of(GCS_ENGINE_MFMA, n, cin, cout, kvol);
+  const size_t need = forward_ws_bytes(e, n, cout);
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than gcs_subm_workspace_bytes_t");
+  if (need && ((uintptr_t)workspace & 3)) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": the workspace is not 4-byte aligned");
+  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  launch_gemm_h<false>(e.p.fwd, e.fwd_slices, features, cin, weight, cin, (int64_t)kvol * cin, 1, cin, bias, rb.nbr, kvol, 0,
+                       nullptr, out, cout, n, (float*)workspace, (hipStream_t)hip_stream);
+  HIP_TRY(hipGetLastError(), "forward launch");
+  return 0;
+}
+
+int subm_backward_h(const char* who, const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const half_t* features,
+                    int32_t cin, const half_t* weight, int32_t cout, const half_t* dout, half_t* dx, half_t* dw, half_t* db,
+                    void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const std::string me(who);
+  if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
+  if (int rc = check_half_pointers(who, {features, weight, dout, dx, dw, db})) return rc;
+  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
+  const EnginePlan e = engine_plan_of(GCS_ENGINE_MFMA, n, cin, cout, kvol);
+  const Plan& pl = e.p;
+  const BwdWsH ws = carve_bwd_h(workspace, e, n, cin, cout, kvol, dups);
+  if (!workspace || workspace_bytes < ws.bytes)
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than gcs_subm_workspace_bytes_t");
+  if ((uintptr_t)workspace & 3) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": the workspace is not 4-byte aligned");
+  if (n > 0 && (!dout || ((dx || dw) && !features)))
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output gradient");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
+  if (n == 0) {
+    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 2 * (size_t)cout * kvol * cin, st), "dw clear");
+    if (db) HIP_TRY(hipMemsetAsync(db, 0, 2 * (size_t)cout, st), "db clear");
+    return 0;
+  }
+  if (dx) {
+    const half_t* g = dout;
+    if (dups) {
+      k_fold_h<<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
+      g = ws.dyf;
+    }
+    launch_gemm_h<true>(pl.dx, e.dx_slices, g, cout, weight, cin, 1, (int64_t)kvol * cin, cin, nullptr, rb.nbr, kvol, 1,
+                        dups ? rb.rep : nullptr, dx, cin, n, ws.dxp, st);
+  }
+  if (dw) {
+    const int S = pl.dw_slices;
+    launch_dw_h(pl.dw, S, dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, ws.dwp, dw, st);
+    if (S > 1) {
+      const int64_t len = (int64_t)cout * kvol * cin;
+      k_sum_slices_h<<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
+    }
+  }
+  if (db) {
+    const int S = pl.db_slices;
+    k_colsum_h<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
+    k_sum_slices_h<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
+  }
+  HIP_TRY(hipGetLastError(), "backward launch");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -921,6 +1032,84 @@ int gcs_segment_csr_backward(const float* dout, int64_t m, int64_t f, const int6
   if (s > 0) {
     const int64_t nfb = (f + 63) / 64;
     k_seg_bwd<<<(unsigned)(s * nfb), 64, 0, st>>>(dout, m, f, indptr, nfb, reduce, arg, dsrc);
+  }
+  HIP_TRY(hipGetLastError(), "segment_csr backward launch");
+  return 0;
+}
+
+
+// ---- the typed entry points: GCS_F32 is the default entry points above, GCS_F16 the binary16 path of gcs_half.h ---------
+int gcs_dtypes(void) { return (1 << GCS_F32) | (1 << GCS_F16); }
+
+int gcs_subm_workspace_bytes_t(int32_t dtype, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups,
+                               size_t* forward_bytes, size_t* backward_bytes) {
+  if (int rc = check_dtype("gcs_subm_workspace_bytes_t", dtype)) return rc;
+  if (int rc = check_conv_dims("gcs_subm_workspace_bytes_t", n, kvol, cin, cout)) return rc;
+  if (!forward_bytes || !backward_bytes) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_workspace_bytes_t: null output");
+  if (dtype == GCS_F32) {
+    *forward_bytes = 0;
+    *backward_bytes = carve_bwd(nullptr, n, cin, cout, kvol, dups).bytes;
+    return 0;
+  }
+  const EnginePlan e = engine_plan_of(GCS_ENGINE_MFMA, n, cin, cout, kvol);
+  *forward_bytes = forward_ws_bytes(e, n, cout);
+  *backward_bytes = carve_bwd_h(nullptr, e, n, cin, cout, kvol, dups).bytes;
+  return 0;
+}
+
+int gcs_subm_forward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t kvol, const void* features, int32_t cin,
+                       const void* weight, const void* bias, int32_t cout, void* out, void* workspace,
+                       size_t workspace_bytes, void* hip_stream) {
+  if (int rc = check_dtype("gcs_subm_forward_t", dtype)) return rc;
+  if (dtype == GCS_F32)
+    return subm_forward("gcs_subm_forward_t", GCS_ENGINE_VALU, rulebook, n, kvol, (const float*)features, cin,
+                        (const float*)weight, (const float*)bias, cout, (float*)out, nullptr, 0, hip_stream);
+  return subm_forward_h("gcs_subm_forward_t", rulebook, n, kvol, (const half_t*)features, cin, (const half_t*)weight,
+                        (const half_t*)bias, cout, (half_t*)out, workspace, workspace_bytes, hip_stream);
+}
+
+int gcs_subm_backward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const void* features,
+                        int32_t cin, const void* weight, int32_t cout, const void* dout, void* dx, void* dw, void* db,
+                        void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (int rc = check_dtype("gcs_subm_backward_t", dtype)) return rc;
+  if (dtype == GCS_F32)
+    return subm_backward("gcs_subm_backward_t", GCS_ENGINE_VALU, rulebook, n, kvol, dups, (const float*)features, cin,
+                         (const float*)weight, cout, (const float*)dout, (float*)dx, (float*)dw, (float*)db, workspace,
+                         workspace_bytes, hip_stream);
+  return subm_backward_h("gcs_subm_backward_t", rulebook, n, kvol, dups, (const half_t*)features, cin, (const half_t*)weight,
+                         cout, (const half_t*)dout, (half_t*)dx, (half_t*)dw, (half_t*)db, workspace, workspace_bytes,
+                         hip_stream);
+}
+
+int gcs_segment_csr_forward_t(int32_t dtype, const void* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
+                              int32_t reduce, void* out, int64_t* arg, void* hip_stream) {
+  if (int rc = check_dtype("gcs_segment_csr_forward_t", dtype)) return rc;
+  if (dtype == GCS_F32)
+    return gcs_segment_csr_forward((const float*)src, m, f, indptr, s, reduce, (float*)out, arg, hip_stream);
+  if (int rc = check_half_pointers("gcs_segment_csr_forward_t", {src, out})) return rc;
+  if (int rc = check_segment("gcs_segment_csr_forward_t", src, out, indptr, m, f, s, reduce, arg, true)) return rc;
+  if (s == 0) return 0;
+  const int64_t nfb = (f + 63) / 64;
+  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
+  k_seg_fwd_h<<<(unsigned)(s * nfb), 64, 0, (hipStream_t)hip_stream>>>((const half_t*)src, m, f, indptr, nfb, reduce,
+                                                                       (half_t*)out, minmax ? arg : nullptr);
+  HIP_TRY(hipGetLastError(), "segment_csr forward launch");
+  return 0;
+}
+
+int gcs_segment_csr_backward_t(int32_t dtype, const void* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
+                               int32_t reduce, const int64_t* arg, void* dsrc, void* hip_stream) {
+  if (int rc = check_dtype("gcs_segment_csr_backward_t", dtype)) return rc;
+  if (dtype == GCS_F32)
+    return gcs_segment_csr_backward((const float*)dout, m, f, indptr, s, reduce, arg, (float*)dsrc, hip_stream);
+  if (int rc = check_half_pointers("gcs_segment_csr_backward_t", {dout, dsrc})) return rc;
+  if (int rc = check_segment("gcs_segment_csr_backward_t", dsrc, dout, indptr, m, f, s, reduce, arg, true)) return rc;
+  if (m == 0) return 0;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipMemsetAsync(dsrc, 0, 2 * (size_t)m * f, st), "dsrc clear");
+  if (s > 0) {
+    const int64_t nfb = (f + 63) / 64;
+    k_seg_bwd_h<<<(unsigned)(s * nfb), 64, 0, st>>>((const half_t*)dout, m, f, indptr, nfb, reduce, arg, (half_t*)dsrc);
   }
   HIP_TRY(hipGetLastError(), "segment_csr backward launch");
   return 0;

@@ -5,7 +5,7 @@
   segment_csr                                  torch_scatter.segment_csr with a 1-D indptr (reduction along dim 0)
 
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation
-is in the HIP library.  fp32 only.  Semantics that spconv leaves open are fixed here:
+is in the HIP library.  float32 (the default of everything) and float16.  Semantics that spconv leaves open are fixed here:
   * several rows on one voxel: the lowest row is the voxel's representative, every row of the voxel gets the same
     output, and only representatives are read as neighbours;
   * min / max of segment_csr: the gradient goes to the first row that attains the value.
@@ -14,6 +14,12 @@ Two engines run the three products of the convolution, the forward, dX and dW (i
 default, and "mfma", the same products on the f32 matrix cores, the forward and dX cut over the taps where the grid is
 small.  set_engine() / get_engine() choose for the convolutions that start afterwards; the environment variable
 GCS_ENGINE gives the initial value; engine_products() says which products an engine runs on the matrix cores.
+
+float16 (dtypes(); the `_t` entry points of include/gcs.h): a layer whose features, weight and bias are float16
+(`module.half()`) runs its three products on the f16 matrix cores with fp32 accumulation and one rounding on store; there is
+one engine for it, so set_engine() and GCS_ENGINE do not affect such a layer.  Under CUDA autocast, whatever its dtype,
+SubMConv3d casts features, weight and bias to float16 for the call and returns float16, as spconv does
+(custom_fwd(cast_inputs=torch.float16)).  segment_csr dispatches on src.dtype and has no autocast rule, as upstream.
 """
 import ctypes as C
 import functools
@@ -26,14 +32,16 @@ from . import _native_s as S
 from ._loader import current_stream as _stream
 
 _STATS = {"rulebook_builds": 0, "conv_forward_calls_valu": 0, "conv_forward_calls_mfma": 0, "conv_dw_calls_valu": 0,
-          "conv_dw_calls_mfma": 0}
+          "conv_dw_calls_mfma": 0, "conv_forward_calls_half": 0, "conv_dw_calls_half": 0}
+_DTYPES = {torch.float32: "float32", torch.float16: "float16"}
 
 
 def stats():
     """Counters of this process: `rulebook_builds` counts rulebooks built (a reused indice_key does not build),
     `conv_forward_calls_valu` / `conv_forward_calls_mfma` the convolution forwards each engine ran,
     `conv_dw_calls_valu` / `conv_dw_calls_mfma` the weight gradients each engine ran (a backward that is not asked
-    for the weight gradient counts nothing)."""
+    for the weight gradient counts nothing).  `conv_forward_calls_half` / `conv_dw_calls_half` count the float16 calls,
+    which the four engine counters do not."""
     return dict(_STATS)
 
 
@@ -71,6 +79,16 @@ def engine_products(name=None):
     ("forward", "dx", "dw"): () for "valu", all three for "mfma" (gcs_engine_products)."""
     bits = S.engine_products(S.ENGINES[_engine_name(_ENGINE if name is None else name, "engine_products")])
     return tuple(product for product, bit in _PRODUCTS if bits & bit)
+
+
+def dtypes():
+    """The feature dtypes the library runs (gcs_dtypes): ("float32", "float16")."""
+    return S.dtypes()
+
+
+@functools.lru_cache(maxsize=256)
+def _half_workspace_bytes(n, cin, cout, kvol, dups):
+    return S.subm_workspace_bytes_t(S.DTYPE_F16, n, cin, cout, kvol, dups)
 
 
 @functools.lru_cache(maxsize=256)
@@ -122,7 +140,7 @@ class Rulebook:
 
 
 class SparseConvTensor:
-    """spconv.SparseConvTensor: features [N, C] fp32, indices [N, 4] int32 (b, d0, d1, d2)."""
+    """spconv.SparseConvTensor: features [N, C] float32 or float16, indices [N, 4] int32 (b, d0, d1, d2)."""
 
     def __init__(self, features, indices, spatial_shape, batch_size, grid=None, voxel_num=None, indice_dict=None,
                  benchmark=False, permanent_thrust_allocator=False, enable_timer=False, force_algo=None):
@@ -173,10 +191,18 @@ class SubMConvFunction(torch.autograd.Function):
         w = weight.contiguous()
         n, cin, cout = x.shape[0], x.shape[1], w.shape[0]
         out = x.new_empty((n, cout))
-        engine = _ENGINE  # read once: the backward of this call runs the same engine, whatever is set by then
+        # read once: the backward of this call runs the same engine, whatever is set by then; float16 has one engine
+        engine = "half" if x.dtype == torch.float16 else _ENGINE
         b_ptr = bias.contiguous().data_ptr() if bias is not None else None
         with torch.cuda.device(x.device):
-            if engine == "valu":
+            if engine == "half":
+                ws_bytes = _half_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)[0]
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+                S.check(S.lib().gcs_subm_forward_t(S.DTYPE_F16, rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None,
+                                                   cin, w.data_ptr(), b_ptr, cout, out.data_ptr() if n else None,
+                                                   ws.data_ptr() if ws is not None else None, ws_bytes, _stream()),
+                        "gcs_subm_forward_t")
+            elif engine == "valu":
                 S.check(S.lib().gcs_subm_forward(rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None, cin,
                                                  w.data_ptr(), b_ptr, cout, out.data_ptr() if n else None, _stream()),
                         "gcs_subm_forward")
@@ -199,7 +225,7 @@ class SubMConvFunction(torch.autograd.Function):
     def backward(ctx, dout):
         x, w = ctx.saved_tensors
         rb = ctx.rb
-        dy = dout.contiguous()
+        dy = dout.contiguous().to(x.dtype)
         n, cin, cout = x.shape[0], x.shape[1], w.shape[0]
         want_x, want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         dx = x.new_empty(x.shape) if want_x else None
@@ -207,7 +233,14 @@ class SubMConvFunction(torch.autograd.Function):
         db = w.new_empty((cout,)) if want_b else None
         L = S.lib()
         ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
-        if ctx.engine == "valu":
+        if ctx.engine == "half":
+            ws_bytes = _half_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)[1]
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+            with torch.cuda.device(x.device):
+                S.check(L.gcs_subm_backward_t(S.DTYPE_F16, rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x), cin, w.data_ptr(),
+                                              cout, ptr(dy), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(), ws_bytes, _stream()),
+                        "gcs_subm_backward_t")
+        elif ctx.engine == "valu":
             ws_bytes = L.gcs_subm_backward_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)
             ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
             with torch.cuda.device(x.device):
@@ -230,7 +263,12 @@ class SubMConv3d(SparseModule):
     """spconv.SubMConv3d: submanifold 3-D convolution; output rows are the input rows.
 
     weight [out, kD, kH, kW, in] (spconv 2.x KRSC), bias [out] or None.  Odd kernel sizes only; stride and groups
-    must be 1; padding, algo and fp32_accum are accepted and ignored (the centre tap is kernel_size // 2)."""
+    must be 1; padding, algo and fp32_accum are accepted and ignored (the centre tap is kernel_size // 2).
+
+    float32 or float16: features, weight and bias share one dtype (`module.half()` for float16).  While CUDA autocast is
+    enabled, whatever its dtype, the three are cast to float16 for the call, from any floating dtype (the bfloat16 a
+    Linear emits under bfloat16 autocast included), and the output is float16, as spconv does; float32 parameters then
+    receive float32 gradients through the cast.  Outside autocast bfloat16 and float64 are a TypeError."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  indice_key=None, algo=None, fp32_accum=None, large_kernel_fast_algo=False, name=None):
@@ -288,8 +326,15 @@ class SubMConv3d(SparseModule):
 
     def forward(self, x):
         f, idx = x.features, x.indices
-        if f.dtype != torch.float32 or self.weight.dtype != torch.float32:
-            raise TypeError("SubMConv3d supports float32 only (features %s, weight %s)" % (f.dtype, self.weight.dtype))
+        w, b = self.weight, self.bias
+        given = [t.dtype for t in (f, w, b) if t is not None]
+        autocast = torch.is_autocast_enabled()
+        # under autocast every floating dtype is cast to float16 below (custom_fwd casts bfloat16 and float64 too)
+        if any(not d.is_floating_point if autocast else d not in _DTYPES for d in given):
+            raise TypeError("SubMConv3d supports float32 and float16 only (features %s, weight %s)" % (f.dtype, w.dtype))
+        if not autocast and len(set(given)) != 1:
+            raise TypeError("SubMConv3d needs features, weight and bias of one dtype, float32 or float16, outside autocast "
+                            "(features %s, weight %s%s)" % (f.dtype, w.dtype, "" if b is None else ", bias %s" % b.dtype))
         if idx.dtype != torch.int32:
             raise TypeError("indices must be int32, got %s" % idx.dtype)
         if f.dim() != 2 or idx.dim() != 2 or idx.shape[1] != 4 or f.shape[0] != idx.shape[0]:
@@ -301,7 +346,12 @@ class SubMConv3d(SparseModule):
         if not idx.is_contiguous():
             x = SparseConvTensor(f, idx.contiguous(), x.spatial_shape, x.batch_size, indice_dict=x.indice_dict)
         rb = self._rulebook(x)
-        return x.replace_feature(SubMConvFunction.apply(f, self.weight, self.bias, rb))
+        if not autocast:
+            return x.replace_feature(SubMConvFunction.apply(f, w, b, rb))
+        # spconv's custom_fwd(cast_inputs=torch.float16): float16 operands, the call itself outside autocast
+        half = lambda t: None if t is None else t.to(torch.float16)  # noqa: E731
+        with torch.autocast("cuda", enabled=False):
+            return x.replace_feature(SubMConvFunction.apply(half(f), half(w), half(b), rb))
 
 
 class SegmentCSRFunction(torch.autograd.Function):
@@ -313,35 +363,37 @@ class SegmentCSRFunction(torch.autograd.Function):
         f = math.prod(x.shape[1:])
         out = x.new_empty((nseg,) + tuple(x.shape[1:]))
         code = S.REDUCE[reduce]
+        dtype = S.DTYPES[_DTYPES[x.dtype]]
         arg = torch.empty((nseg, f), dtype=torch.int64, device=x.device) if code >= 2 else None
         if nseg and f:
             with torch.cuda.device(x.device):
-                S.check(S.lib().gcs_segment_csr_forward(x.data_ptr() if m else None, m, f, ip.data_ptr(), nseg, code,
-                                                        out.data_ptr(), arg.data_ptr() if arg is not None else None,
-                                                        _stream()), "gcs_segment_csr_forward")
+                S.check(S.lib().gcs_segment_csr_forward_t(dtype, x.data_ptr() if m else None, m, f, ip.data_ptr(), nseg, code,
+                                                          out.data_ptr(), arg.data_ptr() if arg is not None else None,
+                                                          _stream()), "gcs_segment_csr_forward_t")
         ctx.save_for_backward(ip, arg) if arg is not None else ctx.save_for_backward(ip)
-        ctx.meta = (tuple(x.shape), m, f, nseg, code)
+        ctx.meta = (tuple(x.shape), m, f, nseg, code, x.dtype)
         if arg is not None:
             ctx.mark_non_differentiable(arg)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        shape, m, f, nseg, code = ctx.meta
+        shape, m, f, nseg, code, dt = ctx.meta
         saved = ctx.saved_tensors
         ip, arg = saved[0], (saved[1] if len(saved) > 1 else None)
-        dy = dout.contiguous()
+        dy = dout.contiguous().to(dt)
         dsrc = dy.new_zeros(shape) if not (m and f) else dy.new_empty(shape)
         if m and f:
             with torch.cuda.device(dy.device):
-                S.check(S.lib().gcs_segment_csr_backward(dy.data_ptr() if nseg else None, m, f, ip.data_ptr(), nseg, code,
-                                                         arg.data_ptr() if arg is not None else None, dsrc.data_ptr(),
-                                                         _stream()), "gcs_segment_csr_backward")
+                S.check(S.lib().gcs_segment_csr_backward_t(S.DTYPES[_DTYPES[dt]], dy.data_ptr() if nseg else None, m, f,
+                                                           ip.data_ptr(), nseg, code,
+                                                           arg.data_ptr() if arg is not None else None, dsrc.data_ptr(),
+                                                           _stream()), "gcs_segment_csr_backward_t")
         return dsrc, None, None
 
 
 def segment_csr(src, indptr, out=None, reduce="sum"):
-    """torch_scatter.segment_csr for a 1-D int64 indptr: reduces fp32 `src` along dim 0 over the rows
+    """torch_scatter.segment_csr for a 1-D int64 indptr: reduces float32 or float16 `src` along dim 0 over the rows
     [indptr[s], indptr[s+1]) of every segment s.  reduce: sum / add / mean / min / max; an empty segment gives 0."""
     if out is not None:
         raise NotImplementedError("segment_csr(out=...) is not supported")
@@ -349,8 +401,8 @@ def segment_csr(src, indptr, out=None, reduce="sum"):
         raise NotImplementedError("segment_csr supports a 1-D indptr only (got %d-D)" % indptr.dim())
     if reduce not in S.REDUCE:
         raise ValueError("reduce must be one of sum, add, mean, min, max (got %r)" % (reduce,))
-    if src.dtype != torch.float32:
-        raise TypeError("segment_csr supports float32 src only (got %s)" % src.dtype)
+    if src.dtype not in _DTYPES:
+        raise TypeError("segment_csr supports float32 and float16 src only (got %s)" % src.dtype)
     if indptr.dtype != torch.int64:
         raise TypeError("indptr must be int64 (got %s)" % indptr.dtype)
     if src.dim() < 1 or indptr.numel() < 1:

@@ -118,6 +118,52 @@ int gcs_segment_csr_forward(const float* src, int64_t m, int64_t f, const int64_
 int gcs_segment_csr_backward(const float* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
                              int32_t reduce, const int64_t* arg, float* dsrc, void* hip_stream);
 
+
+/* Typed entry points: binary16.  GCS_ABI_VERSION stays 4 -- the additions below change no existing symbol, signature or
+ * value, so a binding written for v4 keeps working; gcs_dtypes() is how a binding learns whether the library has them.
+ * The convention is gce.h's `_t(dtype, ...)`: every typed tensor (features, weight, bias, out, dout, dx, dw, db, src,
+ * dsrc) is void* and holds `dtype`; layouts and NULL rules are those of the float entry points; `arg`, `indptr` and the
+ * rulebook do not depend on the dtype, and ONE rulebook serves both.
+ *
+ * GCS_F32: exactly the default entry points above (gcs_subm_forward, gcs_subm_backward with the workspace of
+ * gcs_subm_backward_workspace_bytes, gcs_segment_csr_*): the same launches, the same bits; the forward ignores its
+ * workspace and gcs_subm_workspace_bytes_t reports 0 for it.
+ *
+ * GCS_F16: IEEE binary16.  The convolution has ONE engine, the matrix cores (v_mfma_f32_16x16x16_f16), and no chooser of
+ * its own: its launch plan is gcs_subm_engine_plan(GCS_ENGINE_MFMA, n, cin, cout, kvol) -- the tiles of the forward and of
+ * dX, their tap slices, the dW tile, the dW and dB slice counts -- so a test can assert which variant a shape reaches
+ * without another query.  The engine of the `_engine` calls (and whatever a binding keeps as its default engine) does not
+ * affect it.  Rows are cin (cout) halves long, any count, odd ones included.
+ * Numerics: operands are read as binary16; every product is exact in fp32; accumulation is fp32, inside the matrix cores and
+ * across taps, slices and chunks, in a fixed order; the bias is added in fp32 after the sum; y, dx, dw and db are rounded
+ * to binary16 exactly ONCE, on the store (nearest even, overflow to +-inf as the conversion does).  With dups != 0 the fold
+ * of dy onto the representatives is summed in fp32 and stored as binary16: one more rounding in what reads the fold (dx);
+ * rows of one voxel still get identical outputs.  No float atomics: results are bit-identical from run to run.
+ * Workspace: partial tiles and partial dw / db are fp32, the fold is binary16; gcs_subm_workspace_bytes_t reports the
+ * sizes, which never exceed those of gcs_subm_engine_workspace_bytes(GCS_ENGINE_MFMA, ...) for the same shape; its
+ * previous contents never matter; nothing is allocated and the host never waits.
+ * segment_csr: sum and mean accumulate in fp32 in row order, mean divides in fp32, one rounding follows; min and max are
+ * exact, `arg` is the FIRST row attaining the value, an empty segment gives 0 and arg -1.  Backward: sum copies bits, mean
+ * is dout / count in fp32 rounded once, min and max route the bits to `arg`.
+ * Errors, all GCS_ERR_INVALID_ARGUMENT before anything is queued: an unknown dtype; a workspace that is missing or too
+ * small when the plan needs one; with GCS_F16 a typed pointer that is not 2-byte aligned, or a workspace that is not 4-byte
+ * aligned (it holds fp32 partials).  The float entry points above do not check their workspace's alignment: it must be
+ * 4-byte aligned there too. */
+enum gcs_dtype { GCS_F32 = 0, GCS_F16 = 1 };
+int gcs_dtypes(void); /* host only: bit (1 << dtype) for every dtype the library runs: 3 */
+int gcs_subm_workspace_bytes_t(int32_t dtype, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups,
+                               size_t* forward_bytes, size_t* backward_bytes);
+int gcs_subm_forward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t kvol, const void* features, int32_t cin,
+                       const void* weight, const void* bias, int32_t cout, void* out,
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
+int gcs_subm_backward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const void* features,
+                        int32_t cin, const void* weight, int32_t cout, const void* dout, void* dx, void* dw, void* db,
+                        void* workspace, size_t workspace_bytes, void* hip_stream);
+int gcs_segment_csr_forward_t(int32_t dtype, const void* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
+                              int32_t reduce, void* out, int64_t* arg, void* hip_stream);
+int gcs_segment_csr_backward_t(int32_t dtype, const void* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
+                               int32_t reduce, const int64_t* arg, void* dsrc, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
