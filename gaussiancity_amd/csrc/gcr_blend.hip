@@ -142,6 +142,30 @@ GCR_DEV uint8_t gcr_video_byte(float c) {
 // exact for slots < 2048)
 GCR_DEV uint32_t slot_of_offset(uint32_t off) { return (off * 1366u) >> 16; }
 
+// K7's start state for a pixel whose walk goes on behind piece `kpiece` (gcr_internal.h "backward pieces"): T behind the
+// piece, and the colour the forward blended behind it -- the forward's piece-local colour sums of the pieces kpiece + 1
+// .. the pixel's last one (slot m of the tile: {T behind piece m, sum of piece m}), added from the back.  A pixel that
+// ends in this piece (or before it) gets zeros and does not use them.  The loads do not wait for n_contrib: every slot
+// behind the piece is fetched (they lie in the tile's own slot range; one the forward never wrote is selected away).
+struct K7Behind {
+  float T, s0, s1, s2;
+};
+GCR_DEV K7Behind k7_behind(const float4* __restrict__ ckpt, uint32_t sbase, uint32_t kpiece, uint32_t npieces, uint32_t cs,
+                           uint32_t last_contributor, uint32_t thread) {
+  K7Behind r = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (kpiece + 1u >= npieces) return r;  // (item-uniform) the list ends with this piece
+  r.T = ckpt[(size_t)(sbase + kpiece) * 256u + thread].x;
+  const uint32_t my_last = last_contributor > 0u ? (last_contributor - 1u) / cs : 0u;  // the piece of the pixel's last contributor
+  for (uint32_t m = npieces - 1u; m > kpiece; m--) {
+    const float4 d = ckpt[(size_t)(sbase + m) * 256u + thread];
+    const bool mine = m <= my_last;
+    r.s0 += mine ? d.y : 0.0f;
+    r.s1 += mine ? d.z : 0.0f;
+    r.s2 += mine ? d.w : 0.0f;
+  }
+  return r;
+}
+
 // ------------------------------------------------------------------------------------- K6
 // What bounds this loop is VALU issue, priced per kind (tools/valu_probe.hip, profiles/r04_valu_probe.jsonl): fp32 add /
 // mul / fma and integer add / and issue in ~2.5 cycles per wave64; compares, selects, min / max, shifts, v_lshl_add_u32,
@@ -318,6 +342,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     Tw = (g0.pxi < a.W && g0.pyi < a.H) ? 1.0f : -1.0f;
   }
   float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+  // STATE: the colour blended by the entries of the CURRENT piece alone.  The backward needs, per pixel, the colour that
+  // is blended BEHIND a piece; as C_final - C_prefix that is a difference of two sums of the size of the whole image
+  // colour, and for a Gaussian under a lot of others (T small) its rounding error is 1 / T times the Gaussian's own
+  // signal (measured: per-Gaussian gradient errors up to 1 000 times the oracle's).  A sum of
+  // piece-local sums, added from the back, is as good as the oracle's recursion.
+  float D0 = 0.0f, D1 = 0.0f, D2 = 0.0f;
   uint32_t last_contributor = 0;
   // pieces (gcr_internal.h "backward pieces"): the list is walked in equal pieces of <= a.piece entries
   const uint32_t piece_P = (uint32_t)a.piece;
@@ -382,6 +412,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       C0 = __builtin_fmaf(QB.z * wgt, Tw, C0);                                               \
       C1 = __builtin_fmaf(QB.w * wgt, Tw, C1);                                               \
       C2 = __builtin_fmaf(QC.x * wgt, Tw, C2);                                               \
+      if (STATE) { /* the same addends, summed from zero in every piece (see D0 above) */    \
+        D0 = __builtin_fmaf(QB.z * wgt, Tw, D0);                                             \
+        D1 = __builtin_fmaf(QB.w * wgt, Tw, D1);                                             \
+        D2 = __builtin_fmaf(QC.x * wgt, Tw, D2);                                             \
+      }                                                                                      \
       last_off = (keep && valid) ? (OFF) : last_off;                                         \
       Tw = keep ? test_T : -__builtin_fabsf(Tw);                                             \
     }                                                                                        \
@@ -424,14 +459,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       break;
     }
     if (!SORT && lz_sorted < (uint32_t)(base + min(cs, total - base))) break;  // sort on, then come back
-    // crossing a piece boundary: checkpoint of the per-pixel state for the backward (|Tw| = T; a finished pixel's
-    // checkpoint is never read).  256 x 16 bytes, one coalesced 4 KB store per boundary.
+    // crossing a piece boundary: checkpoint of the per-pixel state for the backward -- T behind the piece and the piece's
+    // own colour sum (|Tw| = T; a finished pixel's T is never read, its later sums are zero).  256 x 16 bytes, one
+    // coalesced 4 KB store per boundary.
     if (STATE && entered > 0u && a.ckpt != nullptr) {
       // (the thread index is re-read behind an opaque barrier so that the store's address arithmetic is done here and
       // does not sit in registers across the walk: 76 -> 71 VGPRs, seven waves per SIMD again)
       uint32_t t_op = threadIdx.x;
       asm volatile("" : "+v"(t_op));
-      a.ckpt[(size_t)(sbase + entered - 1u) * 256u + lane6_to_k7_thread(t_op)] = make_float4(__builtin_fabsf(Tw), C0, C1, C2);
+      a.ckpt[(size_t)(sbase + entered - 1u) * 256u + lane6_to_k7_thread(t_op)] = make_float4(__builtin_fabsf(Tw), D0, D1, D2);
+      D0 = D1 = D2 = 0.0f;
     }
     entered++;
     const int n = min(cs, total - base);
@@ -590,11 +627,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   if (a.clock_buf != nullptr && tid == 0) a.clock_buf[(size_t)tile * 16 + 2] = __builtin_readcyclecounter();
 #endif
   if (STATE && a.work != nullptr) {
-    // a tile that crossed a boundary also leaves its final colour (without background) in its last slot: a
-    // backward piece that starts from a checkpoint needs C_final - C_prefix
+    // a tile that crossed a boundary also leaves the colour sum of the last piece it walked into, in that piece's slot:
+    // a backward piece that starts from a checkpoint adds up the sums of the pieces behind it
     if (entered >= 2u)
-      a.ckpt[(size_t)(sbase + gcr_piece_count((uint32_t)total, piece_P) - 1u) * 256u + lane6_to_k7_thread((uint32_t)tid)] =
-          make_float4(__builtin_fabsf(Tw), C0, C1, C2);
+      a.ckpt[(size_t)(sbase + entered - 1u) * 256u + lane6_to_k7_thread((uint32_t)tid)] =
+          make_float4(__builtin_fabsf(Tw), D0, D1, D2);
     // work items of the backward blend, one per slot of [slot_base(tile), slot_base(tile + 1)): the pieces this
     // workgroup walked into carry {tile, list start, list length, piece}; the others (behind a saturated tile's last
     // piece; the gap slot) carry nothing.  Fixed places: no atomic, no barrier at the end of the forward.
@@ -882,11 +919,7 @@ __global__ __launch_bounds__(64) GCR_K7_OCC void k_blend_bwd(const GcrBlendArgs 
         dLp2 = a.dL_dpix[2 * iplane + in_id];
       }
     }
-    float4 ck = make_float4(0.0f, 0.0f, 0.0f, 0.0f), cf = ck;
-    if (kpiece + 1u < npieces) {  // the list goes on behind this piece
-      ck = ckpt[(size_t)(sbase + kpiece) * 256u + (uint32_t)(q * 64 + lane)];
-      cf = ckpt[(size_t)(sbase + npieces - 1u) * 256u + (uint32_t)(q * 64 + lane)];
-    }
+    const K7Behind ck = k7_behind(ckpt, sbase, kpiece, npieces, cs, last_contributor, (uint32_t)(q * 64 + lane));
     float bg_dot_dpixel = 0;
     bg_dot_dpixel += bg0 * dLp0;
     bg_dot_dpixel += bg1 * dLp1;
@@ -908,16 +941,16 @@ __global__ __launch_bounds__(64) GCR_K7_OCC void k_blend_bwd(const GcrBlendArgs 
 
     // Start state of the reverse walk.  A pixel whose last contributor lies in this piece (or before it) starts as
     // upstream: T_final, accum_rec = 0.  A pixel that goes on behind the piece starts from the forward's checkpoint
-    // at boundary hi: T after entry hi - 1, and accum_rec = what is blended behind it, normalised:
-    // (C_final - C_prefix(hi)) / T(hi) -- which the first update `a = last_alpha * lc + (1 - last_alpha) * acc`
+    // at boundary hi: T after entry hi - 1, and accum_rec = what is blended behind it (k7_behind), normalised by
+    // T(hi) -- which the first update `a = last_alpha * lc + (1 - last_alpha) * acc`
     // with last_alpha = 0 hands to the first contributing entry unchanged.
     float T = T_final;
     float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;  // accum_rec
     if (last_contributor > hi) {
-      T = ck.x;
-      acc0 = (cf.y - ck.y) / ck.x;
-      acc1 = (cf.z - ck.z) / ck.x;
-      acc2 = (cf.w - ck.w) / ck.x;
+      T = ck.T;
+      acc0 = ck.s0 / ck.T;
+      acc1 = ck.s1 / ck.T;
+      acc2 = ck.s2 / ck.T;
     }
     const float nbg = -T_final * bg_dot_dpixel;  // the background term's pixel constant (cr/backward.cu:556-560)
     float last_alpha = 0.0f, lc0 = 0.0f, lc1 = 0.0f, lc2 = 0.0f;
@@ -1026,14 +1059,17 @@ __global__ __launch_bounds__(64) GCR_K7_OCC void k_blend_bwd(const GcrBlendArgs 
               } else {  // fixed point with the Gaussian's own binary point, order-independent (gcr_internal.h)
                 const uint32_t gid = sId[slot];
                 const float4 q2 = a.rec[(size_t)gid * GCR_REC_QUADS + 2];
-                const int kc = gcr_det_frac_bits(sE[slot].a.x, sE[slot].a.y, __float_as_uint(q2.z), __float_as_uint(q2.w), a.W, a.H, true);
-                const int ko = gcr_det_frac_bits(sE[slot].a.x, sE[slot].a.y, __float_as_uint(q2.z), __float_as_uint(q2.w), a.W, a.H, false);
-                const int kf = (rec_idx >= 4) ? kc : ko;  // record slots 4..8 = the five moments with a pixel offset in them
+                const int kc = gcr_det_frac_bits(sE[slot].a.x, sE[slot].a.y, __float_as_uint(q2.z), __float_as_uint(q2.w), 2);
+                const int ko = gcr_det_frac_bits(sE[slot].a.x, sE[slot].a.y, __float_as_uint(q2.z), __float_as_uint(q2.w), 0);
+                const int k1 = gcr_det_frac_bits(sE[slot].a.x, sE[slot].a.y, __float_as_uint(q2.z), __float_as_uint(q2.w), 1);
+                const int cls = gcr_det_class(rec_idx);  // second moments | first moments | colour sums and S
+                const int kf = cls == 2 ? kc : (cls == 1 ? k1 : ko);
                 const float sc = __builtin_ldexpf(v, kf);  // exact: a power of two (or +-inf: saturates below)
                 const long long q = sc >= 9.2e18f ? 0x7fffffffffffffffll : (sc <= -9.2e18f ? -0x7fffffffffffffffll : __float2ll_rn(sc));
                 unsigned long long* const r64 = reinterpret_cast<unsigned long long*>(a.grad_rec) + (size_t)gid * (GCR_GRAD_REC_FLOATS_DET / 2);
                 atomicAdd(r64 + rec_idx, (unsigned long long)q);
-                r64[GCR_DET_K_SLOT] = (unsigned long long)(kc + 64) | ((unsigned long long)(ko + 64) << 8);  // (the same from every flush)
+                r64[GCR_DET_K_SLOT] = (unsigned long long)(kc + 64) | ((unsigned long long)(ko + 64) << 8) |
+                                      ((unsigned long long)(k1 + 64) << 16);  // (the same from every flush)
               }
             }
           }
@@ -1154,11 +1190,7 @@ __global__ __launch_bounds__(256) GCR_K7_ITEM_OCC void k_blend_bwd_item(const Gc
         dLp2 = a.dL_dpix[2 * iplane + in_id];
       }
     }
-    float4 ck = make_float4(0.0f, 0.0f, 0.0f, 0.0f), cf = ck;
-    if (kpiece + 1u < npieces) {  // the list goes on behind this piece
-      ck = ckpt[(size_t)(sbase + kpiece) * 256u + (uint32_t)tid];
-      cf = ckpt[(size_t)(sbase + npieces - 1u) * 256u + (uint32_t)tid];
-    }
+    const K7Behind ck = k7_behind(ckpt, sbase, kpiece, npieces, cs, last_contributor, (uint32_t)tid);
     // the accumulators of this item's entries start at zero (stores, no wait)
     for (int k = tid; k < n * 9; k += 256) sAcc[k] = 0.0;
 
@@ -1195,10 +1227,10 @@ __global__ __launch_bounds__(256) GCR_K7_ITEM_OCC void k_blend_bwd_item(const Gc
     float T = T_final;
     float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;  // accum_rec; start state as in k_blend_bwd
     if (last_contributor > hi) {
-      T = ck.x;
-      acc0 = (cf.y - ck.y) / ck.x;
-      acc1 = (cf.z - ck.z) / ck.x;
-      acc2 = (cf.w - ck.w) / ck.x;
+      T = ck.T;
+      acc0 = ck.s0 / ck.T;
+      acc1 = ck.s1 / ck.T;
+      acc2 = ck.s2 / ck.T;
     }
     const float nbg = -T_final * bg_dot_dpixel;
     float last_alpha = 0.0f, lc0 = 0.0f, lc1 = 0.0f, lc2 = 0.0f;

@@ -119,36 +119,39 @@ struct GcrPreprocessBwdArgs {
 // The binary point is PER GAUSSIAN (round 4; a fixed Q31.32 before): the sums of a Gaussian that covers many pixels far
 // from its centre are large -- dL_dconic adds 0.5 d.x^2 dL_dG per pixel, 3.5e9 for a 300-pixel footprint, beyond Q31.32
 // (found by tools/fuzz_parity.py, seed 41 case 635: gradients wrong by 15 x max, silently) -- while a small Gaussian's
-// need the fine end.  k = fractional bits, a function of the Gaussian's projected record and the image size alone, one
-// for the three conic sums and one for the other six (a conic-sized range would cost the dL_dmean2D sums, which the
-// projection multiplies by focal / depth afterwards, their precision: 0.27 on a dL_dmean3D of 12 in the same case):
-//     B_conic = pixels of its tile rectangle * max(squared distance centre -> farthest rectangle corner, 8 max(W, H)) * 64
-//               (the five moments with a pixel offset in them: record slots 4..8)
-//     B_other = pixels of its tile rectangle * 8 max(W, H) * 64   (colour sums and S: slots 0..3)
-//     k = clamp(61 - (floor(log2 B) + 1), -16, 32)
-// (the sums are bounded by pixels * {d^2 | W, 1} * |dL_dG|: B leaves |dL_dG| up to 64 per pixel before a sum can wrap;
-// an addend beyond the range still saturates).  The blend gradient kernel computes both when it flushes and leaves
-// (k_conic + 64) | (k_other + 64) << 8 in the record's last slot (every flush of a Gaussian stores the same value); the
-// preprocess gradient kernel reads them.
+// need the fine end.  k = fractional bits, a function of the Gaussian's projected record alone, one per CLASS of sums --
+// a range sized for the second moments would cost the others their precision (0.27 on a dL_dmean3D of 12 in the same
+// case).  With d = distance centre -> farthest corner of the Gaussian's tile rectangle:
+//     class 2, second moments Sxx, Sxy, Syy (slots 6..8):  B = pixels of the rectangle * max(d^2, 64) * 64
+//     class 1, first moments Sx, Sy (slots 4, 5):          B = pixels of the rectangle * max(d, 64) * 64
+//     class 0, colour sums and S (slots 0..3):             B = pixels of the rectangle * 64 * 64
+//     k = clamp(61 - (floor(log2 B) + 1), -16, 44)
+// (a sum is bounded by pixels * {d^2 | d | 1} * the per-pixel factor: B leaves that factor up to 64 -- 4096 for class 0
+// and for a small Gaussian's class 1 -- before a sum can wrap; an addend beyond the range still saturates).  Earlier
+// there were two classes, both carried a factor 8 max(W, H) that the sums stopped containing when K7 went over to
+// moments, and k stopped at 32: a small Gaussian's addends of 1e-9 were quantised at 2.3e-10, and its rows came out 17
+// to 57 times (99th percentile) as far from the binary64 reference as the binary32 oracle's
+// (tests/test_gpu_grad_rows.py).  The blend gradient kernel computes the three when it flushes and leaves
+// (k2 + 64) | (k0 + 64) << 8 | (k1 + 64) << 16 in the record's last slot (every flush of a Gaussian stores the same
+// value); the preprocess gradient kernel reads them.
 #define GCR_GRAD_REC_FLOATS_DET 32
 #define GCR_DET_K_SLOT 15   // 64-bit slot of the record that holds k + 64 (0 = never flushed: all sums are zero)
-static inline __host__ __device__ int gcr_det_frac_bits(float x, float y, uint32_t rect_x, uint32_t rect_y, int W, int H,
-                                                        bool conic) {
+static inline __host__ __device__ int gcr_det_class(int rec_slot) { return rec_slot >= 6 ? 2 : (rec_slot >= 4 ? 1 : 0); }
+static inline __host__ __device__ int gcr_det_frac_bits(float x, float y, uint32_t rect_x, uint32_t rect_y, int cls) {
   const float minx = 16.0f * (float)(rect_x & 0xffffu), maxx = 16.0f * (float)(rect_x >> 16);
   const float miny = 16.0f * (float)(rect_y & 0xffffu), maxy = 16.0f * (float)(rect_y >> 16);
   const float npix = (maxx - minx) * (maxy - miny);
   const float ax = x - minx, bx = x - maxx, ay = y - miny, by = y - maxy;
   const float dx2 = ax * ax > bx * bx ? ax * ax : bx * bx, dy2 = ay * ay > by * by ? ay * ay : by * by;
-  const float wh = 8.0f * (float)(W > H ? W : H);
-  float d2 = conic ? dx2 + dy2 : wh;
-  d2 = d2 > wh ? d2 : wh;  // (a NaN centre compares false: wh)
+  float d2 = cls == 2 ? dx2 + dy2 : (cls == 1 ? __builtin_sqrtf(dx2 + dy2) : 64.0f);
+  d2 = d2 > 64.0f ? d2 : 64.0f;  // (a NaN centre compares false: 64)
   float B = npix * d2 * 64.0f;
   B = B > 1.0f ? B : 1.0f;
   union { float f; uint32_t u; } c;
   c.f = B;
   const int e = (int)((c.u >> 23) & 0xffu) - 127 + 1;  // > log2 B (255 - 126 for inf / NaN: the coarse end)
   const int k = 61 - e;
-  return k > 32 ? 32 : (k < -16 ? -16 : k);
+  return k > 44 ? 44 : (k < -16 ? -16 : k);
 }
 
 // The dense zero fill of the backward's outputs (every Gaussian K8 does not visit keeps gradient 0): up to eight
@@ -164,15 +167,20 @@ struct GcrFillArgs {
 
 // ---- backward pieces -------------------------------------------------------------------------------------
 // The forward blend walks a tile's list in PIECES of equal size (<= P entries, P = option "bwd_piece") and leaves,
-// at every piece boundary it crosses, a CHECKPOINT of the per-pixel state (T, prefix colour) -- 16 bytes x 256
-// pixels -- plus the final state once it has crossed one.  The backward blend then works on (tile, piece) ITEMS
+// at every piece boundary it crosses, a CHECKPOINT of the per-pixel state -- T behind the piece and the colour the
+// piece's own entries blended (summed from zero in every piece), 16 bytes x 256 pixels -- plus the same for the last
+// piece it walked into once it has crossed a boundary.  The backward blend then works on (tile, piece) ITEMS
 // instead of whole tiles: a piece that is not the pixel's last starts from the checkpoint behind it (T from the
-// forward, accum_rec = (C_final - C_prefix) / T) instead of walking everything behind it first
-// (cr/backward.cu:495-580 walks the whole list per tile).
+// forward, accum_rec = (the sum of the later pieces' colour sums, added from the back) / T) instead of walking
+// everything behind it first (cr/backward.cu:495-580 walks the whole list per tile).  (Earlier
+// the checkpoint held the PREFIX colour and accum_rec was (C_final - C_prefix) / T: a difference of two sums of the
+// size of the image colour, whose rounding error is 1 / T times the signal of a Gaussian under many others --
+// per-Gaussian gradient errors of 10 to 1 000 times the oracle's, tests/test_gpu_grad_rows.py.)
 // Checkpoint slots: tile t's pieces own the slots from
 //   slot_base(t) = floor(ranges[t].start / P) + t,   slot_base(t) + ceil(len / P) <= slot_base(t + 1),
 // so neither a prefix sum over tiles nor a host-side count is needed; total slots = floor(R / P) + T.  Slot
-// slot_base(t) + k holds the checkpoint at boundary k + 1 (k < pieces - 1); the tile's LAST slot holds the final state.
+// slot_base(t) + k holds {T at boundary k + 1, colour sum of piece k} for every piece k the forward walked into (the
+// last of them: {final T, its colour sum}, written at the end of the walk if the tile crossed a boundary at all).
 // Work items: slot s of tile t's range also holds a 16-byte item {tile, list start, list length, piece} if the
 // forward walked into that piece, {GCR_NO_TILE} otherwise (a saturated tile's remaining pieces, the gap slot between two
 // tiles); the backward launches one wave per (slot, quadrant).

@@ -991,9 +991,10 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(const GcrPreprocessBwdAr
     const long long kslot = r64[GCR_DET_K_SLOT];
     const int kc = kslot != 0 ? (int)(kslot & 0xff) - 64 : 32;  // (never flushed: every sum is zero)
     const int ko = kslot != 0 ? (int)((kslot >> 8) & 0xff) - 64 : 32;
+    const int k1 = kslot != 0 ? (int)((kslot >> 16) & 0xff) - 64 : 32;
     float f[9];
 #pragma unroll
-    for (int k = 0; k < 9; k++) f[k] = (float)__builtin_ldexp((double)r64[k], k >= 4 ? -kc : -ko);
+    for (int k = 0; k < 9; k++) f[k] = (float)__builtin_ldexp((double)r64[k], k >= 6 ? -kc : (k >= 4 ? -k1 : -ko));
     g0 = make_float4(f[0], f[1], f[2], f[3]);
     g1 = make_float4(f[4], f[5], f[6], f[7]);
     g2 = make_float4(f[8], 0.0f, 0.0f, 0.0f);

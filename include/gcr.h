@@ -239,7 +239,7 @@ typedef struct gcr_layout {
                            length, piece} written by the forward blend for every piece it walked into */
   size_t bin_mask;      /* uint16 per instance, sorted-list order: which of the tile's sixteen 4x4 blocks the
                            entry can reach (computed by the forward blend while staging, reused by the backward) */
-  size_t bin_ckpt;      /* 4096 B per slot: per-pixel (T, prefix colour) at the piece boundaries the forward
+  size_t bin_ckpt;      /* 4096 B per slot: per-pixel (T, the piece's colour sum) at the piece boundaries the forward
                            blend crossed -- what lets the backward blend start in the middle of a tile list */
   size_t bin_total;
   size_t bin_lean_total; /* everything in front of bin_work: all a frame with gcr_camera.backward == 0 uses */

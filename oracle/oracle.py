@@ -90,6 +90,8 @@ def lib64():
         L.orc_render_backward.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p]
         L.orc_preprocess_backward.restype = None
         L.orc_preprocess_backward.argtypes = [C.c_void_p] * 4
+        L.orc_set_state32.restype = None
+        L.orc_set_state32.argtypes = [C.c_int]
         _lib64 = L
     return _lib64
 
@@ -152,7 +154,27 @@ class Frame:
     def __init__(self, *, img_h, img_w, tanfovx, tanfovy, bg, scale_modifier, view_matrix,
                  proj_matrix, sh_degree, campos, means3D, opacities, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
+        self._bind(img_h=img_h, img_w=img_w, tanfovx=tanfovx, tanfovy=tanfovy, bg=bg, scale_modifier=scale_modifier,
+                   view_matrix=view_matrix, proj_matrix=proj_matrix, sh_degree=sh_degree, campos=campos, means3D=means3D,
+                   opacities=opacities, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+                   cov3D_precomp=cov3D_precomp)
         L = self._lib_fn()
+        P = self.P
+        # K1 + K2
+        self.R = int(L.orc_preprocess(C.byref(self.cam), C.byref(self.g), C.byref(self.geo))) if P else 0
+        self._bind_binning()
+        # K3 + K4 + K5
+        L.orc_bin(C.byref(self.cam), P, C.byref(self.geo), self.R, C.byref(self.bin),
+                  C.byref(self.img))
+        # K6
+        L.orc_render(C.byref(self.cam), C.byref(self.geo), _ptr(self.colors), C.byref(self.bin),
+                     C.byref(self.img), _ptr(self.out_color))
+
+    state32 = False        # Frame64.from_frame: the backward takes its discrete decisions as the binary32 build does
+
+    def _bind(self, *, img_h, img_w, tanfovx, tanfovy, bg, scale_modifier, view_matrix, proj_matrix, sh_degree, campos,
+              means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp):
+        """Inputs -> arrays of the build's type and the C argument records; the forward state, zeroed."""
         _f32, FT = self._f, self.FT
         self.H, self.W = int(img_h), int(img_w)
         self.means3D = _f32(means3D, (-1, 3))
@@ -194,9 +216,9 @@ class Frame:
         self.final_T = np.zeros(self.H * self.W, FT)
         self.img = _Image(_ptr(self.ranges), _ptr(self.n_contrib), _ptr(self.final_T))
         self.out_color = np.zeros((3, self.H, self.W), FT)
+        self.colors = self.colors_precomp if self.colors_precomp is not None else self.rgb
 
-        # K1 + K2
-        self.R = int(L.orc_preprocess(C.byref(self.cam), C.byref(self.g), C.byref(self.geo))) if P else 0
+    def _bind_binning(self):
         R = max(self.R, 1)
         self.keys_unsorted = np.zeros(R, np.uint64)
         self.keys = np.zeros(R, np.uint64)
@@ -204,13 +226,6 @@ class Frame:
         self.point_list = np.zeros(R, np.uint32)
         self.bin = _Binning(_ptr(self.keys_unsorted), _ptr(self.keys), _ptr(self.list_unsorted),
                             _ptr(self.point_list))
-        # K3 + K4 + K5
-        L.orc_bin(C.byref(self.cam), P, C.byref(self.geo), self.R, C.byref(self.bin),
-                  C.byref(self.img))
-        # K6
-        self.colors = self.colors_precomp if self.colors_precomp is not None else self.rgb
-        L.orc_render(C.byref(self.cam), C.byref(self.geo), _ptr(self.colors), C.byref(self.bin),
-                     C.byref(self.img), _ptr(self.out_color))
 
     def backward(self, dL_dpix):
         """K7 + K8; returns dict with the reference's eight gradient tensors (+dL_dconic)."""
@@ -228,11 +243,17 @@ class Frame:
                                            "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale",
                                            "dL_drot")])
         if self.P:
-            L.orc_render_backward(C.byref(self.cam), C.byref(self.geo), _ptr(self.colors),
-                                  C.byref(self.bin), C.byref(self.img), self.R, _ptr(dpix),
-                                  C.byref(gs))
-            L.orc_preprocess_backward(C.byref(self.cam), C.byref(self.g), C.byref(self.geo),
+            if self.state32:
+                L.orc_set_state32(1)
+            try:
+                L.orc_render_backward(C.byref(self.cam), C.byref(self.geo), _ptr(self.colors),
+                                      C.byref(self.bin), C.byref(self.img), self.R, _ptr(dpix),
                                       C.byref(gs))
+                L.orc_preprocess_backward(C.byref(self.cam), C.byref(self.g), C.byref(self.geo),
+                                          C.byref(gs))
+            finally:
+                if self.state32:
+                    L.orc_set_state32(0)
         for k in g:
             g[k] = g[k][: self.P]
         return g
@@ -254,6 +275,33 @@ class Frame64(Frame):
     FT = np.float64
     _camera_t = _Camera64
     _lib_fn = staticmethod(lambda: lib64())
+
+    _STATE = ("depths", "clamped", "radii", "means2D", "cov3D", "conic_opacity", "rgb", "tiles_touched", "point_offsets",
+              "ranges", "n_contrib", "final_T", "out_color")
+
+    @classmethod
+    def from_frame(cls, fr):
+        """The state-consistent reference of tests/grad_rows.py: a binary64 frame that runs NO forward of its own -- it
+        holds the binary32 Frame `fr`'s inputs and forward state (per-Gaussian state, tile ranges, n_contrib, final_T,
+        the sorted list), widened, and its backward() evaluates K7 and K8's statements in binary64 while taking every
+        discrete decision on binary32 values as the binary32 build takes it (gcr_oracle.c, orc_set_state32): the value of
+        the backward formulas on exactly the forward state that the GPU reproduces bit for bit."""
+        assert type(fr) is Frame, "from_frame wants the binary32 oracle's frame"
+        self = cls.__new__(cls)
+        cam = fr.cam   # the scalars as binary32 holds them: they are inputs of the binary32 frame
+        self._bind(img_h=fr.H, img_w=fr.W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=fr.bg,
+                   scale_modifier=cam.scale_modifier, view_matrix=fr.view, proj_matrix=fr.proj, sh_degree=cam.sh_degree,
+                   campos=fr.campos, means3D=fr.means3D, opacities=fr.opacities, shs=fr.shs,
+                   colors_precomp=fr.colors_precomp, scales=fr.scales, rotations=fr.rotations,
+                   cov3D_precomp=fr.cov3D_precomp)
+        for k in cls._STATE:
+            getattr(self, k)[...] = getattr(fr, k)
+        self.R = fr.R
+        self._bind_binning()
+        for k in ("keys_unsorted", "keys", "list_unsorted", "point_list"):
+            getattr(self, k)[...] = getattr(fr, k)
+        self.state32 = True
+        return self
 
 
 def mark_visible(means3D, view_matrix, proj_matrix):

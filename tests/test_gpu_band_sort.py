@@ -45,12 +45,13 @@ def _k1_grid(P, max_blocks=2048):
 
 
 def _vis_rec(P, W, H, out):
-    """K1's survivor lists and records, decoded: {index: (depth bits, rect_x, rect_y)} over every K1 block."""
+    """K1's survivor counts (one per block K1 launches, no word more: the rest of the buffer is nobody's), lists and
+    records, decoded."""
     from gaussiancity_amd import _native as N
     R, _, radii, geom, _, _ = out
     L = N.get_layout(P, W, H, R)
     gb = geom.cpu().numpy()
-    nblk = (P + 255) // 256 + 1
+    nblk = _k1_grid(P)[0]
     counts = gb[L.geom_vis_count:L.geom_vis_count + 4 * nblk].view(np.uint32)
     lists = gb[L.geom_vis_list:L.geom_vis_list + 4 * P].view(np.uint32)
     recs = gb[L.geom_vis_rec:L.geom_vis_rec + 16 * P].view(np.uint32).reshape(P, 4)

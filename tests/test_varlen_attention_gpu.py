@@ -5,11 +5,7 @@ Bar: every element of out, dQ, dK, dV within 4 UNITS of the float64 value, one u
 absolute values) + the subnormal floor (attn_ref's docstring).  2 units is the derived bound for out and dV (two
 roundings to binary16: the operand P and the stored result), dQ and dK add the rounding of dS and of the stored out
 inside D; 4 leaves room for fp32 summation order and the hardware exponential.  Bit-exact where the rule is a copy
-(one-hot attention), bit-identical between two runs (no float atomics).
-
-The module's name puts it after the rasteriser's GPU modules on purpose: test_gpu_band_sort reads one survivor count more
-than K1 writes (a word of a torch.empty buffer) and passes only while that word is memory nobody has written yet, so
-these tests, which fill and free hundreds of MB, must not run before it in the same process."""
+(one-hot attention), bit-identical between two runs (no float atomics)."""
 import numpy as np
 import pytest
 import torch
