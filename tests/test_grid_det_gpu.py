@@ -2,7 +2,8 @@
 gaussiancity_amd/csrc/gce_det.h).  Bars: grad_embeddings max|d| <= 1e-5 * max(1, max|ref|) in float32 (the project's bar
 for this output; a strictly sequential float32 sum in id order stays at 0.05 - 0.20 of it on these shapes), 1e-12 * max in
 double, 2e-2 * max in half; grad_inputs bit-exact as with the atomic path; and every result BIT-IDENTICAL from run to run,
-across streams and whatever the workspace held."""
+across streams and whatever the workspace held.  The per-element bar of the same output -- every element within the
+summation bound of its own terms -- is tests/test_grid_rows_gpu.py; the bars here stay as they are."""
 import ctypes
 import math
 

@@ -1,6 +1,7 @@
 """-m gpu: the HIP hash-grid encoder (gaussiancity_amd.grid_encoder -> C ABI include/gce.h -> gfx950 kernels)
 against the oracle.  Bars (gce-fp32-v1): outputs, dy_dx and grad_inputs BIT-EXACT; grad_embeddings is a sum of
-float atomics (order-dependent) -> max|d| <= 1e-5 * max(1, max|ref|)."""
+float atomics (order-dependent) -> max|d| <= 1e-5 * max(1, max|ref|), and, element by element, the summation bound of
+tests/test_grid_rows_gpu.py."""
 import math
 
 import numpy as np
