@@ -15,8 +15,10 @@
 // Opt-in second engine (GCS_ENGINE_MFMA, gcs_mfma.h): the same three products (forward, dX, dW) on the f32 matrix cores,
 // the gather-GEMM in tap slices where the tile grid cannot fill the GPU; the entry points without `_engine` in their
 // names are the VALU engine.
-// Binary16 (GCS_F16 of the `_t` entry points, gcs_half.h): the same products on v_mfma_f32_16x16x16_f16, fp32 sums, one
-// rounding on store, under the matrix-core engine's plan; binary16 segment_csr.
+// Binary16 (GCS_F16 of the `_t` entry points, gcs_mfma.h): the same products on v_mfma_f32_16x16x16_f16 under the
+// matrix-core engine's plan; binary16 segment_csr.  Everything outside the three products is one kernel and one host
+// path for both element types T (float, half_t): sums are fp32 in a fixed order, T is converted on the load and ONCE
+// on the final store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -24,12 +26,15 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "../../include/gcs.h"
 #define GC_ERR_HIP GCS_ERR_HIP
 #include "gc_host.h"
 
 namespace {
+
+typedef _Float16 half_t;  // binary16, the element type of GCS_F16
 
 constexpr uint64_t kEmpty = ~0ull;
 constexpr int kScanThreads = 256;
@@ -290,6 +295,32 @@ __global__ void k_group_sort(int64_t n, const int32_t* hdr, const int32_t* __res
 // 256 threads; a thread owns MR rows x MC columns; TRANS picks the coalesced order of the weight tile load.
 constexpr int KC = 16;
 constexpr int KR = 16;  // pairs per LDS chunk of the dW kernels (k_subm_dw below, k_subm_dw_mfma in gcs_mfma.h)
+
+// The head of a tap, shared by the gather-GEMM kernels of both engines and both element types: the tile's neighbour
+// rows under tap k of the loop order go to sN (-1 = absent, and beyond n); returns whether any row of the tile has the
+// tap.  The answer is block-uniform (__syncthreads_or), so a workgroup skips an absent tap as one.
+template <int TM>
+__device__ __forceinline__ int tap_head(const int32_t* __restrict__ nbr, int K, int k, int mirror, int64_t row0, int64_t n,
+                                        int32_t* sN) {
+  const int kn = mirror ? K - 1 - k : k;
+  int any = 0;
+  for (int r = threadIdx.x; r < TM; r += 256) {
+    const int64_t row = row0 + r;
+    const int32_t j = row < n ? nbr[row * K + kn] : -1;
+    sN[r] = j;
+    any |= j >= 0;
+  }
+  return __syncthreads_or(any);
+}
+// The one store of an output element whose fp32 sum is s: into the fp32 partials when the sum continues elsewhere
+// (`part`), else the final value -- 0 for a row the mask excludes, the bias added in fp32, ONE conversion to T.
+template <typename T>
+__device__ __forceinline__ void store_out(float s, int64_t at, int o, bool zero, const T* bias, T* y, float* part) {
+  if (part)
+    part[at] = s;
+  else
+    y[at] = (T)(zero ? 0.0f : (bias ? s + (float)bias[o] : s));
+}
 template <int TM, int TN, int MR, int MC, bool TRANS>
 __global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, int cin, const float* __restrict__ w,
                                                    int64_t sk, int64_t sn, int64_t sc, const float* __restrict__ bias,
@@ -311,15 +342,7 @@ __global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, 
     for (int j = 0; j < MC; j++) acc[i][j] = 0.0f;
 
   for (int k = 0; k < K; k++) {
-    const int kn = mirror ? K - 1 - k : k;
-    int any = 0;
-    for (int r = tid; r < TM; r += 256) {
-      const int64_t row = row0 + r;
-      const int32_t j = row < n ? nbr[row * K + kn] : -1;
-      sN[r] = j;
-      any |= j >= 0;
-    }
-    if (!__syncthreads_or(any)) continue;
+    if (!tap_head<TM>(nbr, K, k, mirror, row0, n, sN)) continue;
     for (int c0 = 0; c0 < cin; c0 += KC) {
       for (int e = tid; e < TM * KC; e += 256) {
         const int r = e / KC, cc = e % KC, c = c0 + cc;
@@ -355,9 +378,59 @@ __global__ __launch_bounds__(256) void k_subm_gemm(const float* __restrict__ x, 
 #pragma unroll
     for (int j = 0; j < MC; j++) {
       const int o = n0 + tx * MC + j;
-      if (o < nout) y[row * nout + o] = zero ? 0.0f : (bias ? acc[i][j] + bias[o] : acc[i][j]);
+      if (o < nout) y[row * nout + o] = zero ? 0.0f : (bias ? acc[i][j] + bias[o] : acc[i][j]);  // store_out, final
     }
   }
+}
+
+// ---- the launches of the gather-GEMM and of dW: one argument block, one tile dispatch each --------------------------
+// y[n][nout] = bias + sum over the taps of x[nbr[.][tap]] . W(k), in the terms of k_subm_gemm above
+template <typename T>
+struct Gemm {
+  const T* x;
+  int cin;
+  const T* w;
+  int64_t sk, sn, sc;
+  const T* bias;
+  const int32_t* nbr;
+  int K, mirror;
+  const int32_t* rowmask;
+  T* y;
+  int nout;
+  int64_t n;
+};
+template <int TM_, int TN_>
+struct Tile {
+  static constexpr int TM = TM_, TN = TN_;
+};
+unsigned blocks_for(int64_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
+
+// GCS_TILE_* of a gather-GEMM -> launch(Tile<TM, TN>, grid): TM x TN tiles over n x nout, S tap slices
+template <typename F>
+void for_gemm_tile(int tile, int64_t n, int nout, int S, F&& launch) {
+  if (tile == GCS_TILE_64X64)
+    launch(Tile<64, 64>(), dim3(blocks_for(n, 64), blocks_for(nout, 64), (unsigned)S));
+  else if (tile == GCS_TILE_128X32)
+    launch(Tile<128, 32>(), dim3(blocks_for(n, 128), 1, (unsigned)S));  // nout <= 32: one column tile
+  else
+    launch(Tile<32, 32>(), dim3(blocks_for(n, 32), blocks_for(nout, 32), (unsigned)S));
+}
+// GCS_TILE_* of dW -> launch(Tile<T, T>, grid): T x T tiles over cout x cin, per tap, S pair slices
+template <typename F>
+void for_dw_tile(int tile, int cin, int cout, int K, int S, F&& launch) {
+  if (tile == GCS_TILE_64X64)
+    launch(Tile<64, 64>(), dim3(blocks_for(cout, 64) * blocks_for(cin, 64), (unsigned)K, (unsigned)S));
+  else
+    launch(Tile<32, 32>(), dim3(blocks_for(cout, 32) * blocks_for(cin, 32), (unsigned)K, (unsigned)S));
+}
+
+template <bool TRANS>
+void launch_gemm(int tile, const Gemm<float>& g, hipStream_t st) {
+  for_gemm_tile(tile, g.n, g.nout, 1, [&](auto t, dim3 grid) {
+    constexpr int TM = decltype(t)::TM, TN = decltype(t)::TN, M = TM * TN == 32 * 32 ? 2 : 4;  // M x M per thread
+    k_subm_gemm<TM, TN, M, M, TRANS><<<grid, 256, 0, st>>>(g.x, g.cin, g.w, g.sk, g.sn, g.sc, g.bias, g.nbr, g.K, g.mirror,
+                                                           g.rowmask, g.y, g.nout, g.n);
+  });
 }
 
 #include "gcs_mfma.h"
@@ -431,33 +504,47 @@ __global__ __launch_bounds__(256) void k_subm_dw(const float* __restrict__ dy, i
   }
 }
 
-// out[e] = sum_s part[s][e], s ascending
-__global__ void k_sum_slices(const float* __restrict__ part, int nslice, int64_t len, float* __restrict__ out) {
+// the VALU launch of dW; `part` is [S][cout][K][cin] when S > 1, else dw itself receives the sums
+void launch_dw(int tile, int S, const float* dy, int cout, const float* x, int cin, const int32_t* nbr, int K,
+               const int32_t* prow, const int32_t* hdr, int64_t n, float* part, float* dw, hipStream_t st) {
+  for_dw_tile(tile, cin, cout, K, S, [&](auto t, dim3 grid) {
+    constexpr int T = decltype(t)::TM;
+    k_subm_dw<T, T, T / 16, T / 16><<<grid, 256, 0, st>>>(dy, cout, x, cin, nbr, K, prow, hdr, n, S, S > 1 ? part : dw);
+  });
+}
+
+// ---- the element-wise kernels, one for both element types T: fp32 sums in a fixed order, T converted on the load and
+// once on the store (no conversion at all for float) ------------------------------------------------------------------
+// out[e] = T(sum_s part[s][e]), s ascending
+template <typename T>
+__global__ void k_sum_slices(const float* __restrict__ part, int nslice, int64_t len, T* __restrict__ out) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= len) return;
   float v = part[e];
   for (int s = 1; s < nslice; s++) v += part[(int64_t)s * len + e];
-  out[e] = v;
+  out[e] = (T)v;
 }
 
 // column sums of dy over a slice of rows: 64 columns x 4 row phases per block, phases combined in order
-__global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ dy, int64_t n, int cout, int nslice,
+template <typename T>
+__global__ __launch_bounds__(256) void k_colsum(const T* __restrict__ dy, int64_t n, int cout, int nslice,
                                                 float* __restrict__ part) {
   __shared__ float red[4][64];
   const int col = blockIdx.x * 64 + threadIdx.x % 64, ph = threadIdx.x / 64, s = blockIdx.y;
   const int64_t per = (n + nslice - 1) / nslice, r0 = s * per, r1 = r0 + per < n ? r0 + per : n;
   float v = 0.0f;
   if (col < cout)
-    for (int64_t r = r0 + ph; r < r1; r += 4) v += dy[r * cout + col];
+    for (int64_t r = r0 + ph; r < r1; r += 4) v += (float)dy[r * cout + col];
   red[ph][threadIdx.x % 64] = v;
   __syncthreads();
   if (ph == 0 && col < cout) part[(int64_t)s * cout + col] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-// dyf[r] = sum of dy over the rows of representative r's voxel, row order; other rows are never read
-__global__ void k_fold(const float* __restrict__ dy, int64_t n, int cout, const int32_t* __restrict__ rep,
+// dyf[r] = T(fp32 sum of dy over the rows of representative r's voxel, row order); other rows are never read
+template <typename T>
+__global__ void k_fold(const T* __restrict__ dy, int64_t n, int cout, const int32_t* __restrict__ rep,
                        const int32_t* __restrict__ gstart, const int32_t* __restrict__ gcnt,
-                       const int32_t* __restrict__ glist, float* __restrict__ dyf) {
+                       const int32_t* __restrict__ glist, T* __restrict__ dyf) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n * cout) return;
   const int64_t r = e / cout;
@@ -469,9 +556,9 @@ __global__ void k_fold(const float* __restrict__ dy, int64_t n, int cout, const 
     return;
   }
   const int32_t* g = glist + gstart[r];
-  float v = dy[(int64_t)g[0] * cout + o];
-  for (int q = 1; q < cnt; q++) v += dy[(int64_t)g[q] * cout + o];
-  dyf[e] = v;
+  float v = (float)dy[(int64_t)g[0] * cout + o];
+  for (int q = 1; q < cnt; q++) v += (float)dy[(int64_t)g[q] * cout + o];
+  dyf[e] = (T)v;
 }
 
 // ---- segment_csr -------------------------------------------------------------------------------------------------
@@ -483,49 +570,52 @@ __device__ __forceinline__ void seg_bounds(const int64_t* indptr, int64_t s, int
   *hi = b;
 }
 
-// one wave per (segment, block of 64 columns), rows summed in index order
-__global__ __launch_bounds__(64) void k_seg_fwd(const float* __restrict__ src, int64_t m, int64_t f,
+// one wave per (segment, block of 64 columns).  Sum and mean: fp32 in row order, mean divided in fp32, one conversion
+// to T.  Min and max compare exactly and copy bits; the arg is the first row that attains the value.
+template <typename T>
+__global__ __launch_bounds__(64) void k_seg_fwd(const T* __restrict__ src, int64_t m, int64_t f,
                                                 const int64_t* __restrict__ indptr, int64_t nfb, int reduce,
-                                                float* __restrict__ out, int64_t* __restrict__ arg) {
+                                                T* __restrict__ out, int64_t* __restrict__ arg) {
   const int64_t s = blockIdx.x / nfb, col = (blockIdx.x % nfb) * 64 + threadIdx.x;
   if (col >= f) return;
   int64_t lo, hi;
   seg_bounds(indptr, s, m, &lo, &hi);
-  float v = 0.0f;
+  T res = (T)0.0f;
   int64_t best = -1;
   if (reduce == GCS_SUM || reduce == GCS_MEAN) {
-    for (int64_t r = lo; r < hi; r++) v += src[r * f + col];
+    float v = 0.0f;
+    for (int64_t r = lo; r < hi; r++) v += (float)src[r * f + col];
     if (reduce == GCS_MEAN && hi > lo) v = v / (float)(hi - lo);
+    res = (T)v;
   } else if (hi > lo) {
-    v = src[lo * f + col];
+    res = src[lo * f + col];
     best = lo;
     for (int64_t r = lo + 1; r < hi; r++) {
-      const float u = src[r * f + col];
-      if (reduce == GCS_MAX ? u > v : u < v) {
-        v = u;
+      const T u = src[r * f + col];
+      if (reduce == GCS_MAX ? (float)u > (float)res : (float)u < (float)res) {
+        res = u;
         best = r;
       }
     }
   }
-  out[s * f + col] = v;
+  out[s * f + col] = res;
   if (arg) arg[s * f + col] = best;
 }
 
-__global__ __launch_bounds__(64) void k_seg_bwd(const float* __restrict__ dout, int64_t m, int64_t f,
+template <typename T>
+__global__ __launch_bounds__(64) void k_seg_bwd(const T* __restrict__ dout, int64_t m, int64_t f,
                                                 const int64_t* __restrict__ indptr, int64_t nfb, int reduce,
-                                                const int64_t* __restrict__ arg, float* __restrict__ dsrc) {
+                                                const int64_t* __restrict__ arg, T* __restrict__ dsrc) {
   const int64_t s = blockIdx.x / nfb, col = (blockIdx.x % nfb) * 64 + threadIdx.x;
   if (col >= f) return;
   int64_t lo, hi;
   seg_bounds(indptr, s, m, &lo, &hi);
-  float g = dout[s * f + col];
-  if (reduce == GCS_MEAN && hi > lo) g = g / (float)(hi - lo);
+  T g = dout[s * f + col];
+  if (reduce == GCS_MEAN && hi > lo) g = (T)((float)g / (float)(hi - lo));
   const int64_t a = (reduce == GCS_MIN || reduce == GCS_MAX) ? arg[s * f + col] : -1;
   for (int64_t r = lo; r < hi; r++)
-    dsrc[r * f + col] = (reduce == GCS_SUM || reduce == GCS_MEAN) ? g : (r == a ? g : 0.0f);
+    dsrc[r * f + col] = (reduce == GCS_SUM || reduce == GCS_MEAN) ? g : (r == a ? g : (T)0.0f);
 }
-
-#include "gcs_half.h"
 
 // ---- host helpers ----------------------------------------------------------------------------------------------
 int check_conv_dims(const char* who, int64_t n, int32_t K, int32_t cin, int32_t cout) {
@@ -609,158 +699,50 @@ size_t forward_ws_bytes(const EnginePlan& e, int64_t n, int32_t cout) {
   return e.fwd_slices > 1 ? align_up(4 * (size_t)e.fwd_slices * n * cout) : 0;
 }
 
-struct BwdWs {
-  float* dyf;    // [N][Cout] when dups
-  float* dwp;    // [S][Cout][K][Cin] when S > 1
-  float* dbp;    // [Sb][Cout]
-  float* dxp;    // [Sx][N][Cin] when dX runs in Sx > 1 tap slices (matrix-core engine)
-  size_t bytes;
-};
-BwdWs carve_bwd(void* base, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups, int dx_slices = 1) {
-  BwdWs w;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char* q = (p && b) ? p + off : nullptr;
-    off += align_up(b);
-    return (float*)q;
-  };
-  const Plan pl = plan_of(n, cin, cout, K);
-  w.dyf = take(dups ? 4 * (size_t)n * cout : 0);
-  w.dwp = take(pl.dw_slices > 1 ? 4 * (size_t)pl.dw_slices * cout * K * cin : 0);
-  w.dbp = take(4 * (size_t)pl.db_slices * cout);
-  w.dxp = take(dx_slices > 1 ? 4 * (size_t)dx_slices * n * cin : 0);
-  w.bytes = off;
-  return w;
-}
-
-template <bool TRANS>
-void launch_gemm(int tile, const float* x, int cin, const float* w, int64_t sk, int64_t sn, int64_t sc, const float* bias,
-                 const int32_t* nbr, int K, int mirror, const int32_t* rowmask, float* y, int nout, int64_t n,
-                 hipStream_t st) {
-  if (tile == GCS_TILE_64X64) {
-    dim3 grid((unsigned)((n + 63) / 64), (unsigned)((nout + 63) / 64));
-    k_subm_gemm<64, 64, 4, 4, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
-  } else if (tile == GCS_TILE_128X32) {
-    dim3 grid((unsigned)((n + 127) / 128), 1);  // nout <= 32: one column tile
-    k_subm_gemm<128, 32, 4, 4, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
-  } else {
-    dim3 grid((unsigned)((n + 31) / 32), (unsigned)((nout + 31) / 32));
-    k_subm_gemm<32, 32, 2, 2, TRANS><<<grid, 256, 0, st>>>(x, cin, w, sk, sn, sc, bias, nbr, K, mirror, rowmask, y, nout, n);
-  }
-}
-
-unsigned blocks_for(int64_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
-
-// the forward and the backward of both engines; `who` names the entry point in the error texts
-int subm_forward(const char* who, int32_t engine, const void* rulebook, int64_t n, int32_t kvol, const float* features,
-                 int32_t cin, const float* weight, const float* bias, int32_t cout, float* out, void* workspace,
-                 size_t workspace_bytes, void* hip_stream) {
-  const std::string me(who);
-  if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
-  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
-  if (n == 0) return 0;
-  if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output");
-  const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
-  const size_t need = forward_ws_bytes(e, n, cout);
-  if (need && (!workspace || workspace_bytes < need))
-    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than gcs_subm_engine_workspace_bytes");
-  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (engine == GCS_ENGINE_MFMA)
-    launch_gemm_mfma<false>(e.p.fwd, e.fwd_slices, features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0,
-                            nullptr, out, cout, n, (float*)workspace, st);
-  else
-    launch_gemm<false>(e.p.fwd, features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0, nullptr, out,
-                       cout, n, st);
-  HIP_TRY(hipGetLastError(), "forward launch");
-  return 0;
-}
-
-int subm_backward(const char* who, int32_t engine, const void* rulebook, int64_t n, int32_t kvol, int32_t dups,
-                  const float* features, int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx,
-                  float* dw, float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  const std::string me(who);
-  if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
-  if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
-  const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
-  const Plan& pl = e.p;
-  const BwdWs ws = carve_bwd(workspace, n, cin, cout, kvol, dups, e.dx_slices);
-  if (!workspace || workspace_bytes < ws.bytes)
-    return fail(GCS_ERR_INVALID_ARGUMENT,
-                me + (engine == GCS_ENGINE_VALU ? ": workspace missing or smaller than gcs_subm_backward_workspace_bytes"
-                                                : ": workspace missing or smaller than gcs_subm_engine_workspace_bytes"));
-  if (n > 0 && (!dout || ((dx || dw) && !features)))
-    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output gradient");
-  hipStream_t st = (hipStream_t)hip_stream;
-  const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
-  if (n == 0) {
-    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 4 * (size_t)cout * kvol * cin, st), "dw clear");
-    if (db) HIP_TRY(hipMemsetAsync(db, 0, 4 * (size_t)cout, st), "db clear");
-    return 0;
-  }
-  if (dx) {
-    const float* g = dout;
-    if (dups) {
-      k_fold<<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
-      g = ws.dyf;
-    }
-    // dX[j][c] = sum_k sum_o W[o][k][c] * g[nbr[j][K-1-k]][o]: reduction over o (stride K*Cin), output c (stride 1)
-    if (engine == GCS_ENGINE_MFMA)
-      launch_gemm_mfma<true>(pl.dx, e.dx_slices, g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1,
-                             dups ? rb.rep : nullptr, dx, cin, n, ws.dxp, st);
-    else
-      launch_gemm<true>(pl.dx, g, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1,
-                        dups ? rb.rep : nullptr, dx, cin, n, st);
-  }
-  if (dw) {
-    const int S = pl.dw_slices;
-    float* dst = S > 1 ? ws.dwp : dw;
-    if (engine == GCS_ENGINE_MFMA) {
-      launch_dw_mfma(pl.dw, S, dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, dst, st);
-    } else if (pl.dw == GCS_TILE_64X64) {
-      dim3 grid((unsigned)(((cout + 63) / 64) * ((cin + 63) / 64)), (unsigned)kvol, (unsigned)S);
-      k_subm_dw<64, 64, 4, 4><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
-    } else {
-      dim3 grid((unsigned)(((cout + 31) / 32) * ((cin + 31) / 32)), (unsigned)kvol, (unsigned)S);
-      k_subm_dw<32, 32, 2, 2><<<grid, 256, 0, st>>>(dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, S, dst);
-    }
-    if (S > 1) {
-      const int64_t len = (int64_t)cout * kvol * cin;
-      k_sum_slices<<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
-    }
-  }
-  if (db) {
-    const int S = pl.db_slices;
-    k_colsum<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
-    k_sum_slices<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
-  }
-  HIP_TRY(hipGetLastError(), "backward launch");
-  return 0;
-}
-
-
-// ---- binary16 (GCS_F16 of the `_t` entry points): one engine, the matrix cores, under engine_plan_of(GCS_ENGINE_MFMA) -----
+// ---- the host path of the convolution, one for both element types T ------------------------------------------------
 int check_dtype(const char* who, int32_t dtype) {
   if (dtype != GCS_F32 && dtype != GCS_F16)
     return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown dtype (GCS_F32 or GCS_F16)");
   return 0;
 }
-int check_half_pointers(const char* who, std::initializer_list<const void*> ptrs) {
+// binary16 pointers are 2-byte aligned (float pointers are taken as they come)
+template <typename T>
+int check_pointers(const char* who, std::initializer_list<const void*> ptrs) {
   for (const void* p : ptrs)
-    if ((uintptr_t)p & 1) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": a binary16 pointer is not 2-byte aligned");
+    if (sizeof(T) == 2 && ((uintptr_t)p & 1))
+      return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": a binary16 pointer is not 2-byte aligned");
+  return 0;
+}
+// a workspace of a binary16 call holds fp32 partials
+template <typename T>
+int check_workspace_alignment(const char* who, const void* workspace) {
+  if (sizeof(T) == 2 && ((uintptr_t)workspace & 3))
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": the workspace is not 4-byte aligned");
   return 0;
 }
 
-struct BwdWsH {
-  half_t* dyf;  // [N][Cout] binary16 when dups
+// What an entry point runs: the engine (binary16 has one, the matrix cores under engine_plan_of(GCS_ENGINE_MFMA)) and
+// the workspace query its error text cites.
+struct Route {
+  int32_t engine;
+  const char* ws_query;
+};
+Route route_f32(int32_t engine) {
+  return Route{engine, engine == GCS_ENGINE_VALU ? "gcs_subm_backward_workspace_bytes" : "gcs_subm_engine_workspace_bytes"};
+}
+const Route kRouteF16{GCS_ENGINE_MFMA, "gcs_subm_workspace_bytes_t"};
+
+template <typename T>
+struct BwdWs {
+  T* dyf;       // [N][Cout] when dups: the fold, in the element type
   float* dwp;   // [S][Cout][K][Cin] when S > 1
   float* dbp;   // [Sb][Cout]
-  float* dxp;   // [Sx][N][Cin] when dX runs in Sx > 1 tap slices
+  float* dxp;   // [Sx][N][Cin] when dX runs in Sx > 1 tap slices (matrix cores)
   size_t bytes;
 };
-BwdWsH carve_bwd_h(void* base, const EnginePlan& e, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups) {
-  BwdWsH w;
+template <typename T>
+BwdWs<T> carve_bwd(void* base, const EnginePlan& e, int64_t n, int32_t cin, int32_t cout, int32_t K, int32_t dups) {
+  BwdWs<T> w;
   char* p = (char*)base;
   size_t off = 0;
   auto take = [&](size_t b) {
@@ -768,7 +750,7 @@ BwdWsH carve_bwd_h(void* base, const EnginePlan& e, int64_t n, int32_t cin, int3
     off += align_up(b);
     return (void*)q;
   };
-  w.dyf = (half_t*)take(dups ? 2 * (size_t)n * cout : 0);
+  w.dyf = (T*)take(dups ? sizeof(T) * (size_t)n * cout : 0);
   w.dwp = (float*)take(e.p.dw_slices > 1 ? 4 * (size_t)e.p.dw_slices * cout * K * cin : 0);
   w.dbp = (float*)take(4 * (size_t)e.p.db_slices * cout);
   w.dxp = (float*)take(e.dx_slices > 1 ? 4 * (size_t)e.dx_slices * n * cin : 0);
@@ -776,72 +758,139 @@ BwdWsH carve_bwd_h(void* base, const EnginePlan& e, int64_t n, int32_t cin, int3
   return w;
 }
 
-int subm_forward_h(const char* who, const void* rulebook, int64_t n, int32_t kvol, const half_t* features, int32_t cin,
-                   const half_t* weight, const half_t* bias, int32_t cout, half_t* out, void* workspace,
-                   size_t workspace_bytes, void* hip_stream) {
+// the gather-GEMM and dW of a route: the VALU kernels exist for float only
+template <bool TRANS, typename T>
+void run_gemm(int32_t engine, int tile, int S, const Gemm<T>& g, float* part, hipStream_t st) {
+  if constexpr (std::is_same<T, float>::value)
+    if (engine == GCS_ENGINE_VALU) return launch_gemm<TRANS>(tile, g, st);
+  launch_gemm_mfma<TRANS>(tile, S, g, part, st);
+}
+template <typename T>
+void run_dw(int32_t engine, int tile, int S, const T* dy, int cout, const T* x, int cin, const Rulebook& rb, int K, int64_t n,
+            float* part, T* dw, hipStream_t st) {
+  if constexpr (std::is_same<T, float>::value)
+    if (engine == GCS_ENGINE_VALU) return launch_dw(tile, S, dy, cout, x, cin, rb.nbr, K, rb.prow, rb.hdr, n, part, dw, st);
+  launch_dw_mfma(tile, S, dy, cout, x, cin, rb.nbr, K, rb.prow, rb.hdr, n, part, dw, st);
+}
+
+// the forward and the backward of every route; `who` names the entry point in the error texts
+template <typename T>
+int subm_forward(const char* who, Route rt, const void* rulebook, int64_t n, int32_t kvol, const T* features, int32_t cin,
+                 const T* weight, const T* bias, int32_t cout, T* out, void* workspace, size_t workspace_bytes,
+                 void* hip_stream) {
   const std::string me(who);
   if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
-  if (int rc = check_half_pointers(who, {features, weight, bias, out})) return rc;
+  if (int rc = check_pointers<T>(who, {features, weight, bias, out})) return rc;
   if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
   if (n == 0) return 0;
   if (!features || !out) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output");
-  const EnginePlan e = engine_plan_of(GCS_ENGINE_MFMA, n, cin, cout, kvol);
+  const EnginePlan e = engine_plan_of(rt.engine, n, cin, cout, kvol);
   const size_t need = forward_ws_bytes(e, n, cout);
   if (need && (!workspace || workspace_bytes < need))
-    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than gcs_subm_workspace_bytes_t");
-  if (need && ((uintptr_t)workspace & 3)) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": the workspace is not 4-byte aligned");
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than " + rt.ws_query);
+  if (need)
+    if (int rc = check_workspace_alignment<T>(who, workspace)) return rc;
   const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
-  launch_gemm_h<false>(e.p.fwd, e.fwd_slices, features, cin, weight, cin, (int64_t)kvol * cin, 1, cin, bias, rb.nbr, kvol, 0,
-                       nullptr, out, cout, n, (float*)workspace, (hipStream_t)hip_stream);
+  const Gemm<T> g{features, cin, weight, cin, (int64_t)kvol * cin, 1, bias, rb.nbr, kvol, 0, nullptr, out, cout, n};
+  run_gemm<false>(rt.engine, e.p.fwd, e.fwd_slices, g, (float*)workspace, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError(), "forward launch");
   return 0;
 }
 
-int subm_backward_h(const char* who, const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const half_t* features,
-                    int32_t cin, const half_t* weight, int32_t cout, const half_t* dout, half_t* dx, half_t* dw, half_t* db,
-                    void* workspace, size_t workspace_bytes, void* hip_stream) {
+template <typename T>
+int subm_backward(const char* who, Route rt, const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const T* features,
+                  int32_t cin, const T* weight, int32_t cout, const T* dout, T* dx, T* dw, T* db, void* workspace,
+                  size_t workspace_bytes, void* hip_stream) {
   const std::string me(who);
   if (int rc = check_conv_dims(who, n, kvol, cin, cout)) return rc;
-  if (int rc = check_half_pointers(who, {features, weight, dout, dx, dw, db})) return rc;
+  if (int rc = check_pointers<T>(who, {features, weight, dout, dx, dw, db})) return rc;
   if (!rulebook || !weight) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null rulebook or weight");
-  const EnginePlan e = engine_plan_of(GCS_ENGINE_MFMA, n, cin, cout, kvol);
+  const EnginePlan e = engine_plan_of(rt.engine, n, cin, cout, kvol);
   const Plan& pl = e.p;
-  const BwdWsH ws = carve_bwd_h(workspace, e, n, cin, cout, kvol, dups);
+  const BwdWs<T> ws = carve_bwd<T>(workspace, e, n, cin, cout, kvol, dups);
   if (!workspace || workspace_bytes < ws.bytes)
-    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than gcs_subm_workspace_bytes_t");
-  if ((uintptr_t)workspace & 3) return fail(GCS_ERR_INVALID_ARGUMENT, me + ": the workspace is not 4-byte aligned");
+    return fail(GCS_ERR_INVALID_ARGUMENT, me + ": workspace missing or smaller than " + rt.ws_query);
+  if (int rc = check_workspace_alignment<T>(who, workspace)) return rc;
   if (n > 0 && (!dout || ((dx || dw) && !features)))
     return fail(GCS_ERR_INVALID_ARGUMENT, me + ": null features or output gradient");
   hipStream_t st = (hipStream_t)hip_stream;
   const Rulebook rb = carve_rulebook((void*)rulebook, n, kvol);
   if (n == 0) {
-    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, 2 * (size_t)cout * kvol * cin, st), "dw clear");
-    if (db) HIP_TRY(hipMemsetAsync(db, 0, 2 * (size_t)cout, st), "db clear");
+    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, sizeof(T) * (size_t)cout * kvol * cin, st), "dw clear");
+    if (db) HIP_TRY(hipMemsetAsync(db, 0, sizeof(T) * (size_t)cout, st), "db clear");
     return 0;
   }
   if (dx) {
-    const half_t* g = dout;
+    const T* gy = dout;
     if (dups) {
-      k_fold_h<<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
-      g = ws.dyf;
+      k_fold<T><<<blocks_for(n * cout, 256), 256, 0, st>>>(dout, n, cout, rb.rep, rb.gstart, rb.gcnt, rb.glist, ws.dyf);
+      gy = ws.dyf;
     }
-    launch_gemm_h<true>(pl.dx, e.dx_slices, g, cout, weight, cin, 1, (int64_t)kvol * cin, cin, nullptr, rb.nbr, kvol, 1,
-                        dups ? rb.rep : nullptr, dx, cin, n, ws.dxp, st);
+    // dX[j][c] = sum_k sum_o W[o][k][c] * gy[nbr[j][K-1-k]][o]: reduction over o (stride K*Cin), output c (stride 1)
+    const Gemm<T> g{gy, cout, weight, cin, 1, (int64_t)kvol * cin, nullptr, rb.nbr, kvol, 1, dups ? rb.rep : nullptr,
+                    dx, cin, n};
+    run_gemm<true>(rt.engine, pl.dx, e.dx_slices, g, ws.dxp, st);
   }
   if (dw) {
     const int S = pl.dw_slices;
-    launch_dw_h(pl.dw, S, dout, cout, features, cin, rb.nbr, kvol, rb.prow, rb.hdr, n, ws.dwp, dw, st);
+    run_dw(rt.engine, pl.dw, S, dout, cout, features, cin, rb, kvol, n, ws.dwp, dw, st);
     if (S > 1) {
       const int64_t len = (int64_t)cout * kvol * cin;
-      k_sum_slices_h<<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
+      k_sum_slices<T><<<blocks_for(len, 256), 256, 0, st>>>(ws.dwp, S, len, dw);
     }
   }
   if (db) {
     const int S = pl.db_slices;
-    k_colsum_h<<<dim3((unsigned)((cout + 63) / 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
-    k_sum_slices_h<<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
+    k_colsum<T><<<dim3(blocks_for(cout, 64), (unsigned)S), 256, 0, st>>>(dout, n, cout, S, ws.dbp);
+    k_sum_slices<T><<<blocks_for(cout, 256), 256, 0, st>>>(ws.dbp, S, cout, db);
   }
   HIP_TRY(hipGetLastError(), "backward launch");
+  return 0;
+}
+
+// ---- segment_csr: one typed body per direction ------------------------------------------------------------------
+int check_segment(const char* who, const void* a, const void* b, const int64_t* indptr, int64_t m, int64_t f, int64_t s,
+                  int32_t reduce, const int64_t* arg, bool arg_read) {
+  if (m < 0 || f < 1 || s < 0 || f > (int64_t)INT32_MAX)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": sizes out of range");
+  if (reduce < GCS_SUM || reduce > GCS_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown reduce");
+  const bool needs_arg = reduce == GCS_MIN || reduce == GCS_MAX;
+  if (s > 0 && (!b || !indptr)) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (m > 0 && !a) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+  if (s > 0 && needs_arg && !arg && arg_read)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": min and max need the arg buffer");
+  const int64_t nfb = (f + 63) / 64;
+  if (s * nfb > (int64_t)INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many segments");
+  return 0;
+}
+
+template <typename T>
+int segment_forward(const char* who, const T* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s, int32_t reduce,
+                    T* out, int64_t* arg, void* hip_stream) {
+  if (int rc = check_pointers<T>(who, {src, out})) return rc;
+  if (int rc = check_segment(who, src, out, indptr, m, f, s, reduce, arg, true)) return rc;
+  if (s == 0) return 0;
+  const int64_t nfb = (f + 63) / 64;
+  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
+  k_seg_fwd<T><<<(unsigned)(s * nfb), 64, 0, (hipStream_t)hip_stream>>>(src, m, f, indptr, nfb, reduce, out,
+                                                                        minmax ? arg : nullptr);
+  HIP_TRY(hipGetLastError(), "segment_csr forward launch");
+  return 0;
+}
+
+template <typename T>
+int segment_backward(const char* who, const T* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s, int32_t reduce,
+                     const int64_t* arg, T* dsrc, void* hip_stream) {
+  if (int rc = check_pointers<T>(who, {dout, dsrc})) return rc;
+  if (int rc = check_segment(who, dsrc, dout, indptr, m, f, s, reduce, arg, true)) return rc;
+  if (m == 0) return 0;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipMemsetAsync(dsrc, 0, sizeof(T) * (size_t)m * f, st), "dsrc clear");
+  if (s > 0) {
+    const int64_t nfb = (f + 63) / 64;
+    k_seg_bwd<T><<<(unsigned)(s * nfb), 64, 0, st>>>(dout, m, f, indptr, nfb, reduce, arg, dsrc);
+  }
+  HIP_TRY(hipGetLastError(), "segment_csr backward launch");
   return 0;
 }
 
@@ -862,7 +911,8 @@ size_t gcs_subm_rulebook_scratch_bytes(int64_t n) {
 }
 size_t gcs_subm_backward_workspace_bytes(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups) {
   if (check_conv_dims("gcs_subm_backward_workspace_bytes", n, kvol, cin, cout)) return 0;
-  return carve_bwd(nullptr, n, cin, cout, kvol, dups).bytes;
+  const EnginePlan e = engine_plan_of(GCS_ENGINE_VALU, n, cin, cout, kvol);
+  return carve_bwd<float>(nullptr, e, n, cin, cout, kvol, dups).bytes;
 }
 
 int gcs_subm_plan(int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t plan[5]) {
@@ -941,28 +991,28 @@ int gcs_subm_rulebook(const int32_t* indices, int64_t n, int32_t batch_size, con
 
 int gcs_subm_forward(const void* rulebook, int64_t n, int32_t kvol, const float* features, int32_t cin,
                      const float* weight, const float* bias, int32_t cout, float* out, void* hip_stream) {
-  return subm_forward("gcs_subm_forward", GCS_ENGINE_VALU, rulebook, n, kvol, features, cin, weight, bias, cout, out, nullptr,
+  return subm_forward("gcs_subm_forward", route_f32(GCS_ENGINE_VALU), rulebook, n, kvol, features, cin, weight, bias, cout, out, nullptr,
                       0, hip_stream);
 }
 int gcs_subm_forward_engine(int32_t engine, const void* rulebook, int64_t n, int32_t kvol, const float* features,
                             int32_t cin, const float* weight, const float* bias, int32_t cout, float* out,
                             void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (int rc = check_engine("gcs_subm_forward_engine", engine)) return rc;
-  return subm_forward("gcs_subm_forward_engine", engine, rulebook, n, kvol, features, cin, weight, bias, cout, out, workspace,
+  return subm_forward("gcs_subm_forward_engine", route_f32(engine), rulebook, n, kvol, features, cin, weight, bias, cout, out, workspace,
                       workspace_bytes, hip_stream);
 }
 
 int gcs_subm_backward(const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const float* features,
                       int32_t cin, const float* weight, int32_t cout, const float* dout, float* dx, float* dw,
                       float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  return subm_backward("gcs_subm_backward", GCS_ENGINE_VALU, rulebook, n, kvol, dups, features, cin, weight, cout, dout, dx, dw,
+  return subm_backward("gcs_subm_backward", route_f32(GCS_ENGINE_VALU), rulebook, n, kvol, dups, features, cin, weight, cout, dout, dx, dw,
                        db, workspace, workspace_bytes, hip_stream);
 }
 int gcs_subm_backward_engine(int32_t engine, const void* rulebook, int64_t n, int32_t kvol, int32_t dups,
                              const float* features, int32_t cin, const float* weight, int32_t cout, const float* dout,
                              float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (int rc = check_engine("gcs_subm_backward_engine", engine)) return rc;
-  return subm_backward("gcs_subm_backward_engine", engine, rulebook, n, kvol, dups, features, cin, weight, cout, dout, dx, dw,
+  return subm_backward("gcs_subm_backward_engine", route_f32(engine), rulebook, n, kvol, dups, features, cin, weight, cout, dout, dx, dw,
                        db, workspace, workspace_bytes, hip_stream);
 }
 
@@ -992,53 +1042,20 @@ int gcs_subm_engine_workspace_bytes(int32_t engine, int64_t n, int32_t cin, int3
     return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_engine_workspace_bytes: null output");
   const EnginePlan e = engine_plan_of(engine, n, cin, cout, kvol);
   *forward_bytes = forward_ws_bytes(e, n, cout);
-  *backward_bytes = carve_bwd(nullptr, n, cin, cout, kvol, dups, e.dx_slices).bytes;
-  return 0;
-}
-
-static int check_segment(const char* who, const void* a, const void* b, const int64_t* indptr, int64_t m, int64_t f,
-                         int64_t s, int32_t reduce, const int64_t* arg, bool arg_read) {
-  if (m < 0 || f < 1 || s < 0 || f > (int64_t)INT32_MAX)
-    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": sizes out of range");
-  if (reduce < GCS_SUM || reduce > GCS_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown reduce");
-  const bool needs_arg = reduce == GCS_MIN || reduce == GCS_MAX;
-  if (s > 0 && (!b || !indptr)) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-  if (m > 0 && !a) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-  if (s > 0 && needs_arg && !arg && arg_read)
-    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": min and max need the arg buffer");
-  const int64_t nfb = (f + 63) / 64;
-  if (s * nfb > (int64_t)INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": too many segments");
+  *backward_bytes = carve_bwd<float>(nullptr, e, n, cin, cout, kvol, dups).bytes;
   return 0;
 }
 
 int gcs_segment_csr_forward(const float* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s, int32_t reduce,
                             float* out, int64_t* arg, void* hip_stream) {
-  if (int rc = check_segment("gcs_segment_csr_forward", src, out, indptr, m, f, s, reduce, arg, true)) return rc;
-  if (s == 0) return 0;
-  const int64_t nfb = (f + 63) / 64;
-  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
-  k_seg_fwd<<<(unsigned)(s * nfb), 64, 0, (hipStream_t)hip_stream>>>(src, m, f, indptr, nfb, reduce, out,
-                                                                     minmax ? arg : nullptr);
-  HIP_TRY(hipGetLastError(), "segment_csr forward launch");
-  return 0;
+  return segment_forward("gcs_segment_csr_forward", src, m, f, indptr, s, reduce, out, arg, hip_stream);
 }
-
 int gcs_segment_csr_backward(const float* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
                              int32_t reduce, const int64_t* arg, float* dsrc, void* hip_stream) {
-  if (int rc = check_segment("gcs_segment_csr_backward", dsrc, dout, indptr, m, f, s, reduce, arg, true)) return rc;
-  if (m == 0) return 0;
-  hipStream_t st = (hipStream_t)hip_stream;
-  HIP_TRY(hipMemsetAsync(dsrc, 0, 4 * (size_t)m * f, st), "dsrc clear");
-  if (s > 0) {
-    const int64_t nfb = (f + 63) / 64;
-    k_seg_bwd<<<(unsigned)(s * nfb), 64, 0, st>>>(dout, m, f, indptr, nfb, reduce, arg, dsrc);
-  }
-  HIP_TRY(hipGetLastError(), "segment_csr backward launch");
-  return 0;
+  return segment_backward("gcs_segment_csr_backward", dout, m, f, indptr, s, reduce, arg, dsrc, hip_stream);
 }
 
-
-// ---- the typed entry points: GCS_F32 is the default entry points above, GCS_F16 the binary16 path of gcs_half.h ---------
+// ---- the typed entry points: GCS_F32 is the default entry points above, GCS_F16 the same host paths on half_t ------------
 int gcs_dtypes(void) { return (1 << GCS_F32) | (1 << GCS_F16); }
 
 int gcs_subm_workspace_bytes_t(int32_t dtype, int64_t n, int32_t cin, int32_t cout, int32_t kvol, int32_t dups,
@@ -1046,14 +1063,10 @@ int gcs_subm_workspace_bytes_t(int32_t dtype, int64_t n, int32_t cin, int32_t co
   if (int rc = check_dtype("gcs_subm_workspace_bytes_t", dtype)) return rc;
   if (int rc = check_conv_dims("gcs_subm_workspace_bytes_t", n, kvol, cin, cout)) return rc;
   if (!forward_bytes || !backward_bytes) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_subm_workspace_bytes_t: null output");
-  if (dtype == GCS_F32) {
-    *forward_bytes = 0;
-    *backward_bytes = carve_bwd(nullptr, n, cin, cout, kvol, dups).bytes;
-    return 0;
-  }
-  const EnginePlan e = engine_plan_of(GCS_ENGINE_MFMA, n, cin, cout, kvol);
+  const EnginePlan e = engine_plan_of(dtype == GCS_F32 ? GCS_ENGINE_VALU : GCS_ENGINE_MFMA, n, cin, cout, kvol);
   *forward_bytes = forward_ws_bytes(e, n, cout);
-  *backward_bytes = carve_bwd_h(nullptr, e, n, cin, cout, kvol, dups).bytes;
+  *backward_bytes = dtype == GCS_F32 ? carve_bwd<float>(nullptr, e, n, cin, cout, kvol, dups).bytes
+                                     : carve_bwd<half_t>(nullptr, e, n, cin, cout, kvol, dups).bytes;
   return 0;
 }
 
@@ -1062,10 +1075,10 @@ int gcs_subm_forward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t k
                        size_t workspace_bytes, void* hip_stream) {
   if (int rc = check_dtype("gcs_subm_forward_t", dtype)) return rc;
   if (dtype == GCS_F32)
-    return subm_forward("gcs_subm_forward_t", GCS_ENGINE_VALU, rulebook, n, kvol, (const float*)features, cin,
+    return subm_forward("gcs_subm_forward_t", route_f32(GCS_ENGINE_VALU), rulebook, n, kvol, (const float*)features, cin,
                         (const float*)weight, (const float*)bias, cout, (float*)out, nullptr, 0, hip_stream);
-  return subm_forward_h("gcs_subm_forward_t", rulebook, n, kvol, (const half_t*)features, cin, (const half_t*)weight,
-                        (const half_t*)bias, cout, (half_t*)out, workspace, workspace_bytes, hip_stream);
+  return subm_forward("gcs_subm_forward_t", kRouteF16, rulebook, n, kvol, (const half_t*)features, cin, (const half_t*)weight,
+                      (const half_t*)bias, cout, (half_t*)out, workspace, workspace_bytes, hip_stream);
 }
 
 int gcs_subm_backward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t kvol, int32_t dups, const void* features,
@@ -1073,12 +1086,12 @@ int gcs_subm_backward_t(int32_t dtype, const void* rulebook, int64_t n, int32_t 
                         void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (int rc = check_dtype("gcs_subm_backward_t", dtype)) return rc;
   if (dtype == GCS_F32)
-    return subm_backward("gcs_subm_backward_t", GCS_ENGINE_VALU, rulebook, n, kvol, dups, (const float*)features, cin,
-                         (const float*)weight, cout, (const float*)dout, (float*)dx, (float*)dw, (float*)db, workspace,
+    return subm_backward("gcs_subm_backward_t", route_f32(GCS_ENGINE_VALU), rulebook, n, kvol, dups, (const float*)features,
+                         cin, (const float*)weight, cout, (const float*)dout, (float*)dx, (float*)dw, (float*)db, workspace,
                          workspace_bytes, hip_stream);
-  return subm_backward_h("gcs_subm_backward_t", rulebook, n, kvol, dups, (const half_t*)features, cin, (const half_t*)weight,
-                         cout, (const half_t*)dout, (half_t*)dx, (half_t*)dw, (half_t*)db, workspace, workspace_bytes,
-                         hip_stream);
+  return subm_backward("gcs_subm_backward_t", kRouteF16, rulebook, n, kvol, dups, (const half_t*)features, cin,
+                       (const half_t*)weight, cout, (const half_t*)dout, (half_t*)dx, (half_t*)dw, (half_t*)db, workspace,
+                       workspace_bytes, hip_stream);
 }
 
 int gcs_segment_csr_forward_t(int32_t dtype, const void* src, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
@@ -1086,15 +1099,8 @@ int gcs_segment_csr_forward_t(int32_t dtype, const void* src, int64_t m, int64_t
   if (int rc = check_dtype("gcs_segment_csr_forward_t", dtype)) return rc;
   if (dtype == GCS_F32)
     return gcs_segment_csr_forward((const float*)src, m, f, indptr, s, reduce, (float*)out, arg, hip_stream);
-  if (int rc = check_half_pointers("gcs_segment_csr_forward_t", {src, out})) return rc;
-  if (int rc = check_segment("gcs_segment_csr_forward_t", src, out, indptr, m, f, s, reduce, arg, true)) return rc;
-  if (s == 0) return 0;
-  const int64_t nfb = (f + 63) / 64;
-  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
-  k_seg_fwd_h<<<(unsigned)(s * nfb), 64, 0, (hipStream_t)hip_stream>>>((const half_t*)src, m, f, indptr, nfb, reduce,
-                                                                       (half_t*)out, minmax ? arg : nullptr);
-  HIP_TRY(hipGetLastError(), "segment_csr forward launch");
-  return 0;
+  return segment_forward("gcs_segment_csr_forward_t", (const half_t*)src, m, f, indptr, s, reduce, (half_t*)out, arg,
+                         hip_stream);
 }
 
 int gcs_segment_csr_backward_t(int32_t dtype, const void* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
@@ -1102,17 +1108,8 @@ int gcs_segment_csr_backward_t(int32_t dtype, const void* dout, int64_t m, int64
   if (int rc = check_dtype("gcs_segment_csr_backward_t", dtype)) return rc;
   if (dtype == GCS_F32)
     return gcs_segment_csr_backward((const float*)dout, m, f, indptr, s, reduce, arg, (float*)dsrc, hip_stream);
-  if (int rc = check_half_pointers("gcs_segment_csr_backward_t", {dout, dsrc})) return rc;
-  if (int rc = check_segment("gcs_segment_csr_backward_t", dsrc, dout, indptr, m, f, s, reduce, arg, true)) return rc;
-  if (m == 0) return 0;
-  hipStream_t st = (hipStream_t)hip_stream;
-  HIP_TRY(hipMemsetAsync(dsrc, 0, 2 * (size_t)m * f, st), "dsrc clear");
-  if (s > 0) {
-    const int64_t nfb = (f + 63) / 64;
-    k_seg_bwd_h<<<(unsigned)(s * nfb), 64, 0, st>>>((const half_t*)dout, m, f, indptr, nfb, reduce, arg, (half_t*)dsrc);
-  }
-  HIP_TRY(hipGetLastError(), "segment_csr backward launch");
-  return 0;
+  return segment_backward("gcs_segment_csr_backward_t", (const half_t*)dout, m, f, indptr, s, reduce, arg, (half_t*)dsrc,
+                          hip_stream);
 }
 
 }  // extern "C"

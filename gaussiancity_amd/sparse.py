@@ -92,8 +92,19 @@ def _half_workspace_bytes(n, cin, cout, kvol, dups):
 
 
 @functools.lru_cache(maxsize=256)
-def _engine_workspace_bytes(engine, n, cin, cout, kvol, dups):
-    return S.subm_engine_workspace_bytes(engine, n, cin, cout, kvol, dups)
+def _mfma_workspace_bytes(n, cin, cout, kvol, dups):
+    return S.subm_engine_workspace_bytes(S.ENGINE_MFMA, n, cin, cout, kvol, dups)
+
+
+def _valu_workspace_bytes(n, cin, cout, kvol, dups):
+    return 0, S.lib().gcs_subm_backward_workspace_bytes(n, cin, cout, kvol, dups)
+
+
+# The routes of SubMConvFunction, by the suffix of their `_STATS` keys: the suffix of gcs_subm_forward / gcs_subm_backward,
+# the leading engine / dtype argument of those entry points, the workspace query -> (forward bytes, backward bytes).
+_ROUTES = {"valu": ("", (), _valu_workspace_bytes),
+           "mfma": ("_engine", (S.ENGINE_MFMA,), _mfma_workspace_bytes),
+           "half": ("_t", (S.DTYPE_F16,), _half_workspace_bytes)}
 
 
 def _triple(v, name):
@@ -193,27 +204,18 @@ class SubMConvFunction(torch.autograd.Function):
         out = x.new_empty((n, cout))
         # read once: the backward of this call runs the same engine, whatever is set by then; float16 has one engine
         engine = "half" if x.dtype == torch.float16 else _ENGINE
+        suffix, lead, workspace_bytes = _ROUTES[engine]
+        name = "gcs_subm_forward" + suffix
+        ws_args = ()  # the plain forward takes no workspace
+        if lead:
+            ws_bytes = workspace_bytes(n, cin, cout, rb.kvol, rb.dups)[0]
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+            ws_args = (ws.data_ptr() if ws is not None else None, ws_bytes)
         b_ptr = bias.contiguous().data_ptr() if bias is not None else None
         with torch.cuda.device(x.device):
-            if engine == "half":
-                ws_bytes = _half_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)[0]
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-                S.check(S.lib().gcs_subm_forward_t(S.DTYPE_F16, rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None,
-                                                   cin, w.data_ptr(), b_ptr, cout, out.data_ptr() if n else None,
-                                                   ws.data_ptr() if ws is not None else None, ws_bytes, _stream()),
-                        "gcs_subm_forward_t")
-            elif engine == "valu":
-                S.check(S.lib().gcs_subm_forward(rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None, cin,
-                                                 w.data_ptr(), b_ptr, cout, out.data_ptr() if n else None, _stream()),
-                        "gcs_subm_forward")
-            else:
-                ws_bytes = _engine_workspace_bytes(S.ENGINES[engine], n, cin, cout, rb.kvol, rb.dups)[0]
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-                S.check(S.lib().gcs_subm_forward_engine(S.ENGINES[engine], rb.buf.data_ptr(), n, rb.kvol,
-                                                        x.data_ptr() if n else None, cin, w.data_ptr(), b_ptr, cout,
-                                                        out.data_ptr() if n else None,
-                                                        ws.data_ptr() if ws is not None else None, ws_bytes, _stream()),
-                        "gcs_subm_forward_engine")
+            S.check(getattr(S.lib(), name)(*lead, rb.buf.data_ptr(), n, rb.kvol, x.data_ptr() if n else None, cin,
+                                           w.data_ptr(), b_ptr, cout, out.data_ptr() if n else None, *ws_args, _stream()),
+                    name)
         _STATS["conv_forward_calls_" + engine] += 1
         ctx.save_for_backward(x, w)
         ctx.rb = rb
@@ -231,29 +233,14 @@ class SubMConvFunction(torch.autograd.Function):
         dx = x.new_empty(x.shape) if want_x else None
         dw = w.new_empty(w.shape) if want_w else None
         db = w.new_empty((cout,)) if want_b else None
-        L = S.lib()
         ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
-        if ctx.engine == "half":
-            ws_bytes = _half_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)[1]
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-            with torch.cuda.device(x.device):
-                S.check(L.gcs_subm_backward_t(S.DTYPE_F16, rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x), cin, w.data_ptr(),
-                                              cout, ptr(dy), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(), ws_bytes, _stream()),
-                        "gcs_subm_backward_t")
-        elif ctx.engine == "valu":
-            ws_bytes = L.gcs_subm_backward_workspace_bytes(n, cin, cout, rb.kvol, rb.dups)
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-            with torch.cuda.device(x.device):
-                S.check(L.gcs_subm_backward(rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x), cin, w.data_ptr(), cout,
-                                            ptr(dy), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(), ws_bytes, _stream()),
-                        "gcs_subm_backward")
-        else:
-            ws_bytes = _engine_workspace_bytes(S.ENGINES[ctx.engine], n, cin, cout, rb.kvol, rb.dups)[1]
-            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-            with torch.cuda.device(x.device):
-                S.check(L.gcs_subm_backward_engine(S.ENGINES[ctx.engine], rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x),
-                                                   cin, w.data_ptr(), cout, ptr(dy), ptr(dx), ptr(dw), ptr(db),
-                                                   ws.data_ptr(), ws_bytes, _stream()), "gcs_subm_backward_engine")
+        suffix, lead, workspace_bytes = _ROUTES[ctx.engine]
+        name = "gcs_subm_backward" + suffix
+        ws_bytes = workspace_bytes(n, cin, cout, rb.kvol, rb.dups)[1]
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            S.check(getattr(S.lib(), name)(*lead, rb.buf.data_ptr(), n, rb.kvol, rb.dups, ptr(x), cin, w.data_ptr(), cout,
+                                           ptr(dy), ptr(dx), ptr(dw), ptr(db), ws.data_ptr(), ws_bytes, _stream()), name)
         if want_w:
             _STATS["conv_dw_calls_" + ctx.engine] += 1
         return dx, dw, db, None

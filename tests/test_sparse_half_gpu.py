@@ -1,4 +1,4 @@
-"""-m gpu: the float16 path of libgcs_hip.so (GCS_F16 of the `_t` entry points, gaussiancity_amd/csrc/gcs_half.h, DESIGN.md
+"""-m gpu: the float16 path of libgcs_hip.so (GCS_F16 of the `_t` entry points, gaussiancity_amd/csrc/gcs_mfma.h, DESIGN.md
 section 15): the convolution's three products on v_mfma_f32_16x16x16_f16, the binary16 fold / dB / slice sums, binary16
 segment_csr, and the autocast rule of SubMConv3d.  As in test_sparse_engine_gpu.py every test first ASSERTS the plan of its
 shape -- the float16 convolution launches under gcs_subm_engine_plan(GCS_ENGINE_MFMA, ...) and has no chooser of its own.
