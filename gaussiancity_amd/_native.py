@@ -89,6 +89,7 @@ class FrameInfo(C.Structure):
 
 
 ABI_VERSION = 9
+BACKWARD_IMAGE_ONLY = 2  # gcr_camera.backward: an inference frame whose per-pixel state is not written either (include/gcr.h)
 TICKET_WORDS = 8  # 64-bit pinned host words per asynchronous frame (include/gcr.h, gcr_forward_async)
 RESIZE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 

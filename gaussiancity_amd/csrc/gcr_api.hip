@@ -371,6 +371,7 @@ GcrBlendArgs blend_args(const FrameSetup& f, const gcr_camera* cam, const uint32
   b.flip_x = cam->flip_x != 0; b.flip_y = cam->flip_y != 0;
   b.win_x = cam->win_x; b.win_y = cam->win_y; b.win_w = cam->win_w; b.win_h = cam->win_h;
   b.out_u8 = cam->out_u8 != 0 && cam->backward != 1;
+  b.image_only = cam->backward == GCR_BACKWARD_IMAGE_ONLY;
   fill_cam(b.cam, cam);
   b.final_T = f.final_T;
   b.n_contrib = f.n_contrib;
@@ -831,8 +832,8 @@ class RescueService {
       }
       hipStream_t s = streams_[d];
       gcr_camera cam = f.cam;
-      cam.backward = 0;  // the temporary buffer dies with the rescue: no backward state (gcr_forward_render with
-      //                    out_color == NULL rebuilds it in a buffer of the caller's when a backward follows)
+      if (cam.backward == 1) cam.backward = 0;  // the temporary buffer dies with the rescue: no backward state (gcr_forward_render
+      //                    with out_color == NULL rebuilds it in a buffer of the caller's when a backward follows)
       cam.options = f.has_opt ? &f.opt : nullptr;
       if (cam.host_camera) {
         cam.view_matrix = f.camvals;

@@ -50,12 +50,12 @@ __global__ __launch_bounds__(256) void k_emit(int P, const uint32_t* __restrict_
 // scatter as slow as the radix sort it was meant to replace.  So slots are claimed in LDS:
 //   A'  k_tile_table<false>: K1's per-block survivor lists are grouped into NG <= 512 groups;
 //       workgroup g counts its instances per tile in an LDS table (ds_add) and stores the row
-//       to table[g][0..T).
-//   B'  k_table_colscan: exclusive prefix down every tile column (base[g][t] = instances of
-//       tile t owned by groups < g), the tile totals, their prefix inside each 64-tile block and
+//       to table[row(g)][0..T), row = gcr_tt_row (gcr_tt_row.h): the groups that share an L2 in consecutive rows.
+//   B'  k_table_colscan: exclusive prefix down every tile column (base[r][t] = instances of
+//       tile t owned by the rows in front of r), the tile totals, their prefix inside each 64-tile block and
 //       the block totals; R and the longest list are accumulated into the frame summary.
 //   C'  k_tile_table<true>: every workgroup rebuilds the tile starts from the block totals
-//       (a <= 640-element scan), writes its slice of `ranges`, loads start + base[g][t] into LDS cursors and
+//       (a <= 640-element scan), writes its slice of `ranges`, loads start + base[row(g)][t] into LDS cursors and
 //       claims slots with LDS returning atomics; the (depth<<32|index) key goes straight to its
 //       final tile segment.
 //   D'  k_tile_sort: bitonic sort of every tile segment in LDS.
@@ -68,6 +68,9 @@ constexpr int RANK_MERGE_MAX = 1024;  // chunked rank sort + merge below, bitoni
 // groups (gcr_tile_table_groups: fewer, fatter groups = fewer table rows through HBM; rounds 1-2 ran 512 groups of 512
 // threads while two tables fit a CU's LDS).  At 4K a table (130 KiB) only leaves room for one workgroup per CU anyway;
 // the scatter there is bound by its 8-byte stores landing in 32-byte sectors, not by occupancy.
+// Row order (round 7): with the rows XCD class by XCD class the C3 scatter writes 17.2 MB instead of 37.3 MB for its 9.4 MB
+// of keys and takes 19.3 instead of 23.8 us alone (profiles/r07_traffic.json, r07_kernel_trace_stats_one_stream*.txt); at
+// C5 the band sort has made a group's keys neighbours already and the row order changes nothing (173.2 against 173.6 MB).
 constexpr int TT_MAX_TBLOCKS = 640;  // 64-tile blocks: T <= 40960 > the LDS limit of 148 KiB / 4 B
 
 // The K1 blocks' survivor lists laid end to end: pre[k] = survivors of blocks < k, pre[nblocks] = all of them.
@@ -148,7 +151,14 @@ __global__ __launch_bounds__(TT_THREADS) void k_tile_table(int T, int gx, int G,
   __shared__ uint32_t blk_base[TT_MAX_TBLOCKS];           // first instance of every 64-tile block
   __shared__ uint32_t wtot[TT_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  uint32_t* __restrict__ row = table + (size_t)blockIdx.x * T;
+  // The workgroup's table row: XCD class by XCD class (gcr_tt_row.h), so that what one L2 writes of a tile segment is one
+  // run of `pairs`.  Both instantiations take the same row; the column scan and the layout know nothing of it.
+#ifdef GCR_EXPERIMENTS  // GCR_TT_ROWS_NUMERIC=1 (A/B): row = workgroup, as until round 6 (handed over as G < 0)
+  const uint32_t my_row = G < 0 ? blockIdx.x : gcr_tt_row(blockIdx.x, gridDim.x);
+#else
+  const uint32_t my_row = gcr_tt_row(blockIdx.x, gridDim.x);
+#endif
+  uint32_t* __restrict__ row = table + (size_t)my_row * T;
   TtPrefix<TT_THREADS> blocks;
   blocks.load(vis_count, nblocks_k1, tid);
   if (!SCATTER) {
@@ -802,6 +812,13 @@ static hipError_t tile_table_attr() {
   return done;
 }
 static inline bool tile_table_wide(int) { return true; }  // (the 512-thread instantiations remain for A/B builds)
+static inline int tile_table_G(int G) {
+#ifdef GCR_EXPERIMENTS
+  static const bool numeric = getenv("GCR_TT_ROWS_NUMERIC") != nullptr && atoi(getenv("GCR_TT_ROWS_NUMERIC")) != 0;
+  if (numeric) return -1;
+#endif
+  return G;
+}
 
 hipError_t gcr_launch_tile_count(int T, int gx, int NG, int G, int nblocks_k1, int chunk, const uint4* vis_rec,
                                  const uint32_t* vis_count, uint32_t* table,
@@ -821,11 +838,11 @@ hipError_t gcr_launch_tile_count(int T, int gx, int NG, int G, int nblocks_k1, i
   }
   if (tile_table_wide(T))
     k_tile_table<false, 1024><<<NG, 1024, (size_t)T * sizeof(uint32_t), s>>>(
-        T, gx, G, nblocks_k1, chunk, vis_rec, vis_count, table, nullptr, nullptr, nullptr, nullptr, nullptr,
+        T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, nullptr, nullptr, nullptr, nullptr, nullptr,
         frame, 0ull, 0ull, host_R, seq, block_tiles, banded, banded_capacity);
   else
     k_tile_table<false, 512><<<NG, 512, (size_t)T * sizeof(uint32_t), s>>>(
-        T, gx, G, nblocks_k1, chunk, vis_rec, vis_count, table, nullptr, nullptr, nullptr, nullptr, nullptr,
+        T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, nullptr, nullptr, nullptr, nullptr, nullptr,
         frame, 0ull, 0ull, host_R, seq, block_tiles, banded, banded_capacity);
   k_table_colscan<<<(T + 63) / 64, 1024, 0, s>>>(table, NG, T, tile_total, tile_local, blk_total, frame);
   return hipGetLastError();
@@ -842,11 +859,11 @@ hipError_t gcr_launch_tile_scatter(int T, int gx, int NG, int G, int nblocks_k1,
   if (e != hipSuccess) return e;
   if (tile_table_wide(T))
     k_tile_table<true, 1024><<<NG, 1024, (size_t)T * sizeof(uint32_t), s>>>(
-        T, gx, G, nblocks_k1, chunk, vis_rec, vis_count, table, tile_total, tile_local, blk_total, ranges, pairs,
+        T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, tile_total, tile_local, blk_total, ranges, pairs,
         frame, cap_instances, cap_list, host_longest, 0u, nullptr, banded, banded_capacity);
   else
     k_tile_table<true, 512><<<NG, 512, (size_t)T * sizeof(uint32_t), s>>>(
-        T, gx, G, nblocks_k1, chunk, vis_rec, vis_count, table, tile_total, tile_local, blk_total, ranges, pairs,
+        T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, tile_total, tile_local, blk_total, ranges, pairs,
         frame, cap_instances, cap_list, host_longest, 0u, nullptr, banded, banded_capacity);
   return hipGetLastError();
 }

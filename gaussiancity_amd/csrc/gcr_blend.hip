@@ -286,8 +286,15 @@ __device__ __noinline__ void k6_frame_gate(unsigned long long* words, unsigned i
 // STATE (template): the backward's per-piece state -- checkpoints at the piece boundaries, work items, the block mask
 // of every staged entry -- is written only by frames rendered with gcr_camera.backward == 1.  Every other frame (the
 // headline inference workload) runs the instantiation without a single instruction of it; gcr_backward on such a
-// frame regenerates the state with one more pass of this kernel (a.out_color == nullptr: no pixel is stored).
-template <bool SORT, bool STATE>
+// frame regenerates the state with one more pass of this kernel (a.out_color == nullptr: no colour is stored).
+//
+// PIXSTATE (template; false only with STATE = false): the per-pixel state final_T / n_contrib is stored.  An image-only
+// frame (gcr_camera.backward == GCR_BACKWARD_IMAGE_ONLY: nobody will ever read the frame's buffers, a.image_only) runs
+// the instantiation without it -- no last-contributor select in the step (two v_cndmask_b32 and two v_mov_b32 of a
+// two-entry trip's 80 VALU instructions), no 8 bytes per pixel of stores; the step is otherwise the same instruction for
+// instruction.  The state-only pass stores the two arrays itself (it computes them anyway), so a backward after an
+// image-only frame reads what that pass wrote.
+template <bool SORT, bool STATE, bool PIXSTATE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_blend_fwd(const GcrBlendArgs a) {
   __shared__ StagedEntry sE[K6_SENT_SLOT + 1];
   __shared__ uint32_t sMask[CHUNK];
@@ -417,7 +424,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         D1 = __builtin_fmaf(QB.w * wgt, Tw, D1);                                             \
         D2 = __builtin_fmaf(QC.x * wgt, Tw, D2);                                             \
       }                                                                                      \
-      last_off = (keep && valid) ? (OFF) : last_off;                                         \
+      if (PIXSTATE) last_off = (keep && valid) ? (OFF) : last_off;                           \
       Tw = keep ? test_T : -__builtin_fabsf(Tw);                                             \
     }                                                                                        \
   }
@@ -574,7 +581,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 #ifdef GCR_EXPERIMENTS
     if (a.clock_buf != nullptr && tid == 0 && base == 0) a.clock_buf[(size_t)tile * 16 + 6] = __builtin_readcyclecounter();
 #endif
-    if (last_off != NO_ENTRY) last_contributor = (uint32_t)base + slot_of_offset(last_off) + 1u;
+    if (PIXSTATE && last_off != NO_ENTRY) last_contributor = (uint32_t)base + slot_of_offset(last_off) + 1u;
   }
   }
 #undef GCR_BLEND_STEP
@@ -582,7 +589,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   int tid_end = threadIdx.x;
   asm volatile("" : "+v"(tid_end));
   const LaneGeom6 g = lane_geom6(tid_end, tx, ty);
-  if (g.pxi < a.W && g.pyi < a.H && (!STATE || a.out_color != nullptr)) {  // (state-only pass: pixels already stored)
+  static_assert(PIXSTATE || !STATE, "the backward reads final_T / n_contrib");
+  if (g.pxi < a.W && g.pyi < a.H) {
     const float Tout = __builtin_fabsf(Tw);
     const size_t pix_id = (size_t)a.W * g.pyi + g.pxi;
     // a.nt_out (block-uniform; round 6): an inference frame's per-pixel outputs are not read again on the device -- stored
@@ -590,19 +598,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // for every frame's num_rendered (one frame alone 0.262 -> 0.253 ms with it); beside two other frames' kernels it
     // buys nothing (profiles/r06_cache_policy_ab.jsonl), and a training frame's backward reads all of it.
     const bool nt_out = !STATE && a.nt_out != 0;
-    if (nt_out) {
+    if (!PIXSTATE) {
+      // image-only frame: nobody reads the per-pixel state
+    } else if (nt_out) {
       __builtin_nontemporal_store(Tout, a.final_T + pix_id);
       __builtin_nontemporal_store(last_contributor, a.n_contrib + pix_id);
     } else {
+      // (the state-only pass too: the frame it re-renders may have been an image-only one -- the same bits otherwise)
       a.final_T[pix_id] = Tout;
       a.n_contrib[pix_id] = last_contributor;
     }
     // the image may be stored mirrored (the wrapper's flip_lr / flip_ud without a copy kernel) and / or as a window of
     // the frame (the helpers' crop without slice kernels); the per-pixel state is neither
-    size_t oplane;
+    size_t oplane = 0;
     int px_op = g.pxi, py_op = g.pyi;  // opaque copies: the index arithmetic below must not be hoisted above the walk
     asm volatile("" : "+v"(px_op), "+v"(py_op));
-    const long long out_id = gcr_out_index(a, px_op, py_op, &oplane);
+    const long long out_id = (!STATE || a.out_color != nullptr) ? gcr_out_index(a, px_op, py_op, &oplane) : -1;  // (state-only pass: no colour)
     if (out_id >= 0) {
       const float c0 = C0 + Tout * GCR_CAM(a, bg, a.bg, 0);
       const float c1 = C1 + Tout * GCR_CAM(a, bg, a.bg, 1);
@@ -1303,9 +1314,11 @@ static void launch_blend_fwd_state(const GcrBlendArgs& a, int T, hipStream_t s) 
   if (const char* e = getenv("GCR_K6_LDS_PAD")) pad = (size_t)atoll(e);
 #endif
   if (a.work != nullptr)  // the backward's state is wanted (gcr_camera.backward == 1, or gcr_backward's regeneration pass)
-    k_blend_fwd<SORT, true><<<T, 256, pad, s>>>(a);
+    k_blend_fwd<SORT, true, true><<<T, 256, pad, s>>>(a);
+  else if (!SORT && a.image_only)  // (under "sort_in_blend" an image-only frame runs the kernel of every inference frame)
+    k_blend_fwd<false, false, false><<<T, 256, pad, s>>>(a);
   else
-    k_blend_fwd<SORT, false><<<T, 256, pad, s>>>(a);
+    k_blend_fwd<SORT, false, true><<<T, 256, pad, s>>>(a);
 }
 
 hipError_t gcr_launch_blend_fwd(const GcrBlendArgs& a, bool sort_in_kernel, hipStream_t s) {

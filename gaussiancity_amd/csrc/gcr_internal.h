@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/gcr.h"
+#include "gcr_tt_row.h"
 
 // One Gaussian's projected state, written by K1 and gathered by K3/K6/K7/K8.  ONE 64-byte block, four 16-byte quads:
 //   q0 = (x, y, conic.x, conic.y)   q1 = (conic.z, opacity, r, g)
@@ -238,6 +239,7 @@ struct GcrBlendArgs {
   int flip_x, flip_y;       // fwd: out_color stored mirrored; bwd: dL_dpix loaded mirrored (gcr_camera.flip_x / flip_y)
   int out_u8;               // fwd: out_color is uint8 [H,W,3] video frames (gcr_camera.out_u8)
   int nt_out;               // fwd, frames without backward state: final_T / n_contrib / float image stored with the non-temporal policy
+  int image_only;           // fwd, frames without backward state: final_T / n_contrib are not stored at all (GCR_BACKWARD_IMAGE_ONLY)
   GcrCamVals cam;           // bg by value when cam.by_value
   int debug_flags;  // experiment builds only (GCR_EXPERIMENTS, "k7_skip_flush"): bit 0 = K7 drops its global atomics
   // pieces / checkpoints (above)

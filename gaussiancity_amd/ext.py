@@ -269,7 +269,8 @@ def _camera(device, bg, view, proj, campos, tan_fovx, tan_fovy, H, W, scale_modi
     cam.host_camera = int(on_host)
     cam.flip_x = int(bool(flip_x))
     cam.flip_y = int(bool(flip_y))
-    cam.backward = int(bool(for_backward))
+    # (N.BACKWARD_IMAGE_ONLY: an inference frame whose buffers nobody will read -- _rasterize's _IMAGE frames)
+    cam.backward = N.BACKWARD_IMAGE_ONLY if for_backward == N.BACKWARD_IMAGE_ONLY else int(bool(for_backward))
     cam.out_u8 = int(bool(out_u8))
     opt = _current_options()
     if opt is not None:
@@ -506,10 +507,13 @@ def _rasterize(mode, for_backward, background, means3D, colors, opacity, scales,
     H, W = int(image_height), int(image_width)
     if P == 0:
         return _empty_frame(device, H, W, mode)
+    # an _IMAGE frame's geometry, image and binning state never leave the call: the library need not write the per-pixel
+    # state either (gcr_camera.backward = GCR_BACKWARD_IMAGE_ONLY).  _INT and _TICKET frames hand their buffers out.
+    state = N.BACKWARD_IMAGE_ONLY if (mode == _IMAGE and not for_backward) else bool(for_backward)
     with _on_device(device):
         if _cull.enabled() and not for_backward:  # a static scene's cull cache: same bits, fewer bytes (cull_cache.py)
             cam, keep_c = _camera(device, background, viewmatrix, projmatrix, campos, tan_fovx,
-                                  tan_fovy, H, W, scale_modifier, degree, prefiltered, debug, for_backward)
+                                  tan_fovy, H, W, scale_modifier, degree, prefiltered, debug, state)
             g, keep_g = _gaussians(device, P, means3D, opacity, sh, colors, scales, rotations,
                                    cov3D_precomp)
             keep = (keep_c, keep_g, _cull.attach(g, scale_modifier, (means3D, scales, rotations, cov3D_precomp, opacity),
@@ -517,7 +521,7 @@ def _rasterize(mode, for_backward, background, means3D, colors, opacity, scales,
         else:
             cam, g, keep = _records(device, P, H, W, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                                     cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, sh, degree, campos,
-                                    bool(prefiltered), bool(debug), bool(for_backward), _current_options())
+                                    bool(prefiltered), bool(debug), state, _current_options())
         out = _forward(L, device, cam, g, P, H, W, mode)
         del keep
     return out

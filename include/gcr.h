@@ -119,7 +119,17 @@ typedef struct gcr_camera {
                           backward it never runs) and the binning buffer may be the smaller gcr_binning_bytes_lean().
                           gcr_backward needs a frame rendered with 1: on a frame rendered with 0 the gradients of every
                           rendered Gaussian come out as NaN (never as plausible zeros) -- render its state first with
-                          gcr_forward_render(out_color = NULL, backward = 1) into a gcr_binning_bytes() buffer */
+                          gcr_forward_render(out_color = NULL, backward = 1) into a gcr_binning_bytes() buffer.
+                          GCR_BACKWARD_IMAGE_ONLY (2) = an inference frame of which only out_color and radii will ever be
+                          read: everything 0 says holds (lean binning buffer, out_u8 allowed, no backward state), and the
+                          per-pixel state final_T / n_contrib (gcr_layout.img_final_T / img_n_contrib) is NOT WRITTEN
+                          either -- the forward blend neither tracks a pixel's last contributor nor stores the two arrays;
+                          the image is the same bits.  The state-only pass above stores final_T / n_contrib itself (for
+                          every frame: the same bits where they were there already), so a backward after it works on an
+                          image-only frame as on a frame rendered with 0; gcr_backward directly on an image-only frame
+                          gives the same NaN gradients.  Under option "sort_in_blend" an image-only frame is rendered
+                          by the kernel of a frame with 0 and its per-pixel state is written after all: do not rely on
+                          either.  Any other value: as 0 */
   const gcr_options *options; /* HOST pointer or NULL (= all defaults); read during the call only */
   int32_t out_u8;      /* !=0 (forward of an inference frame only, backward == 0): out_color is NOT float [3,H,W] but the
                           video frame the reference's render loop makes of it with five elementwise kernels
@@ -127,6 +137,7 @@ typedef struct gcr_camera {
                           uint8 [H,W,3] (or [win_h,win_w,3]), value = (uint8)(((clamp(c, -1, 1) / 2 + 0.5) * 255)) in
                           float32 arithmetic, the same roundings in the same order -- the same bytes */
 } gcr_camera;
+#define GCR_BACKWARD_IMAGE_ONLY 2 /* gcr_camera.backward (no struct changed size: the ABI number stays) */
 
 /* Per-Gaussian inputs (argument list of cr/rasterizer.h:25-37) */
 typedef struct gcr_gaussians {
@@ -350,7 +361,9 @@ long gcr_rescue_dropped_count(void); /* ... and calls for help that were not ans
  * the reference's stable radix sort by tile|depth) + K5 (tile ranges) + K6 (blend).
  * out_color is [3,H,W].  *info must be what gcr_forward_preprocess returned.
  * out_color == NULL (ABI v6): state only -- binning, sort and the forward blend's walk with cam->backward == 1, no
- * pixel is stored: what gcr_backward needs after an asynchronous frame overflowed its binning buffer. */
+ * colour is stored: what gcr_backward needs after an asynchronous frame overflowed its binning buffer, or after a frame
+ * rendered with cam->backward == 0 or GCR_BACKWARD_IMAGE_ONLY.  The pass writes the per-pixel state final_T / n_contrib
+ * too (an image-only frame never did; for every other frame they are the bits that were there). */
 int gcr_forward_render(const gcr_camera *cam, const gcr_gaussians *g, void *geom,
                        size_t geom_bytes, void *binning, size_t binning_bytes, void *img,
                        size_t img_bytes, const gcr_frame_info *info, float *out_color,
