@@ -8,14 +8,22 @@ import ctypes as C
 
 from . import _loader
 
-STAGE_NAMES = ("extrude_count", "extrude_emit", "volume_clear", "volume_scatter", "occupancy", "traversal")
-ABI_VERSION = 4
+STAGE_NAMES = ("extrude_count", "extrude_emit", "volume_clear", "volume_scatter", "occupancy", "traversal",
+               "visible_count", "visible_emit")
+ABI_VERSION = 5
 
 
 class SegIns(C.Structure):
     """gcv_seg_ins == segInsMap (footprint_extruder.cpp:90-100,201)."""
     _fields_ = [(n, C.c_int16) for n in ("bldg_ins_min_id", "car_ins_min_id", "car_semantic_id",
                                          "bldg_facade_semantic_id", "roof_ins_offset")]
+
+
+class ClassRule(C.Structure):
+    """gcv_class_rule: instance id -> class and z-scale (scripts/inference.py:544-598, utils/helpers.py:212-222)."""
+    _fields_ = [(n, C.c_int32) for n in ("bldg_ins_min", "bldg_ins_max", "car_ins_min", "facade_class", "roof_class",
+                                         "car_class")] + [("special_z_classes", C.c_uint32),
+                                                          ("point_scale_factor", C.c_float)]
 
 
 _vp, _i32, _i64, _sz, _f32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_int
@@ -36,6 +44,10 @@ _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argt
     "gcv_rows_erase_volume": (_int, [_i64, _vp, _pi32, _i32, _i32, _i32, _vp, _vp]),
     "gcv_ray_voxel_intersection": (_int, [_vp, _pi32, C.POINTER(_i64), _vp, _pf32, _pf32, _pf32, _f32, _pf32, _pi32, _i32,
                                           _vp, _vp, _vp, _vp]),
+    "gcv_visible_workspace_bytes": (_sz, [_i64, _i64]),
+    "gcv_visible_count": (_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _sz, C.POINTER(_i64), _vp]),
+    "gcv_visible_emit": (_int, [_vp, _i64, _vp, _i64, _vp, _i32, C.POINTER(ClassRule), _vp, _sz, _i64, _i64,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gcv_set_option": (_int, [C.c_char_p, _int]),
     "gcv_get_stage_ms": (_int, [_pf32, _int]),
 }

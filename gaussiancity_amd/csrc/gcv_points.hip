@@ -1,5 +1,5 @@
 // gcv_points.hip -- MI355X (gfx950) kernels + C ABI (include/gcv.h) of the point-generation /
-// visibility path: footprint extruder (K15), points -> volume (K14), ray/voxel traversal (K12).
+// visibility path: footprint extruder (K15), points -> volume (K14), ray/voxel traversal (K12), visible point set (K16).
 // Reference behaviour: extensions/footprint_extruder/footprint_extruder.cpp ("fe/"),
 // extensions/voxlib/{points_to_volume,ray_voxel_intersection}.cu, voxlib_common.h ("vox/").
 //
@@ -27,7 +27,7 @@ std::atomic<int> g_timing{0};
 std::atomic<int> g_entry_jump{1};  // option "entry_jump": closed-form walk from the camera to the grid (A/B knob)
 
 // ---- stage timers (non-blocking; resolved lazily) ---------------------------------------------
-enum Stage { ST_COUNT = 0, ST_EMIT, ST_CLEAR, ST_SCATTER, ST_OCC, ST_TRAVERSE, ST_N };
+enum Stage { ST_COUNT = 0, ST_EMIT, ST_CLEAR, ST_SCATTER, ST_OCC, ST_TRAVERSE, ST_VIS_COUNT, ST_VIS_EMIT, ST_N };
 StageSlot g_slots[ST_N];  // process-wide: the stages of every thread (gc_host.h)
 StageSlot* stage_slot(int stage) { return g_timing.load() ? &g_slots[stage] : nullptr; }
 
@@ -734,6 +734,274 @@ __global__ __launch_bounds__(64) void k_rvip(int32_t* __restrict__ out_voxel_id,
   }
 }
 
+// =============================================================================================== K16
+// scripts/inference.py:338-360 and :229-237 (_get_bev_points' np.unique of the first-hit map, _get_normalized_pt_cords'
+// loop over instances, _instances_to_classes, get_point_scales) for rows and a map that never leave the device.
+//   mark   one thread per pixel: an atomic OR sets the point's bit in a bitmap over the N points (neighbouring pixels
+//          mostly see the same point, so a lane whose left neighbour holds the same value leaves the bit to it);
+//   count  one block per 32 768 points (256 threads x one 16-byte load of four bitmap words): popcounts -> block sum;
+//          every set bit reads its row's instance and sets that id's bit in a 65 536-bit presence table (first in LDS,
+//          then one OR per non-zero word), and counts the instances the centers table does not know;
+//   scan   one 1024-thread block: block sums -> block offsets and M; presence words -> rank of each word's first id and K;
+//   emit   the count kernel's blocks again: a set bit's output slot = block offset + popcounts in front of it, which is
+//          np.unique's ascending order without a sort; the 10-byte row is read once and every per-point output
+//          written from it; the rank of its instance = rank of the presence word + popcount of the bits below.
+// Visible points are neighbours in the row order, so a few threads' words hold most of a block's set bits.  The emit
+// kernel, with a dozen loads and stores per point, therefore hands the block's set bits out round-robin
+// (vis_block_points: slot t goes to thread t % 256, which finds the owning thread's words by a search over the block's
+// prefix sums in LDS), which took a third off its time at the city shape.  The count kernel does one 2-byte load and
+// one table test per point and measured faster with each thread walking its own four words than handed out.
+// Integer work except the relative coordinates, which are binary64 in upstream's expression order (IEEE division,
+// no contraction) rounded once to binary32.  No float atomics; the only order-free operations are the bit ORs.
+constexpr int VS_BLOCK = 256;
+constexpr int VS_CHUNK_WORDS = 4 * VS_BLOCK;  // bitmap words per block (one uint4 per thread) = 32 768 points
+constexpr int VS_INS_WORDS = 2048;            // presence table: one bit per int16 value, bit index = instance + 32768
+enum { VS_HEAD_M = 0, VS_HEAD_K, VS_HEAD_UNKNOWN, VS_HEAD_BAD, VS_HEAD_WORDS = 8 };
+
+// workspace: [head u64 x 8][presence u32 x 2048][bitmap, a whole number of uint4] -- cleared by every count --
+// then [rank u32 x 2048][block sums / offsets u32 x n_blocks]
+struct VisLayout {
+  size_t presence, bitmap, rank, sums, total;
+  long long n_words;  // bitmap words, a multiple of 4
+  int n_blocks;
+};
+VisLayout vis_layout(long long n_points) {
+  VisLayout l;
+  l.n_words = ((n_points + 127) / 128) * 4;
+  l.n_blocks = (int)((l.n_words + VS_CHUNK_WORDS - 1) / VS_CHUNK_WORDS);
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  l.presence = up(sizeof(unsigned long long) * VS_HEAD_WORDS);
+  l.bitmap = l.presence + sizeof(uint32_t) * VS_INS_WORDS;
+  l.rank = up(l.bitmap + sizeof(uint32_t) * (size_t)l.n_words);
+  l.sums = l.rank + sizeof(uint32_t) * VS_INS_WORDS;
+  l.total = up(l.sums + sizeof(uint32_t) * (size_t)(l.n_blocks + 1));
+  return l;
+}
+
+__global__ __launch_bounds__(VS_BLOCK) void k_vis_mark(const long long* __restrict__ vp_map, long long n_pixels,
+                                                       long long n_points, uint32_t* __restrict__ bitmap,
+                                                       unsigned long long* __restrict__ head) {
+  const long long p = (long long)blockIdx.x * VS_BLOCK + threadIdx.x;
+  const long long v = p < n_pixels ? vp_map[p] : -1ll;
+  const long long left = __shfl_up(v, 1, 64);
+  const bool first = (threadIdx.x & 63) == 0 || left != v;
+  if (v >= n_points)
+    atomicAdd(&head[VS_HEAD_BAD], 1ull);  // never used as an index
+  else if (v >= 0 && first)
+    atomicOr(&bitmap[v >> 5], 1u << (v & 31));
+}
+
+__device__ __forceinline__ bool vis_known(int ins, const double* __restrict__ centers, int n_centers) {
+  if (ins < 0 || ins >= n_centers) return false;
+  const double cx = centers[5 * (long long)ins];
+  return cx == cx;
+}
+
+// exclusive scan over NW waves of 64; *total = block sum
+template <int NW>
+__device__ __forceinline__ uint32_t vs_block_excl_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t incl = wave_incl_scan(v, lane);
+  if (lane == 63) lds[w] = incl;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < NW; k++) {
+    const uint32_t s = lds[k];
+    if (k < w) base += s;
+    tot += s;
+  }
+  *total = tot;
+  __syncthreads();
+  return base + incl - v;
+}
+
+__device__ __forceinline__ uint4 vis_load_words(const uint32_t* __restrict__ bitmap, long long n_words, long long w0) {
+  uint4 q = {0u, 0u, 0u, 0u};
+  if (w0 < n_words) q = *reinterpret_cast<const uint4*>(bitmap + w0);  // n_words is a multiple of 4
+  return q;
+}
+
+// Calls f(point index, slot) for every set bit of the block's VS_CHUNK_WORDS bitmap words, slot = its rank among them
+// (ascending), slot t on thread t % VS_BLOCK.  q: this thread's four words; local: exclusive prefix of its popcount;
+// total: the block's popcount.  s_words [VS_CHUNK_WORDS] and s_pre [VS_BLOCK] are LDS.
+template <class F>
+__device__ __forceinline__ void vis_block_points(const uint4 q, uint32_t local, uint32_t total, long long block_word0,
+                                                 uint32_t* s_words, uint32_t* s_pre, F f) {
+  const int tid = threadIdx.x;
+  s_words[4 * tid] = q.x; s_words[4 * tid + 1] = q.y; s_words[4 * tid + 2] = q.z; s_words[4 * tid + 3] = q.w;
+  s_pre[tid] = local;
+  __syncthreads();
+  for (uint32_t t = tid; t < total; t += VS_BLOCK) {
+    int lo = 0, hi = VS_BLOCK - 1;  // owner = the last thread whose prefix is <= t (threads without a bit share a prefix)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (s_pre[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    uint32_t r = t - s_pre[lo];  // the r-th set bit of the owner's four words
+    int wi = 4 * lo;
+    uint32_t w = s_words[wi];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const uint32_t c = (uint32_t)__popc(w);
+      if (r >= c) {
+        r -= c;
+        wi++;
+        w = s_words[wi];
+      }
+    }
+    for (; r; --r) w &= w - 1;
+    f((block_word0 + wi) * 32 + (__ffs((int)w) - 1), t);
+  }
+}
+
+__global__ __launch_bounds__(VS_BLOCK) void k_vis_count(const uint32_t* __restrict__ bitmap, long long n_words,
+                                                        const int16_t* __restrict__ rows,
+                                                        const double* __restrict__ centers, int n_centers,
+                                                        uint32_t* __restrict__ presence, uint32_t* __restrict__ sums,
+                                                        unsigned long long* __restrict__ head) {
+  __shared__ uint32_t pres[VS_INS_WORDS];
+  __shared__ uint32_t lds4[VS_BLOCK / 64];
+  const int tid = threadIdx.x;
+  for (int k = tid; k < VS_INS_WORDS; k += VS_BLOCK) pres[k] = 0u;
+  __syncthreads();
+  const long long w0 = ((long long)blockIdx.x * VS_BLOCK + tid) * 4;
+  const uint4 q = vis_load_words(bitmap, n_words, w0);
+  const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
+  uint32_t cnt = 0, unknown = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    uint32_t w = wd[j];
+    cnt += (uint32_t)__popc(w);
+    while (w) {
+      const int b = __ffs((int)w) - 1;
+      w &= w - 1;
+      const long long i = (w0 + j) * 32 + b;  // < n_points: the mark kernel sets no other bit
+      const int ins = rows[5 * i + 4];
+      const uint32_t u = (uint32_t)(ins + 32768);
+      atomicOr(&pres[u >> 5], 1u << (u & 31));
+      unknown += vis_known(ins, centers, n_centers) ? 0u : 1u;
+    }
+  }
+  uint32_t total;
+  vs_block_excl_scan<VS_BLOCK / 64>(cnt, lds4, &total);  // (its barriers also order the LDS ORs before the flush)
+  if (tid == 0) sums[blockIdx.x] = total;
+  if (unknown) atomicAdd(&head[VS_HEAD_UNKNOWN], (unsigned long long)unknown);
+  if (total == 0u) return;  // block-uniform: nothing to flush
+  for (int k = tid; k < VS_INS_WORDS; k += VS_BLOCK) {
+    const uint32_t w = pres[k];
+    if (w) atomicOr(&presence[k], w);
+  }
+}
+
+// block sums -> exclusive block offsets (in place) and M; presence words -> rank of each word's first id, and K
+__global__ __launch_bounds__(1024) void k_vis_scan(uint32_t* __restrict__ sums, int n_blocks,
+                                                   const uint32_t* __restrict__ presence, uint32_t* __restrict__ rank,
+                                                   unsigned long long* __restrict__ head) {
+  __shared__ uint32_t lds16[16];
+  const int tid = threadIdx.x;
+  const int per = (n_blocks + 1023) / 1024;
+  const int beg = min(n_blocks, tid * per), end = min(n_blocks, beg + per);
+  uint32_t s = 0, total;
+  for (int i = beg; i < end; i++) s += sums[i];
+  uint32_t run = vs_block_excl_scan<16>(s, lds16, &total);
+  for (int i = beg; i < end; i++) {
+    const uint32_t t = sums[i];
+    sums[i] = run;
+    run += t;
+  }
+  if (tid == 0) head[VS_HEAD_M] = total;
+  const uint32_t p0 = presence[2 * tid], p1 = presence[2 * tid + 1];  // VS_INS_WORDS == 2 * 1024
+  const uint32_t c0 = (uint32_t)__popc(p0), c1 = (uint32_t)__popc(p1);
+  const uint32_t r = vs_block_excl_scan<16>(c0 + c1, lds16, &total);
+  rank[2 * tid] = r;
+  rank[2 * tid + 1] = r + c0;
+  if (tid == 0) head[VS_HEAD_K] = total;
+}
+static_assert(VS_INS_WORDS == 2048, "k_vis_scan reads two presence words per thread of its 1024");
+
+__global__ __launch_bounds__(VS_BLOCK) void k_vis_instances(const uint32_t* __restrict__ presence,
+                                                            const uint32_t* __restrict__ rank,
+                                                            int16_t* __restrict__ instances, long long n_instances) {
+  const int k = blockIdx.x * VS_BLOCK + threadIdx.x;  // grid = VS_INS_WORDS / VS_BLOCK
+  uint32_t w = presence[k];
+  long long r = rank[k];
+  while (w) {
+    const int b = __ffs((int)w) - 1;
+    w &= w - 1;
+    if (r < n_instances) instances[r] = (int16_t)(k * 32 + b - 32768);
+    r++;
+  }
+}
+
+struct VisEmitArgs {
+  const uint32_t *bitmap, *sums, *presence, *rank;
+  long long n_words, n_points, n_visible;
+  const int16_t* rows;
+  const double* centers;
+  int n_centers;
+  gcv_class_rule rule;
+  long long* point_index;
+  float *points8, *classes, *scales3;
+  int32_t* batch_index;
+};
+
+__device__ __forceinline__ void vis_emit_point(const VisEmitArgs& a, long long i, long long o) {
+  const int16_t* r = a.rows + 5 * i;
+  const int x = r[0], y = r[1], z = r[2], sc = r[3], ins = r[4];
+  double cx = 0.0, cy = 0.0, w = 0.0, h = 0.0, d = 0.0;  // an unknown instance: all three zero branches
+  if (vis_known(ins, a.centers, a.n_centers)) {
+    const double* c = a.centers + 5 * (long long)ins;
+    cx = c[0]; cy = c[1]; w = c[2]; h = c[3]; d = c[4];
+  }
+  // inference.py:353-357 in binary64, then one rounding to binary32 (the assignment into the float32 array)
+  const double rx = w > 0.0 ? ((double)x - cx) / w * 2.0 : 0.0;
+  const double ry = h > 0.0 ? ((double)y - cy) / h * 2.0 : 0.0;
+  double rz = 0.0;
+  if (d > 0.0) {
+    rz = (double)z / d * 2.0 - 1.0;
+    rz = rz < -1.0 ? -1.0 : (rz > 1.0 ? 1.0 : rz);
+  }
+  a.point_index[o] = i;
+  float4* p8 = reinterpret_cast<float4*>(a.points8 + 8 * o);
+  p8[0] = make_float4((float)x, (float)y, (float)z, (float)sc);
+  p8[1] = make_float4((float)ins, (float)rx, (float)ry, (float)rz);
+  if (a.batch_index != nullptr) {
+    const uint32_t u = (uint32_t)(ins + 32768);
+    a.batch_index[o] = (int32_t)(a.rank[u >> 5] + (uint32_t)__popc(a.presence[u >> 5] & ((1u << (u & 31)) - 1u)));
+  }
+  if (a.classes != nullptr || a.scales3 != nullptr) {
+    const gcv_class_rule& q = a.rule;
+    int cls = ins;  // inference.py:544-598
+    if (ins >= q.bldg_ins_min && (q.bldg_ins_max <= 0 || ins < q.bldg_ins_max)) cls = (ins & 1) ? q.roof_class : q.facade_class;
+    if (q.car_ins_min > 0 && ins >= q.car_ins_min) cls = q.car_class;
+    if (a.classes != nullptr) a.classes[o] = (float)cls;
+    if (a.scales3 != nullptr) {  // utils/helpers.py:212-222 on pts[:, :, [3]] * POINT_SCALE_FACTOR
+      const float s = (float)sc * q.point_scale_factor;
+      const bool special = cls >= 0 && cls < 32 && ((q.special_z_classes >> cls) & 1u);
+      a.scales3[3 * o] = s;
+      a.scales3[3 * o + 1] = s;
+      a.scales3[3 * o + 2] = special ? 1.0f : s;
+    }
+  }
+}
+
+__global__ __launch_bounds__(VS_BLOCK) void k_vis_emit(const VisEmitArgs a) {
+  __shared__ uint32_t s_words[VS_CHUNK_WORDS], s_pre[VS_BLOCK];
+  __shared__ uint32_t lds4[VS_BLOCK / 64];
+  const long long block_word0 = (long long)blockIdx.x * VS_CHUNK_WORDS;
+  const uint4 q = vis_load_words(a.bitmap, a.n_words, block_word0 + 4 * threadIdx.x);
+  const uint32_t cnt = (uint32_t)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
+  uint32_t total;
+  const uint32_t local = vs_block_excl_scan<VS_BLOCK / 64>(cnt, lds4, &total);
+  if (total == 0u) return;  // block-uniform
+  const long long o0 = (long long)a.sums[blockIdx.x];
+  vis_block_points(q, local, total, block_word0, s_words, s_pre, [&](long long i, uint32_t t) {
+    const long long o = o0 + t;
+    if (i < a.n_points && o < a.n_visible) vis_emit_point(a, i, o);  // a stale workspace or count stays in bounds
+  });
+}
+
 // host half of vox/ray_voxel_intersection.cu:256-266 (same float operations, -ffp-contract=off)
 void host_normalize3(float* a) {
   float len = 0.0f;
@@ -755,6 +1023,23 @@ int make_extrude_args(int inc_btm, const int16_t* lut, const gcv_seg_ins* m, int
   if (scratch_bytes < gcv_extrude_scratch_bytes(H, W)) return fail(GCV_ERR_BUFFER_TOO_SMALL, "extrude scratch too small");
   a->inc_btm = inc_btm ? 1 : 0;
   a->H = H; a->W = W; a->lut = lut; a->m = *m; a->seg = seg; a->td = td; a->bu = bu; a->pts = pts;
+  return 0;
+}
+
+bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+// the argument checks gcv_visible_count and gcv_visible_emit share; nothing is queued before they pass
+int vis_check(const int64_t* vp_map, int64_t n_pixels, const int16_t* rows, int64_t n_points, const double* centers,
+              int32_t n_centers, const void* workspace, size_t workspace_bytes) {
+  if (n_pixels < 0 || n_points < 0 || n_centers < 0)
+    return fail(GCV_ERR_INVALID_ARGUMENT, "visible set: n_pixels, n_points and n_centers must not be negative");
+  if (n_pixels >= 2147483648ll || n_points >= 2147483648ll)
+    return fail(GCV_ERR_INVALID_ARGUMENT, "visible set: n_pixels and n_points must be below 2^31");
+  if (!workspace || (n_pixels > 0 && !vp_map) || (n_points > 0 && !rows) || (n_centers > 0 && !centers))
+    return fail(GCV_ERR_INVALID_ARGUMENT, "visible set: null vp_map / rows / centers / workspace");
+  if (misaligned(vp_map, 8) || misaligned(rows, 2) || misaligned(centers, 8) || misaligned(workspace, 16))
+    return fail(GCV_ERR_INVALID_ARGUMENT, "visible set: misaligned vp_map / rows / centers / workspace (16 bytes)");
+  if (workspace_bytes < vis_layout(n_points).total) return fail(GCV_ERR_BUFFER_TOO_SMALL, "visible set workspace too small");
   return 0;
 }
 
@@ -995,6 +1280,84 @@ int gcv_ray_voxel_intersection(const int32_t* volume, const int32_t dims[3], con
       k_rvip<false, false><<<grid, 64, 0, s>>>(out_voxel_id, out_depth, out_raydirs, volume, nullptr, p);
   }
   HIP_TRY(hipGetLastError(), "ray_voxel_intersection launch");
+  return 0;
+}
+
+size_t gcv_visible_workspace_bytes(int64_t n_points, int64_t n_pixels) {
+  if (n_points < 0 || n_pixels < 0 || n_points >= 2147483648ll || n_pixels >= 2147483648ll) {
+    fail(GCV_ERR_INVALID_ARGUMENT, "gcv_visible_workspace_bytes: n_points and n_pixels must be in [0, 2^31)");
+    return 0;
+  }
+  return vis_layout(n_points).total;
+}
+
+int gcv_visible_count(const int64_t* vp_map, int64_t n_pixels, const int16_t* rows, int64_t n_points,
+                      const double* centers, int32_t n_centers, void* workspace, size_t workspace_bytes,
+                      int64_t counts_host[3], void* hip_stream) {
+  if (int rc = vis_check(vp_map, n_pixels, rows, n_points, centers, n_centers, workspace, workspace_bytes)) return rc;
+  if (!counts_host) return fail(GCV_ERR_INVALID_ARGUMENT, "gcv_visible_count: null counts_host");
+  hipStream_t s = (hipStream_t)hip_stream;
+  const VisLayout l = vis_layout(n_points);
+  char* ws = (char*)workspace;
+  unsigned long long* head = (unsigned long long*)ws;
+  uint32_t *presence = (uint32_t*)(ws + l.presence), *bitmap = (uint32_t*)(ws + l.bitmap);
+  uint32_t *rank = (uint32_t*)(ws + l.rank), *sums = (uint32_t*)(ws + l.sums);
+  {
+    StageTimer t(s, stage_slot(ST_VIS_COUNT));
+    HIP_TRY(hipMemsetAsync(ws, 0, l.rank, s), "visible workspace clear");  // head, presence table and bitmap
+    if (n_pixels > 0)
+      k_vis_mark<<<(unsigned)((n_pixels + VS_BLOCK - 1) / VS_BLOCK), VS_BLOCK, 0, s>>>(
+          (const long long*)vp_map, (long long)n_pixels, (long long)n_points, bitmap, head);
+    if (l.n_blocks > 0)
+      k_vis_count<<<l.n_blocks, VS_BLOCK, 0, s>>>(bitmap, l.n_words, rows, centers, n_centers, presence, sums, head);
+    k_vis_scan<<<1, 1024, 0, s>>>(sums, l.n_blocks, presence, rank, head);
+  }
+  HIP_TRY(hipGetLastError(), "visible count launch");
+  unsigned long long h[4];
+  HIP_TRY(hipMemcpyAsync(h, head, sizeof(h), hipMemcpyDeviceToHost, s), "visible count read-back");
+  HIP_TRY(hipStreamSynchronize(s), "visible count sync");
+  if (h[VS_HEAD_BAD] != 0ull) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "vp_map holds %llu value(s) >= n_points = %lld", h[VS_HEAD_BAD], (long long)n_points);
+    return fail(GCV_ERR_INVALID_ARGUMENT, msg);
+  }
+  counts_host[0] = (int64_t)h[VS_HEAD_M];
+  counts_host[1] = (int64_t)h[VS_HEAD_K];
+  counts_host[2] = (int64_t)h[VS_HEAD_UNKNOWN];
+  return 0;
+}
+
+int gcv_visible_emit(const int64_t* vp_map, int64_t n_pixels, const int16_t* rows, int64_t n_points,
+                     const double* centers, int32_t n_centers, const gcv_class_rule* rule, void* workspace,
+                     size_t workspace_bytes, int64_t n_visible, int64_t n_instances, int64_t* point_index,
+                     float* points8, int32_t* batch_index, int16_t* instances, float* classes, float* scales3,
+                     void* hip_stream) {
+  if (int rc = vis_check(vp_map, n_pixels, rows, n_points, centers, n_centers, workspace, workspace_bytes)) return rc;
+  if (!rule) return fail(GCV_ERR_INVALID_ARGUMENT, "gcv_visible_emit: null class rule");
+  if (n_visible < 0 || n_instances < 0 || n_visible > n_points || n_instances > n_visible)
+    return fail(GCV_ERR_INVALID_ARGUMENT, "gcv_visible_emit: need 0 <= n_instances <= n_visible <= n_points");
+  if (n_visible == 0) return 0;
+  if (!point_index || !points8) return fail(GCV_ERR_INVALID_ARGUMENT, "gcv_visible_emit: null point_index / points8");
+  if (misaligned(point_index, 8) || misaligned(points8, 16) || misaligned(batch_index, 4) || misaligned(instances, 2) ||
+      misaligned(classes, 4) || misaligned(scales3, 4))
+    return fail(GCV_ERR_INVALID_ARGUMENT, "gcv_visible_emit: misaligned output (points8 needs 16 bytes)");
+  hipStream_t s = (hipStream_t)hip_stream;
+  const VisLayout l = vis_layout(n_points);
+  char* ws = (char*)workspace;
+  VisEmitArgs a;
+  a.bitmap = (const uint32_t*)(ws + l.bitmap); a.sums = (const uint32_t*)(ws + l.sums);
+  a.presence = (const uint32_t*)(ws + l.presence); a.rank = (const uint32_t*)(ws + l.rank);
+  a.n_words = l.n_words; a.n_points = n_points; a.n_visible = n_visible;
+  a.rows = rows; a.centers = centers; a.n_centers = n_centers; a.rule = *rule;
+  a.point_index = (long long*)point_index; a.points8 = points8; a.classes = classes; a.scales3 = scales3;
+  a.batch_index = batch_index;
+  {
+    StageTimer t(s, stage_slot(ST_VIS_EMIT));
+    k_vis_emit<<<l.n_blocks, VS_BLOCK, 0, s>>>(a);
+    if (instances)
+      k_vis_instances<<<VS_INS_WORDS / VS_BLOCK, VS_BLOCK, 0, s>>>(a.presence, a.rank, instances, (long long)n_instances);
+  }
+  HIP_TRY(hipGetLastError(), "visible emit launch");
   return 0;
 }
 

@@ -7,10 +7,13 @@
   ray_voxel_intersection_perspective
                                extensions.voxlib.ray_voxel_intersection_perspective (bindings.cpp:33)
   get_visible_points           scripts/dataset_generator.py:1414-1461 (the caller of the two above)
+  visible_point_set            scripts/inference.py:338-360 and :229-237 (visible rows, box-relative coordinates,
+                               instance ranks, classes and scales: what render() hands the generator)
 
 torch supplies device memory and the current stream; every computation happens in the HIP library.
 There is no CPU path: without a GPU (or without the built library) these raise RuntimeError.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -252,6 +255,121 @@ def visible_point_map(rows, cam_rig, cam_pos, cam_quat, null_class_id=0, use_jum
         ins_map = rows[:, 4][vp_map.clamp(min=0)]
         ins_map[vp_map == -1] = null_class_id
     return vp_map, ins_map
+
+
+# ---- visible point set: first-hit map -> generator inputs (scripts/inference.py:338-360, :229-237) ----------------
+ClassRule = collections.namedtuple("ClassRule", "bldg_ins_min bldg_ins_max car_ins_min facade_class roof_class car_class "
+                                                "special_z_classes point_scale_factor")
+ClassRule.__doc__ = """Instance id -> class and z-scale (gcv_class_rule).  Instances in [bldg_ins_min, bldg_ins_max) are
+facade_class if even and roof_class if odd (bldg_ins_max <= 0: no upper bound); instances >= car_ins_min are car_class
+(applied last; <= 0: no cars); every other instance keeps its id.  special_z_classes: the classes whose z-scale is 1."""
+# scripts/inference.py:33-54 (POINT_SCALE_FACTOR, SPECIAL_Z_SCALE_CLASSES) with scripts/dataset_generator.py:42-65
+# (CLASSES) and :96,110-111 (BLDG_INST_RANGE, CAR_INST_RANGE); :544-561 tests no upper bound for GOOGLE_EARTH
+CLASS_RULE_GOOGLE_EARTH = ClassRule(100, 0, 0, 2, 7, 0, (1, 5, 6), 0.45)       # ROAD, WATER, ZONE
+CLASS_RULE_KITTI_360 = ClassRule(100, 10000, 10000, 2, 7, 3, (1, 6), 0.5)      # ROAD, ZONE
+
+VisibleSet = collections.namedtuple("VisibleSet", "index pts batch_idx instances classes scales")
+
+
+def _native_rule(rule, point_scale_factor=None):
+    mask = 0
+    for c in rule.special_z_classes:
+        if not 0 <= int(c) < 32:
+            raise ValueError("special z-scale classes must be in [0, 32)")
+        mask |= 1 << int(c)
+    f = rule.point_scale_factor if point_scale_factor is None else point_scale_factor
+    return V.ClassRule(int(rule.bldg_ins_min), int(rule.bldg_ins_max), int(rule.car_ins_min), int(rule.facade_class),
+                       int(rule.roof_class), int(rule.car_class), mask, float(f))
+
+
+_centers_cache = {}  # id(dict) -> [len(dict), float64 CPU table, {device: copy}]
+
+
+def centers_table(centers, device=None):
+    """CENTERS.pkl as scripts/inference.py:131 loads it, {instance: (cx, cy, w, h, d)}, as the float64 [n,5] table
+    gcv_visible_count reads: row i = instance i, NaN rows for ids the dict does not have.  Built once per dict and kept
+    (keyed on the dict's id and length: a dict that grew is converted again); `device`: the copy on that device."""
+    e = _centers_cache.get(id(centers))
+    if e is None or e[0] != len(centers):
+        keys = [int(k) for k in centers]
+        if any(k < 0 or k > 32767 for k in keys):
+            raise KeyError("instance ids are int16 and not negative: %r" % [k for k in keys if k < 0 or k > 32767][:4])
+        tab = np.full((max(keys) + 1 if keys else 0, 5), np.nan, np.float64)
+        for k, v in centers.items():
+            tab[int(k)] = v
+        e = _centers_cache[id(centers)] = [len(centers), torch.from_numpy(tab), {}]
+    if device is None:
+        return e[1]
+    device = torch.device(device)
+    if device not in e[2]:
+        e[2][device] = e[1].to(device)
+    return e[2][device]
+
+
+class VisibleSetWorkspace:
+    """The workspace gcv_visible_count / gcv_visible_emit share, kept across frames (grows on demand; every count
+    clears what it uses).  One workspace per stream."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.buf = None
+
+    def take(self, nbytes):
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = None
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return self.buf
+
+
+def visible_point_set(rows, vp_map, centers, class_rule, point_scale_factor=None, workspace=None):
+    """scripts/inference.py:338-360 and :229-237 on the device.  rows: int16 CUDA [N,5] as extrude_points writes them;
+    vp_map: int64 CUDA first-hit map as visible_point_map returns it (negative = no point); centers: the dict
+    {instance: (cx, cy, w, h, d)} or a float64 CUDA [n,5] table (centers_table); class_rule: a ClassRule.
+    Returns VisibleSet(index int64 [M], pts float32 [1,M,8], batch_idx int32 [1,M,1], instances int16 [K],
+    classes float32 [1,M,1], scales float32 [1,M,3]) -- what render() holds after :237.  A visible point whose
+    instance `centers` does not have raises KeyError, as :351 does."""
+    if not rows.is_cuda or rows.dtype != torch.int16 or rows.dim() != 2 or rows.shape[1] != 5:
+        raise RuntimeError("rows must be an int16 CUDA tensor [N,5]")
+    dev = rows.device
+    if not vp_map.is_cuda or vp_map.dtype != torch.int64 or vp_map.device != dev:
+        raise RuntimeError("vp_map must be an int64 CUDA tensor on the device of rows")
+    if isinstance(centers, dict):
+        table = centers_table(centers, dev)
+    else:
+        table = centers
+        if not table.is_cuda or table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 5 or table.device != dev:
+            raise RuntimeError("centers must be a dict or a float64 CUDA tensor [n,5] on the device of rows")
+    rows, vp, table = rows.contiguous(), vp_map.contiguous().view(-1), table.contiguous()
+    n, npix, nc = int(rows.shape[0]), int(vp.numel()), int(table.shape[0])
+    rule = _native_rule(class_rule, point_scale_factor)
+    L = V.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.gcv_visible_workspace_bytes(n, npix)
+        if nbytes == 0:
+            V.check(-1, "gcv_visible_workspace_bytes")
+        ws = (workspace.take(nbytes) if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        a = (vp.data_ptr(), npix, rows.data_ptr(), n, table.data_ptr(), nc)
+        counts = (C.c_int64 * 3)()
+        V.check(L.gcv_visible_count(*a, ws.data_ptr(), nbytes, counts, _stream()), "gcv_visible_count")
+        m, k, unknown = int(counts[0]), int(counts[1]), int(counts[2])
+        index = torch.empty(m, dtype=torch.int64, device=dev)
+        pts = torch.empty((1, m, 8), dtype=torch.float32, device=dev)
+        instances = torch.empty(k, dtype=torch.int16, device=dev)
+        if unknown:  # name them: the instance list against the table, on the host
+            V.check(L.gcv_visible_emit(*a, C.byref(rule), ws.data_ptr(), nbytes, m, k, index.data_ptr(), pts.data_ptr(),
+                                       None, instances.data_ptr(), None, None, _stream()), "gcv_visible_emit")
+            tab = table.cpu().numpy()
+            bad = [int(i) for i in instances.cpu().numpy() if i < 0 or i >= nc or np.isnan(tab[i, 0])]
+            raise KeyError("%d visible point(s) of instance(s) %s%s not in centers"
+                           % (unknown, bad[:8], " ..." if len(bad) > 8 else ""))
+        batch_idx = torch.empty((1, m, 1), dtype=torch.int32, device=dev)
+        classes = torch.empty((1, m, 1), dtype=torch.float32, device=dev)
+        scales = torch.empty((1, m, 3), dtype=torch.float32, device=dev)
+        if m:
+            V.check(L.gcv_visible_emit(*a, C.byref(rule), ws.data_ptr(), nbytes, m, k, index.data_ptr(), pts.data_ptr(),
+                                       batch_idx.data_ptr(), instances.data_ptr(), classes.data_ptr(),
+                                       scales.data_ptr(), _stream()), "gcv_visible_emit")
+    return VisibleSet(index, pts, batch_idx, instances, classes, scales)
 
 
 def get_camera_look_at(cam_position, cam_quaternion, step=1000):

@@ -14,6 +14,10 @@
  *                                          (extensions/voxlib/maps_to_volume.cu:21-142, bindings.cpp:38; no in-tree caller)
  *   gcv_ray_voxel_intersection             voxlib.ray_voxel_intersection_perspective
  *                                          (extensions/voxlib/ray_voxel_intersection.cu:54-332, bindings.cpp:33)
+ *   gcv_visible_count / gcv_visible_emit   scripts/inference.py:338-341 (_get_bev_points: the visible rows),
+ *                                          :345-360 (_get_normalized_pt_cords), :229-237 with :535-598
+ *                                          (_instances_to_classes) and utils/helpers.py:197-223 (get_point_scales):
+ *                                          numpy / a Python loop over instances upstream (ABI v5)
  *   gcv_build_occupancy                    (none upstream: 1 bit per 16x16x16 macro cell; lets the traversal
  *                                           jump across empty macro cells, reproducing the reference walk
  *                                           exactly -- results unchanged)
@@ -31,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GCV_ABI_VERSION 4
+#define GCV_ABI_VERSION 5
 
 enum gcv_status {
   GCV_OK = 0,
@@ -119,9 +123,56 @@ int gcv_ray_voxel_intersection(const int32_t* volume, const int32_t dims[3], con
                                const int32_t img_dims[2], int32_t max_samples, int32_t* out_voxel_id,
                                float* out_depth, float* out_raydirs, void* hip_stream);
 
+/* ---- K16: visible point set -> generator inputs (ABI v5) ------------------------------------------
+ * What scripts/inference.py does on the host between get_visible_points and the generator, for rows and a
+ * first-hit map that are already on the device.  M = number of distinct non-negative values of vp_map.
+ *   vp_map   int64 [n_pixels]: row index of the point a pixel sees, any negative value = none
+ *            (gcv_ray_voxel_intersection's ids - 1); a value >= n_points is GCV_ERR_INVALID_ARGUMENT, reported by
+ *            gcv_visible_count through a device flag, and is never used as an index
+ *   rows     int16 [n_points][5] = (x, y, z, scale, instance), as gcv_extrude_emit writes them
+ *   centers  float64 [n_centers][5] = (cx, cy, w, h, d); row i belongs to instance id i, cx = NaN marks an
+ *            instance that is not in the table (CENTERS.pkl is a dict upstream, :131)
+ * Outputs of gcv_visible_emit (all written in full; all but point_index and points8 may be NULL = skipped):
+ *   point_index int64 [M]     the distinct non-negative values of vp_map, ascending (:339-340)
+ *   points8     float [M][8]  columns 0-4 the int16 row as float; 5-7 the box-relative coordinates of :353-357,
+ *                             each evaluated in binary64 in upstream's order and rounded once to binary32:
+ *                               rel_x = w > 0 ? (x - cx) / w * 2 : 0,  rel_y likewise with cy, h,
+ *                               rel_z = d > 0 ? clip(z / d * 2 - 1, -1, 1) : 0        (16-byte aligned)
+ *   instances   int16 [K]     the distinct instance ids of the visible points, ascending (:346)
+ *   batch_index int32 [M]     rank of the point's instance in `instances` (:349,358)
+ *   classes     float [M]     gcv_class_rule applied to the instance id (:544-598)
+ *   scales3     float [M][3]  float(scale) * point_scale_factor (one fp32 multiply) on the three axes, axis 2 = 1
+ *                             where the class is in special_z_classes (utils/helpers.py:212-222)
+ * A visible point whose instance is negative, >= n_centers or marked NaN is UNKNOWN (KeyError upstream, :351);
+ * gcv_visible_count counts them, gcv_visible_emit gives them relative coordinates 0.
+ * Count / emit convention of K15: gcv_visible_count enqueues mark + scan, waits, and stores
+ * counts_host = {M, K, visible points with an unknown instance}; gcv_visible_emit enqueues and returns.  The
+ * workspace (gcv_visible_workspace_bytes, 16-byte aligned) carries the marks from _count to _emit; _count clears
+ * what it needs, so one workspace serves frame after frame.  Nothing is allocated inside.  Argument errors (null or
+ * misaligned pointers, negative sizes, a small workspace) come back before anything is queued.
+ * gcv_visible_workspace_bytes is host only; it returns 0 and sets gcv_last_error() for negative sizes and for
+ * n_points or n_pixels >= 2^31. */
+typedef struct gcv_class_rule {
+  int32_t bldg_ins_min, bldg_ins_max; /* instances in [min, max): facade if even, roof if odd; max <= 0: no upper bound */
+  int32_t car_ins_min;                /* instances >= this are cars (applied last, as upstream); <= 0: no cars */
+  int32_t facade_class, roof_class, car_class;
+  uint32_t special_z_classes;         /* bit c set: class c gets z-scale 1 */
+  float point_scale_factor;
+} gcv_class_rule;                     /* every other instance keeps its id as its class */
+size_t gcv_visible_workspace_bytes(int64_t n_points, int64_t n_pixels);
+int gcv_visible_count(const int64_t* vp_map, int64_t n_pixels, const int16_t* rows, int64_t n_points,
+                      const double* centers, int32_t n_centers, void* workspace, size_t workspace_bytes,
+                      int64_t counts_host[3], void* hip_stream);
+int gcv_visible_emit(const int64_t* vp_map, int64_t n_pixels, const int16_t* rows, int64_t n_points,
+                     const double* centers, int32_t n_centers, const gcv_class_rule* rule_host, void* workspace,
+                     size_t workspace_bytes, int64_t n_visible, int64_t n_instances, int64_t* point_index,
+                     float* points8, int32_t* batch_index, int16_t* instances, float* classes, float* scales3,
+                     void* hip_stream);
+
 /* avg device ms per stage since the last call (option "timing" of gcv_set_option; hipEvent pairs on the caller's
  * stream, a ring of 8 pairs per stage, so recording never waits for a stage still in flight):
- * 0 extrude_count, 1 extrude_emit, 2 volume_clear, 3 volume_scatter, 4 occupancy, 5 traversal */
+ * 0 extrude_count, 1 extrude_emit, 2 volume_clear, 3 volume_scatter, 4 occupancy, 5 traversal, 6 visible_count,
+ * 7 visible_emit */
 int gcv_set_option(const char* name, int value);
 int gcv_get_stage_ms(float* out, int n);
 
