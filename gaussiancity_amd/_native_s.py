@@ -13,6 +13,7 @@ ENGINES = {"valu": ENGINE_VALU, "mfma": ENGINE_MFMA}
 PRODUCT_FORWARD, PRODUCT_DX, PRODUCT_DW = 1, 2, 4  # GCS_PRODUCT_*: the bits of gcs_engine_products
 DTYPE_F32, DTYPE_F16 = 0, 1  # enum gcs_dtype
 DTYPES = {"float32": DTYPE_F32, "float16": DTYPE_F16}  # the `_t` entry points; gcs_dtypes() says which the library runs
+ORDERS = {"cord": 0, "z": 1, "z-trans": 2, "hilbert": 3, "hilbert-trans": 4}  # enum gcs_order; gcs_index_orders() has the bits
 ABI_VERSION = 4
 
 _vp, _sz, _i32, _i64, _int = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int
@@ -42,6 +43,11 @@ _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argt
     "gcs_subm_backward_t": (_int, [_i32, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gcs_segment_csr_forward_t": (_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "gcs_segment_csr_backward_t": (_int, [_i32, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "gcs_index_orders": (_int, []),
+    "gcs_serialize_workspace_bytes": (_sz, [_i64, _i32]),
+    "gcs_serialize": (_int, [_vp, _vp, _i64, _i32, _i32, C.c_float, C.c_float, _pi32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcs_patch_plan_count": (_int, [_vp, _i32, _i64, _vp, _vp]),
+    "gcs_patch_plan_emit": (_int, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _L = _loader.Library("gcs", "libgcs_hip.so", ABI_VERSION, _SIGNATURES)

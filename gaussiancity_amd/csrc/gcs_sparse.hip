@@ -896,7 +896,104 @@ int segment_backward(const char* who, const T* dout, int64_t m, int64_t f, const
 
 }  // namespace
 
+#include "gcs_index.h"
+
+namespace {
+
+// The argument checks of gcs_serialize that need no pointer; `orders` receives the checked list.
+int check_serialize(const char* who, int64_t n, int32_t n_batches, int32_t depth, const int32_t* orders_host,
+                    int32_t n_orders, IndexOrders* orders) {
+  const std::string w(who);
+  if (n < 0 || n > INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": n must be in 0...2^31 - 1");
+  if (n_orders < 1 || n_orders > IX_ORDERS) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": n_orders must be in 1...5");
+  if (!orders) return 0;
+  if (depth < 1 || depth > 16) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": depth must be in 1...16");
+  if (n_batches < 1) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": n_batches must be positive");
+  int bit_length = 0;
+  while (n_batches >> bit_length) bit_length++;
+  if (3 * depth + bit_length > 63)
+    return fail(GCS_ERR_INVALID_ARGUMENT, w + ": 3 * depth + bit_length(n_batches) exceeds 63 bits");
+  if (!orders_host) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": null orders_host");
+  orders->n = n_orders;
+  uint32_t seen = 0;
+  for (int o = 0; o < n_orders; o++) {
+    const int32_t v = orders_host[o];
+    if (v < 0 || v >= IX_ORDERS) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": unknown order in orders_host");
+    if (seen >> v & 1u) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": repeated order in orders_host");
+    seen |= 1u << v;
+    orders->v[o] = v;
+  }
+  return 0;
+}
+
+int check_patch_plan(const char* who, const int64_t* offset, int32_t n_batches, int64_t patch_size) {
+  const std::string w(who);
+  if (n_batches < 1) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": n_batches must be positive");
+  if (patch_size < 1) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": patch_size must be positive");
+  if (!offset) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": null offset");
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
+
+int gcs_index_orders(void) { return (1 << IX_ORDERS) - 1; }
+
+size_t gcs_serialize_workspace_bytes(int64_t n, int32_t n_orders) {
+  if (check_serialize("gcs_serialize_workspace_bytes", n, 1, 1, nullptr, n_orders, nullptr)) return 0;
+  return index_layout(n, n_orders).total;
+}
+
+int gcs_serialize(const int32_t* grid_coord, const int64_t* batch, int64_t n, int32_t n_batches, int32_t depth,
+                  float cord_div_x, float cord_div_y, const int32_t* orders_host, int32_t n_orders, int64_t* code,
+                  int64_t* order, int64_t* inverse, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const char* who = "gcs_serialize";
+  IndexOrders orders = {};
+  if (int rc = check_serialize(who, n, n_batches, depth, orders_host, n_orders, &orders)) return rc;
+  if (cord_div_x != cord_div_x || cord_div_y != cord_div_y || cord_div_x == 0.0f || cord_div_y == 0.0f)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_serialize: cord_div_x and cord_div_y must be non-zero numbers");
+  if (!workspace || workspace_bytes < index_layout(n, n_orders).total)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_serialize: workspace missing or smaller than gcs_serialize_workspace_bytes");
+  if (n == 0) return 0;
+  if (!grid_coord) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_serialize: null grid_coord");
+  if (!code || !order || !inverse) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_serialize: null code, order or inverse");
+  HIP_TRY(index_serialize_launch(grid_coord, batch, n, depth, cord_div_x, cord_div_y, orders, code, order, inverse,
+                                 (char*)workspace, (hipStream_t)hip_stream), "serialize launch");
+  return 0;
+}
+
+int gcs_patch_plan_count(const int64_t* offset, int32_t n_batches, int64_t patch_size, int64_t counts_host[2],
+                         void* hip_stream) {
+  if (int rc = check_patch_plan("gcs_patch_plan_count", offset, n_batches, patch_size)) return rc;
+  if (!counts_host) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_patch_plan_count: null counts_host");
+  void* counts = nullptr;
+  if (hipHostGetDevicePointer(&counts, counts_host, 0) != hipSuccess || !counts) {
+    (void)hipGetLastError();
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_patch_plan_count: counts_host must be pinned host memory (the kernel writes it)");
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  k_patch_count<<<1, IX_THREADS, 0, st>>>(offset, n_batches, patch_size, (int64_t*)counts);
+  HIP_TRY(hipGetLastError(), "patch count launch");
+  HIP_TRY(hipStreamSynchronize(st), "patch count wait");
+  return 0;
+}
+
+int gcs_patch_plan_emit(const int64_t* offset, int32_t n_batches, int64_t patch_size, int64_t padded, int64_t n_cu,
+                        int64_t* pad, int64_t* unpad, int32_t* cu_seqlens, void* hip_stream) {
+  if (int rc = check_patch_plan("gcs_patch_plan_emit", offset, n_batches, patch_size)) return rc;
+  if (padded < 0 || padded > INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_patch_plan_emit: padded must be in 0...2^31 - 1 (cu_seqlens is int32)");
+  if (n_cu < 1 || n_cu > padded + n_batches + 1) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_patch_plan_emit: n_cu is not a count of gcs_patch_plan_count");
+  if (!cu_seqlens || (padded > 0 && (!pad || !unpad)))
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_patch_plan_emit: null pad, unpad or cu_seqlens");
+  // slices of a batch's rows: about 4 rows a thread at an even split, so that one long batch still fills the device
+  int64_t slices = padded / ((int64_t)n_batches * IX_THREADS * 4) + 1;
+  if (slices > 256) slices = 256;
+  k_patch_emit<<<dim3((unsigned)n_batches, (unsigned)slices), IX_THREADS, 0, (hipStream_t)hip_stream>>>(
+      offset, n_batches, patch_size, padded, n_cu, pad, unpad, cu_seqlens);
+  HIP_TRY(hipGetLastError(), "patch emit launch");
+  return 0;
+}
 
 int gcs_abi_version(void) { return GCS_ABI_VERSION; }
 const char* gcs_last_error(void) { return g_err.c_str(); }

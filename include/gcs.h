@@ -164,6 +164,51 @@ int gcs_segment_csr_forward_t(int32_t dtype, const void* src, int64_t m, int64_t
 int gcs_segment_csr_backward_t(int32_t dtype, const void* dout, int64_t m, int64_t f, const int64_t* indptr, int64_t s,
                                int32_t reduce, const int64_t* arg, void* dsrc, void* hip_stream);
 
+
+/* Index plans of the point backbone.  GCS_ABI_VERSION stays 4, as for the typed entry points:
+ * nothing existing changes, and gcs_index_orders() is how a binding learns whether the library has the plans.  The
+ * library allocates nothing, everything runs on the caller's stream, and an argument error is GCS_ERR_INVALID_ARGUMENT
+ * before anything is queued.
+ *
+ * gcs_serialize: what models/pt_v3.py's Point.serialization computes.  grid_coord int32 [n][3], batch int64 [n] or NULL,
+ * orders_host the n_orders requested gcs_order values (HOST memory, each at most once); code, order, inverse int64
+ * [n_orders][n], row r for orders_host[r].  The host never waits.
+ *   codes    The four curve orders take a coordinate modulo 2^depth.  Z: bit i of x, y, z goes to bit 3i+2, 3i+1, 3i.
+ *            HILBERT: Skilling's transform of the three axes, Gray step, interleave with axis 0 most significant.  The
+ *            `_TRANS` orders swap x and y first.  CORD: (int64) trunc((float(x) / cord_div_x + float(y) / cord_div_y) +
+ *            float(z)) in binary32 with IEEE division, coordinates as they are; for the reference's grid_size pass
+ *            cord_div_x = (float)(grid_size * grid_size), cord_div_y = (float)grid_size.  With batch the code is
+ *            batch << 3 * depth | code.
+ *   order    order[r] sorts code[r] ascending as SIGNED int64, ties to the lower row (a stable sort), and
+ *            inverse[r][order[r][j]] = j.
+ *   refused  n outside 0...2^31-1, depth outside 1...16, n_batches < 1, 3 * depth + bit_length(n_batches) > 63, an unknown
+ *            or repeated order, n_orders outside 1...5, a zero or NaN divisor, a workspace that is missing or smaller than
+ *            gcs_serialize_workspace_bytes(n, n_orders) (0 with an error for arguments out of range); n == 0 does nothing.
+ *
+ * gcs_patch_plan_*: what SerializedAttention.get_padding_and_inverse computes from offset int64 [n_batches] (device,
+ * inclusive row ends of the batches, non-decreasing) and the patch size P.  A batch of n_i rows is padded to
+ * n_i > P ? ceil(n_i / P) * P : n_i rows; off_pad are the padded starts.  unpad[j] = j + off_pad[i] - off[i];
+ * pad[p] = (p >= off_pad[i] + n_i ? p - P : p) - (off_pad[i] - off[i]); cu_seqlens lists every off_pad[i] + m * P below
+ * off_pad[i + 1], in batch order, then the padded total.
+ *   _count   one launch that writes counts_host[0] = padded rows and counts_host[1] = cu_seqlens entries, and the call's
+ *            ONE wait for the stream.  counts_host must be pinned host memory (hipHostMalloc, a torch pinned tensor):
+ *            the kernel writes it directly.
+ *   _emit    fills pad [padded], unpad [offset[n_batches - 1]] and cu_seqlens [n_cu] for the counts _count reported;
+ *            never waits.  Every store is held inside those lengths.  A batch's padded start is summed over the batches
+ *            before it by the batch's own workgroups: meant for the hundreds of batches of a frame, not for millions.
+ *   refused  n_batches < 1, patch_size < 1, a null pointer, counts_host that the device cannot write, padded beyond
+ *            2^31-1 (cu_seqlens is int32), n_cu that no _count call can have reported. */
+enum gcs_order { GCS_ORDER_CORD = 0, GCS_ORDER_Z = 1, GCS_ORDER_Z_TRANS = 2, GCS_ORDER_HILBERT = 3, GCS_ORDER_HILBERT_TRANS = 4 };
+int gcs_index_orders(void); /* host only: bit (1 << order) for every order the library computes: 31 */
+size_t gcs_serialize_workspace_bytes(int64_t n, int32_t n_orders);
+int gcs_serialize(const int32_t* grid_coord, const int64_t* batch, int64_t n, int32_t n_batches, int32_t depth,
+                  float cord_div_x, float cord_div_y, const int32_t* orders_host, int32_t n_orders, int64_t* code,
+                  int64_t* order, int64_t* inverse, void* workspace, size_t workspace_bytes, void* hip_stream);
+int gcs_patch_plan_count(const int64_t* offset, int32_t n_batches, int64_t patch_size, int64_t counts_host[2],
+                         void* hip_stream);
+int gcs_patch_plan_emit(const int64_t* offset, int32_t n_batches, int64_t patch_size, int64_t padded, int64_t n_cu,
+                        int64_t* pad, int64_t* unpad, int32_t* cu_seqlens, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
