@@ -24,7 +24,13 @@ std::atomic<int> g_timing{0};
 std::atomic<int> g_force_radix{0};
 std::atomic<int> g_force_global_cursor{0};
 std::atomic<int> g_lazy_sort{1};         // 1: long tile lists are sorted segment by segment, as far as the blend walks (gcr_sort.h)
-std::atomic<int> g_sort_in_blend{0};     // 1: the forward blend sorts short tile lists itself (lower frame latency, lower throughput)
+std::atomic<int> g_sort_in_blend{0};     // 1: asks for the "tile ids" mode below whatever "blend_ranks" says (the round-3 option's name; its own code is gone)
+// 1: frames with short tile lists scatter 4-byte Gaussian indices and the forward blend ranks its own tile from the records
+// it gathers ("tile ids", enqueue_render_lds): five launches, no per-tile sort kernel
+std::atomic<int> g_blend_ranks{GCR_BLEND_RANKS_DEFAULT};
+// the mode the most recent forward blend enqueued by this process took (gcr_get_option("last_tile_ids"); not an option:
+// it cannot be set -- tests and A/B runs check that the path they mean to exercise is the one that ran)
+std::atomic<int> g_last_tile_ids{0};
 std::atomic<int> g_split_preprocess{0};  // 1: K1 as two kernels (streaming cull, then exact pass) instead of the fused one
 std::atomic<int> g_deterministic{0};  // 1: fixed-point gradient records (order-independent sums), gcr_internal.h
 std::atomic<int> g_bwd_wave_units{0};  // 1: the backward blend as one wave per (work item, quadrant) (round 4) instead of one workgroup per item
@@ -58,7 +64,7 @@ std::atomic<unsigned long long*> g_clock_buf{nullptr};  // K7 per-wave phase clo
 // One call's options: the process-wide defaults above, overridden field by field by gcr_camera.options (ABI v6).
 // Resolved once at the top of every entry point and handed down by value -- nothing below reads the globals.
 struct Opts {
-  int lazy_sort, sort_in_blend, bwd_piece, deterministic, split_preprocess, force_radix, force_global_cursor, bwd_wave_units;
+  int lazy_sort, sort_in_blend, blend_ranks, bwd_piece, deterministic, split_preprocess, force_radix, force_global_cursor, bwd_wave_units;
   int band_sort_min;  // process-wide only (no field in gcr_options: the record keeps its size)
   int stream_policy;  // process-wide only
 };
@@ -83,6 +89,7 @@ const OptionRow g_options[] = {
     {"split_preprocess", &g_split_preprocess, opt_raw, &Opts::split_preprocess, &gcr_options::split_preprocess},
     {"sort_in_blend", &g_sort_in_blend, opt_raw, &Opts::sort_in_blend, &gcr_options::sort_in_blend},
     {"lazy_sort", &g_lazy_sort, opt_bool, &Opts::lazy_sort, &gcr_options::lazy_sort},
+    {"blend_ranks", &g_blend_ranks, opt_bool, &Opts::blend_ranks, nullptr},
     {"deterministic_backward", &g_deterministic, opt_bool, &Opts::deterministic, &gcr_options::deterministic_backward},
     {"bwd_wave_units", &g_bwd_wave_units, opt_bool, &Opts::bwd_wave_units, &gcr_options::bwd_wave_units},
     {"bwd_piece", &g_bwd_piece, opt_piece, &Opts::bwd_piece, &gcr_options::bwd_piece},
@@ -136,12 +143,6 @@ inline void gcr_cpu_relax() {
   __asm__ __volatile__("yield");
 #endif
 }
-
-// Longest tile list (the caller's expectation, or the exact maximum on the staged path) up to which the forward
-// blend sorts its tiles itself.  Its fast path covers lists of one blend chunk (256); a somewhat longer list is
-// still ranked correctly by the same workgroup through global loads (n^2/256 compares per thread), so the
-// threshold leaves room for the longest list to grow from one frame to the next.
-constexpr int64_t GCR_SORT_IN_BLEND_MAX = 384;
 
 // Stage timer (gc_host.h); the slots are this thread's: gcr_get_stage_ms() reports the stages this thread enqueued.
 thread_local StageSlot g_slots[ST_COUNT];
@@ -410,6 +411,7 @@ int gcr_set_option(const char* name, int value) {
 }
 
 int gcr_get_option(const char* name) {
+  if (name && !strcmp(name, "last_tile_ids")) return g_last_tile_ids.load();
   const OptionRow* o = find_option(name);
   return o ? o->global->load() : INT32_MIN;
 }
@@ -420,6 +422,12 @@ int gcr_get_stage_ms(float* ms_out, int capacity) { return stage_report(g_slots,
 // counted; the count kernel records the answer in frame[GCR_FRAME_BANDED], and the scatter follows that word.)
 static inline bool band_sort_slot_free(const Opts& op) {
   return !op.split_preprocess && !op.force_radix && !op.force_global_cursor;
+}
+// Band sort for frames expected to hold many instances (the caller's capacity guess: ~0 = no guess, the staged entry
+// points).  The preprocess and the render half of a frame are handed the same guess and take the same decision.
+static inline bool band_sort_wanted(const Opts& op, const FrameSetup& f, unsigned long long cap_instances) {
+  return f.NG > 0 && f.banded && band_sort_slot_free(op) && op.band_sort_min >= 0 &&
+         (op.band_sort_min == 0 || (cap_instances != ~0ull && cap_instances >= (unsigned long long)op.band_sort_min));
 }
 
 // Enqueues K1 + tile counting + tile scan; leaves {R, longest list, go flag} in the frame words (f.frame).
@@ -461,10 +469,8 @@ static int enqueue_preprocess(const Opts& op, const gcr_camera* cam, const gcr_g
   if (int rc = debug_sync(cam, s, "preprocess")) return rc;
   StageTimer t(s, stage_slot(ST_SCAN));
   if (f.NG > 0) {
-    // Band sort for frames expected to hold many instances (the caller's capacity guess: ~0 = no guess, the staged entry
-    // point): the renumbered survivors go where only K1a's candidates (split mode) and the radix fallback keep anything
-    const bool band = f.banded && band_sort_slot_free(op) && op.band_sort_min >= 0 &&
-                      (op.band_sort_min == 0 || (cap_instances != ~0ull && cap_instances >= (unsigned long long)op.band_sort_min));
+    // the renumbered survivors go where only K1a's candidates (split mode) and the radix fallback keep anything
+    const bool band = band_sort_wanted(op, f, cap_instances);
     // tile_total | tile_local | blk_total share the (T x 128 B) cursor region, unused on this path
     HIP_TRY(gcr_launch_tile_count(T, f.gx, f.NG, f.G, f.nblocks, f.chunk, f.vis_rec, f.vis_count, f.table, f.cursor,
                                   f.cursor + (size_t)T, f.cursor + 2 * (size_t)T, f.frame, f.block_tiles, host_R, seq,
@@ -520,13 +526,26 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
   const int64_t R_layout = f.R_layout;
   uint64_t* pairs = f.keys[0];
   const unsigned long long* frame_guard = speculative ? f.frame : nullptr;
+  // FRAME MODE "tile ids" (option "blend_ranks"; the old "sort_in_blend" asks for the same code): the scatter writes the
+  // 4-byte Gaussian index alone into the tile segments (the `pairs` region as a uint32 array), the per-tile sort kernel is
+  // not launched, and the forward blend ranks its own tile by the depth in the records it gathers anyway -- five launches.
+  // For frames whose lists the blend's LDS ranks (the caller's longest-list hint, or the exact maximum on the staged path;
+  // a list that outgrew a stale hint is still ranked correctly, through global memory) and whose scatter is the sector-bound
+  // one: a band-sorted frame (many instances, neighbours already) and the A/B binning paths keep the six launches.
+  // Training frames (gcr_camera.backward == 1) take the mode only under "sort_in_blend": their blend grows by more than
+  // their sort kernel took (C2: 31.1 -> 38.0 us for 9.9 us), and beside other frames' blends that sort kernel was hidden
+  // (C2 forward + backward: medians 8 297 -> 8 174 frames/s with them in the mode, profiles/r08_ab_c2_backward_training_in_mode.jsonl).
+  const bool tile_ids = R_layout > 0 && f.NG > 0 && (op.sort_in_blend != 0 || (op.blend_ranks != 0 && cam->backward != 1)) &&
+                        list_length_hint <= GCR_BLEND_RANKS_MAX && !op.force_radix && !op.force_global_cursor &&
+                        !band_sort_wanted(op, f, cap_instances);
+  g_last_tile_ids.store(tile_ids ? 1 : 0);
   {
     StageTimer t(s, stage_slot(ST_EMIT));
     if (f.NG > 0) {
       // also rebuilds `ranges` from the block totals, so it runs even when nothing is rendered
       HIP_TRY(gcr_launch_tile_scatter(f.T, f.gx, f.NG, f.G, f.nblocks, f.chunk, f.vis_rec, f.vis_count, f.table, f.cursor,
                                       f.cursor + (size_t)f.T, f.cursor + 2 * (size_t)f.T, f.ranges, pairs, f.frame,
-                                      cap_instances, cap_list, host_longest, f.banded, g->P / 4, s),
+                                      cap_instances, cap_list, host_longest, f.banded, g->P / 4, tile_ids, s),
               "tile scatter");
     } else if (R_layout > 0) {
       HIP_TRY(gcr_launch_scatter_instances(f.nblocks, f.chunk, f.vis_list, f.vis_count, f.rec, f.gx, f.cursor, pairs,
@@ -535,14 +554,8 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
     }
   }
   if (int rc = debug_sync(cam, s, "scatter instances")) return rc;
-  // Option "sort_in_blend": short lists (the caller's expectation, or the exact maximum on the staged path) are
-  // sorted by the blend's own workgroups and K4 does not run as a kernel.  Measured at C3: one frame alone 0.287 ->
-  // 0.273 ms (one launch less on the critical path), but 4 870 -> 4 580 frames/s with two frames in flight (the
-  // VALU-bound blend grows by 14 us, while the separate latency-bound sort kernel hides behind the other frame's
-  // work) -- so it is off by default.
-  const bool sort_in_blend = R_layout > 0 && list_length_hint <= GCR_SORT_IN_BLEND_MAX && op.sort_in_blend != 0;
-  uint4* lazy = (R_layout > 0 && !sort_in_blend && op.lazy_sort != 0) ? f.lazy : nullptr;
-  if (R_layout > 0 && !sort_in_blend) {
+  uint4* lazy = (R_layout > 0 && op.lazy_sort != 0) ? f.lazy : nullptr;  // ("tile ids": the blend writes the states, whole lists)
+  if (R_layout > 0 && !tile_ids) {
     StageTimer t(s, stage_slot(ST_SORT));
     // LDS of the sort sized for 1.5x the expected longest list (longer ones take its run + merge path)
     HIP_TRY(gcr_launch_tile_sort(f.ranges, f.T, pairs, f.keys[1], f.list, list_length_hint + list_length_hint / 2 + 64,
@@ -555,6 +568,7 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
   b.out_color = out_color;
   b.frame = frame_guard;
   b.pairs = pairs;
+  b.key_scratch = f.keys[1];
   b.list_out = f.list;
   b.lazy = lazy;
   set_piece_args(op, b, cam->backward == 1, f);
@@ -579,7 +593,7 @@ static int enqueue_render_lds(const Opts& op, const gcr_camera* cam, const gcr_g
 #endif
   {
     StageTimer t(s, stage_slot(ST_BLEND_FWD));
-    HIP_TRY(gcr_launch_blend_fwd(b, sort_in_blend, s), "blend forward");
+    HIP_TRY(gcr_launch_blend_fwd(b, tile_ids, s), "blend forward");
   }
 #ifdef GCR_EXPERIMENTS
   if (chain) {
@@ -1123,6 +1137,7 @@ int gcr_forward_render(const gcr_camera* cam, const gcr_gaussians* g, void* geom
   GcrBlendArgs b = blend_args(f, cam, f.vals[half]);
   b.out_color = out_color;
   set_piece_args(op, b, cam->backward == 1, f);
+  g_last_tile_ids.store(0);
   {
     StageTimer t(s, stage_slot(ST_BLEND_FWD));
     HIP_TRY(gcr_launch_blend_fwd(b, false, s), "blend forward");

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_emit(int P, const uint32_t* __restrict_
 // deterministic: positive-float depth bits ascending, ties in ascending Gaussian index -- the
 // order the reference gets from its stable radix sort on tile<<32|depth over instances emitted
 // in index order (cr/rasterizer_impl.cu:66-99,255-260).
-constexpr int RANK_MERGE_MAX = 1024;  // chunked rank sort + merge below, bitonic network above
+constexpr int RANK_MERGE_MAX = GCR_RANK_MERGE_MAX;  // chunked rank sort + merge (gcr_sort.h) up to here, bitonic network above
 // Threads per workgroup of the tile-table kernels (template parameter TT_THREADS): 1024, one workgroup per CU, 256
 // groups (gcr_tile_table_groups: fewer, fatter groups = fewer table rows through HBM; rounds 1-2 ran 512 groups of 512
 // threads while two tables fit a CU's LDS).  At 4K a table (130 KiB) only leaves room for one workgroup per CU anyway;
@@ -144,7 +144,8 @@ __global__ __launch_bounds__(TT_THREADS) void k_tile_table(int T, int gx, int G,
                                                            unsigned long long* __restrict__ host_word,
                                                            unsigned int seq,
                                                            const unsigned long long* __restrict__ block_tiles,
-                                                           const uint4* __restrict__ banded, int banded_capacity) {
+                                                           const uint4* __restrict__ banded, int banded_capacity,
+                                                           int tile_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gcr_smem[];
   uint32_t* cnt = reinterpret_cast<uint32_t*>(gcr_smem);  // [T]
   __shared__ uint32_t pre[GCR_K1_MAX_BLOCKS + 1];         // prefix of ALL K1 blocks' list lengths
@@ -262,12 +263,19 @@ __global__ __launch_bounds__(TT_THREADS) void k_tile_table(int T, int gx, int G,
     const uint32_t rx = sv.z, ry = sv.w;
     const uint32_t minx = rx & 0xffffu, maxx = rx >> 16, miny = ry & 0xffffu, maxy = ry >> 16;
     const uint64_t key = ((uint64_t)sv.y << 32) | sv.x;
+    // `tile_ids` (block-uniform; gcr_blend.hip "tile ids"): the frame's blend ranks its tiles itself and takes the depth
+    // from the record it gathers anyway, so a segment holds the 4-byte Gaussian indices alone -- half the bytes, and a
+    // (table row, tile) run covers about half the 32-byte sectors
+    uint32_t* __restrict__ ids = reinterpret_cast<uint32_t*>(pairs);
     for (uint32_t y = miny; y < maxy; y++)
       for (uint32_t x = minx; x < maxx; x++) {
         const uint32_t t = y * (uint32_t)gx + x;
         if (SCATTER) {
           const uint32_t pos = atomicAdd(&cnt[t], 1u);  // ds_add_rtn_u32
-          pairs[pos] = key;
+          if (tile_ids)
+            ids[pos] = sv.x;
+          else
+            pairs[pos] = key;
         } else {
           atomicAdd(&cnt[t], 1u);  // ds_add_u32
         }
@@ -524,66 +532,18 @@ __global__ __launch_bounds__(256) void k_tile_sort(const uint32_t* __restrict__ 
     if (tid == 0) list[r0] = (uint32_t)pairs[r0];
     return;
   }
-  if (n <= RANK_MERGE_MAX) {
-    // Chunked rank sort + binary-search merge (one barrier).  Keys are unique, so
-    //   final position(i) = #{keys < key_i} = rank inside its own 64-key chunk
-    //                                         + sum over the other chunks of lower_bound(key_i).
-    // Phase 1: a wave's 64 keys belong to one chunk, so it counts with wave-uniform (broadcast)
-    // 16-byte LDS reads and drops each key at its rank into the sorted copy `sb`.
-    // Phase 2: six-step binary searches in the other sorted chunks.
-    const int nchunks = (n + 63) >> 6, npad = nchunks << 6;
-    uint64_t* sb = s + npad;
-    for (int i = tid; i < npad; i += 256) s[i] = i < n ? pairs[r0 + i] : ~0ull;
-    __syncthreads();
-    const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s);
+  if (n <= RANK_MERGE_MAX) {  // chunked rank sort + binary-search merge (gcr_sort.h)
     uint64_t mine[RANK_MERGE_MAX / 256];
-    uint32_t rank[RANK_MERGE_MAX / 256];
+    uint32_t pos[RANK_MERGE_MAX / 256];
 #pragma unroll
     for (int e = 0; e < RANK_MERGE_MAX / 256; e++) {
       const int i = tid + e * 256;
-      if (i < npad) {  // wave-uniform: npad is a multiple of 64
-        const int c = i >> 6;
-        const uint64_t key = s[i];
-        uint32_t r = 0;
-#pragma unroll 8
-        for (int j = 0; j < 32; j++) {
-          const ulonglong2 kk = s2[c * 32 + j];
-          r += (kk.x < key ? 1u : 0u) + (kk.y < key ? 1u : 0u);
-        }
-        mine[e] = key;
-        rank[e] = r;
-        if (i < n) sb[c * 64 + r] = key;  // pads (~0) rank behind every real key of the chunk
-      }
+      mine[e] = i < n ? pairs[r0 + i] : ~0ull;
     }
-    __syncthreads();
-    const int last_real = n - (nchunks - 1) * 64;  // real keys in the last chunk (1..64)
+    gcr_rank_merge(s, n, mine, pos, tid);
 #pragma unroll
-    for (int e = 0; e < RANK_MERGE_MAX / 256; e++) {
-      const int i = tid + e * 256;
-      if (i < n) {
-        const int c = i >> 6;
-        const uint64_t key = mine[e];
-        uint32_t pos = rank[e];
-        for (int c2 = 0; c2 < nchunks; c2++) {
-          if (c2 == c) continue;  // wave-uniform
-          const uint64_t* chunk = sb + c2 * 64;
-          const int len = c2 == nchunks - 1 ? last_real : 64;
-          int lo = 0, hi = len;  // lower_bound: first index whose key is not < key
-#pragma unroll
-          for (int step = 0; step < 7; step++) {
-            if (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              if (chunk[mid] < key)
-                lo = mid + 1;
-              else
-                hi = mid;
-            }
-          }
-          pos += (uint32_t)lo;
-        }
-        list[r0 + pos] = (uint32_t)key;
-      }
-    }
+    for (int e = 0; e < RANK_MERGE_MAX / 256; e++)
+      if (tid + e * 256 < n) list[r0 + pos[e]] = (uint32_t)mine[e];
     return;
   }
   int N2 = 2;
@@ -839,11 +799,11 @@ hipError_t gcr_launch_tile_count(int T, int gx, int NG, int G, int nblocks_k1, i
   if (tile_table_wide(T))
     k_tile_table<false, 1024><<<NG, 1024, (size_t)T * sizeof(uint32_t), s>>>(
         T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, nullptr, nullptr, nullptr, nullptr, nullptr,
-        frame, 0ull, 0ull, host_R, seq, block_tiles, banded, banded_capacity);
+        frame, 0ull, 0ull, host_R, seq, block_tiles, banded, banded_capacity, 0);
   else
     k_tile_table<false, 512><<<NG, 512, (size_t)T * sizeof(uint32_t), s>>>(
         T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, nullptr, nullptr, nullptr, nullptr, nullptr,
-        frame, 0ull, 0ull, host_R, seq, block_tiles, banded, banded_capacity);
+        frame, 0ull, 0ull, host_R, seq, block_tiles, banded, banded_capacity, 0);
   k_table_colscan<<<(T + 63) / 64, 1024, 0, s>>>(table, NG, T, tile_total, tile_local, blk_total, frame);
   return hipGetLastError();
 }
@@ -854,17 +814,17 @@ hipError_t gcr_launch_tile_scatter(int T, int gx, int NG, int G, int nblocks_k1,
                                    const uint32_t* blk_total, uint32_t* ranges, uint64_t* pairs,
                                    unsigned long long* frame, unsigned long long cap_instances,
                                    unsigned long long cap_list, unsigned long long* host_longest,
-                                   const uint4* banded, int banded_capacity, hipStream_t s) {
+                                   const uint4* banded, int banded_capacity, bool tile_ids, hipStream_t s) {
   hipError_t e = tile_table_attr();
   if (e != hipSuccess) return e;
   if (tile_table_wide(T))
     k_tile_table<true, 1024><<<NG, 1024, (size_t)T * sizeof(uint32_t), s>>>(
         T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, tile_total, tile_local, blk_total, ranges, pairs,
-        frame, cap_instances, cap_list, host_longest, 0u, nullptr, banded, banded_capacity);
+        frame, cap_instances, cap_list, host_longest, 0u, nullptr, banded, banded_capacity, tile_ids ? 1 : 0);
   else
     k_tile_table<true, 512><<<NG, 512, (size_t)T * sizeof(uint32_t), s>>>(
         T, gx, tile_table_G(G), nblocks_k1, chunk, vis_rec, vis_count, table, tile_total, tile_local, blk_total, ranges, pairs,
-        frame, cap_instances, cap_list, host_longest, 0u, nullptr, banded, banded_capacity);
+        frame, cap_instances, cap_list, host_longest, 0u, nullptr, banded, banded_capacity, tile_ids ? 1 : 0);
   return hipGetLastError();
 }
 

@@ -40,6 +40,14 @@ constexpr int K6_SENT_SLOT = 223;
 constexpr int K6_LIST_STRIDE = 232;          // bytes per sub-row list: 223 entries + 3 pipeline pads, 8-aligned
 static_assert(GCR_PIECE_MAX <= K6_SENT_SLOT, "a K6 chunk must leave slot 255 to the sentinel");
 constexpr uint32_t NO_ENTRY = 0xFFFFFFFFu;
+// K6's LDS, one block: 224 staged records | 256 block masks | 4 x 8 sub-row lists
+constexpr int K6_LDS_MASK = (K6_SENT_SLOT + 1) * (int)ENTRY_BYTES;
+constexpr int K6_LDS_LIST = K6_LDS_MASK + CHUNK * 4;
+constexpr int K6_LDS_BYTES = K6_LDS_LIST + 4 * 8 * K6_LIST_STRIDE;
+static_assert(K6_LDS_MASK % 16 == 0 && K6_LDS_LIST % 16 == 0, "K6's LDS arrays are read and filled as quads");
+static_assert(GCR_BLEND_RANKS_MAX == GCR_RANK_MERGE_MAX, "the host sends frames with lists up to here to the SORT kernels");
+static_assert(2 * GCR_RANK_MERGE_MAX * 8 <= K6_LDS_BYTES, "k6_rank_ids ranks up to GCR_RANK_MERGE_MAX keys in K6's LDS");
+static_assert(2 * CHUNK * 8 <= 4 * 8 * K6_LIST_STRIDE, "a one-chunk tile is ranked in the list area while its records are staged");
 
 // One staged list entry: 48 bytes, read by the blend loops as three 16-byte quads at one address.
 //   K6: a = (x, y, -0.5*conic.x, -conic.y)   b = (-0.5*conic.z, opacity, r, g)   c = (b, pmin, -, -)
@@ -189,13 +197,21 @@ GCR_DEV K7Behind k7_behind(const float4* __restrict__ ckpt, uint32_t sbase, uint
 //         NON-FINITE colour poisons every pixel of the 2x4 blocks whose list holds the Gaussian (the conservative
 //         block mask; upstream: only pixels it contributes to), and an accumulator that is exactly -0.0 (needs a
 //         colour below 1e-40) may become +0.0.
-//   * SORT (template): the workgroup sorts its own tile first.  GaussianCity's scenes have ~150 entries per tile, and
-//     sorting 150 keys is a microsecond of work for the workgroup that is about to gather them anyway -- as a
-//     separate kernel (K4) it is a latency-bound launch of 18 us on the frame's critical path.  Lists of up to one
-//     chunk (223 keys) are rank-sorted in LDS (every thread counts the keys below its own through wave-uniform 16-byte
-//     reads; unique keys => rank = position); a longer list -- only possible when the caller's length hint was
-//     stale, the host then switches to the K4 path -- is ranked the same way through global loads: slow, correct.
-//     The sorted indices are also written to `list_out` for the backward.
+//   * SORT (template; frames in the "tile ids" mode, gcr_api.hip enqueue_render_lds): the tile's segment holds the 4-byte
+//     Gaussian indices in the scatter's arbitrary order and the workgroup ranks its own tile -- the per-tile sort kernel
+//     (K4) is not launched, and its `pairs` -> `list` round trip through memory is gone.  The sort key (depth bits << 32 |
+//     index) is formed from the record the staging thread gathers anyway, and the ranking is K4's (gcr_sort.h
+//     gcr_rank_merge: rank inside 64-key chunks, binary-search merge; unique keys => rank = position):
+//       - a list of one chunk (<= 223 entries; GaussianCity's tiles: mean 145, p90 187): every thread fetches its
+//         entry's depth, the keys are ranked in the list area of the LDS, and the thread gathers and stages its entry AT
+//         ITS RANK.  (Gathering the whole record first and holding it across the rank spilt 12-19 registers to scratch;
+//         parked in the thread's own LDS slot and moved after the rank it still spilt; the depth's cache line is the
+//         record's, so the record gather that follows hits.)  Frames whose buffers may be read again (not image-only
+//         ones) also store the sorted indices to `list_out` and the tile's lazy-sort state (sorted whole);
+//       - a longer list of up to GCR_RANK_MERGE_MAX entries is ranked in front of the walk from the depths alone, in all
+//         of the kernel's LDS, written to `list_out` and walked from there like a sorted list;
+//       - beyond that -- only possible when the caller's length hint was stale -- k6_rank_ids counts through global
+//         memory: slow, correct.
 // The step's wave-uniform skip ("no lane of the wave is in range of its sub-row's entry") is compiled OUT: with eight
 // sub-rows on eight different entries it almost never fires, the body is exact for a wave without a lane in range (every use
 // is behind a select), and without the branch the two steps of a trip are one basic block: round 4 A/B at C3, same box, blend
@@ -239,6 +255,48 @@ __device__ __noinline__ uint32_t k6_lazy_extend(uint64_t* s, const uint64_t* key
   }
   __syncthreads();
   return ns;
+}
+
+// K6's SORT instantiations ("tile ids"), a list longer than one chunk: ids[0, n) are the tile's Gaussian indices in any
+// order; out[0, n) receives them in blend order, i.e. by ascending (depth bits << 32 | index), the depth gathered from
+// the records (the third quad's .y: what the scatter builds its 8-byte keys from).  Up to GCR_RANK_MERGE_MAX keys are
+// ranked in LDS (`s`: all of K6's LDS, nothing of it is live yet); a longer list -- only possible when the caller's
+// length hint was stale -- parks its keys in `scratch` (the tile's segment of the spare key buffer) and every key
+// counts the smaller ones through global loads: slow, correct.  Inlined: it runs in front of the walk, where nothing but
+// the pixels' start state is live (as a real call it cost the kernel 68 bytes of stack).
+GCR_DEV void k6_rank_ids(uint64_t* s, const uint32_t* __restrict__ ids, const float4* __restrict__ rec,
+                                         uint64_t* __restrict__ scratch, uint32_t n, uint32_t* __restrict__ out) {
+  const int tid = threadIdx.x;
+  if (n <= (uint32_t)GCR_RANK_MERGE_MAX) {
+    uint64_t key[GCR_RANK_MERGE_MAX / 256];
+    uint32_t pos[GCR_RANK_MERGE_MAX / 256];
+#pragma unroll
+    for (int e = 0; e < GCR_RANK_MERGE_MAX / 256; e++) {
+      const uint32_t i = (uint32_t)tid + (uint32_t)e * 256u;
+      key[e] = ~0ull;
+      if (i < n) {
+        const uint32_t id = ids[i];
+        key[e] = ((uint64_t)__float_as_uint(rec[(size_t)id * GCR_REC_QUADS + 2].y) << 32) | id;
+      }
+    }
+    gcr_rank_merge(s, (int)n, key, pos, tid);
+#pragma unroll
+    for (int e = 0; e < GCR_RANK_MERGE_MAX / 256; e++)
+      if ((uint32_t)tid + (uint32_t)e * 256u < n) out[pos[e]] = (uint32_t)key[e];
+  } else {
+    for (uint32_t i = tid; i < n; i += 256u) {
+      const uint32_t id = ids[i];
+      scratch[i] = ((uint64_t)__float_as_uint(rec[(size_t)id * GCR_REC_QUADS + 2].y) << 32) | id;
+    }
+    __syncthreads();  // workgroup-scope visibility of the keys
+    for (uint32_t i = tid; i < n; i += 256u) {
+      const uint64_t mine = scratch[i];
+      uint32_t rank = 0;
+      for (uint32_t j = 0; j < n; j++) rank += scratch[j] < mine ? 1u : 0u;
+      out[rank] = (uint32_t)mine;
+    }
+  }
+  __syncthreads();  // the LDS is free again; the sorted indices are visible to the workgroup
 }
 
 // THE FRAME GATE of an asynchronous frame (gcr_forward_async, include/gcr.h).  A frame that fitted its binning buffer
@@ -296,9 +354,28 @@ __device__ __noinline__ void k6_frame_gate(unsigned long long* words, unsigned i
 // image-only frame reads what that pass wrote.
 template <bool SORT, bool STATE, bool PIXSTATE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_blend_fwd(const GcrBlendArgs a) {
-  __shared__ StagedEntry sE[K6_SENT_SLOT + 1];
-  __shared__ uint32_t sMask[CHUNK];
-  __shared__ __attribute__((aligned(16))) uint8_t sList[4][8][K6_LIST_STRIDE];  // [wave][sub-row]: slots of sE, list order
+  // LDS: the staged records, their block masks, and [wave][sub-row] lists of slots of sE in list order.  The SORT kernels
+  // declare them as ONE block, because a list longer than a chunk borrows all of it before the walk (k6_rank_ids); the
+  // others keep the three arrays they always had (as one block their register assignment came out one spill worse).
+  StagedEntry* sE;
+  uint32_t* sMask;
+  uint8_t(*sList)[8][K6_LIST_STRIDE];
+  unsigned char* k6_lds;
+  if constexpr (SORT) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_block[K6_LDS_BYTES];
+    k6_lds = lds_block;
+    sE = reinterpret_cast<StagedEntry*>(lds_block);
+    sMask = reinterpret_cast<uint32_t*>(lds_block + K6_LDS_MASK);
+    sList = reinterpret_cast<uint8_t(*)[8][K6_LIST_STRIDE]>(lds_block + K6_LDS_LIST);
+  } else {
+    __shared__ StagedEntry lds_E[K6_SENT_SLOT + 1];
+    __shared__ uint32_t lds_mask[CHUNK];
+    __shared__ __attribute__((aligned(16))) uint8_t lds_list[4][8][K6_LIST_STRIDE];
+    k6_lds = reinterpret_cast<unsigned char*>(lds_E);
+    sE = lds_E;
+    sMask = lds_mask;
+    sList = lds_list;
+  }
 
   if (a.frame != nullptr && a.frame[2] == 0ull) {  // speculative launch vetoed
     if (a.gate_words != nullptr && blockIdx.x == 0 && threadIdx.x == 0) k6_frame_gate(a.gate_words, a.gate_seq, a.gate_polls);
@@ -309,6 +386,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const int tid = threadIdx.x;
   const float tile_x0 = (float)(tx * GCR_TILE_X), tile_y0 = (float)(ty * GCR_TILE_Y);
   const uint32_t r0 = a.ranges[2 * tile], r1 = a.ranges[2 * tile + 1];
+  // SORT: the per-tile sort kernel did not run on this frame; what it would have said of the tile's list (gcr_sort.h
+  // "lazy tile sort": sorted whole -- by the end of this workgroup; a tile outside the window is not sorted at all)
+  if (SORT && PIXSTATE && a.lazy != nullptr && tid == 0)
+    a.lazy[tile] = make_uint4(gcr_tile_in_window(a, tx, ty) ? r1 - r0 : 0u, 0u, ~0u, ~0u);
   if (!gcr_tile_in_window(a, tx, ty)) {
     // none of this tile's pixels is wanted (gcr_camera.win_*): nothing to blend, and no work for the backward either
     if (STATE && a.work != nullptr) {
@@ -336,7 +417,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     o[10] = __builtin_readcyclecounter();
   }
 #endif
-  if (tid == 0) {  // the sentinel: behind everything that borrows the record buffer (sort keys: 2 KB, lazy sort: 10 KB)
+  if (!SORT && tid == 0) {  // the sentinel: behind everything that borrows the record buffer (lazy sort: 10 KB)
     sE[K6_SENT_SLOT].a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     sE[K6_SENT_SLOT].b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     sE[K6_SENT_SLOT].c = make_float4(0.0f, __builtin_inff(), 0.0f, 0.0f);
@@ -366,40 +447,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   uint32_t lz_sorted = (uint32_t)max(total, 0);
   if (!SORT && a.lazy != nullptr) lz_sorted = a.lazy[tile].x;
 
-  uint32_t sorted_id = 0;  // SORT, total <= CHUNK: the Gaussian of list position `tid`
-  if (SORT && total > 0) {
-    const uint64_t* __restrict__ seg = a.pairs + r0;
-    uint32_t* __restrict__ out = a.list_out + r0;
-    if (total <= K6_SENT_SLOT) {
-      // keys into LDS (aliasing the record buffer, which is not live yet), padded with ~0 to a multiple of 2
-      uint64_t* sKey = reinterpret_cast<uint64_t*>(sE);
-      const uint64_t mine = tid < total ? seg[tid] : ~0ull;
-      sKey[tid] = mine;
-      __syncthreads();
-      const ulonglong2* k2 = reinterpret_cast<const ulonglong2*>(sKey);
-      uint32_t rank = 0;
-      for (int j = 0; j < (total + 1) / 2; j++) {  // wave-uniform (broadcast) reads
-        const ulonglong2 kk = k2[j];
-        rank += (kk.x < mine ? 1u : 0u) + (kk.y < mine ? 1u : 0u);
-      }
-      __syncthreads();  // every thread has read the keys: sMask may be written (it does not alias, sE does)
-      if (tid < total) {
-        sMask[rank] = (uint32_t)mine;  // sMask doubles as the sorted index list until the staging overwrites it
-        out[rank] = (uint32_t)mine;
-      }
-      __syncthreads();
-      sorted_id = tid < total ? sMask[tid] : 0u;
-      __syncthreads();  // sMask / sE are free for the staging below
-    } else {
-      // stale length hint: rank through global memory (n^2 / 256 compares per thread), then blend from list_out
-      for (int i = tid; i < total; i += 256) {
-        const uint64_t mine = seg[i];
-        uint32_t rank = 0;
-        for (int j = 0; j < total; j++) rank += seg[j] < mine ? 1u : 0u;
-        out[rank] = (uint32_t)mine;
-      }
-      __syncthreads();  // workgroup-scope visibility of list_out for the staging loads below
-    }
+  // SORT ("tile ids"): the tile's segment holds unsorted Gaussian indices.  A list of one chunk is ranked while it is
+  // staged (in the walk below); a longer one is ranked here, from the depths alone, and walked from list_out.
+  const bool rank_staged = SORT && cs == total;  // block-uniform (then total <= a.piece <= 223)
+  if (SORT && total > 0 && !rank_staged)
+    k6_rank_ids(reinterpret_cast<uint64_t*>(k6_lds), reinterpret_cast<const uint32_t*>(a.pairs) + r0, a.rec, a.key_scratch + r0,
+                (uint32_t)total, a.list_out + r0);
+  if (SORT && tid == 0) {  // (SORT: the sentinel is written once k6_rank_ids has used all of the LDS)
+    sE[K6_SENT_SLOT].a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    sE[K6_SENT_SLOT].b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    sE[K6_SENT_SLOT].c = make_float4(0.0f, __builtin_inff(), 0.0f, 0.0f);
   }
 
 // One list entry (record QA/QB/QC at byte offset OFF) against this lane's pixel.
@@ -480,9 +537,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     entered++;
     const int n = min(cs, total - base);
     uint32_t my_mask = 0;
+    uint32_t slot = (uint32_t)tid;  // the entry's list position inside the chunk = its slot of sE / sMask
+    uint32_t id = 0;
+    if (SORT && rank_staged) {
+      // SORT, the whole list in this chunk (base == 0, n == total): the segment holds the indices in any order.  Every
+      // thread fetches its entry's depth (the third quad's .y: the bits the 8-byte keys are built from), the workgroup
+      // ranks the (depth << 32 | index) keys -- in the list area, free until the lists are built behind the barrier
+      // below -- and the entry is gathered and staged at its rank.  (The whole record gathered before the rank would
+      // sit in twelve registers across it, which this kernel does not have; the depth's cache line is the record's.)
+      int t = threadIdx.x;  // (behind an opaque barrier, as in the walk: nothing derived from it here is kept across the walk)
+      asm volatile("" : "+v"(t));
+      uint64_t key[1] = {~0ull};
+      if (t < n) {
+        id = reinterpret_cast<const uint32_t*>(a.pairs)[r0 + t];
+        key[0] = ((uint64_t)__float_as_uint(a.rec[(size_t)id * GCR_REC_QUADS + 2].y) << 32) | id;
+      }
+      uint32_t pos[1];
+      gcr_rank_merge<1, 2>(reinterpret_cast<uint64_t*>(&sList[0][0][0]), n, key, pos, t);
+      if (t < n) {
+        slot = pos[0];
+        if (PIXSTATE) a.list_out[r0 + slot] = id;  // (an image-only frame: nobody reads its buffers)
+      }
+    }
     if (tid < n) {
-      const uint32_t id = !SORT ? a.list[r0 + base + tid]
-                                : ((total <= K6_SENT_SLOT && cs == total) ? sorted_id : a.list_out[r0 + base + tid]);
+      if (!SORT)
+        id = a.list[r0 + base + tid];
+      else if (!rank_staged)
+        id = a.list_out[r0 + base + tid];
       const float4* __restrict__ rec = a.rec + (size_t)id * GCR_REC_QUADS;
 #ifdef GCR_EXPERIMENTS  // hop clocks of thread 0's first entry: ids arrived (the address below needs them) / records arrived
       if (a.clock_buf != nullptr && tid == 0 && base == 0) {
@@ -501,19 +582,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       my_mask = gcr_block_mask_2x4(q0.x, q0.y, q0.z, q0.w, q1.x, pmin, tile_x0, tile_y0);
       const float4 sa = make_float4(q0.x, q0.y, -0.5f * q0.z, -q0.w), sb = make_float4(-0.5f * q1.x, q1.y, q1.z, q1.w);
       const float4 sc = make_float4(q2.x, pmin, 0.0f, 0.0f);
-      sE[tid].a = sa;
-      sE[tid].b = sb;
-      sE[tid].c = sc;
+      sE[slot].a = sa;
+      sE[slot].b = sb;
+      sE[slot].c = sc;
       if (STATE && a.staged_out != nullptr) {  // the backward's records, in list order: one coalesced block per piece there
-        float4* __restrict__ so = a.staged_out + (size_t)(r0 + (uint32_t)base + (uint32_t)tid) * 3;
+        float4* __restrict__ so = a.staged_out + (size_t)(r0 + (uint32_t)base + slot) * 3;
         so[0] = sa;
         so[1] = sb;
         so[2] = sc;
       }
     }
-    sMask[tid] = my_mask;
+    sMask[slot] = my_mask;  // (a thread without an entry: its own slot, behind the chunk's n entries)
     if (STATE && tid < n && a.mask_out != nullptr)  // reused by the backward, whose rows are 4x4 blocks
-      a.mask_out[r0 + base + tid] = (uint16_t)gcr_block_mask_4x4_of_2x4(my_mask);
+      a.mask_out[r0 + base + slot] = (uint16_t)gcr_block_mask_4x4_of_2x4(my_mask);
     __syncthreads();
 #ifdef GCR_EXPERIMENTS  // first chunk, wave 0: records staged / lists built / walk done
     if (a.clock_buf != nullptr && tid == 0 && base == 0) a.clock_buf[(size_t)tile * 16 + 4] = __builtin_readcyclecounter();
@@ -1315,8 +1396,8 @@ static void launch_blend_fwd_state(const GcrBlendArgs& a, int T, hipStream_t s) 
 #endif
   if (a.work != nullptr)  // the backward's state is wanted (gcr_camera.backward == 1, or gcr_backward's regeneration pass)
     k_blend_fwd<SORT, true, true><<<T, 256, pad, s>>>(a);
-  else if (!SORT && a.image_only)  // (under "sort_in_blend" an image-only frame runs the kernel of every inference frame)
-    k_blend_fwd<false, false, false><<<T, 256, pad, s>>>(a);
+  else if (a.image_only)
+    k_blend_fwd<SORT, false, false><<<T, 256, pad, s>>>(a);
   else
     k_blend_fwd<SORT, false, true><<<T, 256, pad, s>>>(a);
 }

@@ -211,6 +211,10 @@ static inline __host__ __device__ unsigned long long gcr_piece_slots(unsigned lo
                                 // frame words' slot in the geometry buffer is 128 bytes, words 10..15 are free
 // default of the process-wide option "band_sort_min" (instances of the caller's capacity guess; tuned in round 6)
 #define GCR_BAND_SORT_MIN_DEFAULT 6000000
+#define GCR_BLEND_RANKS_DEFAULT 1  // default of the process-wide option "blend_ranks" (gcr_api.hip "tile ids")
+// longest tile list (the caller's expectation, or the exact maximum on the staged path) up to which a frame takes the
+// "tile ids" mode: what the forward blend ranks in its LDS (gcr_sort.h GCR_RANK_MERGE_MAX)
+#define GCR_BLEND_RANKS_MAX 1024
 #define GCR_FRAME_BANDED 9      // != 0: the tile table of this frame was counted over the band-sorted survivors
                                 // (gcr_binning.hip "band sort"; set by the count kernel, read by the scatter kernel)
 // Has the forward left the backward's state in a buffer of `binning_bytes`?  (frame word 3 is zeroed by the count
@@ -222,8 +226,10 @@ static inline __host__ __device__ bool gcr_frame_has_state(const unsigned long l
 struct GcrBlendArgs {
   const uint32_t* ranges;  // [T][2]
   const uint32_t* list;    // sorted instance -> Gaussian
-  const uint64_t* pairs;   // fwd, sort-in-kernel variant: the tile segments of unsorted (depth << 32 | index) keys
+  const uint64_t* pairs;   // fwd: the tile segments of unsorted (depth << 32 | index) keys (lazy sort); "tile ids" frames: of
+                           // unsorted 4-byte Gaussian indices in the same region
   uint32_t* list_out;      // ... and where the sorted indices go (the backward walks them)
+  uint64_t* key_scratch;   // fwd, "tile ids" frames: the spare key buffer (a list beyond GCR_RANK_MERGE_MAX parks its keys there)
   const float4* rec;
   int W, H, gx, gy;
   const float* bg;
@@ -304,7 +310,7 @@ hipError_t gcr_launch_tile_scatter(int T, int gx, int NG, int G, int nblocks_k1,
                                    const uint32_t* blk_total, uint32_t* ranges, uint64_t* pairs,
                                    unsigned long long* frame, unsigned long long cap_instances,
                                    unsigned long long cap_list, unsigned long long* host_longest,
-                                   const uint4* banded, int banded_capacity, hipStream_t s);
+                                   const uint4* banded, int banded_capacity, bool tile_ids, hipStream_t s);
 hipError_t gcr_launch_scatter_instances(int nblocks, int chunk, const uint32_t* vis_list,
                                         const uint32_t* vis_count, const float4* rec, int gx,
                                         uint32_t* tile_cursor, uint64_t* pairs, const uint32_t* ranges, int T,

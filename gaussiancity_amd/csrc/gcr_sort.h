@@ -38,6 +38,73 @@ GCR_DEV void gcr_bitonic_sort_lds(uint64_t* s, int N2, int tid) {
   __syncthreads();
 }
 
+// Chunked rank sort + binary-search merge of n <= 256 * E unique keys (one barrier between the phases), used by the tile
+// sort kernel and by the forward blend that ranks its own tile (gcr_blend.hip "tile ids").  Thread `tid` hands in the
+// keys of the elements tid + 256 e (~0 for an element beyond n) and gets their final positions:
+//   position(i) = #{keys < key_i} = rank inside its own 64-key chunk + sum over the other chunks of lower_bound(key_i).
+// Phase 1: a wave's 64 keys belong to one chunk, so it counts with wave-uniform (broadcast) 16-byte LDS reads and drops
+// each key at its rank into the sorted copy of its chunk.  Phase 2: six-step binary searches in the other sorted chunks.
+// `s`: 2 * (n rounded up to 64) 64-bit LDS words nobody else is using when the call starts; no barrier at the end --
+// the caller puts one in front of the next writer of `s`.  UNROLL: 16-byte reads of phase 1 in flight together (four
+// registers each: the forward blend, which has none to spare, asks for fewer than the sort kernel).
+constexpr int GCR_RANK_MERGE_MAX = 1024;
+template <int E, int UNROLL = 8>
+GCR_DEV void gcr_rank_merge(uint64_t* s, int n, const uint64_t (&key)[E], uint32_t (&pos)[E], int tid) {
+  const int nchunks = (n + 63) >> 6, npad = nchunks << 6;
+  uint64_t* sb = s + npad;
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int i = tid + e * 256;
+    if (i < npad) s[i] = key[e];
+  }
+  __syncthreads();
+  const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s);
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int i = tid + e * 256;
+    pos[e] = 0;
+    if (i < npad) {  // wave-uniform: npad is a multiple of 64
+      const int c = i >> 6;
+      uint32_t r = 0;
+#pragma unroll UNROLL
+      for (int j = 0; j < 32; j++) {
+        const ulonglong2 kk = s2[c * 32 + j];
+        r += (kk.x < key[e] ? 1u : 0u) + (kk.y < key[e] ? 1u : 0u);
+      }
+      pos[e] = r;
+      if (i < n) sb[c * 64 + r] = key[e];  // pads (~0) rank behind every real key of the chunk
+    }
+  }
+  __syncthreads();
+  const int last_real = n - (nchunks - 1) * 64;  // real keys in the last chunk (1..64)
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int i = tid + e * 256;
+    if (i < n) {
+      const int c = i >> 6;
+      uint32_t p = pos[e];
+      for (int c2 = 0; c2 < nchunks; c2++) {
+        if (c2 == c) continue;  // wave-uniform
+        const uint64_t* chunk = sb + c2 * 64;
+        const int len = c2 == nchunks - 1 ? last_real : 64;
+        int lo = 0, hi = len;  // lower_bound: first index whose key is not < key
+#pragma unroll
+        for (int step = 0; step < 7; step++) {
+          if (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (chunk[mid] < key[e])
+              lo = mid + 1;
+            else
+              hi = mid;
+          }
+        }
+        p += (uint32_t)lo;
+      }
+      pos[e] = p;
+    }
+  }
+}
+
 // A tile list LONGER than the LDS this launch was given (dense general 3DGS scenes beyond the 4096-key maximum;
 // or simply a list that outgrew the caller's length hint -- GaussianCity's own scenes have ~150 entries per
 // tile): the same workgroup sorts it in three steps, everything else of the frame is untouched.

@@ -127,9 +127,8 @@ typedef struct gcr_camera {
                           the image is the same bits.  The state-only pass above stores final_T / n_contrib itself (for
                           every frame: the same bits where they were there already), so a backward after it works on an
                           image-only frame as on a frame rendered with 0; gcr_backward directly on an image-only frame
-                          gives the same NaN gradients.  Under option "sort_in_blend" an image-only frame is rendered
-                          by the kernel of a frame with 0 and its per-pixel state is written after all: do not rely on
-                          either.  Any other value: as 0 */
+                          gives the same NaN gradients.  (In the "tile ids" mode -- option "blend_ranks" -- an
+                          image-only frame does not store its sorted tile lists either.)  Any other value: as 0 */
   const gcr_options *options; /* HOST pointer or NULL (= all defaults); read during the call only */
   int32_t out_u8;      /* !=0 (forward of an inference frame only, backward == 0): out_color is NOT float [3,H,W] but the
                           video frame the reference's render loop makes of it with five elementwise kernels
@@ -293,10 +292,10 @@ int gcr_forward_preprocess(const gcr_camera *cam, const gcr_gaussians *g, void *
  * gcr_binning_bytes(binning_capacity) bytes; binning_capacity is the caller's guess of
  * num_rendered (e.g. 1.5 x the previous frame's value; 0 = no guess) and tile_list_capacity the
  * longest per-tile list it expects (e.g. the previous frame's; 0 = 4096).  The list expectation only
- * sizes the LDS of the per-tile sort (1.5 x the expectation; with option "sort_in_blend" an
- * expectation <= 384 moves the sort into the forward blend) and never affects the result: a list
+ * sizes the LDS of the per-tile sort (1.5 x the expectation; with option "blend_ranks", the default,
+ * an expectation <= 1024 moves the sort into the forward blend) and never affects the result: a list
  * longer than expected is sorted by a slower path of the same kernel (any length; the sort kernel
- * merges sorted runs through the spare key buffer).  All kernels of the frame are enqueued at once --
+ * merges sorted runs through the spare key buffer, the blend counts through it).  All kernels of the frame are enqueued at once --
  * they take the tile ranges from device memory and a device-side flag vetoes them if
  * binning_capacity was too small -- and the host waits only for num_rendered, which the exact
  * projection pass accumulates and the next kernel's first workgroup stores into a pinned host word the calling
@@ -399,8 +398,13 @@ int64_t gcr_rasterize_forward(gcr_resize_fn geometry_buffer, void *geometry_user
  *   "force_radix"  1: always use the global LSD radix sort path for binning          default 0
  *   "force_global_cursor" 1: count/scatter with device-scope atomics instead of LDS  default 0
  *                     tile tables (the variant used when T*4 B does not fit in LDS)
- *   "sort_in_blend" 1: the forward blend sorts its own tile when the expected longest list  default 0
- *                     is <= 384 (one launch less: lower frame latency, lower throughput)
+ *   "blend_ranks"  (process-wide only) 1: an inference frame (gcr_camera.backward != 1) whose expected longest tile     default 1
+ *                     list is <= 1024 and that is not band-sorted takes the "tile ids" mode: the scatter writes the 4-byte Gaussian index alone into the
+ *                     tile segments, the per-tile sort kernel is not launched and the forward blend ranks its own tile by
+ *                     the depth in the records it gathers (five launches; the same order, bit for bit).  0: six launches.
+ *                     gcr_get_option("last_tile_ids") says which mode the most recently enqueued frame took (read only).
+ *   "sort_in_blend" 1: asks for the same mode whatever "blend_ranks" says, and for training frames                   default 0
+ *                     (gcr_camera.backward == 1) too (the name of the round-3 option, whose own code is gone: it read 8-byte keys and ranked every key against all others in every thread)
  *   "split_preprocess" 1: K1 as two kernels (streaming cull, then exact pass) instead of   default 0
  *                     the fused one (A/B)
  *   "deterministic_backward" 1: gcr_backward accumulates the per-Gaussian blend gradients as 64-bit       default 0
