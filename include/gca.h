@@ -29,6 +29,22 @@
  * Rounding: inputs are read as binary16, every product accumulates in fp32 on the matrix cores, the softmax
  * maximum, row sum and log-sum-exp are fp32, the probabilities and dS are rounded to binary16 as matrix-core
  * operands, out and dqkv are rounded to binary16 once, on store.
+ *
+ * The `_t` entry points take the element type of qkv, out, dout and dqkv first (gca_dtype; gca_dtypes() has a bit
+ * 1 << dtype for every one the library runs).  GCA_F16 is the above, launch for launch and bit for bit.  GCA_F32:
+ * the same arguments and layouts in binary32, strides positive multiples of 4 elements, pointers 16-byte aligned;
+ * lse, the workspace and every guarantee above are unchanged.
+ *
+ * Rounding, float32: inputs are read as binary32 and every product runs on the exact f32-input matrix instruction,
+ * a fp32 fmaf chain in the order of the summed index, one rounding per term.  Scores, the softmax maximum, row sum,
+ * log-sum-exp, the probabilities, dS and D = rowsum(dout o out) -- from the stored out -- are fp32; nothing is
+ * rounded to binary16 anywhere; out and dqkv are stored as binary32.  Exponents are in natural units: the score is
+ * the fp32 product (q . k) * scale in the forward and in the backward alike, the exponential is the hardware's exp2
+ * of the exponent times log2(e) (about 1 ulp), and lse is maximum + log(row sum) rounded to binary32 ONCE (the
+ * per-row logarithm runs in double).  The backward recomputes P = exp(score - lse) with the rounding errors of the
+ * difference and of its product with log2(e) computed and applied, so that the size of lse -- about log(keys),
+ * whatever the scores -- costs a probability nothing beyond that one rounding per row; where one key holds all the
+ * weight of a row, P is exactly 1 and 0.
  */
 #ifndef GCA_H
 #define GCA_H
@@ -43,8 +59,11 @@ extern "C" {
 
 enum gca_status { GCA_OK = 0, GCA_ERR_INVALID_ARGUMENT = -1, GCA_ERR_HIP = -2 };
 
+enum gca_dtype { GCA_F16 = 0, GCA_F32 = 1 };
+
 int gca_abi_version(void);
 const char* gca_last_error(void);
+int gca_dtypes(void); /* bit 1 << dtype for every gca_dtype the `_t` entry points run: 3 */
 
 /* size queries; 0 with a message in gca_last_error() when an argument is out of range (a valid empty problem,
  * total == 0, also gives 0 and clears the message) */
@@ -60,6 +79,17 @@ int gca_varlen_backward(const void* qkv, int64_t row_stride, int64_t slot_stride
                         const float* lse, const int32_t* cu_seqlens, int64_t nseg, int64_t total, int32_t heads,
                         int32_t head_dim, int64_t max_seqlen, float softmax_scale, void* dqkv, void* workspace,
                         size_t workspace_bytes, void* hip_stream);
+
+/* the two calls above for the element type `dtype`; an unknown dtype is GCA_ERR_INVALID_ARGUMENT */
+int gca_varlen_forward_t(int dtype, const void* qkv, int64_t row_stride, int64_t slot_stride, int64_t head_stride,
+                         const int32_t* cu_seqlens, int64_t nseg, int64_t total, int32_t heads, int32_t head_dim,
+                         int64_t max_seqlen, float softmax_scale, void* out, float* lse, void* hip_stream);
+
+int gca_varlen_backward_t(int dtype, const void* qkv, int64_t row_stride, int64_t slot_stride, int64_t head_stride,
+                          const void* out, const void* dout, int64_t dout_row_stride, int64_t dout_head_stride,
+                          const float* lse, const int32_t* cu_seqlens, int64_t nseg, int64_t total, int32_t heads,
+                          int32_t head_dim, int64_t max_seqlen, float softmax_scale, void* dqkv, void* workspace,
+                          size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
