@@ -1,4 +1,4 @@
-"""The one loader behind the five ctypes bindings (_native*.py): each binding declares its library -- symbol prefix,
+"""The one loader behind the six ctypes bindings (_native*.py): each binding declares its library -- symbol prefix,
 file name, ABI number, one signature table -- and gets lib(), check() and, where the library has them, set_option() and
 stage_ms() from here.
 

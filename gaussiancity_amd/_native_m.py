@@ -1,0 +1,27 @@
+"""ctypes binding of libgcm_hip.so (C ABI in include/gcm.h): the grouped modulated linear layer of the generator's
+attribute head, its backward, the group vector from masks and the head's output transform, all float32.  The
+declarations; gaussiancity_amd/_loader.py loads it.
+The library is the product: no Python/CPU fallback -- a missing library or failing call raises RuntimeError."""
+import ctypes as C
+
+from . import _loader
+
+ABI_VERSION = 1
+KINDS = {"xyz": 0, "rgb": 1, "scale": 2, "opacity": 3}  # enum gcm_kind, by the head's name of the attribute
+
+_vp, _sz, _i32, _i64, _f32 = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_float
+_SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argtypes)
+    "gcm_abi_version": (C.c_int, []),
+    "gcm_last_error": (C.c_char_p, []),
+    "gcm_groups_from_masks": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "gcm_modlinear_forward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _i64,
+                                        _vp]),
+    "gcm_modlinear_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "gcm_modlinear_backward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32,
+                                         _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcm_head_out": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, C.c_int, _f32, _vp, _vp]),
+}
+
+_L = _loader.Library("gcm", "libgcm_hip.so", ABI_VERSION, _SIGNATURES)
+LIB_PATH, EXPORTED_SYMBOLS = _L.path, _L.exported_symbols
+lib, check = _L.lib, _L.check

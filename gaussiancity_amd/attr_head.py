@@ -1,0 +1,124 @@
+"""The attribute head of the building generator over libgcm_hip.so (include/gcm.h):
+GaussianAttrMLP.forward with style codes runs its ModLinear stack once per building instance -- a boolean-mask gather, a
+modulated copy of the weight, three small products and a scatter each.  install() rebinds the method so that every
+instance goes through ONE grouped product per layer (modlinear.modulated_linear): the number of launches does not depend
+on the number of instances, and nothing waits for the device.
+
+  install(generator) / uninstall(generator)   rebind GaussianAttrMLP.forward of a caller's imported models.generator
+  stats() / reset_stats()                      calls that took the fused path, calls that went to the module's own method
+
+The module's own method runs, untouched, for zs None (the background generator), CPU tensors, autocast or a dtype other
+than float32, a batch other than 1, a layer that is not a ModLinear with output_mode=True, mod_bias=True, bias=None, and
+dimensions that are not multiples of 4.
+"""
+import torch
+
+from . import modlinear
+
+_STATS = {"fused_calls": 0, "original_calls": 0}
+_ORIGINAL = "_gaussiancity_amd_attr_head_original"
+
+
+def stats():
+    """Counters of this process: forwards that ran the fused kernels, forwards handed to the module's own method."""
+    return dict(_STATS)
+
+
+def reset_stats():
+    for k in _STATS:
+        _STATS[k] = 0
+
+
+def _layers(self):
+    """(shared layers, {key: its layers}) in the order the method applies them."""
+    first = self.n_shared_layers + 1
+    shared = [getattr(self, "fc_%d" % i) for i in range(2, first)]
+    own = {k: [getattr(self, "fc_%d_%s_%d" % (first, k, i)) for i in range(self.n_layers[k])] for k in self.factors.keys()}
+    return shared, own
+
+
+def _fusable(self, mod_linear, pt_feat, onehots, zs):
+    if zs is None or len(zs) == 0 or torch.is_autocast_enabled():
+        return False
+    if not (pt_feat.is_cuda and onehots.is_cuda) or pt_feat.dtype != torch.float32 or onehots.dtype != torch.float32:
+        return False
+    if pt_feat.dim() != 3 or pt_feat.shape[0] != 1 or not isinstance(self.act, torch.nn.LeakyReLU):
+        return False
+    if not self.act.negative_slope > 0 or any(k not in modlinear.KINDS for k in self.factors.keys()):
+        return False
+    shared, own = _layers(self)
+    for fc in shared + [fc for fcs in own.values() for fc in fcs]:
+        if not isinstance(fc, mod_linear) or fc.bias is not None or not (fc.output_mode and fc.mod_bias):
+            return False
+        if fc.weight.dtype != torch.float32 or fc.weight.shape[0] % 4 or fc.weight.shape[1] % 4:
+            return False
+    if self.fc_1.weight.dtype != torch.float32 or self.fc_1.weight.shape[0] % 4:
+        return False
+    return all(v["z"].dtype == torch.float32 and v["z"].is_cuda and v["idx"].dtype == torch.bool and v["idx"].is_cuda
+               for v in zs.values())
+
+
+# ---- the method of models/generator.py, written against its behaviour: the first layer, the instances in dict order
+# (a later instance's assignment wins where masks overlap), shared layers, then each key's layers, fc_out and the output
+# transform; rows that no instance covers stay zeros ---------------------------------------------------------------------
+def _forward(original, mod_linear):
+    def forward(self, pt_feat, onehots, zs):
+        """GaussianAttrMLP.forward with style codes over modlinear.modulated_linear."""
+        if not _fusable(self, mod_linear, pt_feat, onehots, zs):
+            _STATS["original_calls"] += 1
+            return original(self, pt_feat, onehots, zs)
+        n = pt_feat.shape[1]
+        slope = self.act.negative_slope
+        f = self.act(self.fc_1(pt_feat) + self.fc_m_a(onehots))[0]
+        group = modlinear.groups_from_masks([v["idx"] for v in zs.values()], n)
+        codes = torch.cat([v["z"].reshape(1, -1) for v in zs.values()])
+
+        def layer(fc, h):
+            alpha = torch.addmm(fc.bias_alpha, codes, fc.weight_alpha.t())
+            beta = torch.addmm(fc.bias_beta, codes, fc.weight_beta.t())
+            return modlinear.modulated_linear(h, fc.weight, alpha, beta, None, group, slope)
+
+        shared, own = _layers(self)
+        for fc in shared:
+            f = layer(fc, f)
+        grad = torch.is_grad_enabled()
+        covered = (group >= 0).unsqueeze(1) if grad else None
+        output = {}
+        for k, factor in self.factors.items():
+            h = f
+            for fc in own[k]:
+                h = layer(fc, h)
+            fc_out = getattr(self, "fc_out_%s" % k)
+            if not grad:
+                output[k] = modlinear.head_out(h, fc_out.weight, fc_out.bias, group, k, factor).unsqueeze(0)
+                continue
+            v = fc_out(h)
+            if k == "scale":
+                v = 1 + v.clamp(-1, 1) * factor
+            elif k == "opacity":
+                v = torch.sigmoid(v) * factor + (1 - factor)
+            else:
+                v = (torch.sigmoid(v) - 0.5) * factor
+            output[k] = torch.where(covered, v, torch.zeros((), dtype=v.dtype, device=v.device)).unsqueeze(0)
+        _STATS["fused_calls"] += 1
+        return output
+    return forward
+
+
+def install(generator_module):
+    """Rebind GaussianAttrMLP.forward of the caller's imported models.generator to the grouped kernels.  Idempotent;
+    uninstall() puts the module's own method back."""
+    if getattr(generator_module, _ORIGINAL, None) is not None:
+        return
+    modlinear.dtypes()  # loads the library: a missing build fails here, not inside a forward
+    original = generator_module.GaussianAttrMLP.forward
+    setattr(generator_module, _ORIGINAL, original)
+    generator_module.GaussianAttrMLP.forward = _forward(original, generator_module.ModLinear)
+
+
+def uninstall(generator_module):
+    original = getattr(generator_module, _ORIGINAL, None)
+    if original is None:
+        return
+    generator_module.GaussianAttrMLP.forward = original
+    delattr(generator_module, _ORIGINAL)

@@ -1,5 +1,5 @@
 // gc_host.h -- host scaffold shared by the libraries' C ABI files (gcr_api.hip, gcv_points.hip, gce_grid.hip,
-// gcs_sparse.hip, gca_attention.hip): the error string behind *_last_error, fail / fail_hip / HIP_TRY, and the stage
+// gcs_sparse.hip, gca_attention.hip, gcm_modlinear.hip): the error string behind *_last_error, fail / fail_hip / HIP_TRY, and the stage
 // timer behind option "timing" / *_get_stage_ms.  Host code only.  Everything has internal linkage, so include it
 // from ONE translation unit per library (in libgcr_hip.so that is gcr_api.hip): a second one would get a second error
 // string.  Define GC_ERR_HIP, the library's status code for a HIP runtime error, before including it.

@@ -1,0 +1,628 @@
+// gcm_modlinear.hip -- MI355X (gfx950) kernels + C ABI (include/gcm.h) of the generator's attribute head: the grouped
+// modulated linear layer y = act((x o alpha[g]) W^T + beta[g] + bias), its deterministic backward, the group vector
+// from the instances' masks and the head's output transform.  DESIGN.md section 17.
+//
+// The three products (forward, dX = dpre W, dW = dpre^T xa) run on v_mfma_f32_16x16x4_f32 with the float32 tiles of
+// gcs_mfma.h: a 64 x 64 workgroup tile, 4 waves as 2 x 2, a wave owns 32 x 32 outputs = 2 x 2 accumulators of 4 VGPRs
+// (C/D: col = lane & 15, row = 4 * (lane >> 4) + reg), slices of 16 along the summed index staged in LDS, the global
+// loads of slice c + 1 issued before the MFMAs of slice c.  What differs from a plain GEMM is on the way in and out:
+//   forward   A = x o alpha[group[row]] (one fp32 product per element, rows of one tile may be of different groups);
+//             the epilogue adds beta[group[row]], then bias, applies LeakyReLU, and stores 0 for a row without a group.
+//   dX        A = dpre = dy o (y > 0 ? 1 : slope), 0 for a row without a group; the epilogue stores
+//             dx = dxs o alpha[group[row]] and, for dalpha, t = dxs o x into the workspace.
+//   dW        both operands are staged pair(row)-major; row slices, each a chain from 0 over its rows in order, then a
+//             fold over the slices in slice order (k_subm_dw_mfma's scheme).
+// I, O are multiples of 4 and strides multiples of 4 elements, so every staged element is a 16-byte load that lies
+// wholly inside or wholly outside its row; rows beyond N, channels beyond I / O and rows without a group are staged as
+// zeros: nothing assumes a multiple of 16 or 64.
+//
+// The per-group sums (dalpha, dbeta; dbias from them) are kernels of this library and use no float atomics: a stable
+// counting sort of the rows by group (per 256-row block a count per group, one exclusive scan over (group, block),
+// then each row's rank inside its block) gives `perm`, the rows in group order and ascending inside a group; the sum
+// of a group is S slices of its rows, each one chain in that order, folded in slice order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "../../include/gcm.h"
+#define GC_ERR_HIP GCM_ERR_HIP
+#include "gc_host.h"
+
+namespace {
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr int KC = 16;            // depth of a staged slice
+constexpr int T = 64;             // workgroup tile, both ways
+constexpr int kPitch = KC + 4;    // words between rows of an image that holds the summed index contiguously
+constexpr int kPitchT = T + 16;   // words between rows of an image that holds the summed index in rows
+constexpr int kSortRows = 256;    // rows per block of the counting sort
+constexpr int64_t kMaxRows = (int64_t)1 << 31;
+constexpr int kMaxFeatures = 65536;
+constexpr int kMaxGroups = 1 << 20;
+
+__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
+__device__ __forceinline__ f4 zero4() { return f4{0.0f, 0.0f, 0.0f, 0.0f}; }
+
+// group of a row: 0 without a group vector, -1 for a value outside 0 .. G-1
+__device__ __forceinline__ int32_t row_group(const int32_t* __restrict__ group, int64_t r, int G) {
+  if (!group) return 0;
+  const int32_t g = group[r];
+  return (g >= 0 && g < G) ? g : -1;
+}
+
+// dy o (y > 0 ? 1 : slope), four elements
+__device__ __forceinline__ f4 dpre4(f4 dy, f4 y, float slope) {
+  f4 r;
+#pragma unroll
+  for (int k = 0; k < 4; k++) r[k] = y[k] > 0.0f ? dy[k] : dy[k] * slope;
+  return r;
+}
+
+struct WaveTile {  // wave (wr, wc): tile-relative corner of the wave's 32 x 32 outputs; (fl, fk): the lane in a fragment
+  int wr, wc, fl, fk;
+  __device__ __forceinline__ WaveTile() {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wr = (wave >> 1) * 32;
+    wc = (wave & 1) * 32;
+    fl = lane & 15;
+    fk = lane >> 4;
+  }
+};
+
+__device__ __forceinline__ void clear_acc(f4 (&acc)[2][2]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < 2; j++) acc[i][j] = zero4();
+}
+
+// ---- forward and dX -------------------------------------------------------------------------------------------------
+// BWD == false: out rows = x rows, summed index = I, B[k = i][col = o] = w[o][i] (read along i: Bs[col][k], kPitch).
+// BWD == true:  A = dpre, summed index = O, B[k = o][col = i] = w[o][i] (read along i: Bs[k][col], kPitchT).
+// K: length of the summed index, C: columns of the output.
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_modlinear_gemm(const float* __restrict__ x, int64_t xs, const float* __restrict__ yy,
+                                                        int64_t ys, const float* __restrict__ dy, int64_t dys,
+                                                        const float* __restrict__ w, int64_t ws,
+                                                        const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                        const float* __restrict__ bias, const int32_t* __restrict__ group,
+                                                        int64_t N, int I, int O, int G, float slope, float* __restrict__ out,
+                                                        int64_t outs, float* __restrict__ t) {
+  __shared__ __attribute__((aligned(16))) float As[T * kPitch];
+  __shared__ __attribute__((aligned(16))) float Bs[BWD ? KC * kPitchT : T * kPitch];
+  __shared__ int32_t sG[T];
+  const int tid = threadIdx.x;
+  const WaveTile g;
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int n0 = blockIdx.y * T;
+  const int K = BWD ? O : I, C = BWD ? I : O;
+  if (tid < T) sG[tid] = row0 + tid < N ? row_group(group, row0 + tid, G) : -1;
+  __syncthreads();
+
+  // staging: A -- row tid / 4, four summed-index elements at 4 * (tid % 4); B forward the same of w's row n0 + tid / 4,
+  // B dX -- summed-index row tid / 16, four columns at 4 * (tid % 16)
+  const int ar = tid >> 2, ac = 4 * (tid & 3);
+  const int ga = sG[ar];
+  const int64_t arow = row0 + ar;
+  const int br = BWD ? tid >> 4 : tid >> 2, bc = BWD ? 4 * (tid & 15) : 4 * (tid & 3);
+  f4 va, vb;
+  auto fetch = [&](int c0) {
+    va = zero4();
+    vb = zero4();
+    const int c = c0 + ac;
+    if (ga >= 0 && c < K) {
+      if (BWD) {
+        va = dpre4(ld4(dy + arow * dys + c), ld4(yy + arow * ys + c), slope);
+      } else {
+        va = ld4(x + arow * xs + c);
+        if (alpha) va = va * ld4(alpha + (int64_t)ga * I + c);
+      }
+    }
+    if (BWD) {
+      const int o = c0 + br, i = n0 + bc;
+      if (o < O && i < I) vb = ld4(w + (int64_t)o * ws + i);
+    } else {
+      const int o = n0 + br, i = c0 + bc;
+      if (o < O && i < I) vb = ld4(w + (int64_t)o * ws + i);
+    }
+  };
+
+  f4 acc[2][2];
+  clear_acc(acc);
+  fetch(0);
+  for (int c0 = 0; c0 < K; c0 += KC) {
+    *reinterpret_cast<f4*>(&As[ar * kPitch + ac]) = va;
+    *reinterpret_cast<f4*>(&Bs[BWD ? br * kPitchT + bc : br * kPitch + bc]) = vb;
+    __syncthreads();
+    if (c0 + KC < K) fetch(c0 + KC);
+#pragma unroll
+    for (int kk = 0; kk < KC; kk += 4) {
+      float a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; i++) a[i] = As[(g.wr + 16 * i + g.fl) * kPitch + kk + g.fk];
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        b[j] = BWD ? Bs[(kk + g.fk) * kPitchT + g.wc + 16 * j + g.fl] : Bs[(g.wc + 16 * j + g.fl) * kPitch + kk + g.fk];
+#pragma unroll
+      for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const int rl = g.wr + 16 * i + 4 * g.fk + v;
+      const int64_t row = row0 + rl;
+      if (row >= N) continue;
+      const int gr = sG[rl];
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const int c = n0 + g.wc + 16 * j + g.fl;
+        if (c >= C) continue;
+        float val = acc[i][j][v];
+        if (BWD) {
+          if (t) t[row * I + c] = gr >= 0 ? val * x[row * xs + c] : 0.0f;
+          if (out) out[row * outs + c] = gr >= 0 ? (alpha ? val * alpha[(int64_t)gr * I + c] : val) : 0.0f;
+        } else {
+          if (beta && gr >= 0) val += beta[(int64_t)gr * O + c];
+          if (bias) val += bias[c];
+          val = val > 0.0f ? val : val * slope;
+          out[row * outs + c] = gr >= 0 ? val : 0.0f;
+        }
+      }
+    }
+}
+
+// ---- dW -------------------------------------------------------------------------------------------------------------
+// part[s][o][i] (or dw itself with one slice) = sum over the rows r of slice s, ascending, of dpre[r][o] * xa[r][i].
+// Pair-major images Ds[pair][o] and Xs[pair][i] at kPitchT; a thread stages pair tid / 16, four columns at 4 * (tid % 16).
+__global__ __launch_bounds__(256) void k_modlinear_dw(const float* __restrict__ x, int64_t xs, const float* __restrict__ yy,
+                                                      int64_t ys, const float* __restrict__ dy, int64_t dys,
+                                                      const float* __restrict__ alpha, const int32_t* __restrict__ group,
+                                                      int64_t N, int I, int O, int G, float slope, int64_t per,
+                                                      float* __restrict__ part, float* __restrict__ dw) {
+  __shared__ __attribute__((aligned(16))) float Ds[KC * kPitchT];
+  __shared__ __attribute__((aligned(16))) float Xs[KC * kPitchT];
+  const int tid = threadIdx.x;
+  const WaveTile g;
+  const int tiles_i = (I + T - 1) / T;
+  const int o0 = (blockIdx.x / tiles_i) * T, i0 = (blockIdx.x % tiles_i) * T;
+  const int s = blockIdx.y;
+  const int64_t p0 = s * per, p1 = p0 + per < N ? p0 + per : N;
+  const int sp = tid >> 4, sc = 4 * (tid & 15);
+  f4 vd, vx;
+  auto fetch = [&](int64_t p) {
+    vd = zero4();
+    vx = zero4();
+    const int64_t r = p + sp;
+    if (r >= p1) return;
+    const int gr = row_group(group, r, G);
+    if (gr < 0) return;
+    if (o0 + sc < O) vd = dpre4(ld4(dy + r * dys + o0 + sc), ld4(yy + r * ys + o0 + sc), slope);
+    if (i0 + sc < I) {
+      vx = ld4(x + r * xs + i0 + sc);
+      if (alpha) vx = vx * ld4(alpha + (int64_t)gr * I + i0 + sc);
+    }
+  };
+  f4 acc[2][2];
+  clear_acc(acc);
+  fetch(p0);
+  for (int64_t p = p0; p < p1; p += KC) {
+    *reinterpret_cast<f4*>(&Ds[sp * kPitchT + sc]) = vd;
+    *reinterpret_cast<f4*>(&Xs[sp * kPitchT + sc]) = vx;
+    __syncthreads();
+    if (p + KC < p1) fetch(p + KC);
+#pragma unroll
+    for (int kk = 0; kk < KC; kk += 4) {
+      float a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; i++) a[i] = Ds[(kk + g.fk) * kPitchT + g.wr + 16 * i + g.fl];
+#pragma unroll
+      for (int j = 0; j < 2; j++) b[j] = Xs[(kk + g.fk) * kPitchT + g.wc + 16 * j + g.fl];
+#pragma unroll
+      for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  float* dst = part ? part + (int64_t)s * O * I : dw;
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const int o = o0 + g.wr + 16 * i + 4 * g.fk + v;
+      if (o >= O) continue;
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const int c = i0 + g.wc + 16 * j + g.fl;
+        if (c < I) dst[(int64_t)o * I + c] = acc[i][j][v];
+      }
+    }
+}
+
+// out[e] = sum of part[s][e], s ascending
+__global__ void k_fold_slices(const float* __restrict__ part, int S, int64_t len, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= len) return;
+  float v = part[e];
+  for (int s = 1; s < S; s++) v += part[(int64_t)s * len + e];
+  out[e] = v;
+}
+
+// ---- rows in group order --------------------------------------------------------------------------------------------
+// cnt[g][b]: rows of group g in block b (every entry is written)
+__global__ __launch_bounds__(kSortRows) void k_sort_count(const int32_t* __restrict__ group, int64_t N, int G, int64_t NB,
+                                                          int32_t* __restrict__ cnt) {
+  __shared__ int32_t sg[kSortRows];
+  const int tid = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * kSortRows + tid;
+  sg[tid] = r < N ? row_group(group, r, G) : -1;
+  __syncthreads();
+  for (int gq = tid; gq < G; gq += kSortRows) {
+    int32_t c = 0;
+    for (int j = 0; j < kSortRows; j++) c += sg[j] == gq;
+    cnt[(int64_t)gq * NB + blockIdx.x] = c;
+  }
+}
+
+// exclusive scan of cnt in place (one workgroup: every thread a contiguous run), start[g] = first position of group g,
+// start[G] = the number of rows that have a group
+__global__ __launch_bounds__(1024) void k_sort_scan(int32_t* __restrict__ cnt, int64_t len, int G, int64_t NB,
+                                                    int32_t* __restrict__ start) {
+  __shared__ int32_t sums[1024];
+  const int tid = threadIdx.x;
+  const int64_t run = (len + 1023) / 1024;
+  const int64_t e0 = tid * run, e1 = e0 + run < len ? e0 + run : len;
+  int32_t sum = 0;
+  for (int64_t e = e0; e < e1; e++) sum += cnt[e];
+  sums[tid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    int32_t acc = 0;
+    for (int k = 0; k < 1024; k++) {
+      const int32_t v = sums[k];
+      sums[k] = acc;
+      acc += v;
+    }
+    start[G] = acc;
+  }
+  __syncthreads();
+  int32_t acc = sums[tid];
+  for (int64_t e = e0; e < e1; e++) {
+    const int32_t v = cnt[e];
+    cnt[e] = acc;
+    if (e % NB == 0) start[e / NB] = acc;
+    acc += v;
+  }
+}
+
+// perm[first position of (group, block) + rank of the row among the block's rows of its group] = row
+__global__ __launch_bounds__(kSortRows) void k_sort_place(const int32_t* __restrict__ group, int64_t N, int G, int64_t NB,
+                                                          const int32_t* __restrict__ first, int32_t* __restrict__ perm) {
+  __shared__ int32_t sg[kSortRows];
+  const int tid = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * kSortRows + tid;
+  const int32_t gr = r < N ? row_group(group, r, G) : -1;
+  sg[tid] = gr;
+  __syncthreads();
+  if (gr < 0) return;
+  int32_t rank = 0;
+  for (int j = 0; j < tid; j++) rank += sg[j] == gr;
+  perm[first[(int64_t)gr * NB + blockIdx.x] + rank] = (int32_t)r;
+}
+
+// gpart[s][g][col], col < I: sum of t[r][col]; col >= I: sum of dpre[r][col - I] -- over the rows of slice s of group g,
+// in perm's order.  grid.x = G * column blocks, grid.y = S.  Without perm (no group vector) the rows are 0 .. N-1.
+__global__ __launch_bounds__(256) void k_group_sum(const float* __restrict__ t, const float* __restrict__ yy, int64_t ys,
+                                                   const float* __restrict__ dy, int64_t dys,
+                                                   const int32_t* __restrict__ perm, const int32_t* __restrict__ start,
+                                                   int64_t N, int I, int O, int G, int S, float slope,
+                                                   float* __restrict__ gpart) {
+  const int C = I + O, cblocks = (C + 255) / 256;
+  const int gq = blockIdx.x / cblocks, col = (blockIdx.x % cblocks) * 256 + threadIdx.x, s = blockIdx.y;
+  if (col >= C) return;
+  const int64_t b0 = start ? start[gq] : 0, b1 = start ? start[gq + 1] : (gq == 0 ? N : 0);
+  const int64_t per = (b1 - b0 + S - 1) / S;
+  const int64_t p0 = b0 + s * per, p1 = p0 + per < b1 ? p0 + per : b1;
+  auto term = [&](int64_t p) {
+    const int64_t r = perm ? perm[p] : p;
+    if (col < I) return t ? t[r * I + col] : 0.0f;
+    const int o = col - I;
+    const float d = dy[r * dys + o];
+    return yy[r * ys + o] > 0.0f ? d : d * slope;
+  };
+  float acc = 0.0f;
+  int64_t p = p0;
+  for (; p + 4 <= p1; p += 4) {  // four rows' loads in flight; the sum stays one chain in row order
+    const float v0 = term(p), v1 = term(p + 1), v2 = term(p + 2), v3 = term(p + 3);
+    acc += v0;
+    acc += v1;
+    acc += v2;
+    acc += v3;
+  }
+  for (; p < p1; p++) acc += term(p);
+  gpart[((int64_t)s * G + gq) * C + col] = acc;
+}
+
+// dalpha[g][i], dbeta[g][o]: the slices of gpart in slice order; dbias[o]: the groups in ascending order, each its slices
+__global__ void k_group_fold(const float* __restrict__ gpart, int S, int G, int I, int O, float* __restrict__ dalpha,
+                             float* __restrict__ dbeta, float* __restrict__ dbias) {
+  const int C = I + O;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, per_group = (int64_t)G * C;
+  if (e < per_group) {
+    const int gq = (int)(e / C), col = (int)(e % C);
+    float v = gpart[e];
+    for (int s = 1; s < S; s++) v += gpart[(int64_t)s * per_group + e];
+    if (col < I) {
+      if (dalpha) dalpha[(int64_t)gq * I + col] = v;
+    } else if (dbeta) {
+      dbeta[(int64_t)gq * O + col - I] = v;
+    }
+  } else if (e < per_group + O && dbias) {
+    const int o = (int)(e - per_group);
+    float total = 0.0f;
+    for (int gq = 0; gq < G; gq++) {
+      float v = gpart[(int64_t)gq * C + I + o];
+      for (int s = 1; s < S; s++) v += gpart[(int64_t)s * per_group + (int64_t)gq * C + I + o];
+      total += v;
+    }
+    dbias[o] = total;
+  }
+}
+
+// ---- group vector from the instances' masks ---------------------------------------------------------------------------
+__global__ void k_groups_from_masks(const uint8_t* const* __restrict__ masks, int G, int64_t N, int32_t* __restrict__ group) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= N) return;
+  int32_t found = -1;
+  for (int gq = G - 1; gq >= 0; gq--)
+    if (masks[gq][r]) {
+      found = gq;
+      break;
+    }
+  group[r] = found;
+}
+
+// ---- output transform of the head -------------------------------------------------------------------------------------
+// 16 lanes per row: lane q sums the elements 4 q + 64 k .. + 3 (k ascending), then a fixed exchange tree over the 16.
+template <int NC>
+__global__ __launch_bounds__(256) void k_head_out(const float* __restrict__ f, int64_t fs, const float* __restrict__ w,
+                                                  const float* __restrict__ b, const int32_t* __restrict__ group, int64_t N,
+                                                  int I, int kind, float factor, float* __restrict__ out) {
+  const int q = threadIdx.x & 15;
+  const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool live = row < N;
+  const int gr = !live ? -1 : (group ? (group[row] >= 0 ? 0 : -1) : 0);  // here only "has a group" matters
+  float acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; c++) acc[c] = 0.0f;
+  if (gr >= 0) {
+    for (int i = 4 * q; i < I; i += 64) {
+      const f4 v = ld4(f + row * fs + i);
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        const f4 wv = ld4(w + (int64_t)c * I + i);
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc[c] += v[k] * wv[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; c++)
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) acc[c] += __shfl_xor(acc[c], m, 64);
+  if (!live || q != 0) return;
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    float res = 0.0f;
+    if (gr >= 0) {
+      const float v = b ? acc[c] + b[c] : acc[c];
+      const double sg = 1.0 / (1.0 + exp(-(double)v));
+      double d;
+      if (kind == GCM_SCALE) d = 1.0 + (double)fminf(fmaxf(v, -1.0f), 1.0f) * (double)factor;
+      else if (kind == GCM_OPACITY) d = sg * (double)factor + (1.0 - (double)factor);
+      else d = (sg - 0.5) * (double)factor;
+      res = (float)d;
+    }
+    out[row * NC + c] = res;
+  }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool stride_ok(int64_t s, int width) { return s > 0 && s % 4 == 0 && s >= width; }
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }
+unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+int check_shape(const std::string& w, int64_t N, int32_t I, int32_t O, int32_t G) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (I <= 0 || I % 4 != 0 || I > kMaxFeatures) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": I must be a positive multiple of 4");
+  if (O <= 0 || O % 4 != 0 || O > kMaxFeatures) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": O must be a positive multiple of 4");
+  if (G < 1 || G > kMaxGroups) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": G must be in 1..2^20");
+  return 0;
+}
+// the backward's counting sort keeps one count per (group, block of 256 rows)
+int check_sort(const std::string& w, int64_t N, int32_t G) {
+  if (((N + kSortRows - 1) / kSortRows) * (int64_t)G >= kMaxRows)
+    return fail(GCM_ERR_INVALID_ARGUMENT, w + ": ceil(N / 256) * G does not fit 31 bits");
+  return 0;
+}
+
+// The backward's slices and the carve of its workspace (offsets in bytes, each a multiple of 256).
+struct BackwardPlan {
+  int sw;      // row slices of dW
+  int sg;      // slices of a group's rows
+  int64_t nb;  // blocks of the counting sort
+  size_t t, wpart, cnt, start, perm, gpart, total;
+};
+BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
+  BackwardPlan p;
+  const int64_t tiles = (int64_t)((O + T - 1) / T) * ((I + T - 1) / T);
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(64, 1024 / tiles));
+  p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 127) / 128));
+  p.sg = (int)std::max<int64_t>(1, std::min<int64_t>(256, (N + 64 * (int64_t)G - 1) / (64 * (int64_t)G)));
+  p.nb = (N + kSortRows - 1) / kSortRows;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += round256(bytes);
+    return at;
+  };
+  p.t = take((size_t)N * I * 4);
+  p.wpart = take(p.sw > 1 ? (size_t)p.sw * O * I * 4 : 0);
+  p.cnt = take((size_t)p.nb * G * 4);
+  p.start = take(((size_t)G + 1) * 4);
+  p.perm = take((size_t)N * 4);
+  p.gpart = take((size_t)p.sg * G * ((size_t)I + O) * 4);
+  p.total = off;
+  return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcm_abi_version(void) { return GCM_ABI_VERSION; }
+const char* gcm_last_error(void) { return g_err.c_str(); }
+
+int gcm_groups_from_masks(const void* masks, int64_t G, int64_t N, int32_t* group, void* hip_stream) {
+  const std::string w("gcm_groups_from_masks");
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (G < 0 || G > kMaxGroups) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": G must be in 0..2^20");
+  if (N == 0) return GCM_OK;
+  if (!group) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": null group");
+  if (G > 0 && !masks) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": null masks");
+  if ((reinterpret_cast<uintptr_t>(masks) & 7u) != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": masks must be 8-byte aligned");
+  k_groups_from_masks<<<blocks_for(N, 256), 256, 0, (hipStream_t)hip_stream>>>((const uint8_t* const*)masks, (int)G, N, group);
+  HIP_TRY(hipGetLastError(), "groups_from_masks launch");
+  return GCM_OK;
+}
+
+int gcm_modlinear_forward(const float* x, int64_t x_stride, const float* w, int64_t w_stride, const float* alpha,
+                          const float* beta, const float* bias, const int32_t* group, int64_t N, int32_t I, int32_t O,
+                          int32_t G, float slope, float* y, int64_t y_stride, void* hip_stream) {
+  const std::string who("gcm_modlinear_forward");
+  if (int rc = check_shape(who, N, I, O, G)) return rc;
+  if (!std::isfinite(slope) || slope <= 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": slope must be finite and > 0");
+  if (!stride_ok(x_stride, I) || !stride_ok(w_stride, I) || !stride_ok(y_stride, O))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(w) || !aligned16(alpha) || !aligned16(beta) || !aligned16(bias) || !aligned16(y))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!x || !w || !y) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, w or y");
+  const dim3 grid(blocks_for(N, T), blocks_for(O, T));
+  k_modlinear_gemm<false><<<grid, 256, 0, (hipStream_t)hip_stream>>>(x, x_stride, nullptr, 0, nullptr, 0, w, w_stride, alpha,
+                                                                     beta, bias, group, N, I, O, G, slope, y, y_stride,
+                                                                     nullptr);
+  HIP_TRY(hipGetLastError(), "modlinear forward launch");
+  return GCM_OK;
+}
+
+size_t gcm_modlinear_backward_workspace_bytes(int64_t N, int32_t I, int32_t O, int32_t G) {
+  if (check_shape("gcm_modlinear_backward_workspace_bytes", N, I, O, G)) return 0;
+  if (check_sort("gcm_modlinear_backward_workspace_bytes", N, G)) return 0;
+  g_err.clear();
+  return plan_backward(N, I, O, G).total;
+}
+
+int gcm_modlinear_backward(const float* x, int64_t x_stride, const float* y, int64_t y_stride, const float* dy,
+                           int64_t dy_stride, const float* w, int64_t w_stride, const float* alpha,
+                           const int32_t* group, int64_t N, int32_t I, int32_t O, int32_t G, float slope, float* dx,
+                           int64_t dx_stride, float* dw, float* dalpha, float* dbeta, float* dbias, void* workspace,
+                           size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_modlinear_backward");
+  if (int rc = check_shape(who, N, I, O, G)) return rc;
+  if (int rc = check_sort(who, N, G)) return rc;
+  if (!std::isfinite(slope) || slope <= 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": slope must be finite and > 0");
+  if (!stride_ok(x_stride, I) || !stride_ok(y_stride, O) || !stride_ok(dy_stride, O) || !stride_ok(w_stride, I) ||
+      (dx && !stride_ok(dx_stride, I)))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(y) || !aligned16(dy) || !aligned16(w) || !aligned16(alpha) || !aligned16(dx) ||
+      !aligned16(dw) || !aligned16(dalpha) || !aligned16(dbeta) || !aligned16(dbias))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  const BackwardPlan p = plan_backward(N, I, O, G);
+  if (workspace_bytes < p.total || (p.total && !workspace))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_modlinear_backward_workspace_bytes");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (N > 0 && (!x || !y || !dy || !w)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, y, dy or w");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // nothing to sum: the outputs that do not depend on N are zeros
+    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)O * I * 4, st), "backward clear dw");
+    if (dalpha) HIP_TRY(hipMemsetAsync(dalpha, 0, (size_t)G * I * 4, st), "backward clear dalpha");
+    if (dbeta) HIP_TRY(hipMemsetAsync(dbeta, 0, (size_t)G * O * 4, st), "backward clear dbeta");
+    if (dbias) HIP_TRY(hipMemsetAsync(dbias, 0, (size_t)O * 4, st), "backward clear dbias");
+    return GCM_OK;
+  }
+  char* ws = (char*)workspace;
+  float* t = dalpha ? (float*)(ws + p.t) : nullptr;
+  if (dx || t) {
+    const dim3 grid(blocks_for(N, T), blocks_for(I, T));
+    k_modlinear_gemm<true><<<grid, 256, 0, st>>>(x, x_stride, y, y_stride, dy, dy_stride, w, w_stride, alpha, nullptr,
+                                                 nullptr, group, N, I, O, G, slope, dx, dx_stride, t);
+    HIP_TRY(hipGetLastError(), "modlinear dx launch");
+  }
+  if (dw) {
+    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    float* part = p.sw > 1 ? (float*)(ws + p.wpart) : nullptr;
+    const dim3 grid(blocks_for(O, T) * blocks_for(I, T), (unsigned)p.sw);
+    k_modlinear_dw<<<grid, 256, 0, st>>>(x, x_stride, y, y_stride, dy, dy_stride, alpha, group, N, I, O, G, slope, per,
+                                         part, dw);
+    HIP_TRY(hipGetLastError(), "modlinear dw launch");
+    if (part) {
+      k_fold_slices<<<blocks_for((int64_t)O * I, 256), 256, 0, st>>>(part, p.sw, (int64_t)O * I, dw);
+      HIP_TRY(hipGetLastError(), "modlinear dw fold launch");
+    }
+  }
+  if (dalpha || dbeta || dbias) {
+    int32_t* perm = nullptr;
+    int32_t* start = nullptr;
+    if (group) {
+      int32_t* cnt = (int32_t*)(ws + p.cnt);
+      start = (int32_t*)(ws + p.start);
+      perm = (int32_t*)(ws + p.perm);
+      k_sort_count<<<(unsigned)p.nb, kSortRows, 0, st>>>(group, N, G, p.nb, cnt);
+      k_sort_scan<<<1, 1024, 0, st>>>(cnt, p.nb * G, G, p.nb, start);
+      k_sort_place<<<(unsigned)p.nb, kSortRows, 0, st>>>(group, N, G, p.nb, cnt, perm);
+      HIP_TRY(hipGetLastError(), "modlinear sort launch");
+    }
+    float* gpart = (float*)(ws + p.gpart);
+    const int C = I + O;
+    const dim3 grid((unsigned)G * blocks_for(C, 256), (unsigned)p.sg);
+    k_group_sum<<<grid, 256, 0, st>>>(t, y, y_stride, dy, dy_stride, perm, start, N, I, O, G, p.sg, slope, gpart);
+    k_group_fold<<<blocks_for((int64_t)G * C + O, 256), 256, 0, st>>>(gpart, p.sg, G, I, O, dalpha, dbeta, dbias);
+    HIP_TRY(hipGetLastError(), "modlinear group sums launch");
+  }
+  return GCM_OK;
+}
+
+int gcm_head_out(const float* f, int64_t f_stride, const float* w_out, const float* b, const int32_t* group, int64_t N,
+                 int32_t I, int32_t C, int kind, float factor, float* out, void* hip_stream) {
+  const std::string who("gcm_head_out");
+  if (int rc = check_shape(who, N, I, 4, 1)) return rc;
+  if (C != 1 && C != 3) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": C must be 1 or 3");
+  if (kind != GCM_XYZ && kind != GCM_RGB && kind != GCM_SCALE && kind != GCM_OPACITY)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": unknown kind");
+  if (!std::isfinite(factor)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": factor is not finite");
+  if (!stride_ok(f_stride, I))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(f) || !aligned16(w_out)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!f || !w_out || !out) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null f, w_out or out");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (C == 1) k_head_out<1><<<blocks_for(N, 16), 256, 0, st>>>(f, f_stride, w_out, b, group, N, I, kind, factor, out);
+  else k_head_out<3><<<blocks_for(N, 16), 256, 0, st>>>(f, f_stride, w_out, b, group, N, I, kind, factor, out);
+  HIP_TRY(hipGetLastError(), "head_out launch");
+  return GCM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,182 @@
+"""The grouped modulated linear layer of the generator's attribute head over libgcm_hip.so.
+
+  modulated_linear(x [N, I], weight [O, I], alpha [G, I], beta [G, O], bias [O], group int32 [N], negative_slope)
+        y[r] = leaky_relu((x[r] * alpha[group[r]]) @ weight.T + beta[group[r]] + bias); rows of group -1 give y = 0.
+        alpha, beta, bias and group may each be None; gradients for x, weight, alpha, beta and bias, deterministic.
+  groups_from_masks(masks, n)     int32 [n]: the largest g whose boolean mask has the row set, -1 where none has
+  head_out(f, weight, bias, group, kind, factor)     the head's last linear layer and output transform, inference only
+
+torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
+the HIP library, float32 throughout, and nothing here waits for the device.
+"""
+import torch
+
+from . import _native_m as M
+from ._loader import current_stream as _stream
+
+KINDS = tuple(M.KINDS)
+
+_STATS = {"forward_calls": 0, "backward_calls": 0, "groups_from_masks_calls": 0, "head_out_calls": 0}
+
+
+def stats():
+    """Counters of this process: calls of each entry point of the library."""
+    return dict(_STATS)
+
+
+def reset_stats():
+    for k in _STATS:
+        _STATS[k] = 0
+
+
+def dtypes():
+    """The element types the library's kernels run: (torch.float32,).  Loads the library."""
+    M.lib()
+    return (torch.float32,)
+
+
+def _rows(t):
+    """t [rows, width] as the library wants a row-strided operand: unit stride along the row, a row stride that is a
+    positive multiple of 4 elements and at least the width, 16-byte aligned; a contiguous copy otherwise."""
+    if t.shape[0] == 0:  # no rows: whatever strides the empty tensor carries (numpy's are 0), the library gets dense ones
+        return t.new_empty(t.shape)
+    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= max(t.shape[1], 1) and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class ModulatedLinearFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, alpha, beta, bias, group, slope, G):
+        x, weight = _rows(x), _rows(weight)
+        alpha = None if alpha is None else alpha.contiguous()
+        beta = None if beta is None else beta.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        N, I = x.shape
+        O = weight.shape[0]
+        y = x.new_empty((N, O))
+        with torch.cuda.device(x.device):
+            M.check(M.lib().gcm_modlinear_forward(x.data_ptr(), x.stride(0), weight.data_ptr(), weight.stride(0), _ptr(alpha),
+                                                  _ptr(beta), _ptr(bias), _ptr(group), N, I, O, G, slope, y.data_ptr(),
+                                                  y.stride(0), _stream()), "gcm_modlinear_forward")
+        _STATS["forward_calls"] += 1
+        ctx.save_for_backward(x, y, weight, alpha, group)
+        ctx.meta = (slope, G, beta is not None, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, weight, alpha, group = ctx.saved_tensors
+        slope, G, has_beta, has_bias = ctx.meta
+        N, I = x.shape
+        O = weight.shape[0]
+        dy = _rows(dy if dy.dtype == torch.float32 else dy.float())
+        need = ctx.needs_input_grad
+        dx = x.new_empty((N, I)) if need[0] else None
+        dw = x.new_empty((O, I)) if need[1] else None
+        dalpha = x.new_empty((G, I)) if alpha is not None and need[2] else None
+        dbeta = x.new_empty((G, O)) if has_beta and need[3] else None
+        dbias = x.new_empty((O,)) if has_bias and need[4] else None
+        L = M.lib()
+        ws_bytes = L.gcm_modlinear_backward_workspace_bytes(N, I, O, G)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            M.check(L.gcm_modlinear_backward(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), dy.data_ptr(), dy.stride(0),
+                                             weight.data_ptr(), weight.stride(0), _ptr(alpha), _ptr(group), N, I, O, G, slope,
+                                             _ptr(dx), I, _ptr(dw), _ptr(dalpha), _ptr(dbeta), _ptr(dbias), ws.data_ptr(),
+                                             ws_bytes, _stream()), "gcm_modlinear_backward")
+        _STATS["backward_calls"] += 1
+        return dx, dw, dalpha, dbeta, dbias, None, None, None
+
+
+def _check_float(name, t, shape):
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
+    if not t.is_cuda:
+        raise TypeError("the modulated linear layer runs on the GPU; %s must be a CUDA tensor" % name)
+    if tuple(t.shape) != shape:
+        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
+
+
+def _check_group(group, n):
+    if group is None:
+        return None
+    if not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or not group.is_cuda:
+        raise TypeError("group must be an int32 CUDA tensor")
+    if tuple(group.shape) != (n,):
+        raise ValueError("group must be [%d], got %r" % (n, tuple(group.shape)))
+    return group.contiguous()
+
+
+def modulated_linear(x, weight, alpha=None, beta=None, bias=None, group=None, negative_slope=1.0):
+    """leaky_relu((x * alpha[group]) @ weight.T + beta[group] + bias, negative_slope) for x [N, I], weight [O, I], alpha
+    [G, I], beta [G, O], bias [O] float32 on the GPU and group int32 [N] with values in -1 .. G-1; I and O multiples of 4.
+    A row of group -1 gives zeros and receives a zero gradient.  None for alpha / beta / bias / group means ones /
+    zeros / zeros / every row in group 0; negative_slope 1 means no activation."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or not isinstance(weight, torch.Tensor) or weight.dim() != 2:
+        raise ValueError("x must be [N, I] and weight [O, I]")
+    (N, I), O = x.shape, weight.shape[0]
+    if I % 4 or O % 4 or I == 0 or O == 0:
+        raise ValueError("I and O must be positive multiples of 4, got I = %d, O = %d" % (I, O))
+    G = alpha.shape[0] if isinstance(alpha, torch.Tensor) and alpha.dim() == 2 else (
+        beta.shape[0] if isinstance(beta, torch.Tensor) and beta.dim() == 2 else 1)
+    _check_float("x", x, (N, I))
+    _check_float("weight", weight, (O, I))
+    _check_float("alpha", alpha, (G, I))
+    _check_float("beta", beta, (G, O))
+    _check_float("bias", bias, (O,))
+    if G < 1:
+        raise ValueError("alpha and beta need at least one group")
+    slope = float(negative_slope)
+    if not slope > 0.0:
+        raise ValueError("negative_slope must be > 0 (got %r): the backward reads the sign of the stored output" % slope)
+    return ModulatedLinearFunction.apply(x, weight, alpha, beta, bias, _check_group(group, N), slope, G)
+
+
+def groups_from_masks(masks, n):
+    """int32 [n] on the masks' device: for every row the largest g with masks[g][row] set (upstream's later assignment
+    wins where masks overlap), -1 where no mask is set.  masks: a sequence of boolean CUDA tensors of n elements each.
+    One launch whatever len(masks) is; the table of pointers is one host-to-device copy from pinned memory."""
+    masks = [m.reshape(-1) if m.is_contiguous() else m.contiguous().reshape(-1) for m in masks]
+    if not masks:
+        raise ValueError("groups_from_masks needs at least one mask")
+    for m in masks:
+        if m.dtype != torch.bool or not m.is_cuda or m.numel() != n:
+            raise TypeError("every mask must be a boolean CUDA tensor of %d elements" % n)
+    dev = masks[0].device
+    table = torch.tensor([m.data_ptr() for m in masks], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    group = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        M.check(M.lib().gcm_groups_from_masks(table.data_ptr(), len(masks), n, group.data_ptr(), _stream()),
+                "gcm_groups_from_masks")
+    _STATS["groups_from_masks_calls"] += 1
+    return group
+
+
+def head_out(f, weight, bias, group, kind, factor):
+    """The head's output for one attribute, inference only (no autograd): transform(f @ weight.T + bias) for f [N, I],
+    weight [C, I] (C = 1 or 3), bias [C] or None, kind in KINDS; rows of group -1 are zeros.  Returns [N, C]."""
+    if kind not in M.KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(KINDS), kind))
+    if not isinstance(f, torch.Tensor) or f.dim() != 2 or not isinstance(weight, torch.Tensor) or weight.dim() != 2:
+        raise ValueError("f must be [N, I] and weight [C, I]")
+    (N, I), Cn = f.shape, weight.shape[0]
+    if I % 4 or I == 0 or Cn not in (1, 3):
+        raise ValueError("I must be a positive multiple of 4 and C 1 or 3, got I = %d, C = %d" % (I, Cn))
+    _check_float("f", f, (N, I))
+    _check_float("weight", weight, (Cn, I))
+    _check_float("bias", bias, (Cn,))
+    group = _check_group(group, N)
+    f, weight = _rows(f.detach()), weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    out = f.new_empty((N, Cn))
+    with torch.cuda.device(f.device):
+        M.check(M.lib().gcm_head_out(f.data_ptr(), f.stride(0), weight.data_ptr(), _ptr(bias), _ptr(group), N, I, Cn,
+                                     M.KINDS[kind], float(factor), out.data_ptr(), _stream()), "gcm_head_out")
+    _STATS["head_out_calls"] += 1
+    return out
