@@ -48,6 +48,13 @@ _SIGNATURES = {  # every function include/gcs.h declares: name -> (restype, argt
     "gcs_serialize": (_int, [_vp, _vp, _i64, _i32, _i32, C.c_float, C.c_float, _pi32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gcs_patch_plan_count": (_int, [_vp, _i32, _i64, _vp, _vp]),
     "gcs_patch_plan_emit": (_int, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "gcs_pool_reduces": (_int, []),
+    "gcs_pool_plan_workspace_bytes": (_sz, [_i64, _i32]),
+    "gcs_pool_plan_count": (_int, [_vp, _i32, _i64, _i32, _vp, _sz, _vp, _vp]),
+    "gcs_pool_plan_emit": (_int, [_vp, _i32, _i64, _i32, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gcs_segment_gather_forward_t": (_int, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "gcs_segment_gather_backward_t": (_int, [_i32, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "gcs_segment_expand_add_t": (_int, [_i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
 }
 
 _L = _loader.Library("gcs", "libgcs_hip.so", ABI_VERSION, _SIGNATURES)

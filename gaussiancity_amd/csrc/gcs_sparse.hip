@@ -897,6 +897,7 @@ int segment_backward(const char* who, const T* dout, int64_t m, int64_t f, const
 }  // namespace
 
 #include "gcs_index.h"
+#include "gcs_pool.h"
 
 namespace {
 
@@ -931,6 +932,88 @@ int check_patch_plan(const char* who, const int64_t* offset, int32_t n_batches, 
   if (n_batches < 1) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": n_batches must be positive");
   if (patch_size < 1) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": patch_size must be positive");
   if (!offset) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": null offset");
+  return 0;
+}
+
+// The argument checks that gcs_pool_plan_workspace_bytes (which has no shift), _count and _emit share.
+int check_pool_plan(const char* who, int64_t n, int32_t k, int32_t shift, bool has_shift = true) {
+  const std::string w(who);
+  if (n < 1 || n > INT32_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": n must be in 1...2^31 - 1");
+  if (k < 1 || k > IX_ORDERS) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": k must be in 1...5 order rows");
+  if (has_shift && (shift < 0 || shift > 48 || shift % 3))
+    return fail(GCS_ERR_INVALID_ARGUMENT, w + ": shift must be 3 * pooling_depth in 0...48");
+  return 0;
+}
+int check_pool_workspace(const char* who, int64_t n, int32_t k, const void* workspace, size_t workspace_bytes) {
+  if (!workspace || workspace_bytes < pool_layout(n, k).total || (uintptr_t)workspace % 8)
+    return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": workspace missing, not 8-byte aligned or smaller than gcs_pool_plan_workspace_bytes");
+  return 0;
+}
+
+// The checks of the gathered reduce's three entry points: sizes, the reduce, and typed pointers aligned to their element.
+template <typename T>
+int check_gather(const char* who, int64_t m, int64_t f, int64_t s, int64_t stride, int32_t reduce,
+                 std::initializer_list<const void*> typed, std::initializer_list<const void*> index) {
+  const std::string w(who);
+  if (m < 1 || m > INT32_MAX || s < 1 || s > INT32_MAX || f < 1 || f > INT32_MAX)
+    return fail(GCS_ERR_INVALID_ARGUMENT, w + ": sizes out of range (m, s and f in 1...2^31 - 1)");
+  if (stride < f) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": row stride smaller than f");
+  if (reduce < GCS_SUM || reduce > GCS_MAX) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": unknown reduce");
+  for (const void* p : typed)
+    if (!p) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": null pointer");
+  for (const void* p : index)
+    if (!p || (uintptr_t)p % 8) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": null or misaligned index pointer");
+  for (const void* p : typed)
+    if ((uintptr_t)p % sizeof(T)) return fail(GCS_ERR_INVALID_ARGUMENT, w + ": a typed pointer is not aligned to its element");
+  return 0;
+}
+
+template <typename T>
+int gather_forward(const char* who, const T* src, int64_t stride, int64_t m, int64_t f, const int64_t* indices,
+                   const int64_t* indptr, int64_t s, int32_t reduce, T* out, int64_t* arg, void* hip_stream) {
+  if (int rc = check_gather<T>(who, m, f, s, stride, reduce, {src, out}, {indices, indptr})) return rc;
+  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
+  if (minmax && (!arg || (uintptr_t)arg % 8)) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": min and max need the arg buffer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  constexpr int V = 16 / sizeof(T);
+  if (gather_vector<T>(f, {stride}, {src, out}))
+    k_gather_fwd<T, V><<<gather_blocks(s * (f / V)), GP_THREADS, 0, st>>>(src, stride, m, f, indices, indptr, s, reduce, out,
+                                                                          minmax ? arg : nullptr);
+  else
+    k_gather_fwd<T, 1><<<gather_blocks(s * f), GP_THREADS, 0, st>>>(src, stride, m, f, indices, indptr, s, reduce, out,
+                                                                    minmax ? arg : nullptr);
+  HIP_TRY(hipGetLastError(), "gathered segment forward launch");
+  return 0;
+}
+
+template <typename T>
+int gather_backward(const char* who, const T* dout, int64_t m, int64_t f, const int64_t* cluster, const int64_t* indptr,
+                    int64_t s, int32_t reduce, const int64_t* arg, T* dsrc, int64_t stride, void* hip_stream) {
+  if (int rc = check_gather<T>(who, m, f, s, stride, reduce, {dout, dsrc}, {cluster, indptr})) return rc;
+  const bool minmax = reduce == GCS_MIN || reduce == GCS_MAX;
+  if (minmax && (!arg || (uintptr_t)arg % 8)) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": min and max need the arg buffer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  constexpr int V = 16 / sizeof(T);
+  if (gather_vector<T>(f, {stride}, {dout, dsrc}))
+    k_gather_bwd<T, V><<<gather_blocks(m * (f / V)), GP_THREADS, 0, st>>>(dout, m, f, cluster, indptr, s, reduce, arg, dsrc, stride);
+  else
+    k_gather_bwd<T, 1><<<gather_blocks(m * f), GP_THREADS, 0, st>>>(dout, m, f, cluster, indptr, s, reduce, arg, dsrc, stride);
+  HIP_TRY(hipGetLastError(), "gathered segment backward launch");
+  return 0;
+}
+
+template <typename T>
+int expand_add(const char* who, const T* a, const T* b, const int64_t* cluster, int64_t m, int64_t f, T* out,
+               void* hip_stream) {
+  if (int rc = check_gather<T>(who, m, f, 1, f, GCS_SUM, {b, out}, {cluster})) return rc;
+  if ((uintptr_t)a % sizeof(T)) return fail(GCS_ERR_INVALID_ARGUMENT, std::string(who) + ": a typed pointer is not aligned to its element");
+  hipStream_t st = (hipStream_t)hip_stream;
+  constexpr int V = 16 / sizeof(T);
+  if (gather_vector<T>(f, {}, {a, b, out}))
+    k_expand_add<T, V><<<gather_blocks(m * (f / V)), GP_THREADS, 0, st>>>(a, b, cluster, m, f, out);
+  else
+    k_expand_add<T, 1><<<gather_blocks(m * f), GP_THREADS, 0, st>>>(a, b, cluster, m, f, out);
+  HIP_TRY(hipGetLastError(), "expand add launch");
   return 0;
 }
 
@@ -993,6 +1076,74 @@ int gcs_patch_plan_emit(const int64_t* offset, int32_t n_batches, int64_t patch_
       offset, n_batches, patch_size, padded, n_cu, pad, unpad, cu_seqlens);
   HIP_TRY(hipGetLastError(), "patch emit launch");
   return 0;
+}
+
+int gcs_pool_reduces(void) { return (1 << GCS_SUM) | (1 << GCS_MEAN) | (1 << GCS_MIN) | (1 << GCS_MAX); }
+
+size_t gcs_pool_plan_workspace_bytes(int64_t n, int32_t k) {
+  if (check_pool_plan("gcs_pool_plan_workspace_bytes", n, k, 0, false)) return 0;
+  return pool_layout(n, k).total;
+}
+
+int gcs_pool_plan_count(const int64_t* code, int32_t k, int64_t n, int32_t shift, void* workspace, size_t workspace_bytes,
+                        int64_t counts_host[1], void* hip_stream) {
+  const char* who = "gcs_pool_plan_count";
+  if (int rc = check_pool_plan(who, n, k, shift)) return rc;
+  if (!code) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_pool_plan_count: null code");
+  if (int rc = check_pool_workspace(who, n, k, workspace, workspace_bytes)) return rc;
+  if (!counts_host) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_pool_plan_count: null counts_host");
+  void* counts = nullptr;
+  if (hipHostGetDevicePointer(&counts, counts_host, 0) != hipSuccess || !counts) {
+    (void)hipGetLastError();
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_pool_plan_count: counts_host must be pinned host memory (the kernel writes it)");
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(pool_count_launch(code, n, k, shift, (char*)workspace, (int64_t*)counts, st), "pool plan count launch");
+  HIP_TRY(hipStreamSynchronize(st), "pool plan count wait");
+  return 0;
+}
+
+int gcs_pool_plan_emit(const int64_t* code, int32_t k, int64_t n, int32_t shift, int64_t s, void* workspace,
+                       size_t workspace_bytes, int64_t* cluster, int64_t* indices, int64_t* idx_ptr, int64_t* head,
+                       int64_t* down_code, int64_t* down_order, int64_t* down_inverse, void* hip_stream) {
+  const char* who = "gcs_pool_plan_emit";
+  if (int rc = check_pool_plan(who, n, k, shift)) return rc;
+  if (s < 1 || s > n) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_pool_plan_emit: s is not a count of gcs_pool_plan_count (1...n)");
+  if (!code) return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_pool_plan_emit: null code");
+  if (int rc = check_pool_workspace(who, n, k, workspace, workspace_bytes)) return rc;
+  if (!cluster || !indices || !idx_ptr || !head || !down_code || !down_order || !down_inverse)
+    return fail(GCS_ERR_INVALID_ARGUMENT, "gcs_pool_plan_emit: null cluster, indices, idx_ptr, head, down_code, down_order or down_inverse");
+  HIP_TRY(pool_emit_launch(code, n, k, shift, s, (char*)workspace, cluster, indices, idx_ptr, head, down_code, down_order,
+                           down_inverse, (hipStream_t)hip_stream), "pool plan emit launch");
+  return 0;
+}
+
+int gcs_segment_gather_forward_t(int32_t dtype, const void* src, int64_t src_stride, int64_t m, int64_t f,
+                                 const int64_t* indices, const int64_t* indptr, int64_t s, int32_t reduce, void* out,
+                                 int64_t* arg, void* hip_stream) {
+  const char* who = "gcs_segment_gather_forward_t";
+  if (int rc = check_dtype(who, dtype)) return rc;
+  if (dtype == GCS_F32)
+    return gather_forward(who, (const float*)src, src_stride, m, f, indices, indptr, s, reduce, (float*)out, arg, hip_stream);
+  return gather_forward(who, (const half_t*)src, src_stride, m, f, indices, indptr, s, reduce, (half_t*)out, arg, hip_stream);
+}
+
+int gcs_segment_gather_backward_t(int32_t dtype, const void* dout, int64_t m, int64_t f, const int64_t* cluster,
+                                  const int64_t* indptr, int64_t s, int32_t reduce, const int64_t* arg, void* dsrc,
+                                  int64_t dsrc_stride, void* hip_stream) {
+  const char* who = "gcs_segment_gather_backward_t";
+  if (int rc = check_dtype(who, dtype)) return rc;
+  if (dtype == GCS_F32)
+    return gather_backward(who, (const float*)dout, m, f, cluster, indptr, s, reduce, arg, (float*)dsrc, dsrc_stride, hip_stream);
+  return gather_backward(who, (const half_t*)dout, m, f, cluster, indptr, s, reduce, arg, (half_t*)dsrc, dsrc_stride, hip_stream);
+}
+
+int gcs_segment_expand_add_t(int32_t dtype, const void* a, const void* b, const int64_t* cluster, int64_t m, int64_t f,
+                             void* out, void* hip_stream) {
+  const char* who = "gcs_segment_expand_add_t";
+  if (int rc = check_dtype(who, dtype)) return rc;
+  if (dtype == GCS_F32) return expand_add(who, (const float*)a, (const float*)b, cluster, m, f, (float*)out, hip_stream);
+  return expand_add(who, (const half_t*)a, (const half_t*)b, cluster, m, f, (half_t*)out, hip_stream);
 }
 
 int gcs_abi_version(void) { return GCS_ABI_VERSION; }

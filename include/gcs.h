@@ -209,6 +209,69 @@ int gcs_patch_plan_count(const int64_t* offset, int32_t n_batches, int64_t patch
 int gcs_patch_plan_emit(const int64_t* offset, int32_t n_batches, int64_t patch_size, int64_t padded, int64_t n_cu,
                         int64_t* pad, int64_t* unpad, int32_t* cu_seqlens, void* hip_stream);
 
+/* SerializedPooling / SerializedUnpooling of the point backbone.  GCS_ABI_VERSION stays 4:
+ * nothing existing changes, and gcs_pool_reduces() is how a binding learns whether the library has these entry points.
+ * The library allocates nothing, everything runs on the caller's stream, and an argument error is
+ * GCS_ERR_INVALID_ARGUMENT before anything is queued.
+ *
+ * gcs_pool_plan_*: the cluster plan of models/pt_v3.py's SerializedPooling.forward, a function of the point set's
+ * serialized_code alone.  code int64 [k][n] (device; k order rows), shift = 3 * pooling_depth.
+ *   key        key[j] = code[0][j] >> shift (arithmetic).  Clusters are the distinct keys in ascending SIGNED order,
+ *              numbered 0...S-1.
+ *   cluster    int64 [n]: the number of row j's key (torch.unique(sorted=True, return_inverse=True)).
+ *   idx_ptr    int64 [S + 1]: the exclusive scan of the cluster sizes, idx_ptr[S] = n.
+ *   indices    int64 [n]: the rows sorted by cluster, ties to the LOWER row (torch.sort(cluster, stable=True)).
+ *   head       int64 [S]: indices[idx_ptr[c]], the lowest row of cluster c.
+ *   down_code  int64 [k][S]: code[r][head[c]] >> shift.
+ *   down_order, down_inverse  int64 [k][S]: down_order[r] sorts down_code[r] ascending as signed int64 with ties to the
+ *              lower position (gcs_serialize's rule), down_inverse[r][down_order[r][c]] = c.
+ *   _count     sorts the keys, marks and counts the cluster heads, writes S to counts_host[0] and performs the call's ONE
+ *              wait for the stream.  counts_host must be pinned host memory: a kernel writes it directly.  The workspace
+ *              (gcs_pool_plan_workspace_bytes(n, k) bytes, 8-byte aligned) carries the sorted rows to _emit.
+ *   _emit      with the same code, k, n, shift and workspace and the s that _count reported, fills the seven arrays; never
+ *              waits.  Every store is held inside the lengths n, s + 1, s and k * s, so a workspace that does not belong
+ *              to the call leaves a wrong plan, not a stray write.
+ *   refused    n outside 1...2^31-1, k outside 1...5, shift outside 0...48 or no multiple of 3, a null pointer, a workspace
+ *              that is missing or smaller than the query (0 with an error for arguments out of range), counts_host that
+ *              the device cannot write, s outside 1...n.
+ *
+ * gcs_segment_gather_forward_t: out[c][ch] = reduce over j in [indptr[c], indptr[c + 1]) of src[indices[j]][ch].
+ * src [m][f] of `dtype` with a row stride of src_stride elements (>= f), indices int64 [m], indptr int64 [s + 1] (entries
+ * are clamped to [0, m]), out [s][f] dense.  The numerics are segment_csr's: sum and mean are ONE fp32 chain in ascending
+ * j, mean divides in fp32, one rounding on the store; min and max compare exactly and copy bits; an empty segment gives 0.
+ * arg int64 [s][f] (required for min and max, unused otherwise and may be NULL) receives the SOURCE row indices[j] of the
+ * first j that attains the value, -1 for an empty segment.  The result is segment_csr(src[indices], indptr) bit for bit.
+ * An entry of indices outside [0, m) is skipped.
+ *
+ * gcs_segment_gather_backward_t: the transpose, by row: with g = dout[cluster[r]][ch], dsrc[r][ch] = g (sum), g / count
+ * in fp32 rounded once (mean), arg[cluster[r]][ch] == r ? g : 0 (min, max).  dout [s][f] dense, dsrc [m][f] with a row
+ * stride of dsrc_stride elements.  Every element of dsrc is written exactly once: nothing is cleared first, there are no
+ * atomics, and the result is bit-identical from run to run.  PRECONDITION, not checked on the device: cluster int64 [m]
+ * and indptr come from ONE plan, and every row is in exactly one segment (a cluster entry outside [0, s) gives a zero row).
+ *
+ * gcs_segment_expand_add_t: out[r] = a[r] + b[cluster[r]], one fp32 add rounded once; a may be NULL (out[r] =
+ * b[cluster[r]]).  a and out [m][f], b [rows][f], all dense.  PRECONDITION: every cluster entry is a row of b.  Its
+ * transpose needs no kernel of its own: d_a = dout, d_b = gcs_segment_gather_forward_t(dout, indices, idx_ptr, GCS_SUM).
+ *
+ * The three take 16-byte pieces of a row where f, the strides and the base addresses are multiples of 16 bytes, and single
+ * elements otherwise.  Refused: an unknown dtype or reduce, m, s or f outside 1...2^31-1, a stride below f, a null pointer,
+ * a typed pointer that is not aligned to its element or an index pointer that is not 8-byte aligned. */
+int gcs_pool_reduces(void); /* host only: bit (1 << reduce) for every gcs_reduce the gathered reduce runs: 15 */
+size_t gcs_pool_plan_workspace_bytes(int64_t n, int32_t k);
+int gcs_pool_plan_count(const int64_t* code, int32_t k, int64_t n, int32_t shift, void* workspace, size_t workspace_bytes,
+                        int64_t counts_host[1], void* hip_stream);
+int gcs_pool_plan_emit(const int64_t* code, int32_t k, int64_t n, int32_t shift, int64_t s, void* workspace,
+                       size_t workspace_bytes, int64_t* cluster, int64_t* indices, int64_t* idx_ptr, int64_t* head,
+                       int64_t* down_code, int64_t* down_order, int64_t* down_inverse, void* hip_stream);
+int gcs_segment_gather_forward_t(int32_t dtype, const void* src, int64_t src_stride, int64_t m, int64_t f,
+                                 const int64_t* indices, const int64_t* indptr, int64_t s, int32_t reduce, void* out,
+                                 int64_t* arg, void* hip_stream);
+int gcs_segment_gather_backward_t(int32_t dtype, const void* dout, int64_t m, int64_t f, const int64_t* cluster,
+                                  const int64_t* indptr, int64_t s, int32_t reduce, const int64_t* arg, void* dsrc,
+                                  int64_t dsrc_stride, void* hip_stream);
+int gcs_segment_expand_add_t(int32_t dtype, const void* a, const void* b, const int64_t* cluster, int64_t m, int64_t f,
+                             void* out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
