@@ -203,8 +203,10 @@ GCR_DEV K7Behind k7_behind(const float4* __restrict__ ckpt, uint32_t sbase, uint
 //     index) is formed from the record the staging thread gathers anyway, and the ranking is K4's (gcr_sort.h
 //     gcr_rank_merge: rank inside 64-key chunks, binary-search merge; unique keys => rank = position):
 //       - a list of one chunk (<= 223 entries; GaussianCity's tiles: mean 145, p90 187): every thread fetches its
-//         entry's depth, the keys are ranked in the list area of the LDS, and the thread gathers and stages its entry AT
-//         ITS RANK.  (Gathering the whole record first and holding it across the rank spilt 12-19 registers to scratch;
+//         entry's depth, the keys are ranked in the list area of the LDS, and a thread gathers and stages an entry AT
+//         ITS RANK -- since round 9 not the entry whose depth it fetched but the one whose key its lane holds after the
+//         wave has sorted its 64 keys in registers (gcr_sort.h gcr_sort_merge: 67 VALU instructions for the chunk-local
+//         ranks instead of 208; the record is gathered behind the rank either way).  (Gathering the whole record first and holding it across the rank spilt 12-19 registers to scratch;
 //         parked in the thread's own LDS slot and moved after the rank it still spilt; the depth's cache line is the
 //         record's, so the record gather that follows hits.)  Frames whose buffers may be read again (not image-only
 //         ones) also store the sorted indices to `list_out` and the tile's lazy-sort state (sorted whole);
@@ -230,6 +232,11 @@ GCR_DEV K7Behind k7_behind(const float4* __restrict__ ckpt, uint32_t sbase, uint
 #define GCR_K7_ADD_SENTINEL 0
 #endif
 // (lanes whose row sum is exactly zero left out of the add as well: 90.3 vs 89.4 us, no gain, not kept)
+// The one-chunk "tile ids" path ranks with gcr_sort_merge (gcr_sort.h: the chunk sorted in registers).  0 = gcr_rank_merge,
+// every key against the 64 of its chunk (A/B builds).
+#ifndef GCR_K6_SORT_IN_REGISTERS
+#define GCR_K6_SORT_IN_REGISTERS 1
+#endif
 #ifdef GCR_EXPERIMENTS  /* knock-outs for timing: bit 0 = no step arithmetic, bit 1 = no chunk loop at all */
 #define GCR_K6_STEP_ON !(a.debug_flags & 1)
 #define GCR_K6_LOOP_ON !(a.debug_flags & 2)
@@ -516,6 +523,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const int w_u = __builtin_amdgcn_readfirstlane(g.w);
   const int mask_sh = (w_u >> 1) * 16 + (w_u & 1) * 4;
   uint8_t* const lw = &sList[w_u][0][0];
+  uint8_t* const l0 = &sList[0][0][0];
   for (; base < total; base += cs) {
     // block-wide vote (cr/forward.cu:284-286); also fences the previous chunk's LDS reads
     if (__syncthreads_count(!(Tw > 0.0f)) == 256) {
@@ -553,7 +561,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         key[0] = ((uint64_t)__float_as_uint(a.rec[(size_t)id * GCR_REC_QUADS + 2].y) << 32) | id;
       }
       uint32_t pos[1];
+#if GCR_K6_SORT_IN_REGISTERS
+      // (round 9) the wave sorts its 64 keys in registers; this thread goes on with the key of chunk-local rank `lane`,
+      // i.e. it stages ANOTHER entry of its wave's than the one whose depth it fetched -- the record is gathered below
+      gcr_sort_merge(reinterpret_cast<uint64_t*>(&sList[0][0][0]), n, key[0], pos[0], t);
+      id = (uint32_t)key[0];
+#else
       gcr_rank_merge<1, 2>(reinterpret_cast<uint64_t*>(&sList[0][0][0]), n, key, pos, t);
+#endif
       if (t < n) {
         slot = pos[0];
         if (PIXSTATE) a.list_out[r0 + slot] = id;  // (an image-only frame: nobody reads its buffers)
@@ -600,38 +615,86 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (a.clock_buf != nullptr && tid == 0 && base == 0) a.clock_buf[(size_t)tile * 16 + 4] = __builtin_readcyclecounter();
 #endif
     if (__ballot(Tw > 0.0f) == 0ull) continue;  // this wave's quadrant is finished; keep voting
+    // compact the chunk into this wave's eight sub-row lists (ascending list order is preserved), in TWO LEVELS
+    // (round 9).  An entry reaches 1.42 of a tile's four quadrants on average, so eight ballot rounds over every
+    // group of 64 entries were mostly spent on entries none of this wave's blocks sees.
+    //   Level 1: one ballot per group of 64 entries appends the entries with one of the wave's eight bits set to the
+    //   wave's DENSE list: words of (the eight bits << 8 | slot), at most 223 of them, parked in the wave's own list
+    //   area (1 856 bytes, not in use yet) and read back into at most four registers, one dense group of 64 each.
+    //   Level 2: the sentinel fill, then the eight rounds over the dense groups (one at the mean C3 tile instead of three).
+    // The lists come out the same, slot for slot.  Every running count is a wave-uniform (scalar) value that enters its
+    // store's index as the addend of the v_mbcnt pair, together with the list's offset from the first list of the
+    // workgroup: a round is and, compare, two v_mbcnt and the store (of the word's low byte), in every group.  A chunk of
+    // one group (n <= 64) has nothing to gain from level 1: its dense group is the group itself.
+    uint32_t dg[4] = {0u, 0u, 0u, 0u};  // dense groups
+    int dcnt = 64;                      // (wave-uniform) length of the dense list
+    if (n > 64) {                       // block-uniform
+      uint32_t mk[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) mk[k] = sMask[k * 64 + lane];  // (all 256 slots are written: those behind the n entries hold no bit)
+      uint32_t* const dl = reinterpret_cast<uint32_t*>(lw);
+      dcnt = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        if (k * 64 < n) {  // wave-uniform
+          const uint32_t m = (mk[k] >> mask_sh) & 0x0F0Fu;  // bits 0..3: the upper band's four blocks, bits 8..11: the lower band's
+          const bool mine = m != 0u;
+          const uint64_t bal = __ballot(mine);
+          const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)dcnt));
+          if (mine) dl[at] = (m << 8) | (uint32_t)(k * 64 + lane);
+          dcnt += __popcll(bal);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        if (k * 64 < dcnt) {  // wave-uniform
+          const uint32_t v = dl[k * 64 + lane];  // (the LDS keeps a wave's order: the stores above have landed)
+          dg[k] = k * 64 + lane < dcnt ? v : 0u;
+        }
+      }
+    } else {
+      dg[0] = (((sMask[lane] >> mask_sh) & 0x0F0Fu) << 8) | (uint32_t)lane;
+    }
     // Every list starts as sentinels (shorter lists run on them up to the longest one, and the software pipeline below
-    // reads three slots ahead): 8 x 232 bytes = 116 quads, stored before the entries below (the LDS keeps a wave's order)
+    // reads three slots ahead): 8 x 232 bytes = 116 quads, stored behind the dense list's reads and before the entries
+    // below (the LDS keeps a wave's order)
     {
       constexpr int NQ = 8 * K6_LIST_STRIDE / 16;  // quads of this wave's eight lists
       static_assert(8 * K6_LIST_STRIDE % 16 == 0 && NQ > 64 && NQ <= 128, "list fill: two stores per lane");
+      static_assert(8 * K6_LIST_STRIDE >= CHUNK * 4, "the dense list is parked in the wave's list area");
       uint4* const f = reinterpret_cast<uint4*>(lw);
       const uint32_t sb = 0x01010101u * (uint32_t)K6_SENT_SLOT;
       const uint4 ff = make_uint4(sb, sb, sb, sb);
       f[lane] = ff;
       if (64 + lane < NQ) f[64 + lane] = ff;
     }
-    // compact the chunk into this wave's eight sub-row lists (ascending list order is preserved)
-    int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int lbase = w_u * 8 * K6_LIST_STRIDE;
+    int lend[8];  // (wave-uniform) end of list s, as an index into the workgroup's lists
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (k * 64 < n) {  // wave-uniform
-        const int jj = k * 64 + lane;
-        const uint32_t m = sMask[jj] >> mask_sh;  // bits 0..3: the upper band's four blocks, bits 8..11: the lower band's
+    for (int s = 0; s < 8; s++) lend[s] = lbase + s * K6_LIST_STRIDE;
+#pragma unroll 1
+    for (int d0 = 0; d0 < dcnt; d0 += 64) {  // wave-uniform
+      const uint32_t m = dg[0];
+      dg[0] = dg[1];
+      dg[1] = dg[2];
+      dg[2] = dg[3];
 #pragma unroll
-        for (int s = 0; s < 8; s++) {
-          uint32_t bit = m & (1u << (s < 4 ? s : s + 4));
-          asm volatile("" : "+v"(bit));  // (one compare for the ballot and the store's predicate, not two)
-          const bool rel = bit != 0u;
-          const uint64_t bal = __ballot(rel);
-          const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-          if (rel) lw[s * K6_LIST_STRIDE + cnt[s] + (int)before] = (uint8_t)jj;
-          cnt[s] += __popcll(bal);
-        }
+      for (int s = 0; s < 8; s++) {
+        uint32_t bit = m & (0x100u << (s < 4 ? s : s + 4));
+        asm volatile("" : "+v"(bit));  // (one compare for the ballot and the store's predicate, not two)
+        const bool rel = bit != 0u;
+        const uint64_t bal = __ballot(rel);
+        const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)lend[s]));
+        if (rel) l0[at] = (uint8_t)m;  // the slot
+        lend[s] += __popcll(bal);
       }
     }
-    const int maxcnt = __builtin_amdgcn_readfirstlane(
-        max(max(max(cnt[0], cnt[1]), max(cnt[2], cnt[3])), max(max(cnt[4], cnt[5]), max(cnt[6], cnt[7]))));
+    int maxcnt = lend[0] - lbase;
+#pragma unroll
+    for (int s = 1; s < 8; s++) {
+      maxcnt = max(maxcnt, lend[s] - lbase - s * K6_LIST_STRIDE);
+      asm volatile("" : "+s"(maxcnt));  // (wave-uniform counts: seven s_max_i32; left alone, pairs of them become v_max3_i32)
+    }
     __builtin_amdgcn_wave_barrier();
 #ifdef GCR_EXPERIMENTS
     if (a.clock_buf != nullptr && tid == 0 && base == 0) {

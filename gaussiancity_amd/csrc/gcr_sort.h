@@ -105,6 +105,82 @@ GCR_DEV void gcr_rank_merge(uint64_t* s, int n, const uint64_t (&key)[E], uint32
   }
 }
 
+// ---------------------------------------------------------------------------------------------- chunk sort in registers
+// gcr_rank_merge's phase 1 gives every thread the rank of ITS OWN key: 64 compares per key.  A caller that can go on
+// with whichever key its lane holds after a sort (the forward blend's one-chunk "tile ids" path: it gathers the record
+// behind the rank anyway) sorts the wave's 64 keys with a bitonic network in registers instead: 21 compare-exchange
+// stages of one 64-bit compare and two selects (67 VALU instructions against 208), the partner's key fetched with
+// ds_swizzle (lane ^ 1 .. 16) or ds_bpermute (lane ^ 32), which do not go through the VALU.  Which lanes of a stage
+// keep the larger key is a compile-time constant and reaches the selects as a scalar mask.
+constexpr uint64_t gcr_bitonic_keeps_larger(int K, int J) {  // stage (K, J): lane l is paired with l ^ J, runs of K ascend / descend
+  uint64_t m = 0;
+  for (int l = 0; l < 64; l++)
+    if (((l & J) == 0) != ((l & K) == 0)) m |= 1ull << l;
+  return m;
+}
+template <int J>
+GCR_DEV uint32_t gcr_lane_xor(uint32_t v, int lane) {
+  if constexpr (J <= 16)
+    return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x1F | (J << 10));  // bit mode: and 0x1F, or 0, xor J
+  else
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ J) << 2, (int)v);
+}
+template <int K, int J>
+GCR_DEV void gcr_bitonic_merge_regs(uint32_t& lo, uint32_t& hi, int lane) {
+  const uint32_t olo = gcr_lane_xor<J>(lo, lane), ohi = gcr_lane_xor<J>(hi, lane);
+  const uint64_t mine = ((uint64_t)hi << 32) | lo, other = ((uint64_t)ohi << 32) | olo;
+  // the lane of a pair that keeps the smaller key takes the partner's if it is smaller, the other one if it is not
+  // (equal keys -- two pads -- are the same value either way)
+  const bool take = __builtin_amdgcn_inverse_ballot_w64(__ballot(other < mine) ^ gcr_bitonic_keeps_larger(K, J));
+  lo = take ? olo : lo;
+  hi = take ? ohi : hi;
+  if constexpr (J > 1) gcr_bitonic_merge_regs<K, J / 2>(lo, hi, lane);
+}
+template <int K>
+GCR_DEV void gcr_bitonic_sort_regs(uint32_t& lo, uint32_t& hi, int lane) {
+  if constexpr (K > 2) gcr_bitonic_sort_regs<K / 2>(lo, hi, lane);
+  gcr_bitonic_merge_regs<K, K / 2>(lo, hi, lane);
+}
+
+// gcr_rank_merge<1> for a caller that takes the keys back in another order: n <= 256 unique keys, thread `tid` hands in
+// the key of element tid (~0 beyond n) and gets back, for tid < n, ANOTHER key of its own 64-key chunk -- the one of
+// chunk-local rank tid & 63 -- and that key's final position among all n (a thread beyond n gets a pad back).  Phase 2 is
+// gcr_rank_merge's.  `s`: (n rounded up to 64) 64-bit LDS words nobody else is using; one barrier, none at the end.
+GCR_DEV void gcr_sort_merge(uint64_t* s, int n, uint64_t& key, uint32_t& pos, int tid) {
+  const int nchunks = (n + 63) >> 6, npad = nchunks << 6;
+  const int lane = tid & 63, c = tid >> 6;
+  if (tid < npad) {  // wave-uniform
+    uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+    gcr_bitonic_sort_regs<64>(lo, hi, lane);
+    key = ((uint64_t)hi << 32) | lo;
+    s[tid] = key;  // (pads sort behind every real key of the chunk: the real keys of the last chunk are those of tid < n)
+  }
+  __syncthreads();
+  const int last_real = n - (nchunks - 1) * 64;  // real keys in the last chunk (1..64)
+  pos = 0;
+  if (tid < n) {
+    uint32_t p = (uint32_t)lane;
+    for (int c2 = 0; c2 < nchunks; c2++) {
+      if (c2 == c) continue;  // wave-uniform
+      const uint64_t* chunk = s + c2 * 64;
+      const int len = c2 == nchunks - 1 ? last_real : 64;
+      int lo = 0, hi = len;  // lower_bound: first index whose key is not < key
+#pragma unroll
+      for (int step = 0; step < 7; step++) {
+        if (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (chunk[mid] < key)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+      }
+      p += (uint32_t)lo;
+    }
+    pos = p;
+  }
+}
+
 // A tile list LONGER than the LDS this launch was given (dense general 3DGS scenes beyond the 4096-key maximum;
 // or simply a list that outgrew the caller's length hint -- GaussianCity's own scenes have ~150 entries per
 // tile): the same workgroup sorts it in three steps, everything else of the frame is untouched.
