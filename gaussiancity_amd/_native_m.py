@@ -1,6 +1,7 @@
 """ctypes binding of libgcm_hip.so (C ABI in include/gcm.h): the grouped modulated linear layer of the generator's
-attribute head, its backward, the group vector from masks and the head's output transform, all float32.  The
-declarations; gaussiancity_amd/_loader.py loads it.
+attribute head, its backward, the group vector from masks and the head's output transform, and the feed-forward third
+of a PTv3 Block (gcm_ffn_*: LayerNorm, MLP and residual in one launch, its backward), all float32.  The declarations;
+gaussiancity_amd/_loader.py loads it.
 The library is the product: no Python/CPU fallback -- a missing library or failing call raises RuntimeError."""
 import ctypes as C
 
@@ -20,6 +21,12 @@ _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argt
     "gcm_modlinear_backward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32,
                                          _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gcm_head_out": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, C.c_int, _f32, _vp, _vp]),
+    "gcm_ffn_max_channels": (C.c_int, []),
+    "gcm_ffn_forward": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp,
+                                  _vp, _vp]),
+    "gcm_ffn_backward_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "gcm_ffn_backward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _L = _loader.Library("gcm", "libgcm_hip.so", ABI_VERSION, _SIGNATURES)

@@ -20,6 +20,9 @@
 // counting sort of the rows by group (per 256-row block a count per group, one exclusive scan over (group, block),
 // then each row's rank inside its block) gives `perm`, the rows in group order and ascending inside a group; the sum
 // of a group is S slices of its rows, each one chain in that order, folded in slice order.
+//
+// The library's second row-wise MLP, the feed-forward third of a PTv3 Block (gcm_ffn_*), has its kernels in gcm_ffn.h,
+// included below; its C ABI functions are at the end of this file.  DESIGN.md section 18.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -489,6 +492,21 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 
 }  // namespace
 
+#include "gcm_ffn.h"
+
+namespace {
+
+int check_ffn_shape(const std::string& w, int64_t N, int32_t C, int32_t Hd) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
+  if (Hd <= 0 || Hd % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd must be a positive multiple of 4");
+  if (C > kFfnMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_ffn_max_channels()");
+  if (Hd > 4 * kFfnMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd above 4 * gcm_ffn_max_channels()");
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int gcm_abi_version(void) { return GCM_ABI_VERSION; }
@@ -622,6 +640,100 @@ int gcm_head_out(const float* f, int64_t f_stride, const float* w_out, const flo
   if (C == 1) k_head_out<1><<<blocks_for(N, 16), 256, 0, st>>>(f, f_stride, w_out, b, group, N, I, kind, factor, out);
   else k_head_out<3><<<blocks_for(N, 16), 256, 0, st>>>(f, f_stride, w_out, b, group, N, I, kind, factor, out);
   HIP_TRY(hipGetLastError(), "head_out launch");
+  return GCM_OK;
+}
+
+int gcm_ffn_max_channels(void) { return kFfnMaxChannels; }
+
+int gcm_ffn_forward(const float* x, int64_t x_stride, const float* ln_w, const float* ln_b, float eps, const float* w1,
+                    const float* b1, const float* w2, const float* b2, const float* row_scale, int64_t N, int32_t C,
+                    int32_t Hd, float* y, int64_t y_stride, float* mean, float* rstd, float* a, void* hip_stream) {
+  const std::string who("gcm_ffn_forward");
+  if (int rc = check_ffn_shape(who, N, C, Hd)) return rc;
+  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
+  if (!stride_ok(x_stride, C) || !stride_ok(y_stride, C))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(ln_w) || !aligned16(ln_b) || !aligned16(w1) || !aligned16(b1) || !aligned16(w2) ||
+      !aligned16(b2) || !aligned16(y) || !aligned16(a))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!x || !ln_w || !ln_b || !w1 || !b1 || !w2 || !b2 || !y)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, ln_w, ln_b, w1, b1, w2, b2 or y");
+  if ((mean == nullptr) != (rstd == nullptr) || (a && !mean))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": mean and rstd come together, and a needs both");
+  ffn_launch_forward(C, dim3(blocks_for(N, T)), (hipStream_t)hip_stream, x, x_stride, ln_w, ln_b, eps, w1, b1, w2, b2, row_scale,
+                     N, (int)C, (int)Hd, y, y_stride, mean, rstd, a);
+  HIP_TRY(hipGetLastError(), "ffn forward launch");
+  return GCM_OK;
+}
+
+size_t gcm_ffn_backward_workspace_bytes(int64_t N, int32_t C, int32_t Hd) {
+  if (check_ffn_shape("gcm_ffn_backward_workspace_bytes", N, C, Hd)) return 0;
+  g_err.clear();
+  return ffn_plan(N, C, Hd).total;
+}
+
+int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const float* rstd, const float* a,
+                     const float* dy, int64_t dy_stride, const float* row_scale, const float* ln_w, const float* ln_b,
+                     const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
+                     float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                     size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_ffn_backward");
+  if (int rc = check_ffn_shape(who, N, C, Hd)) return rc;
+  if (!stride_ok(x_stride, C) || !stride_ok(dy_stride, C) || (dx && !stride_ok(dx_stride, C)))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(a) || !aligned16(dy) || !aligned16(ln_w) || !aligned16(ln_b) || !aligned16(w1) ||
+      !aligned16(w2) || !aligned16(dx) || !aligned16(dln_w) || !aligned16(dln_b) || !aligned16(dw1) || !aligned16(db1) ||
+      !aligned16(dw2) || !aligned16(db2))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  const FfnPlan p = ffn_plan(N, C, Hd);
+  if (workspace_bytes < p.total || !workspace)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_ffn_backward_workspace_bytes");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (N > 0 && (!x || !mean || !rstd || !a || !dy || !ln_w || !ln_b || !w1 || !w2))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, mean, rstd, a, dy, ln_w, ln_b, w1 or w2");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
+    const size_t CH = (size_t)C * Hd * 4;
+    if (dln_w) HIP_TRY(hipMemsetAsync(dln_w, 0, (size_t)C * 4, st), "ffn backward clear dln_w");
+    if (dln_b) HIP_TRY(hipMemsetAsync(dln_b, 0, (size_t)C * 4, st), "ffn backward clear dln_b");
+    if (dw1) HIP_TRY(hipMemsetAsync(dw1, 0, CH, st), "ffn backward clear dw1");
+    if (db1) HIP_TRY(hipMemsetAsync(db1, 0, (size_t)Hd * 4, st), "ffn backward clear db1");
+    if (dw2) HIP_TRY(hipMemsetAsync(dw2, 0, CH, st), "ffn backward clear dw2");
+    if (db2) HIP_TRY(hipMemsetAsync(db2, 0, (size_t)C * 4, st), "ffn backward clear db2");
+    return GCM_OK;
+  }
+  char* ws = (char*)workspace;
+  float* da = (float*)(ws + p.da);
+  const bool ln = dln_w || dln_b, first = dw1 || db1, params = first || dw2 || db2;
+  if (dx || ln || first) {
+    float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
+    ffn_launch_bwd_rows(C, dim3((unsigned)p.tiles), st, x, x_stride, mean, rstd, a, dy, dy_stride, row_scale, ln_w, w1, w2, N,
+                        (int)C, (int)Hd, dx, dx_stride, da, lnpart);
+    HIP_TRY(hipGetLastError(), "ffn backward rows launch");
+    if (ln) {
+      const float* rec = lnpart;
+      int64_t count = p.tiles;
+      if (p.groups) {
+        float* grouped = (float*)(ws + p.lngroup);
+        k_ffn_fold_groups<<<dim3(blocks_for(2 * C, 256), (unsigned)p.groups), 256, 0, st>>>(lnpart, p.tiles, 2 * C, p.gper, grouped);
+        rec = grouped;
+        count = p.groups;
+      }
+      k_ffn_fold_ln<<<blocks_for(2 * C, 256), 256, 0, st>>>(rec, count, (int)C, dln_w, dln_b);
+      HIP_TRY(hipGetLastError(), "ffn backward LayerNorm fold launch");
+    }
+  }
+  if (params) {
+    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    float* part = (float*)(ws + p.wpart);
+    const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
+    k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
+                                   part);
+    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(part, p.sw, (int)C, (int)Hd, dw1, dw2, db1, db2);
+    HIP_TRY(hipGetLastError(), "ffn backward weight gradient launch");
+  }
   return GCM_OK;
 }
 

@@ -1,0 +1,113 @@
+"""The feed-forward third of the PTv3 point backbone's Block over libgcm_hip.so (include/gcm.h):
+Block.forward ends with LayerNorm, Linear(C, 4C), GELU, Linear(4C, C), DropPath and the residual add -- five launches
+and the [N, 4C] tensor through memory twice; install() rebinds the method so that this tail is one call of
+ffn.layernorm_mlp_residual.
+
+  install(pt_v3) / uninstall(pt_v3)     rebind Block.forward of a caller's imported models.pt_v3
+  stats() / reset_stats()               calls that took the fused tail, calls that went to the module's own method
+
+The rebound method runs cpe, the first residual, norm1, attn and drop_path through the modules themselves, so
+point_attention, point_index, point_pool and the sparse drop-ins keep composing, and the first DropPath mask is drawn
+first, as upstream.  post-norm Blocks, other norm or activation layers, a tanh GELU, CPU tensors, other dtypes, an active
+autocast and widths the library does not hold go to the module's own method, untouched.
+"""
+import torch
+
+from . import ffn
+
+_STATS = {"fused_calls": 0, "original_calls": 0}
+_ORIGINAL = "_gaussiancity_amd_point_ffn_original"
+
+
+def stats():
+    """Counters of this process: forwards whose tail ran the fused kernels, forwards handed to the module's own method."""
+    return dict(_STATS)
+
+
+def reset_stats():
+    for k in _STATS:
+        _STATS[k] = 0
+
+
+def _only(container):
+    """The one sub-module of a PointSequential, or None."""
+    mods = list(getattr(container, "_modules", {}).values())
+    return mods[0] if len(mods) == 1 else None
+
+
+def _parts(self, point):
+    """(LayerNorm, MLP, DropPath or None) when the Block's tail is what the operator computes, else None."""
+    if not getattr(self, "pre_norm", False):
+        return None
+    norm, mlp, drop = _only(self.norm2), _only(self.mlp), _only(self.drop_path)
+    if type(norm) is not torch.nn.LayerNorm or norm.weight is None or norm.bias is None or len(norm.normalized_shape) != 1:
+        return None
+    fc1, act, fc2 = (getattr(mlp, n, None) for n in ("fc1", "act", "fc2"))
+    if not isinstance(fc1, torch.nn.Linear) or not isinstance(fc2, torch.nn.Linear) or fc1.bias is None or fc2.bias is None:
+        return None
+    if type(act) is not torch.nn.GELU or act.approximate != "none":
+        return None
+    if isinstance(drop, torch.nn.Identity):
+        drop = None
+    elif drop is None or not hasattr(drop, "drop_prob") or not hasattr(drop, "scale_by_keep"):
+        return None
+    feat = point.feat
+    if not feat.is_cuda or feat.dtype != torch.float32 or feat.dim() != 2 or torch.is_autocast_enabled():
+        return None
+    C, Hd = feat.shape[1], fc1.out_features
+    if norm.normalized_shape[0] != C or fc1.in_features != C or fc2.in_features != Hd or fc2.out_features != C:
+        return None
+    if C % 4 or Hd % 4 or C > ffn.max_channels() or Hd > 4 * ffn.max_channels():
+        return None
+    return norm, mlp, drop
+
+
+# ---- the method of models/pt_v3.py, written against its behaviour: the order of its modules, of its residual adds and of
+# the DropPath draws, and the attributes it sets on the point ---------------------------------------------------------------
+def _forward(original):
+    def forward(self, point):
+        """Block.forward (pre_norm) with its last third over ffn.layernorm_mlp_residual."""
+        parts = _parts(self, point)
+        if parts is None:
+            _STATS["original_calls"] += 1
+            return original(self, point)
+        norm, mlp, drop = parts
+        shortcut = point.feat
+        point = self.cpe(point)
+        point.feat = shortcut + point.feat
+        shortcut = point.feat
+        point = self.norm1(point)
+        point = self.drop_path(self.attn(point))
+        point.feat = shortcut + point.feat
+
+        feat, row_scale = point.feat, None
+        if drop is not None and drop.drop_prob and drop.training:  # DropPath._drop_path's mask, drawn as it draws it
+            keep = 1 - drop.drop_prob
+            row_scale = feat.new_empty((feat.shape[0], 1)).bernoulli_(keep)
+            if keep > 0.0 and drop.scale_by_keep:
+                row_scale.div_(keep)
+        point.feat = ffn.layernorm_mlp_residual(feat, norm.weight, norm.bias, norm.eps, mlp.fc1.weight, mlp.fc1.bias,
+                                                mlp.fc2.weight, mlp.fc2.bias, row_scale)
+        point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(point.feat)
+        _STATS["fused_calls"] += 1
+        return point
+    return forward
+
+
+def install(pt_v3_module):
+    """Rebind Block.forward of the caller's imported models.pt_v3 so that its feed-forward tail runs the fused kernels.
+    Idempotent; uninstall() puts the module's own method back."""
+    if getattr(pt_v3_module, _ORIGINAL, None) is not None:
+        return
+    ffn.max_channels()  # loads the library: a build without the operator fails here, not inside a forward
+    original = pt_v3_module.Block.forward
+    setattr(pt_v3_module, _ORIGINAL, original)
+    pt_v3_module.Block.forward = _forward(original)
+
+
+def uninstall(pt_v3_module):
+    original = getattr(pt_v3_module, _ORIGINAL, None)
+    if original is None:
+        return
+    pt_v3_module.Block.forward = original
+    delattr(pt_v3_module, _ORIGINAL)

@@ -46,6 +46,47 @@
  *       GCM_OPACITY        sigmoid(v) * factor + (1 - factor)
  *     The dot product is fp32 (a fixed tree over I), T is evaluated in double and rounded once.  Rows with a
  *     negative group are exact zeros (group NULL: every row has one).
+ *
+ * ---- The feed-forward third of a PTv3 Block (models/pt_v3.py, Block.forward's tail) -------------
+ * For N rows, C channels and Hd hidden features, all float32:
+ *     mean_r = (1/C) sum_c x_rc;  var_r = (1/C) sum_c (x_rc - mean_r)^2;  rstd_r = 1 / sqrt(var_r + eps)
+ *     xn = (x - mean) rstd ln_w + ln_b          torch.nn.LayerNorm (biased variance)
+ *     a  = xn W1^T + b1                         w1 [Hd][C], b1 [Hd], contiguous
+ *     g  = a (1 + erf(a / sqrt 2)) / 2          torch.nn.GELU(approximate='none')
+ *     t  = g W2^T + b2                          w2 [C][Hd], b2 [C], contiguous
+ *     y  = x + s_r t                            row_scale s: float [N] or NULL (NULL: y = x + t)
+ *   C and Hd are positive multiples of 4, C <= gcm_ffn_max_channels() and Hd <= 4 gcm_ffn_max_channels(); N >= 0.
+ *   x, y, dy, dx are row-strided under the rule above (width C); ln_w, ln_b [C]; every float pointer but row_scale
+ *   (4-byte aligned) is 16-byte aligned.
+ *
+ * gcm_ffn_max_channels (host only): the largest C the fused kernels run, 128 in this build; never 0.  A binding asks
+ *     it to learn that the library has the operator and which widths go to it.
+ * gcm_ffn_forward: one launch.  a == NULL (inference): the hidden tensor never reaches memory; mean and rstd may then
+ *     be NULL too (both or neither).  a != NULL: the pre-activation a [N][Hd] is stored once and mean, rstd [N] beside
+ *     it, for the backward.  N == 0 returns 0 and queues nothing.
+ * gcm_ffn_backward: from the stored mean, rstd and a (read, never written: the call may be repeated),
+ *     dt = s_r dy;  dg = dt W2;  da = dg (Phi(a) + a phi(a));  dxn = da W1;
+ *     dx = dy + rstd (u - mean_c(u) - xhat mean_c(u xhat)),  u = dxn ln_w,  xhat = (x - mean) rstd;
+ *     dln_w = sum_r dxn xhat;  dln_b = sum_r dxn;  dw1 [Hd][C] = da^T xn;  db1 = sum_r da;  dw2 [C][Hd] = dt^T g;
+ *     db2 = sum_r dt.
+ *     ln_b is an input of the backward because dw1 is taken against xn, which holds it.  Every output is written
+ *     whole, a NULL output is skipped.  workspace is gcm_ffn_backward_workspace_bytes(N, C, Hd) bytes (never 0 for
+ *     arguments in range), 256-byte aligned; what it held before does not matter.
+ *
+ * Rounding and order: the LayerNorm sums are fp32; four lanes own a row, lane q adds its elements 4 q + 16 k .. + 3 in
+ * ascending order from 0 and the four lanes are added as (q0 + q1) + (q2 + q3); mean and var are the sums divided by
+ * C, rstd is 1 / sqrt with IEEE division and square root.  Every matrix product runs on v_mfma_f32_16x16x4_f32: a and
+ * dg are one fp32 chain from 0 over the channels in ascending order; t and dxn are, per chunk of 64 hidden features
+ * (ascending), one chain from 0 over the chunk, and the chunks' results are added in ascending order; b1, b2 are
+ * added after the chains; s_r t is one fp32 product, then one fp32 add of x -- a row with s_r = 0 has y == x and
+ * dx == dy bit for bit (finite t).  erf and exp are the device library's float32 functions.  No float atomics: dw1,
+ * db1, dw2, db2 are sums over row slices added in slice order; inside a slice every 32 consecutive rows are one chain
+ * from 0 in ascending row order (for db1, db2 four rows a chain, four chains paired as (0 + 1) + (2 + 3) per 16 rows,
+ * the 16-row sums chained) and the 32-row sums are added in ascending order; dln_w, dln_b are sums over tiles of 64
+ * rows (inside a tile, groups of CT / 16 consecutive rows in ascending order, CT = 32, 64 or 128 the smallest that
+ * holds C), the tiles added in ascending order, in groups of consecutive tiles when there are more than 64.  The
+ * slices and groups depend on N, C and Hd alone: every output is bit-identical from run to run and independent of
+ * how many workgroups the device holds at a time.
  */
 #ifndef GCM_H
 #define GCM_H
@@ -82,6 +123,21 @@ int gcm_modlinear_backward(const float* x, int64_t x_stride, const float* y, int
 
 int gcm_head_out(const float* f, int64_t f_stride, const float* w_out, const float* b, const int32_t* group, int64_t N,
                  int32_t I, int32_t C, int kind, float factor, float* out, void* hip_stream);
+
+int gcm_ffn_max_channels(void);
+
+int gcm_ffn_forward(const float* x, int64_t x_stride, const float* ln_w, const float* ln_b, float eps, const float* w1,
+                    const float* b1, const float* w2, const float* b2, const float* row_scale, int64_t N, int32_t C,
+                    int32_t Hd, float* y, int64_t y_stride, float* mean, float* rstd, float* a, void* hip_stream);
+
+/* 0 with a message in gcm_last_error() when an argument is out of range */
+size_t gcm_ffn_backward_workspace_bytes(int64_t N, int32_t C, int32_t Hd);
+
+int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const float* rstd, const float* a,
+                     const float* dy, int64_t dy_stride, const float* row_scale, const float* ln_w, const float* ln_b,
+                     const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
+                     float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                     size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
