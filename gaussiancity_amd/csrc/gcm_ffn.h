@@ -14,8 +14,8 @@
 //             and LDS, dxn accumulators += da W1 (chain over the chunk); then dxn -> LDS, the LayerNorm backward per row,
 //             dx = dy + ..., and the tile's column sums of dxn o xhat and dxn (row groups in ascending order).
 //             k_ffn_dw: dW1 = da^T xn and dW2 = dt^T GELU(a) in row slices (k_modlinear_dw's scheme, both in one
-//             launch), with db1 / db2 as the column sums of the slice's da / dt.  k_ffn_fold_params adds the slices in
-//             slice order; k_ffn_fold_groups / k_ffn_fold_ln add the tiles' LayerNorm partials in tile order.
+//             launch), with db1 / db2 as the column sums of the slice's da / dt.  k_ffn_fold_params adds the slices
+//             pairwise, a fixed tree; k_ffn_fold_groups / k_ffn_fold_ln add the tiles' LayerNorm partials in tile order.
 // Nothing depends on how many workgroups are resident: every sum has a fixed set of terms in a fixed order.
 #pragma once
 
@@ -26,6 +26,7 @@ constexpr int kPitchG = FH + 4;        // words between rows of the g / da chunk
 constexpr int kFfnMaxChannels = 128;   // widest instantiation (NJ = 4)
 constexpr int kFfnFoldTiles = 64;      // LayerNorm partials: up to this many tiles fold in one level
 constexpr int kFfnSumRows = 32;        // weight gradients: a chain runs over this many rows, the chains' results are added in order
+constexpr int kFfnMaxSlices = 64;      // weight gradients: at most this many row slices, the leaves of k_ffn_fold_params' tree
 
 __device__ __forceinline__ float gelu_f(float a) { return 0.5f * a * (1.0f + erff(a * 0.70710678118654752f)); }
 // d/da of gelu: Phi(a) + a phi(a)
@@ -534,7 +535,9 @@ __global__ __launch_bounds__(256) void k_ffn_dw(const float* __restrict__ x, int
   else ffn_dw_tile<1>(x, xs, mean, rstd, a, da, dy, dys, s, lnw, lnb, N, C, Hd, per, rec, Ds, Xs);
 }
 
-// the four parameter gradients: the slices' records in slice order
+// the four parameter gradients: the slices' records added pairwise -- one fixed tree over kFfnMaxSlices leaves (level w =
+// 1, 2, 4 .. adds slice s + w to slice s; a slice beyond S counts as 0 and x + 0 is x), so the rounding grows with the
+// depth of the tree and not with the number of slices: folded as one chain, db2 missed the bar at N = 4097
 __global__ void k_ffn_fold_params(const float* __restrict__ part, int S, int C, int Hd, float* __restrict__ dw1,
                                   float* __restrict__ dw2, float* __restrict__ db1, float* __restrict__ db2) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, len = ffn_record(C, Hd), CH = (int64_t)C * Hd;
@@ -543,9 +546,14 @@ __global__ void k_ffn_fold_params(const float* __restrict__ part, int S, int C, 
                : e < 2 * CH ? (dw2 ? dw2 + (e - CH) : nullptr)
                : e < 2 * CH + Hd ? (db1 ? db1 + (e - 2 * CH) : nullptr) : (db2 ? db2 + (e - 2 * CH - Hd) : nullptr);
   if (!out) return;
-  float v = part[e];
-  for (int s = 1; s < S; s++) v += part[(int64_t)s * len + e];
-  *out = v;
+  float v[kFfnMaxSlices];
+#pragma unroll
+  for (int s = 0; s < kFfnMaxSlices; s++) v[s] = s < S ? part[(int64_t)s * len + e] : 0.0f;
+#pragma unroll
+  for (int w = 1; w < kFfnMaxSlices; w *= 2)
+#pragma unroll
+    for (int s = 0; s < kFfnMaxSlices; s += 2 * w) v[s] += v[s + w];
+  *out = v[0];
 }
 
 // out[q][e] = sum of part[s][e] over the `per` records of group q (blockIdx.y), s ascending
@@ -584,7 +592,7 @@ FfnPlan ffn_plan(int64_t N, int32_t C, int32_t Hd) {
   p.groups = p.tiles > kFfnFoldTiles ? std::min<int64_t>(256, (p.tiles + kFfnFoldTiles - 1) / kFfnFoldTiles) : 0;
   p.gper = p.groups ? (p.tiles + p.groups - 1) / p.groups : 0;
   const int64_t wt = (int64_t)((Hd + T - 1) / T) * ((C + T - 1) / T);
-  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(64, 1024 / wt));
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(kFfnMaxSlices, 1024 / wt));
   p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 63) / 64));
   size_t off = 0;
   auto take = [&](size_t bytes) {

@@ -80,7 +80,8 @@
  * (ascending), one chain from 0 over the chunk, and the chunks' results are added in ascending order; b1, b2 are
  * added after the chains; s_r t is one fp32 product, then one fp32 add of x -- a row with s_r = 0 has y == x and
  * dx == dy bit for bit (finite t).  erf and exp are the device library's float32 functions.  No float atomics: dw1,
- * db1, dw2, db2 are sums over row slices added in slice order; inside a slice every 32 consecutive rows are one chain
+ * db1, dw2, db2 are sums over at most 64 row slices added pairwise (a fixed tree: slice s + w to slice s for w = 1, 2,
+ * 4 .. 32, a slice that does not exist counting as 0); inside a slice every 32 consecutive rows are one chain
  * from 0 in ascending row order (for db1, db2 four rows a chain, four chains paired as (0 + 1) + (2 + 3) per 16 rows,
  * the 16-row sums chained) and the 32-row sums are added in ascending order; dln_w, dln_b are sums over tiles of 64
  * rows (inside a tile, groups of CT / 16 consecutive rows in ascending order, CT = 32, 64 or 128 the smallest that

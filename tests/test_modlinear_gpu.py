@@ -9,13 +9,16 @@ has no term at all (rows without a group, empty groups: those must be exact zero
     dbeta_go, dbias_o    sum |dpre_ro|
 
 dpre = dy * (y > 0 ? 1 : slope) is the header's rule on the STORED y, so the reference takes the sign from the y the
-forward stored (an element whose float64 value is within rounding of 0 has no sign to agree on)."""
+forward stored (an element whose float64 value is within rounding of 0 has no sign to agree on).
+
+Cases, the reference, the runner and the bar are in tests/modlinear_ref.py, shared with tests/test_modlinear_plans_gpu.py."""
 import numpy as np
 import pytest
 import torch
 
+from modlinear_ref import HEAD_FACTORS, exact_zeros, head_reference, hold, make_case, run
+
 pytestmark = pytest.mark.gpu
-BAR = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -27,98 +30,6 @@ def dev():
     yield torch.device("cuda:0")
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
-
-
-def make_case(N, I, O, G, slope, bias, seed, plain=False):
-    """Inputs of one case.  G = 5: rows of the groups interleaved at random, group 3 has no rows; about 5 % of the rows
-    (at least one from 20 rows on) are at -1.  plain: alpha, beta and group absent."""
-    rng = np.random.default_rng(seed)
-    c = {"x": rng.normal(size=(N, I)), "w": rng.normal(size=(O, I)) / np.sqrt(I), "dy": rng.normal(size=(N, O)),
-         "alpha": None, "beta": None, "group": None, "bias": rng.normal(size=O) if bias else None, "slope": slope, "G": G}
-    if not plain:
-        c["alpha"], c["beta"] = 1.0 + 0.5 * rng.normal(size=(G, I)), rng.normal(size=(G, O))
-        group = rng.choice([g for g in range(G) if g != 3], size=N)
-        group[rng.random(N) < 0.05] = -1
-        if N >= 20:
-            group[rng.integers(0, N)] = -1
-        c["group"] = group.astype(np.int32)
-    return {k: v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v for k, v in c.items()}
-
-
-def reference(c, y_stored):
-    """float64 values and the sums of absolute terms of y and the five gradients."""
-    x, w, dy = (c[k].astype(np.float64) for k in ("x", "w", "dy"))
-    (N, I), O, G, slope = x.shape, w.shape[0], c["G"], c["slope"]
-    group = c["group"] if c["group"] is not None else np.zeros(N, np.int32)
-    live = (group >= 0)[:, None]
-    gi = np.maximum(group, 0)
-    a = c["alpha"].astype(np.float64)[gi] if c["alpha"] is not None else np.ones((N, I))
-    be = c["beta"].astype(np.float64)[gi] if c["beta"] is not None else np.zeros((N, O))
-    b = c["bias"].astype(np.float64) if c["bias"] is not None else np.zeros(O)
-    xa = x * a * live
-    pre = xa @ w.T + be + b
-    val = {"y": np.where(pre > 0, pre, pre * slope) * live}
-    mag = {"y": (np.abs(xa) @ np.abs(w).T + np.abs(be) + np.abs(b)) * live}
-    dpre = dy * np.where(y_stored > 0, 1.0, slope) * live
-    reach = np.abs(dpre) @ np.abs(w)            # sum_o |dpre_ro W_oi|
-    dxs = dpre @ w
-    val["dx"], mag["dx"] = dxs * a * live, np.abs(a) * reach * live
-    val["dw"], mag["dw"] = dpre.T @ xa, np.abs(dpre).T @ np.abs(xa)
-    onehot = (group[:, None] == np.arange(G)[None]).astype(np.float64)      # [N, G]
-    val["dalpha"], mag["dalpha"] = onehot.T @ (dxs * x), onehot.T @ (np.abs(x) * reach)
-    val["dbeta"], mag["dbeta"] = onehot.T @ dpre, onehot.T @ np.abs(dpre)
-    val["dbias"], mag["dbias"] = dpre.sum(0), np.abs(dpre).sum(0)
-    return val, mag
-
-
-def run(dev, c, strided=False):
-    """Forward + backward through modulated_linear; y and the gradients as float32 numpy arrays."""
-    from gaussiancity_amd.modlinear import modulated_linear
-    leaf = lambda k: None if c[k] is None else torch.from_numpy(c[k]).to(dev).requires_grad_(True)  # noqa: E731
-    t = {k: leaf(k) for k in ("x", "w", "alpha", "beta", "bias")}
-    x = t["x"]
-    if strided:  # rows 8 elements further apart than they are wide
-        wide = torch.zeros((c["x"].shape[0], c["x"].shape[1] + 8), device=dev)
-        wide[:, :c["x"].shape[1]] = t["x"].detach()
-        x = t["x"] = wide[:, :c["x"].shape[1]].requires_grad_(True)
-        assert x.stride(0) == c["x"].shape[1] + 8 and not x.is_contiguous()
-    group = None if c["group"] is None else torch.from_numpy(c["group"]).to(dev)
-    y = modulated_linear(x, t["w"], t["alpha"], t["beta"], t["bias"], group, c["slope"])
-    assert y.dtype == torch.float32 and tuple(y.shape) == (c["x"].shape[0], c["w"].shape[0])
-    y.backward(torch.from_numpy(c["dy"]).to(dev))
-    res = {"y": y.detach().cpu().numpy()}
-    for name, k in (("dx", "x"), ("dw", "w"), ("dalpha", "alpha"), ("dbeta", "beta"), ("dbias", "bias")):
-        if t[k] is not None:
-            assert t[k].grad is not None and t[k].grad.shape == t[k].shape, name
-            res[name] = t[k].grad.cpu().numpy()
-    return res
-
-
-def hold(c, got, label):
-    val, mag = reference(c, got["y"])
-    if c["x"].shape[0]:
-        live = mag["y"] > 0
-        assert (got["y"][live] > 0).any() and (got["y"][live] < 0).any(), "dy must straddle y = 0"
-    bad = []
-    for name, g in got.items():
-        err = np.abs(g.astype(np.float64) - val[name])
-        units = float((err / np.where(mag[name] > 0, mag[name], 1.0)).max()) if err.size else 0.0
-        print("%s %-6s worst error %.2e of the sum of absolute terms" % (label, name, units))
-        if not (err <= BAR * mag[name]).all():
-            bad.append((name, units, int((err > BAR * mag[name]).sum())))
-    assert not bad, bad
-    return val, mag
-
-
-def exact_zeros(c, got):
-    """Rows of group -1 of y and dx, and an empty group's rows of dalpha and dbeta, are exact zeros."""
-    if c["group"] is None:
-        return
-    bare = c["group"] < 0
-    assert not got["y"][bare].any() and not got["dx"][bare].any()
-    for g in range(c["G"]):
-        if not (c["group"] == g).any():
-            assert not got["dalpha"][g].any() and not got["dbeta"][g].any(), g
 
 
 SHAPES = [(N, I, O) for N in (1, 63, 64, 65, 333) for (I, O) in ((4, 4), (20, 36), (64, 64))]
@@ -217,23 +128,16 @@ def test_head_out_against_float64(dev, kind):
     has slope `factor` inside and 0 outside; a value within the bar of the clamp's corner may sit on either side of it,
     so the slope there is `factor` (the transform's Lipschitz constant)."""
     from gaussiancity_amd.modlinear import head_out
-    N, I, C, factor = 333, 52, 1 if kind == "opacity" else 3, {"xyz": 0.75, "rgb": 2.0, "scale": 0.5, "opacity": 0.6}[kind]
+    N, I, C, factor = 333, 52, 1 if kind == "opacity" else 3, HEAD_FACTORS[kind]
     rng = np.random.default_rng(len(kind))
     f = rng.normal(size=(N, I)).astype(np.float32)
     w = (rng.normal(size=(C, I)) * 1.5 / np.sqrt(I)).astype(np.float32)
     b = (rng.normal(size=C) * 0.2).astype(np.float32)
     group = rng.integers(-1, 4, size=N).astype(np.int32)
-    v = f.astype(np.float64) @ w.astype(np.float64).T + b
-    mag = np.abs(f).astype(np.float64) @ np.abs(w).astype(np.float64).T + np.abs(b)
-    s = 1.0 / (1.0 + np.exp(-v))
+    v, want, bar = head_reference(kind, f, w, b, factor)
     if kind == "scale":
-        want, slope = 1.0 + np.clip(v, -1, 1) * factor, np.where(np.abs(v) <= 1 + BAR * mag, factor, 0.0)
         inside = np.abs(v[group >= 0]) < 1
         assert inside.any() and (~inside).any(), "the clamp must be active on some rows and inactive on others"
-    elif kind == "opacity":
-        want, slope = s * factor + (1 - factor), s * (1 - s) * factor
-    else:
-        want, slope = (s - 0.5) * factor, s * (1 - s) * factor
     for grp in (group, None):
         live = (grp >= 0)[:, None] if grp is not None else np.ones((N, 1), bool)
         got = head_out(torch.from_numpy(f).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(b).to(dev),
@@ -241,7 +145,6 @@ def test_head_out_against_float64(dev, kind):
         assert got.dtype == torch.float32 and tuple(got.shape) == (N, C)
         got = got.cpu().numpy()
         assert not got[~live[:, 0]].any()                    # rows without a group: exact zeros
-        bar = BAR * mag * slope + np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
         err = np.abs(got.astype(np.float64) - want) * live
         print("%s worst error / bar %.3f" % (kind, float((err / bar).max())))
         assert (err <= bar).all(), (kind, float((err / bar).max()))
