@@ -412,50 +412,23 @@ __global__ __launch_bounds__(256, 2) void k_ffn_bwd_rows(const float* __restrict
 // A slice's record in `part`: dW1 [Hd][C], dW2 [C][Hd], db1 [Hd], db2 [C].
 __host__ __device__ inline int64_t ffn_record(int C, int Hd) { return 2 * (int64_t)C * Hd + Hd + C; }
 
-// MODE 0: dW1[h][c] = sum_r da[r][h] xn[r][c], db1[h] = sum_r da[r][h].   MODE 1: dW2[c][h] = sum_r dt[r][c] g[r][h],
-// db2[c] = sum_r dt[r][c].  O, I: the extents of the "d" and the "x" operand; rows p0 .. p1 in ascending order, one chain
-// from 0 per kFfnSumRows rows, those sums added in ascending order (shorter chains: the rounding grows with the root of
-// the chain's length).
-template <int MODE>
-__device__ __forceinline__ void ffn_dw_tile(const float* __restrict__ x, int64_t xs, const float* __restrict__ mean,
-                                            const float* __restrict__ rstd, const float* __restrict__ a,
-                                            const float* __restrict__ da, const float* __restrict__ dy, int64_t dys,
-                                            const float* __restrict__ s, const float* __restrict__ lnw,
-                                            const float* __restrict__ lnb, int64_t N, int C, int Hd, int64_t per,
-                                            float* __restrict__ rec, float* Ds, float* Xs) {
-  const int O = MODE == 0 ? Hd : C, I = MODE == 0 ? C : Hd;
+// One 64 x 64 tile of a row-sliced weight gradient and its bias gradient, shared by k_ffn_dw and k_front_dw (gcm_front.h):
+// dst[o][i] = sum_r d[r][o] x[r][i] (row pitch I) and, from the tiles with i0 == 0, bias[o] = sum_r d[r][o], over the rows
+// p0 .. p1 in ascending order.  fetch(r, od, ix, vd, vx) loads row r's four "d" elements at o0 + sc (when od) and four "x"
+// elements at i0 + sc (when ix); Od, I: the extents of the two operands.  One chain from 0 per kFfnSumRows rows, those sums
+// added in ascending order (shorter chains: the rounding grows with the root of the chain's length).
+template <typename Fetch>
+__device__ __forceinline__ void dw_slice_tile(Fetch fetch_row, int Od, int I, int o0, int i0, int64_t p0, int64_t p1,
+                                              float* __restrict__ dst, float* __restrict__ bias, float* Ds, float* Xs) {
   const int tid = threadIdx.x;
   const WaveTile g;
-  const int tiles_i = (I + T - 1) / T;
-  const int o0 = (blockIdx.x / tiles_i) * T, i0 = (blockIdx.x % tiles_i) * T;
-  const int64_t p0 = blockIdx.y * per, p1 = p0 + per < N ? p0 + per : N;
   const int sp = tid >> 4, sc = 4 * (tid & 15);
-  const bool od = o0 + sc < O, ix = i0 + sc < I;
-  f4 gam = zero4(), bet = zero4();
-  if (MODE == 0 && ix) {
-    gam = ld4(lnw + i0 + sc);
-    bet = ld4(lnb + i0 + sc);
-  }
+  const bool od = o0 + sc < Od, ix = i0 + sc < I;
   f4 vd, vx;
   auto fetch = [&](int64_t p) {
     vd = zero4();
     vx = zero4();
-    const int64_t r = p + sp;
-    if (r >= p1) return;
-    if (MODE == 0) {
-      if (od) vd = ld4(da + r * Hd + o0 + sc);
-      if (ix) vx = (ld4(x + r * xs + i0 + sc) - mean[r]) * rstd[r] * gam + bet;
-    } else {
-      if (od) {
-        vd = ld4(dy + r * dys + o0 + sc);
-        if (s) vd = vd * s[r];
-      }
-      if (ix) {
-        const f4 av = ld4(a + r * Hd + i0 + sc);
-#pragma unroll
-        for (int k = 0; k < 4; k++) vx[k] = gelu_f(av[k]);
-      }
-    }
+    if (p + sp < p1) fetch_row(p + sp, od, ix, vd, vx);
   };
   f4 acc[2][2], tot[2][2];  // acc: the chain over the current kFfnSumRows rows; tot: those sums, ascending
   clear_acc(acc);
@@ -504,21 +477,58 @@ __device__ __forceinline__ void ffn_dw_tile(const float* __restrict__ x, int64_t
     __syncthreads();
   }
   flush();
-  const int64_t CH = (int64_t)C * Hd;
-  float* dst = rec + (MODE == 0 ? 0 : CH);
 #pragma unroll
   for (int i = 0; i < 2; i++)
 #pragma unroll
     for (int v = 0; v < 4; v++) {
       const int o = o0 + g.wr + 16 * i + 4 * g.fk + v;
-      if (o >= O) continue;
+      if (o >= Od) continue;
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         const int c = i0 + g.wc + 16 * j + g.fl;
         if (c < I) dst[(int64_t)o * I + c] = tot[i][j][v];
       }
     }
-  if (i0 == 0 && tid < T && o0 + tid < O) rec[2 * CH + (MODE == 0 ? 0 : Hd) + o0 + tid] = btot;
+  if (i0 == 0 && tid < T && o0 + tid < Od) bias[o0 + tid] = btot;
+}
+
+// MODE 0: dW1[h][c] = sum_r da[r][h] xn[r][c], db1[h] = sum_r da[r][h].   MODE 1: dW2[c][h] = sum_r dt[r][c] g[r][h],
+// db2[c] = sum_r dt[r][c].  O, I: the extents of the "d" and the "x" operand.
+template <int MODE>
+__device__ __forceinline__ void ffn_dw_tile(const float* __restrict__ x, int64_t xs, const float* __restrict__ mean,
+                                            const float* __restrict__ rstd, const float* __restrict__ a,
+                                            const float* __restrict__ da, const float* __restrict__ dy, int64_t dys,
+                                            const float* __restrict__ s, const float* __restrict__ lnw,
+                                            const float* __restrict__ lnb, int64_t N, int C, int Hd, int64_t per,
+                                            float* __restrict__ rec, float* Ds, float* Xs) {
+  const int O = MODE == 0 ? Hd : C, I = MODE == 0 ? C : Hd;
+  const int tiles_i = (I + T - 1) / T;
+  const int o0 = (blockIdx.x / tiles_i) * T, i0 = (blockIdx.x % tiles_i) * T;
+  const int64_t p0 = blockIdx.y * per, p1 = p0 + per < N ? p0 + per : N;
+  const int sc = 4 * (threadIdx.x & 15);
+  f4 gam = zero4(), bet = zero4();
+  if (MODE == 0 && i0 + sc < I) {
+    gam = ld4(lnw + i0 + sc);
+    bet = ld4(lnb + i0 + sc);
+  }
+  auto fetch = [&](int64_t r, bool od, bool ix, f4& vd, f4& vx) {
+    if (MODE == 0) {
+      if (od) vd = ld4(da + r * Hd + o0 + sc);
+      if (ix) vx = (ld4(x + r * xs + i0 + sc) - mean[r]) * rstd[r] * gam + bet;
+    } else {
+      if (od) {
+        vd = ld4(dy + r * dys + o0 + sc);
+        if (s) vd = vd * s[r];
+      }
+      if (ix) {
+        const f4 av = ld4(a + r * Hd + i0 + sc);
+#pragma unroll
+        for (int k = 0; k < 4; k++) vx[k] = gelu_f(av[k]);
+      }
+    }
+  };
+  const int64_t CH = (int64_t)C * Hd;
+  dw_slice_tile(fetch, O, I, o0, i0, p0, p1, rec + (MODE == 0 ? 0 : CH), rec + 2 * CH + (MODE == 0 ? 0 : Hd), Ds, Xs);
 }
 
 // grid: (tiles of 64 x 64 over Hd x C, row slices, 2): z = 0 is dW1 / db1, z = 1 is dW2 / db2
@@ -537,14 +547,16 @@ __global__ __launch_bounds__(256) void k_ffn_dw(const float* __restrict__ x, int
 
 // the four parameter gradients: the slices' records added pairwise -- one fixed tree over kFfnMaxSlices leaves (level w =
 // 1, 2, 4 .. adds slice s + w to slice s; a slice beyond S counts as 0 and x + 0 is x), so the rounding grows with the
-// depth of the tree and not with the number of slices: folded as one chain, db2 missed the bar at N = 4097
-__global__ void k_ffn_fold_params(const float* __restrict__ part, int S, int C, int Hd, float* __restrict__ dw1,
-                                  float* __restrict__ dw2, float* __restrict__ db1, float* __restrict__ db2) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, len = ffn_record(C, Hd), CH = (int64_t)C * Hd;
+// depth of the tree and not with the number of slices: folded as one chain, db2 missed the bar at N = 4097.
+// A record is four pieces of n0, n1, n2, n3 elements (ffn_record; front_record of gcm_front.h); a null output is skipped.
+__global__ void k_ffn_fold_params(const float* __restrict__ part, int S, int64_t n0, int64_t n1, int64_t n2, int64_t n3,
+                                  float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
+                                  float* __restrict__ o3) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, len = n0 + n1 + n2 + n3;
   if (e >= len) return;
-  float* out = e < CH ? (dw1 ? dw1 + e : nullptr)
-               : e < 2 * CH ? (dw2 ? dw2 + (e - CH) : nullptr)
-               : e < 2 * CH + Hd ? (db1 ? db1 + (e - 2 * CH) : nullptr) : (db2 ? db2 + (e - 2 * CH - Hd) : nullptr);
+  float* out = e < n0 ? (o0 ? o0 + e : nullptr)
+               : e < n0 + n1 ? (o1 ? o1 + (e - n0) : nullptr)
+               : e < n0 + n1 + n2 ? (o2 ? o2 + (e - n0 - n1) : nullptr) : (o3 ? o3 + (e - n0 - n1 - n2) : nullptr);
   if (!out) return;
   float v[kFfnMaxSlices];
 #pragma unroll

@@ -22,7 +22,9 @@
 // of a group is S slices of its rows, each one chain in that order, folded in slice order.
 //
 // The library's second row-wise MLP, the feed-forward third of a PTv3 Block (gcm_ffn_*), has its kernels in gcm_ffn.h,
-// included below; its C ABI functions are at the end of this file.  DESIGN.md section 18.
+// included below; its C ABI functions are at the end of this file.  DESIGN.md section 18.  The third, the front of the same
+// Block (gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection), is gcm_front.h,
+// included after it.  DESIGN.md section 19.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -493,6 +495,7 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 }  // namespace
 
 #include "gcm_ffn.h"
+#include "gcm_front.h"
 
 namespace {
 
@@ -502,6 +505,15 @@ int check_ffn_shape(const std::string& w, int64_t N, int32_t C, int32_t Hd) {
   if (Hd <= 0 || Hd % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd must be a positive multiple of 4");
   if (C > kFfnMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_ffn_max_channels()");
   if (Hd > 4 * kFfnMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd above 4 * gcm_ffn_max_channels()");
+  return 0;
+}
+
+int check_front_shape(const std::string& w, int64_t N, int32_t C, int32_t O) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
+  if (O <= 0 || O % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": O must be a positive multiple of 4");
+  if (C > kFrontMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_front_max_channels()");
+  if (O > 3 * kFrontMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": O above 3 * gcm_front_max_channels()");
   return 0;
 }
 
@@ -731,8 +743,118 @@ int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const 
     const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
     k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
                                    part);
-    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(part, p.sw, (int)C, (int)Hd, dw1, dw2, db1, db2);
+    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(part, p.sw, (int64_t)C * Hd, (int64_t)C * Hd, Hd, C, dw1, dw2,
+                                                                          db1, db2);
     HIP_TRY(hipGetLastError(), "ffn backward weight gradient launch");
+  }
+  return GCM_OK;
+}
+
+int gcm_front_max_channels(void) { return kFrontMaxChannels; }
+
+int gcm_front_forward(const float* x, int64_t x_stride, const float* s, int64_t s_stride, const float* wc, const float* bc,
+                      const float* lnc_w, const float* lnc_b, float eps_c, const float* ln1_w, const float* ln1_b,
+                      float eps_1, const float* wq, const float* bq, int64_t N, int32_t C, int32_t O, float* feat,
+                      int64_t feat_stride, float* qkv, int64_t qkv_stride, float* t, float* mean_c, float* rstd_c,
+                      float* mean_1, float* rstd_1, void* hip_stream) {
+  const std::string who("gcm_front_forward");
+  if (int rc = check_front_shape(who, N, C, O)) return rc;
+  if (!std::isfinite(eps_c) || eps_c < 0.0f || !std::isfinite(eps_1) || eps_1 < 0.0f)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps_c and eps_1 must be finite and >= 0");
+  if (!stride_ok(x_stride, C) || !stride_ok(s_stride, C) || !stride_ok(feat_stride, C) || !stride_ok(qkv_stride, O))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(s) || !aligned16(wc) || !aligned16(bc) || !aligned16(lnc_w) || !aligned16(lnc_b) ||
+      !aligned16(ln1_w) || !aligned16(ln1_b) || !aligned16(wq) || !aligned16(bq) || !aligned16(feat) || !aligned16(qkv) ||
+      !aligned16(t))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!x || !s || !wc || !bc || !lnc_w || !lnc_b || !ln1_w || !ln1_b || !wq || !bq || !feat || !qkv)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, s, wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq, feat or qkv");
+  const int stats = (mean_c != nullptr) + (rstd_c != nullptr) + (mean_1 != nullptr) + (rstd_1 != nullptr);
+  if ((stats != 0 && stats != 4) || (t != nullptr) != (stats == 4))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": t and the four statistics come together, all or none");
+  front_launch_forward(C, dim3(blocks_for(N, T)), (hipStream_t)hip_stream, x, x_stride, s, s_stride, wc, bc, lnc_w, lnc_b, eps_c,
+                       ln1_w, ln1_b, eps_1, wq, bq, N, (int)C, (int)O, feat, feat_stride, qkv, qkv_stride, t, mean_c, rstd_c,
+                       mean_1, rstd_1);
+  HIP_TRY(hipGetLastError(), "front forward launch");
+  return GCM_OK;
+}
+
+size_t gcm_front_backward_workspace_bytes(int64_t N, int32_t C, int32_t O) {
+  if (check_front_shape("gcm_front_backward_workspace_bytes", N, C, O)) return 0;
+  g_err.clear();
+  return front_plan(N, C, O).total;
+}
+
+int gcm_front_backward(const float* s, int64_t s_stride, const float* feat, int64_t feat_stride, const float* t,
+                       const float* mean_c, const float* rstd_c, const float* mean_1, const float* rstd_1,
+                       const float* dfeat, int64_t dfeat_stride, const float* dqkv, int64_t dqkv_stride, const float* wc,
+                       const float* lnc_w, const float* ln1_w, const float* ln1_b, const float* wq, int64_t N, int32_t C,
+                       int32_t O, float* dx, int64_t dx_stride, float* ds, int64_t ds_stride, float* dwc, float* dbc,
+                       float* dlnc_w, float* dlnc_b, float* dln1_w, float* dln1_b, float* dwq, float* dbq, void* workspace,
+                       size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_front_backward");
+  if (int rc = check_front_shape(who, N, C, O)) return rc;
+  if (!stride_ok(s_stride, C) || !stride_ok(feat_stride, C) || !stride_ok(dfeat_stride, C) || !stride_ok(dqkv_stride, O) ||
+      (dx && !stride_ok(dx_stride, C)) || (ds && !stride_ok(ds_stride, C)))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(s) || !aligned16(feat) || !aligned16(t) || !aligned16(dfeat) || !aligned16(dqkv) || !aligned16(wc) ||
+      !aligned16(lnc_w) || !aligned16(ln1_w) || !aligned16(ln1_b) || !aligned16(wq) || !aligned16(dx) || !aligned16(ds) ||
+      !aligned16(dwc) || !aligned16(dbc) || !aligned16(dlnc_w) || !aligned16(dlnc_b) || !aligned16(dln1_w) ||
+      !aligned16(dln1_b) || !aligned16(dwq) || !aligned16(dbq))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  const FrontPlan p = front_plan(N, C, O);
+  if (workspace_bytes < p.total || !workspace)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_front_backward_workspace_bytes");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (N > 0 && (!s || !feat || !t || !mean_c || !rstd_c || !mean_1 || !rstd_1 || !dfeat || !dqkv || !wc || !lnc_w || !ln1_w ||
+                !ln1_b || !wq))
+    return fail(GCM_ERR_INVALID_ARGUMENT,
+                who + ": null s, feat, t, mean_c, rstd_c, mean_1, rstd_1, dfeat, dqkv, wc, lnc_w, ln1_w, ln1_b or wq");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
+    if (dwc) HIP_TRY(hipMemsetAsync(dwc, 0, (size_t)C * C * 4, st), "front backward clear dwc");
+    if (dbc) HIP_TRY(hipMemsetAsync(dbc, 0, (size_t)C * 4, st), "front backward clear dbc");
+    if (dlnc_w) HIP_TRY(hipMemsetAsync(dlnc_w, 0, (size_t)C * 4, st), "front backward clear dlnc_w");
+    if (dlnc_b) HIP_TRY(hipMemsetAsync(dlnc_b, 0, (size_t)C * 4, st), "front backward clear dlnc_b");
+    if (dln1_w) HIP_TRY(hipMemsetAsync(dln1_w, 0, (size_t)C * 4, st), "front backward clear dln1_w");
+    if (dln1_b) HIP_TRY(hipMemsetAsync(dln1_b, 0, (size_t)C * 4, st), "front backward clear dln1_b");
+    if (dwq) HIP_TRY(hipMemsetAsync(dwq, 0, (size_t)O * C * 4, st), "front backward clear dwq");
+    if (dbq) HIP_TRY(hipMemsetAsync(dbq, 0, (size_t)O * 4, st), "front backward clear dbq");
+    return GCM_OK;
+  }
+  char* ws = (char*)workspace;
+  float* dt = (float*)(ws + p.dt);
+  const bool ln = dln1_w || dln1_b || dlnc_w || dlnc_b, conv = dwc || dbc, proj = dwq || dbq;
+  if (dx || ds || ln || conv) {
+    float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
+    front_launch_bwd_rows(C, dim3((unsigned)p.tiles), st, feat, feat_stride, t, mean_c, rstd_c, mean_1, rstd_1, dfeat,
+                          dfeat_stride, dqkv, dqkv_stride, wc, lnc_w, ln1_w, wq, N, (int)C, (int)O, dx, dx_stride, ds, ds_stride,
+                          dt, lnpart);
+    HIP_TRY(hipGetLastError(), "front backward rows launch");
+    if (ln) {
+      const float* rec = lnpart;
+      int64_t count = p.tiles;
+      if (p.groups) {
+        float* grouped = (float*)(ws + p.lngroup);
+        k_ffn_fold_groups<<<dim3(blocks_for(4 * C, 256), (unsigned)p.groups), 256, 0, st>>>(lnpart, p.tiles, 4 * C, p.gper, grouped);
+        rec = grouped;
+        count = p.groups;
+      }
+      k_front_fold_ln<<<blocks_for(4 * C, 256), 256, 0, st>>>(rec, count, (int)C, dln1_w, dln1_b, dlnc_w, dlnc_b);
+      HIP_TRY(hipGetLastError(), "front backward LayerNorm fold launch");
+    }
+  }
+  if (conv || proj) {
+    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    float* part = (float*)(ws + p.wpart);
+    const dim3 grid(p.wt, (unsigned)p.sw, (conv ? 1u : 0u) + (proj ? 1u : 0u));
+    k_front_dw<<<grid, 256, 0, st>>>(s, s_stride, feat, feat_stride, mean_1, rstd_1, ln1_w, ln1_b, dqkv, dqkv_stride, dt, N,
+                                     (int)C, (int)O, per, proj ? 0 : 1, part);
+    k_ffn_fold_params<<<blocks_for(front_record(C, O), 256), 256, 0, st>>>(part, p.sw, (int64_t)O * C, (int64_t)C * C, O, C, dwq, dwc,
+                                                                          dbq, dbc);
+    HIP_TRY(hipGetLastError(), "front backward weight gradient launch");
   }
   return GCM_OK;
 }

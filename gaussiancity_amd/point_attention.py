@@ -5,6 +5,8 @@ features' own dtype -- float32 features in fp32 throughout, float16 features (au
 
   install(pt_v3) / uninstall(pt_v3)     rebind SerializedAttention.forward of a caller's imported models.pt_v3
   stats() / reset_stats()               calls that took the fused path, calls that went to the module's own method
+  forward_from_qkv(attn, point, qkv)    the rebound method from the qkv projection on, for a caller that has the
+                                        projection already (point_front computes it in the Block front's one launch)
 
 Independent of point_index.install: the rebound method calls self.get_padding_and_inverse, whoever provides it.  Relative
 position encoding, active attention dropout, the flash branch, CPU tensors and other dtypes go to the module's own method,
@@ -41,6 +43,23 @@ def _fusable(self, point):
 
 # ---- the method of models/pt_v3.py, written against its behaviour: the attributes it sets, its one wait for the smallest
 # batch element, the keys it reads, and the order of gather, attention, scatter, projection and dropout ----------------
+def forward_from_qkv(self, point, qkv):
+    """SerializedAttention.forward's non-flash branch from the projected qkv [N, 3C] on, over attention.varlen_attention:
+    the caller has checked _fusable(self, point) and that qkv's dtype is one of attention.dtypes().  Counted as a fused call."""
+    counts = torch.diff(point.offset, prepend=point.offset.new_zeros(1))
+    self.patch_size = min(counts.min().tolist(), self.patch_size_max)  # the method's one wait
+    H, C = self.num_heads, self.channels
+    pad, unpad, cu_seqlens = self.get_padding_and_inverse(point)
+    order = point.serialized_order[self.order_index][pad]
+    inverse = unpad[point.serialized_inverse[self.order_index]]
+    feat = attention.varlen_attention(qkv[order].reshape(-1, 3, H, C // H), cu_seqlens, max_seqlen=self.patch_size,
+                                      softmax_scale=self.scale)
+    feat = feat.reshape(-1, C)[inverse]
+    point.feat = self.proj_drop(self.proj(feat))
+    _STATS["fused_calls"] += 1
+    return point
+
+
 def _forward(original):
     def forward(self, point):
         """SerializedAttention.forward's non-flash branch over attention.varlen_attention."""
@@ -48,18 +67,7 @@ def _forward(original):
         if qkv is None or qkv.dtype not in attention.dtypes():
             _STATS["original_calls"] += 1
             return original(self, point)
-        counts = torch.diff(point.offset, prepend=point.offset.new_zeros(1))
-        self.patch_size = min(counts.min().tolist(), self.patch_size_max)  # the method's one wait
-        H, C = self.num_heads, self.channels
-        pad, unpad, cu_seqlens = self.get_padding_and_inverse(point)
-        order = point.serialized_order[self.order_index][pad]
-        inverse = unpad[point.serialized_inverse[self.order_index]]
-        feat = attention.varlen_attention(qkv[order].reshape(-1, 3, H, C // H), cu_seqlens, max_seqlen=self.patch_size,
-                                          softmax_scale=self.scale)
-        feat = feat.reshape(-1, C)[inverse]
-        point.feat = self.proj_drop(self.proj(feat))
-        _STATS["fused_calls"] += 1
-        return point
+        return forward_from_qkv(self, point, qkv)
     return forward
 
 

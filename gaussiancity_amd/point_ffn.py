@@ -10,6 +10,9 @@ The rebound method runs cpe, the first residual, norm1, attn and drop_path throu
 point_attention, point_index, point_pool and the sparse drop-ins keep composing, and the first DropPath mask is drawn
 first, as upstream.  post-norm Blocks, other norm or activation layers, a tanh GELU, CPU tensors, other dtypes, an active
 autocast and widths the library does not hold go to the module's own method, untouched.
+
+fused_tail(point, parts) is the tail alone, for point_front, whose rebound method runs it after its own front; installed over
+point_front's method, this one hands it the Blocks it accepts (point_front.py).
 """
 import torch
 
@@ -62,16 +65,35 @@ def _parts(self, point):
     return norm, mlp, drop
 
 
+def fused_tail(point, parts):
+    """Block.forward's last third on point.feat (the tail's shortcut) over ffn.layernorm_mlp_residual; parts is what
+    _parts accepted.  Sets point.feat and point.sparse_conv_feat as the method does; counted as a fused call."""
+    norm, mlp, drop = parts
+    feat, row_scale = point.feat, None
+    if drop is not None and drop.drop_prob and drop.training:  # DropPath._drop_path's mask, drawn as it draws it
+        keep = 1 - drop.drop_prob
+        row_scale = feat.new_empty((feat.shape[0], 1)).bernoulli_(keep)
+        if keep > 0.0 and drop.scale_by_keep:
+            row_scale.div_(keep)
+    point.feat = ffn.layernorm_mlp_residual(feat, norm.weight, norm.bias, norm.eps, mlp.fc1.weight, mlp.fc1.bias,
+                                            mlp.fc2.weight, mlp.fc2.bias, row_scale)
+    point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(point.feat)
+    _STATS["fused_calls"] += 1
+    return point
+
+
 # ---- the method of models/pt_v3.py, written against its behaviour: the order of its modules, of its residual adds and of
 # the DropPath draws, and the attributes it sets on the point ---------------------------------------------------------------
 def _forward(original):
     def forward(self, point):
         """Block.forward (pre_norm) with its last third over ffn.layernorm_mlp_residual."""
+        front_accepts = getattr(original, "block_front_accepts", None)
+        if front_accepts is not None and front_accepts(self, point):
+            return original(self, point)  # point_front's method, bound before this one: it runs this tail itself
         parts = _parts(self, point)
         if parts is None:
             _STATS["original_calls"] += 1
             return original(self, point)
-        norm, mlp, drop = parts
         shortcut = point.feat
         point = self.cpe(point)
         point.feat = shortcut + point.feat
@@ -79,18 +101,7 @@ def _forward(original):
         point = self.norm1(point)
         point = self.drop_path(self.attn(point))
         point.feat = shortcut + point.feat
-
-        feat, row_scale = point.feat, None
-        if drop is not None and drop.drop_prob and drop.training:  # DropPath._drop_path's mask, drawn as it draws it
-            keep = 1 - drop.drop_prob
-            row_scale = feat.new_empty((feat.shape[0], 1)).bernoulli_(keep)
-            if keep > 0.0 and drop.scale_by_keep:
-                row_scale.div_(keep)
-        point.feat = ffn.layernorm_mlp_residual(feat, norm.weight, norm.bias, norm.eps, mlp.fc1.weight, mlp.fc1.bias,
-                                                mlp.fc2.weight, mlp.fc2.bias, row_scale)
-        point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(point.feat)
-        _STATS["fused_calls"] += 1
-        return point
+        return fused_tail(point, parts)
     return forward
 
 

@@ -88,6 +88,44 @@
  * holds C), the tiles added in ascending order, in groups of consecutive tiles when there are more than 64.  The
  * slices and groups depend on N, C and Hd alone: every output is bit-identical from run to run and independent of
  * how many workgroups the device holds at a time.
+ *
+ * ---- The front of a PTv3 Block (models/pt_v3.py, Block.forward between the sparse convolution and the attention;
+ * DESIGN.md section 19) ---------------------------------------------------------------------------------------------------
+ * For N rows, C channels and O projected features, all float32:
+ *     t    = s Wc^T + bc                        s [N][C] the convolution's output, wc [C][C], bc [C]   (cpe[1])
+ *     u    = that lnc_w + lnc_b                 that = (t - mean_c) rstd_c, eps_c                       (cpe[2])
+ *     feat = x + u                              x [N][C] the Block's shortcut                           -> output 1
+ *     n    = fhat ln1_w + ln1_b                 fhat = (feat - mean_1) rstd_1, eps_1                    (norm1)
+ *     qkv  = n Wq^T + bq                        wq [O][C], bq [O]                                       -> output 2
+ *   mean and rstd as above (biased variance).  C and O are positive multiples of 4, C <= gcm_front_max_channels() and
+ *   O <= 3 gcm_front_max_channels(); N >= 0.  x, s, feat, qkv, dfeat, dqkv, dx, ds are row-strided under the rule above
+ *   (width C, or O for qkv and dqkv); the parameters, t [N][C] and the statistics [N] are contiguous; every float pointer
+ *   but the four statistics (4-byte aligned) is 16-byte aligned.
+ *
+ * gcm_front_max_channels (host only): the largest C the fused kernels run, 128 in this build; never 0.
+ * gcm_front_forward: one launch.  t == NULL (inference): nothing but feat and qkv reaches memory and the four statistics
+ *     are NULL too.  t != NULL: the pre-norm product t and mean_c, rstd_c, mean_1, rstd_1 are stored once for the
+ *     backward; all four are then required.  N == 0 returns 0 and queues nothing.
+ * gcm_front_backward: from the stored s, feat, t and statistics (read, never written: the call may be repeated) and the
+ *     two gradients dfeat [N][C] and dqkv [N][O], both required,
+ *     dn = dqkv Wq;  df = dfeat + rstd_1 (v - mean_c(v) - fhat mean_c(v fhat)), v = dn ln1_w;  dx = df;
+ *     dt = rstd_c (w - mean_c(w) - that mean_c(w that)), w = df lnc_w;  ds = dt Wc;
+ *     dwq [O][C] = dqkv^T n;  dbq = sum_r dqkv;  dwc [C][C] = dt^T s;  dbc = sum_r dt;
+ *     dln1_w = sum_r dn fhat;  dln1_b = sum_r dn;  dlnc_w = sum_r df that;  dlnc_b = sum_r df.
+ *     ln1_b is an input because dwq is taken against n, which holds it.  Every output is written whole, a NULL output is
+ *     skipped.  workspace is gcm_front_backward_workspace_bytes(N, C, O) bytes (never 0 for arguments in range), 256-byte
+ *     aligned; what it held before does not matter.  Four launches, five when N is beyond 64 tiles of 64 rows.
+ *
+ * Rounding and order: every product of two matrices runs on v_mfma_f32_16x16x4_f32.  t, qkv and ds are one fp32 chain
+ * from 0 over the channels in ascending order, bc / bq added after the chain; dn is, per chunk of 64 outputs (ascending),
+ * one chain from 0 over the chunk, the chunks' results added in ascending order.  The LayerNorm sums follow the
+ * feed-forward's four-lanes-per-row rule above, forward and backward; u is evaluated as
+ * ((t - mean_c) rstd_c) lnc_w + lnc_b with one rounding per operation, and feat = x + u is one fp32 add.  No float
+ * atomics: dwq, dbq, dwc, dbc are sums over at most 64 row slices added in the feed-forward's pairwise tree, inside a
+ * slice every 32 consecutive rows one chain (the bias sums as db1 / db2 above); the four LayerNorm gradients are sums
+ * over tiles of 64 rows (inside a tile as dln_w above), the tiles added in ascending order, in groups of consecutive
+ * tiles when there are more than 64.  Slices and groups depend on N, C and O alone: every output is bit-identical from
+ * run to run and independent of how many workgroups the device holds at a time.
  */
 #ifndef GCM_H
 #define GCM_H
@@ -139,6 +177,25 @@ int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const 
                      const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
                      float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
                      size_t workspace_bytes, void* hip_stream);
+
+int gcm_front_max_channels(void);
+
+int gcm_front_forward(const float* x, int64_t x_stride, const float* s, int64_t s_stride, const float* wc, const float* bc,
+                      const float* lnc_w, const float* lnc_b, float eps_c, const float* ln1_w, const float* ln1_b,
+                      float eps_1, const float* wq, const float* bq, int64_t N, int32_t C, int32_t O, float* feat,
+                      int64_t feat_stride, float* qkv, int64_t qkv_stride, float* t, float* mean_c, float* rstd_c,
+                      float* mean_1, float* rstd_1, void* hip_stream);
+
+/* 0 with a message in gcm_last_error() when an argument is out of range */
+size_t gcm_front_backward_workspace_bytes(int64_t N, int32_t C, int32_t O);
+
+int gcm_front_backward(const float* s, int64_t s_stride, const float* feat, int64_t feat_stride, const float* t,
+                       const float* mean_c, const float* rstd_c, const float* mean_1, const float* rstd_1,
+                       const float* dfeat, int64_t dfeat_stride, const float* dqkv, int64_t dqkv_stride, const float* wc,
+                       const float* lnc_w, const float* ln1_w, const float* ln1_b, const float* wq, int64_t N, int32_t C,
+                       int32_t O, float* dx, int64_t dx_stride, float* ds, int64_t ds_stride, float* dwc, float* dbc,
+                       float* dlnc_w, float* dlnc_b, float* dln1_w, float* dln1_b, float* dwq, float* dbq, void* workspace,
+                       size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
