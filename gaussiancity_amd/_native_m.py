@@ -1,8 +1,9 @@
 """ctypes binding of libgcm_hip.so (C ABI in include/gcm.h): the grouped modulated linear layer of the generator's
 attribute head, its backward, the group vector from masks and the head's output transform, and the feed-forward third
 of a PTv3 Block (gcm_ffn_*: LayerNorm, MLP and residual in one launch, its backward) and the front of the same Block
-(gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection in one launch, its backward),
-all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
+(gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection in one launch, its backward)
+and the middle of the same Block (gcm_mid_*: the patch gather and its gradient, the scatter back, the output projection,
+DropPath and the residual in one launch, its backward), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
 The library is the product: no Python/CPU fallback -- a missing library or failing call raises RuntimeError."""
 import ctypes as C
 
@@ -35,6 +36,13 @@ _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argt
     "gcm_front_backward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
                                      _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _sz, _vp]),
+    "gcm_mid_max_channels": (C.c_int, []),
+    "gcm_mid_slot_plan": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "gcm_mid_gather_forward": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp]),
+    "gcm_mid_gather_backward": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "gcm_mid_forward": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "gcm_mid_backward_workspace_bytes": (_sz, [_i64, _i32]),
+    "gcm_mid_backward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _L = _loader.Library("gcm", "libgcm_hip.so", ABI_VERSION, _SIGNATURES)

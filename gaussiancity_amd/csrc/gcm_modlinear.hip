@@ -24,7 +24,9 @@
 // The library's second row-wise MLP, the feed-forward third of a PTv3 Block (gcm_ffn_*), has its kernels in gcm_ffn.h,
 // included below; its C ABI functions are at the end of this file.  DESIGN.md section 18.  The third, the front of the same
 // Block (gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection), is gcm_front.h,
-// included after it.  DESIGN.md section 19.
+// included after it.  DESIGN.md section 19.  The fourth, the middle of the same Block around its attention (gcm_mid_*: the
+// patch gather, and the scatter back, the output projection, DropPath and the residual in one launch), is gcm_mid.h,
+// included last.  DESIGN.md section 20.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -496,6 +498,7 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 
 #include "gcm_ffn.h"
 #include "gcm_front.h"
+#include "gcm_mid.h"
 
 namespace {
 
@@ -516,6 +519,20 @@ int check_front_shape(const std::string& w, int64_t N, int32_t C, int32_t O) {
   if (O > 3 * kFrontMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": O above 3 * gcm_front_max_channels()");
   return 0;
 }
+
+int check_mid_shape(const std::string& w, int64_t N, int32_t C) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
+  if (C > kMidMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_mid_max_channels()");
+  return 0;
+}
+// rows of W floats copied in 16-byte pieces, one thread a piece
+int check_mid_width(const std::string& w, int64_t rows, int32_t W) {
+  if (W <= 0 || W % 4 != 0 || W > kMaxFeatures) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": W must be a positive multiple of 4");
+  if ((rows * (W / 4) + 255) / 256 >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": rows * W / 4 does not fit 39 bits");
+  return 0;
+}
+bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace
 
@@ -855,6 +872,127 @@ int gcm_front_backward(const float* s, int64_t s_stride, const float* feat, int6
     k_ffn_fold_params<<<blocks_for(front_record(C, O), 256), 256, 0, st>>>(part, p.sw, (int64_t)O * C, (int64_t)C * C, O, C, dwq, dwc,
                                                                           dbq, dbc);
     HIP_TRY(hipGetLastError(), "front backward weight gradient launch");
+  }
+  return GCM_OK;
+}
+
+int gcm_mid_max_channels(void) { return kMidMaxChannels; }
+
+int gcm_mid_slot_plan(const int64_t* order, int64_t T_slots, const int64_t* inverse, int64_t N, int32_t* extra,
+                      void* hip_stream) {
+  const std::string who("gcm_mid_slot_plan");
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": N out of range");
+  if (T_slots < 0 || T_slots >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T out of range");
+  if (T_slots < N) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T below N");
+  if (!aligned8(order) || !aligned8(inverse) || (reinterpret_cast<uintptr_t>(extra) & 3u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": order and inverse must be 8-byte aligned, extra 4-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!order || !inverse || !extra) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null order, inverse or extra");
+  hipStream_t st = (hipStream_t)hip_stream;
+  k_mid_fill<<<blocks_for(N, 256), 256, 0, st>>>(extra, N);
+  k_mid_slot_plan<<<blocks_for(T_slots, 256), 256, 0, st>>>(order, T_slots, inverse, N, extra);
+  HIP_TRY(hipGetLastError(), "mid slot plan launch");
+  return GCM_OK;
+}
+
+int gcm_mid_gather_forward(const float* x, int64_t x_stride, const int64_t* order, int64_t T_slots, int32_t W, float* y,
+                           void* hip_stream) {
+  const std::string who("gcm_mid_gather_forward");
+  if (T_slots < 0 || T_slots >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T out of range");
+  if (int rc = check_mid_width(who, T_slots, W)) return rc;
+  if (!stride_ok(x_stride, W))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(y)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!aligned8(order)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": order must be 8-byte aligned");
+  if (T_slots == 0) return GCM_OK;
+  if (!x || !order || !y) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, order or y");
+  k_mid_gather_forward<<<blocks_for(T_slots * (W / 4), 256), 256, 0, (hipStream_t)hip_stream>>>(x, x_stride, order, T_slots,
+                                                                                               W / 4, y);
+  HIP_TRY(hipGetLastError(), "mid gather forward launch");
+  return GCM_OK;
+}
+
+int gcm_mid_gather_backward(const float* dy, int64_t dy_stride, const int64_t* inverse, const int32_t* extra, int64_t N,
+                            int32_t W, float* dx, void* hip_stream) {
+  const std::string who("gcm_mid_gather_backward");
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": N out of range");
+  if (int rc = check_mid_width(who, N, W)) return rc;
+  if (!stride_ok(dy_stride, W))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(dy) || !aligned16(dx)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!aligned8(inverse) || (reinterpret_cast<uintptr_t>(extra) & 3u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": inverse must be 8-byte aligned, extra 4-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!dy || !inverse || !extra || !dx) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null dy, inverse, extra or dx");
+  k_mid_gather_backward<<<blocks_for(N * (W / 4), 256), 256, 0, (hipStream_t)hip_stream>>>(dy, dy_stride, inverse, extra, N,
+                                                                                          W / 4, dx);
+  HIP_TRY(hipGetLastError(), "mid gather backward launch");
+  return GCM_OK;
+}
+
+int gcm_mid_forward(const float* a, int64_t a_stride, const int64_t* inverse, const float* x, int64_t x_stride,
+                    const float* wp, const float* bp, const float* row_scale, int64_t N, int32_t C, float* y,
+                    int64_t y_stride, void* hip_stream) {
+  const std::string who("gcm_mid_forward");
+  if (int rc = check_mid_shape(who, N, C)) return rc;
+  if (!stride_ok(a_stride, C) || !stride_ok(x_stride, C) || !stride_ok(y_stride, C))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(a) || !aligned16(x) || !aligned16(wp) || !aligned16(bp) || !aligned16(y))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!aligned8(inverse)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": inverse must be 8-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!a || !inverse || !x || !wp || !bp || !y) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null a, inverse, x, wp, bp or y");
+  mid_launch_forward(C, dim3(blocks_for(N, T)), (hipStream_t)hip_stream, a, a_stride, inverse, x, x_stride, wp, bp, row_scale, N,
+                     (int)C, y, y_stride);
+  HIP_TRY(hipGetLastError(), "mid forward launch");
+  return GCM_OK;
+}
+
+size_t gcm_mid_backward_workspace_bytes(int64_t N, int32_t C) {
+  if (check_mid_shape("gcm_mid_backward_workspace_bytes", N, C)) return 0;
+  g_err.clear();
+  return mid_plan(N, C).total;
+}
+
+int gcm_mid_backward(const float* a, int64_t a_stride, const int64_t* inverse, const int32_t* extra, const float* dy,
+                     int64_t dy_stride, const float* wp, const float* row_scale, int64_t N, int64_t T_slots, int32_t C,
+                     float* da, float* dwp, float* dbp, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_mid_backward");
+  if (int rc = check_mid_shape(who, N, C)) return rc;
+  if (T_slots < 0 || T_slots >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T out of range");
+  if (T_slots < N) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T below N");
+  if (!stride_ok(a_stride, C) || !stride_ok(dy_stride, C))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(a) || !aligned16(dy) || !aligned16(wp) || !aligned16(da) || !aligned16(dwp) || !aligned16(dbp))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!aligned8(inverse) || (reinterpret_cast<uintptr_t>(extra) & 3u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": inverse must be 8-byte aligned, extra 4-byte aligned");
+  const MidPlan p = mid_plan(N, C);
+  if (workspace_bytes < p.total || !workspace)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_mid_backward_workspace_bytes");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (N > 0 && (!a || !inverse || !extra || !dy || !wp))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null a, inverse, extra, dy or wp");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // no row owns a slot: every gradient is zeros
+    if (da && T_slots) HIP_TRY(hipMemsetAsync(da, 0, (size_t)T_slots * C * 4, st), "mid backward clear da");
+    if (dwp) HIP_TRY(hipMemsetAsync(dwp, 0, (size_t)C * C * 4, st), "mid backward clear dwp");
+    if (dbp) HIP_TRY(hipMemsetAsync(dbp, 0, (size_t)C * 4, st), "mid backward clear dbp");
+    return GCM_OK;
+  }
+  if (da) {
+    mid_launch_bwd_rows(C, dim3((unsigned)p.tiles), st, dy, dy_stride, inverse, extra, wp, row_scale, N, T_slots, (int)C, da);
+    HIP_TRY(hipGetLastError(), "mid backward rows launch");
+  }
+  if (dwp || dbp) {
+    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    float* part = (float*)workspace;
+    k_mid_dw<<<dim3(p.wt, (unsigned)p.sw), 256, 0, st>>>(a, a_stride, inverse, dy, dy_stride, row_scale, N, T_slots, (int)C, per,
+                                                         part);
+    k_ffn_fold_params<<<blocks_for(mid_record(C), 256), 256, 0, st>>>(part, p.sw, (int64_t)C * C, C, 0, 0, dwp, dbp, nullptr,
+                                                                     nullptr);
+    HIP_TRY(hipGetLastError(), "mid backward weight gradient launch");
   }
   return GCM_OK;
 }

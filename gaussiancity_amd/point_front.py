@@ -19,7 +19,7 @@ module's own method.
 """
 import torch
 
-from . import attention, front, point_attention, point_ffn
+from . import attention, front, point_attention, point_ffn, point_mid
 
 _STATS = {"fused_calls": 0, "original_calls": 0}
 _ORIGINAL = "_gaussiancity_amd_point_front_original"
@@ -90,8 +90,12 @@ def _forward(original, pt_v3_module):
         feat, proj = front.conv_tail_norm_qkv(x, point.sparse_conv_feat.features, lin.weight, lin.bias, lnc.weight, lnc.bias,
                                               lnc.eps, ln1.weight, ln1.bias, ln1.eps, qkv.weight, qkv.bias)
         point.feat = feat
-        point = self.drop_path(point_attention.forward_from_qkv(self.attn, point, proj))
-        point.feat = feat + point.feat
+        middle = point_mid.accepts(self, point, pt_v3_module)  # None without point_mid's marker
+        if middle is not None:
+            point = point_mid.middle(self, point, feat, proj, middle)
+        else:
+            point = self.drop_path(point_attention.forward_from_qkv(self.attn, point, proj))
+            point.feat = feat + point.feat
         _STATS["fused_calls"] += 1
 
         tail = point_ffn._parts(self, point) if getattr(pt_v3_module, point_ffn._ORIGINAL, None) is not None else None

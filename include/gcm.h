@@ -126,6 +126,42 @@
  * over tiles of 64 rows (inside a tile as dln_w above), the tiles added in ascending order, in groups of consecutive
  * tiles when there are more than 64.  Slices and groups depend on N, C and O alone: every output is bit-identical from
  * run to run and independent of how many workgroups the device holds at a time.
+ *
+ * ---- The middle of a PTv3 Block (models/pt_v3.py, SerializedAttention.forward around its attention, and the Block's
+ * DropPath and residual add after it) ---------------------------------------------------------------
+ * For N rows (points), T >= N slots (padded patch positions), C channels, float32 data, int64 indices as torch has them:
+ *     order [T]    slot -> row            (serialized_order[i][pad])
+ *     inverse [N]  row -> its own slot    (unpad[serialized_inverse[i]])
+ *     extra [N]    int32: the row's duplicate slot, or -1
+ *   PRECONDITION of every data function below: order[inverse[n]] == n for every row, and at most one slot j per row with
+ *   order[j] == n and inverse[n] != j (the duplicate slot: a row of the previous patch borrowed to fill the last one;
+ *   get_padding_and_inverse borrows from one patch, so a row is borrowed at most once).  The functions do not verify it;
+ *   with it, every sum below has at most two terms and every output element exactly one writer.  An index that is
+ *   negative, or not below the range the function knows (N for order in gcm_mid_slot_plan, T for inverse and extra in
+ *   gcm_mid_backward), is not dereferenced: the row is skipped.
+ *     gather            y[j] = x[order[j]]                               x [.][W], y [T][W]
+ *     its gradient      dx[n] = dy[inverse[n]] + dy[extra[n]]            the second term when extra[n] >= 0; one fp32 add
+ *     p = a[inverse[n]] Wp^T + bp                                        a [T][C] the attention's output, wp [C][C], bp [C]
+ *     y = x + p, or y = x + (p r[n])                                     x [N][C] the shortcut, r = row_scale [N] or NULL
+ *   x, a, y, dy are row-strided under the rule above; the gather's y and dx ([T][W], [N][W]), da [T][C] and the parameters
+ *   are contiguous.  Float pointers are 16-byte aligned (row_scale 4-byte), order and inverse 8-byte, extra 4-byte.  W and C
+ *   are positive multiples of 4, C <= gcm_mid_max_channels(); N and T are refused at 2^31 and above, T < N is refused.
+ *   No call waits for the device; a NULL output is skipped.
+ *
+ * gcm_mid_max_channels (host only): the largest C the fused kernels run, 128 in this build; never 0.
+ * gcm_mid_slot_plan: extra from order and inverse; two launches, integer stores only.
+ * gcm_mid_gather_forward, gcm_mid_gather_backward: one launch each, 16-byte copies; every element of y / dx is written
+ *     exactly once.  A two-term fp32 sum is commutative: dx has the bits of torch's index_put_(accumulate=True).
+ * gcm_mid_forward: one launch.  p is one fp32 chain from 0 over the channels in ascending order on v_mfma_f32_16x16x4_f32,
+ *     bp added after the chain; p r[n] is one multiply and x + . one add, not contracted.
+ * gcm_mid_backward: with g = r o dy (recomputed where needed, never stored; dy is only read: the call may be repeated),
+ *     da [T][C]: row inverse[n] = g[n] Wp (one chain over the channels), row extra[n] = exact zeros: written whole;
+ *     dwp [C][C] = g^T a[inverse];  dbp = sum_n g[n]: sums over at most 64 row slices added in the feed-forward's pairwise
+ *     tree, inside a slice every 32 consecutive rows one chain (the bias sums as db1 / db2 above).  No float atomics.
+ *     The gradient of the shortcut x is dy itself and is not computed.  workspace is
+ *     gcm_mid_backward_workspace_bytes(N, C) bytes (never 0 for arguments in range), 256-byte aligned; what it held before
+ *     does not matter.  One launch for da, two for dwp / dbp, whatever N is.  The slices depend on N and C alone: every
+ *     output is bit-identical from run to run and independent of how many workgroups the device holds at a time.
  */
 #ifndef GCM_H
 #define GCM_H
@@ -196,6 +232,27 @@ int gcm_front_backward(const float* s, int64_t s_stride, const float* feat, int6
                        int32_t O, float* dx, int64_t dx_stride, float* ds, int64_t ds_stride, float* dwc, float* dbc,
                        float* dlnc_w, float* dlnc_b, float* dln1_w, float* dln1_b, float* dwq, float* dbq, void* workspace,
                        size_t workspace_bytes, void* hip_stream);
+
+int gcm_mid_max_channels(void);
+
+int gcm_mid_slot_plan(const int64_t* order, int64_t T, const int64_t* inverse, int64_t N, int32_t* extra, void* hip_stream);
+
+int gcm_mid_gather_forward(const float* x, int64_t x_stride, const int64_t* order, int64_t T, int32_t W, float* y,
+                           void* hip_stream);
+
+int gcm_mid_gather_backward(const float* dy, int64_t dy_stride, const int64_t* inverse, const int32_t* extra, int64_t N,
+                            int32_t W, float* dx, void* hip_stream);
+
+int gcm_mid_forward(const float* a, int64_t a_stride, const int64_t* inverse, const float* x, int64_t x_stride,
+                    const float* wp, const float* bp, const float* row_scale, int64_t N, int32_t C, float* y,
+                    int64_t y_stride, void* hip_stream);
+
+/* 0 with a message in gcm_last_error() when an argument is out of range */
+size_t gcm_mid_backward_workspace_bytes(int64_t N, int32_t C);
+
+int gcm_mid_backward(const float* a, int64_t a_stride, const int64_t* inverse, const int32_t* extra, const float* dy,
+                     int64_t dy_stride, const float* wp, const float* row_scale, int64_t N, int64_t T, int32_t C,
+                     float* da, float* dwp, float* dbp, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
