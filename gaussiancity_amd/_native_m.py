@@ -3,7 +3,8 @@ attribute head, its backward, the group vector from masks and the head's output 
 of a PTv3 Block (gcm_ffn_*: LayerNorm, MLP and residual in one launch, its backward) and the front of the same Block
 (gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection in one launch, its backward)
 and the middle of the same Block (gcm_mid_*: the patch gather and its gradient, the scatter back, the output projection,
-DropPath and the residual in one launch, its backward), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
+DropPath and the residual in one launch, its backward) and the seams between the backbone's stages (gcm_seam_*: Linear,
+BatchNorm1d and GELU as one operator in eval and training mode, its backward), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
 The library is the product: no Python/CPU fallback -- a missing library or failing call raises RuntimeError."""
 import ctypes as C
 
@@ -43,6 +44,15 @@ _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argt
     "gcm_mid_forward": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
     "gcm_mid_backward_workspace_bytes": (_sz, [_i64, _i32]),
     "gcm_mid_backward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcm_seam_max_channels": (C.c_int, []),
+    "gcm_seam_forward_eval": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, C.c_int, _i64, _i32, _i32, _vp, _i64,
+                                        _vp, _vp, _vp]),
+    "gcm_seam_forward_workspace_bytes": (_sz, [_i64, _i32]),
+    "gcm_seam_forward_train": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _f32, _vp, _vp, C.c_int, _i64, _i32, _i32, _vp, _vp, _i64,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcm_seam_backward_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "gcm_seam_backward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, C.c_int, _i64, _i32, _i32,
+                                    _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _L = _loader.Library("gcm", "libgcm_hip.so", ABI_VERSION, _SIGNATURES)

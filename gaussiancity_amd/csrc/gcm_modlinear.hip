@@ -25,8 +25,9 @@
 // included below; its C ABI functions are at the end of this file.  DESIGN.md section 18.  The third, the front of the same
 // Block (gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection), is gcm_front.h,
 // included after it.  DESIGN.md section 19.  The fourth, the middle of the same Block around its attention (gcm_mid_*: the
-// patch gather, and the scatter back, the output projection, DropPath and the residual in one launch), is gcm_mid.h,
-// included last.  DESIGN.md section 20.
+// patch gather, and the scatter back, the output projection, DropPath and the residual in one launch), is gcm_mid.h.
+// DESIGN.md section 20.  The fifth, the seams between the backbone's stages (gcm_seam_*: Linear, BatchNorm1d and GELU as
+// one operator up to 512 channels), is gcm_seam.h, included last.  DESIGN.md section 21.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -499,6 +500,7 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 #include "gcm_ffn.h"
 #include "gcm_front.h"
 #include "gcm_mid.h"
+#include "gcm_seam.h"
 
 namespace {
 
@@ -533,6 +535,15 @@ int check_mid_width(const std::string& w, int64_t rows, int32_t W) {
   return 0;
 }
 bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+int check_seam_shape(const std::string& w, int64_t N, int32_t I, int32_t O, bool product) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (I <= 0 || I % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": I must be a positive multiple of 4");
+  if (O <= 0 || O % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": O must be a positive multiple of 4");
+  if (I > kSeamMaxChannels || O > kSeamMaxChannels)
+    return fail(GCM_ERR_INVALID_ARGUMENT, w + ": I or O above gcm_seam_max_channels()");
+  if (!product && I != O) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": w == NULL needs I == O");
+  return 0;
+}
 
 }  // namespace
 
@@ -993,6 +1004,154 @@ int gcm_mid_backward(const float* a, int64_t a_stride, const int64_t* inverse, c
     k_ffn_fold_params<<<blocks_for(mid_record(C), 256), 256, 0, st>>>(part, p.sw, (int64_t)C * C, C, 0, 0, dwp, dbp, nullptr,
                                                                      nullptr);
     HIP_TRY(hipGetLastError(), "mid backward weight gradient launch");
+  }
+  return GCM_OK;
+}
+
+int gcm_seam_max_channels(void) { return kSeamMaxChannels; }
+
+int gcm_seam_forward_eval(const float* x, int64_t x_stride, const float* w, const float* b, const float* running_mean,
+                          const float* running_var, float eps, const float* bn_w, const float* bn_b, int act, int64_t N,
+                          int32_t I, int32_t O, float* y, int64_t y_stride, float* z, float* rstd, void* hip_stream) {
+  const std::string who("gcm_seam_forward_eval");
+  if (int rc = check_seam_shape(who, N, I, O, w != nullptr)) return rc;
+  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
+  if (!stride_ok(x_stride, I) || !stride_ok(y_stride, O))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(w) || !aligned16(b) || !aligned16(running_mean) || !aligned16(running_var) ||
+      !aligned16(bn_w) || !aligned16(bn_b) || !aligned16(y) || !aligned16(z) || !aligned16(rstd))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!w && (b || z)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": b and z need w (without it z is x itself)");
+  if (N == 0) return GCM_OK;
+  if (!x || !running_mean || !running_var || !bn_w || !bn_b || !y)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, running_mean, running_var, bn_w, bn_b or y");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (w) {
+    seam_launch_forward<true>(O, blocks_for(N, T), st, x, x_stride, w, b, running_mean, running_var, eps, bn_w, bn_b, act, N,
+                              (int)I, (int)O, z, y, y_stride, rstd, (float*)nullptr);
+  } else {
+    k_seam_apply<true><<<blocks_for(N * (O / 4), 256), 256, 0, st>>>(x, x_stride, running_mean, running_var, eps, bn_w, bn_b, act,
+                                                                     N, O / 4, y, y_stride, rstd);
+  }
+  HIP_TRY(hipGetLastError(), "seam forward launch");
+  return GCM_OK;
+}
+
+size_t gcm_seam_forward_workspace_bytes(int64_t N, int32_t O) {
+  if (check_seam_shape("gcm_seam_forward_workspace_bytes", N, 4, O, true)) return 0;
+  g_err.clear();
+  return seam_forward_bytes(N, O);
+}
+
+int gcm_seam_forward_train(const float* x, int64_t x_stride, const float* w, const float* b, float eps, float momentum,
+                           const float* bn_w, const float* bn_b, int act, int64_t N, int32_t I, int32_t O, float* z, float* y,
+                           int64_t y_stride, float* mean, float* rstd, float* running_mean, float* running_var,
+                           int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_seam_forward_train");
+  if (int rc = check_seam_shape(who, N, I, O, w != nullptr)) return rc;
+  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
+  if (!std::isfinite(momentum) || momentum < 0.0f || momentum > 1.0f)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": momentum must be in 0..1");
+  if (!stride_ok(x_stride, I) || !stride_ok(y_stride, O))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(w) || !aligned16(b) || !aligned16(bn_w) || !aligned16(bn_b) || !aligned16(z) ||
+      !aligned16(y) || !aligned16(mean) || !aligned16(rstd) || !aligned16(running_mean) || !aligned16(running_var))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!aligned8(num_batches_tracked)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": num_batches_tracked must be 8-byte aligned");
+  if (!w && (b || z)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": b and z need w (without it z is x itself)");
+  const int buffers = (running_mean != nullptr) + (running_var != nullptr) + (num_batches_tracked != nullptr);
+  if (buffers != 0 && buffers != 3)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": running_mean, running_var and num_batches_tracked come together, all or none");
+  if (N == 0) return GCM_OK;
+  if (N < 2) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": batch statistics need N >= 2");
+  const size_t need = seam_forward_bytes(N, O);
+  if (workspace_bytes < need || !workspace)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_seam_forward_workspace_bytes");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (!x || !bn_w || !bn_b || !y || !mean || !rstd || (w && !z))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, bn_w, bn_b, y, mean, rstd or (with w) z");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const SeamPlan p = seam_plan(N, I, O);
+  float* part = (float*)workspace;
+  if (w) {
+    seam_launch_forward<false>(O, (unsigned)p.tiles, st, x, x_stride, w, b, (const float*)nullptr, (const float*)nullptr, eps,
+                               bn_w, bn_b, act, N, (int)I, (int)O, z, (float*)nullptr, (int64_t)0, (float*)nullptr, part);
+  } else {
+    k_seam_tile_stats<<<dim3((unsigned)p.tiles, blocks_for(O, kSeamChunk)), 256, 0, st>>>(x, x_stride, N, (int)O, part);
+  }
+  HIP_TRY(hipGetLastError(), "seam product launch");
+  k_seam_stats<<<blocks_for(O, 4), 256, 0, st>>>(part, p.tiles, N, (int)O, p.G, p.gper, eps, momentum, mean, rstd, running_mean,
+                                                running_var, num_batches_tracked);
+  HIP_TRY(hipGetLastError(), "seam statistics launch");
+  k_seam_apply<false><<<blocks_for(N * (O / 4), 256), 256, 0, st>>>(w ? z : x, w ? (int64_t)O : x_stride, mean, rstd, eps, bn_w,
+                                                                    bn_b, act, N, O / 4, y, y_stride, (float*)nullptr);
+  HIP_TRY(hipGetLastError(), "seam apply launch");
+  return GCM_OK;
+}
+
+size_t gcm_seam_backward_workspace_bytes(int64_t N, int32_t I, int32_t O) {
+  if (check_seam_shape("gcm_seam_backward_workspace_bytes", N, I, O, true)) return 0;
+  g_err.clear();
+  return seam_plan(N, I, O).total;
+}
+
+int gcm_seam_backward(const float* x, int64_t x_stride, const float* z, int64_t z_stride, const float* mean,
+                      const float* rstd, const float* dy, int64_t dy_stride, const float* w, const float* bn_w,
+                      const float* bn_b, int act, int batch_stats, int64_t N, int32_t I, int32_t O, float* dx,
+                      int64_t dx_stride, float* dw, float* db, float* dbn_w, float* dbn_b, void* workspace,
+                      size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_seam_backward");
+  if (int rc = check_seam_shape(who, N, I, O, w != nullptr)) return rc;
+  if (!stride_ok(x_stride, I) || !stride_ok(z_stride, O) || !stride_ok(dy_stride, O) || (dx && !stride_ok(dx_stride, I)))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
+  if (!aligned16(x) || !aligned16(z) || !aligned16(mean) || !aligned16(rstd) || !aligned16(dy) || !aligned16(w) ||
+      !aligned16(bn_w) || !aligned16(bn_b) || !aligned16(dx) || !aligned16(dw) || !aligned16(db) || !aligned16(dbn_w) ||
+      !aligned16(dbn_b))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (!w && (dw || db)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": dw and db need w");
+  if (batch_stats && N == 1) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": batch statistics need N >= 2");
+  const SeamPlan p = seam_plan(N, I, O);
+  if (workspace_bytes < p.total || !workspace)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_seam_backward_workspace_bytes");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (N > 0 && (!z || !mean || !rstd || !dy || !bn_w || !bn_b || (w && !x)))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null z, mean, rstd, dy, bn_w, bn_b or (with w) x");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
+    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)O * I * 4, st), "seam backward clear dw");
+    if (db) HIP_TRY(hipMemsetAsync(db, 0, (size_t)O * 4, st), "seam backward clear db");
+    if (dbn_w) HIP_TRY(hipMemsetAsync(dbn_w, 0, (size_t)O * 4, st), "seam backward clear dbn_w");
+    if (dbn_b) HIP_TRY(hipMemsetAsync(dbn_b, 0, (size_t)O * 4, st), "seam backward clear dbn_b");
+    return GCM_OK;
+  }
+  char* ws = (char*)workspace;
+  float* keep = (float*)(ws + p.keep);
+  const bool rows = dx || dw || db;  // what reads dz
+  if (dbn_w || dbn_b || (batch_stats && rows)) {
+    float* part = (float*)(ws + p.part);
+    k_seam_bwd_part<<<dim3((unsigned)p.tiles, blocks_for(O, T)), 256, 0, st>>>(dy, dy_stride, z, z_stride, mean, rstd, bn_w, bn_b,
+                                                                              act, N, (int)O, part);
+    k_seam_bwd_fold<<<blocks_for(O, 4), 256, 0, st>>>(part, p.tiles, (int)O, p.G, p.gper, dbn_w, dbn_b, keep);
+    HIP_TRY(hipGetLastError(), "seam backward BatchNorm sums launch");
+  }
+  SeamDz d;
+  d.dy = dy, d.z = z, d.mean = mean, d.rstd = rstd, d.gam = bn_w, d.bet = bn_b;
+  d.kh = batch_stats ? keep : nullptr, d.kg = batch_stats ? keep + O : nullptr;
+  d.dys = dy_stride, d.zs = z_stride, d.inv_n = 1.0f / (float)N, d.act = act;
+  if (dx) {
+    if (w) seam_launch_dx(I, (unsigned)p.tiles, st, d, w, N, (int)I, (int)O, dx, dx_stride);
+    else k_seam_dz<<<blocks_for(N * (O / 4), 256), 256, 0, st>>>(d, N, O / 4, dx, dx_stride);
+    HIP_TRY(hipGetLastError(), "seam backward dx launch");
+  }
+  if (dw || db) {
+    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    float* part = (float*)(ws + p.wpart);
+    k_seam_dw<<<dim3(p.wt, (unsigned)p.sw), 256, 0, st>>>(d, x, x_stride, N, (int)I, (int)O, per, part);
+    k_ffn_fold_params<<<blocks_for(seam_record(I, O), 256), 256, 0, st>>>(part, p.sw, (int64_t)O * I, O, 0, 0, dw, db, nullptr,
+                                                                         nullptr);
+    HIP_TRY(hipGetLastError(), "seam backward weight gradient launch");
   }
   return GCM_OK;
 }

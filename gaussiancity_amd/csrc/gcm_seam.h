@@ -1,0 +1,522 @@
+// gcm_seam.h -- the seams between the PTv3 stages (gcm_seam_*, include/gcm.h): Linear -> BatchNorm1d -> GELU as one
+// operator, y = act(bn(x W^T + b)), up to 512 channels either way; eval mode in ONE launch, training mode in three, the
+// deterministic backward in five, whatever N is.  Included by gcm_modlinear.hip after gcm_mid.h, whose forward shape and
+// row-sliced weight gradient it uses; device code and launch helpers only, the C ABI stays in gcm_modlinear.hip.
+// DESIGN.md section 21.
+//
+//   product    k_seam_forward: 256 threads own T = 64 rows and a block of CT = 32 NJ <= 128 output columns (grid.y walks
+//              the blocks); the inputs are walked in chunks of <= 128 staged in LDS, the accumulators carry across the
+//              chunks: z is one fp32 chain from 0 over the inputs in ascending order, b added after the chain.  The tile
+//              of z goes through LDS: from there it is stored in 16-byte pieces (training) or normalised and stored as y
+//              (eval), and a thread per column walks the tile's valid rows in ascending order: the mean (taken about the
+//              tile's first row), then, about that mean, the centred second moment M2.  A tile's record in the workspace:
+//              [2][O] = mean, M2 (the count of tile t is min(64, N - 64 t)).
+//   statistics k_seam_stats: per column the tiles' (count, mean, M2) merged in ascending tile order (the parallel-variance
+//              merge; never sum z^2 - (sum z)^2 / N); beyond 64 tiles, G <= 64 groups of consecutive tiles are merged
+//              first (each by one thread, the same launch) and the groups then in ascending order.  The mean written is
+//              a compensated sum of count_t mean_t in that same order, divided by N.
+//   apply      k_seam_apply: y = act(((z - mean) rstd) g + h), 16-byte accesses.
+//   backward   k_seam_bwd_part / k_seam_bwd_fold: dh = sum du, dg = sum du zhat, per tile four chains of 16 rows added in
+//              order, the tiles in ascending order (grouped as the statistics).  k_seam_dx: dz recomputed into LDS per 64
+//              rows and chunk of <= 128 outputs, never stored; dx is, PER CHUNK, one fp32 chain from 0 over the chunk's
+//              outputs in ascending order, the chunks' results added in ascending order.  k_seam_dw: dw_slice_tile with a
+//              fetch that recomputes dz, then k_ffn_fold_params' pairwise tree.
+// Channels beyond I / O and rows beyond N are staged as zeros and never stored.
+#pragma once
+
+namespace {
+
+constexpr int kSeamMaxChannels = 512;
+constexpr int kSeamChunk = 128;      // inputs (forward) or outputs (dx) staged at a time
+constexpr int kSeamFoldTiles = 64;   // up to this many tiles fold in one level
+constexpr int kSeamGroups = 64;      // at most this many groups of consecutive tiles
+
+// dz of four columns of one row: zhat = (z - mean) rstd, u = zhat g + h, du = act ? dy gelu'(u) : dy,
+// dz = (g rstd) (du - mh - zhat mg) with mh = dh / N, mg = dg / N under batch statistics, dz = (g rstd) du otherwise
+__device__ __forceinline__ f4 seam_dz4(f4 dy, f4 z, f4 mean, f4 rstd, f4 gam, f4 bet, f4 mh, f4 mg, bool act, bool batch) {
+  const f4 zh = (z - mean) * rstd;
+  f4 du = dy;
+  if (act) {
+    const f4 u = zh * gam + bet;
+#pragma unroll
+    for (int k = 0; k < 4; k++) du[k] = dy[k] * gelu_grad_f(u[k]);
+  }
+  if (batch) du = du - mh - zh * mg;
+  return (gam * rstd) * du;
+}
+__device__ __forceinline__ f4 seam_act4(f4 z, f4 mean, f4 rstd, f4 gam, f4 bet, bool act) {
+  f4 u = ((z - mean) * rstd) * gam + bet;
+  if (act) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) u[k] = gelu_f(u[k]);
+  }
+  return u;
+}
+__device__ __forceinline__ f4 seam_rstd4(f4 var, float eps) {
+  f4 r;
+#pragma unroll
+  for (int k = 0; k < 4; k++) r[k] = 1.0f / sqrtf(var[k] + eps);
+  return r;
+}
+
+// one step of a compensated (Kahan) sum: s + c carries what the float s alone would have rounded away.  The file is built
+// without fast-math and without contraction, so the compiler keeps the three subtractions.
+__device__ __forceinline__ void kahan_add(float& s, float& c, float x) {
+  const float y = x - c, t = s + y;
+  c = (t - s) - y;
+  s = t;
+}
+
+// the tile's column record from its image Zs (rows x columns, pitch zp): thread `col` of the block's first CT.  The mean is
+// taken about the tile's first row, mean = z0 + (sum_r (z_r - z0)) / n with a compensated sum, so that neither a column
+// whose mean is many standard deviations nor the length of the chain costs digits; M2 is then summed about that mean.
+// Both in ascending row order.
+__device__ __forceinline__ void seam_tile_record(const float* Zs, int zp, int col, int nv, float* __restrict__ mean,
+                                                 float* __restrict__ m2) {
+  const float z0 = Zs[col];
+  float s = 0.0f, c = 0.0f;
+  for (int r = 1; r < nv; r++) kahan_add(s, c, Zs[r * zp + col] - z0);
+  const float m = z0 + s / (float)nv;
+  float q = 0.0f;
+  for (int r = 0; r < nv; r++) {
+    const float d = Zs[r * zp + col] - m;
+    q += d * d;
+  }
+  *mean = m;
+  *m2 = q;
+}
+
+// ---- forward: the product ---------------------------------------------------------------------------------------------
+// EVAL: y = act(bn(z)) with the running statistics (mean, var); z and rstd are stored only when asked for.
+// !EVAL: z [N][O] contiguous and the tile's records.
+template <int NJ, bool EVAL>
+__global__ __launch_bounds__(256, 2) void k_seam_forward(const float* __restrict__ x, int64_t xs, const float* __restrict__ w,
+                                                         const float* __restrict__ b, const float* __restrict__ mean,
+                                                         const float* __restrict__ var, float eps,
+                                                         const float* __restrict__ gam, const float* __restrict__ bet, int act,
+                                                         int64_t N, int I, int O, float* __restrict__ z, float* __restrict__ y,
+                                                         int64_t ys, float* __restrict__ rstd_out, float* __restrict__ part) {
+  constexpr int CT = 32 * NJ, XP = kSeamChunk + 4, ZP = CT + 4, NV = NJ > 2 ? NJ / 2 : 1, CQ = CT / 4;
+  __shared__ __attribute__((aligned(16))) float Xs[T * XP];       // a chunk of x: rows x inputs; afterwards the tile of z
+  __shared__ __attribute__((aligned(16))) float Ws[CT * kPitch];  // a 16-deep slice of W
+  const int tid = threadIdx.x;
+  const WaveTile g;
+  const int wcn = (g.wc >> 5) * 16 * NJ;  // the wave's first output column inside the block
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int col0 = blockIdx.y * CT;
+
+  f4 vw[NV];
+  f4 acc[2][NJ];
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < NJ; j++) acc[i][j] = zero4();
+
+  for (int i0 = 0; i0 < I; i0 += kSeamChunk) {
+    const int cw = I - i0 < kSeamChunk ? I - i0 : kSeamChunk;
+    const int Cr = (cw + KC - 1) / KC * KC, c4 = Cr >> 2;
+    for (int e = tid; e < T * c4; e += 256) {
+      const int r = e / c4, c = 4 * (e % c4);
+      f4 v = zero4();
+      if (row0 + r < N && i0 + c < I) v = ld4(x + (row0 + r) * xs + i0 + c);
+      *reinterpret_cast<f4*>(&Xs[r * XP + c]) = v;
+    }
+    // (ordered before the fragment reads by the first __syncthreads of the slice loop)
+    auto fetch = [&](int k0) {  // W slice: output column col0 + e / 4, four inputs at i0 + k0 + 4 * (e % 4)
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int e = tid + 256 * u, c = col0 + (e >> 2), k = i0 + k0 + 4 * (e & 3);
+        vw[u] = (e < 4 * CT && c < O && k < I) ? ld4(w + (int64_t)c * I + k) : zero4();
+      }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < Cr; k0 += KC) {
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int e = tid + 256 * u;
+        if (e < 4 * CT) *reinterpret_cast<f4*>(&Ws[(e >> 2) * kPitch + 4 * (e & 3)]) = vw[u];
+      }
+      __syncthreads();
+      if (k0 + KC < Cr) fetch(k0 + KC);
+#pragma unroll
+      for (int kk = 0; kk < KC; kk += 4) {
+        float fa[2], fb[NJ];
+#pragma unroll
+        for (int i = 0; i < 2; i++) fa[i] = Xs[(g.wr + 16 * i + g.fl) * XP + k0 + kk + g.fk];
+#pragma unroll
+        for (int j = 0; j < NJ; j++) fb[j] = Ws[(wcn + 16 * j + g.fl) * kPitch + kk + g.fk];
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+          for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+  }
+
+  // z = chain + b into the tile image (the last __syncthreads above freed Xs)
+  float* Zs = Xs;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const int cl = wcn + 16 * j + g.fl;
+    const float bias = (b && col0 + cl < O) ? b[col0 + cl] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int v = 0; v < 4; v++) Zs[(g.wr + 16 * i + 4 * g.fk + v) * ZP + cl] = acc[i][j][v] + bias;
+  }
+  __syncthreads();
+
+  for (int e = tid; e < T * CQ; e += 256) {
+    const int r = e / CQ, c = col0 + 4 * (e % CQ);
+    const int64_t row = row0 + r;
+    if (row >= N || c >= O) continue;
+    const f4 zv = *reinterpret_cast<const f4*>(&Zs[r * ZP + 4 * (e % CQ)]);
+    if (z) st4(z + row * O + c, zv);
+    if (EVAL) {
+      const f4 rs = seam_rstd4(ld4(var + c), eps);
+      st4(y + row * ys + c, seam_act4(zv, ld4(mean + c), rs, ld4(gam + c), ld4(bet + c), act != 0));
+      if (rstd_out && row == 0) st4(rstd_out + c, rs);
+    }
+  }
+  if (!EVAL && tid < CT && col0 + tid < O) {
+    const int nv = N - row0 < T ? (int)(N - row0) : T;
+    float* rec = part + (int64_t)blockIdx.x * 2 * O;
+    seam_tile_record(Zs, ZP, tid, nv, rec + col0 + tid, rec + O + col0 + tid);
+  }
+}
+
+// w == NULL, training: the records of x's tiles; grid (tiles, blocks of 128 columns)
+__global__ __launch_bounds__(256) void k_seam_tile_stats(const float* __restrict__ x, int64_t xs, int64_t N, int O,
+                                                         float* __restrict__ part) {
+  constexpr int CT = kSeamChunk, ZP = CT + 4, CQ = CT / 4;
+  __shared__ __attribute__((aligned(16))) float Zs[T * ZP];
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int col0 = blockIdx.y * CT;
+  for (int e = tid; e < T * CQ; e += 256) {
+    const int r = e / CQ, c = 4 * (e % CQ);
+    f4 v = zero4();
+    if (row0 + r < N && col0 + c < O) v = ld4(x + (row0 + r) * xs + col0 + c);
+    *reinterpret_cast<f4*>(&Zs[r * ZP + c]) = v;
+  }
+  __syncthreads();
+  if (tid < CT && col0 + tid < O) {
+    const int nv = N - row0 < T ? (int)(N - row0) : T;
+    float* rec = part + (int64_t)blockIdx.x * 2 * O;
+    seam_tile_record(Zs, ZP, tid, nv, rec + col0 + tid, rec + O + col0 + tid);
+  }
+}
+
+// ---- forward: the statistics --------------------------------------------------------------------------------------------
+// 256 threads = 64 groups x 4 columns; group q merges its gper consecutive tiles in ascending order, then the thread of
+// group 0 merges the groups in ascending order.  G == 1: one level.  The merge carries (count, mean, M2) -- the
+// parallel-variance merge, whose running mean serves M2's correction term -- and beside it a compensated sum of
+// count_t mean_t in the same order, from which the column's mean is taken: total / N, one rounding.
+__global__ __launch_bounds__(256) void k_seam_stats(const float* __restrict__ part, int64_t tiles, int64_t N, int O, int G,
+                                                    int64_t gper, float eps, float momentum, float* __restrict__ mean,
+                                                    float* __restrict__ rstd, float* __restrict__ rmean,
+                                                    float* __restrict__ rvar, int64_t* __restrict__ tracked) {
+  __shared__ float Sn[kSeamGroups][4], Sm[kSeamGroups][4], Sq[kSeamGroups][4], Ss[kSeamGroups][4], Sc[kSeamGroups][4];
+  const int q = threadIdx.x >> 2, cl = threadIdx.x & 3, c = blockIdx.x * 4 + cl;
+  float n = 0.0f, m = 0.0f, m2 = 0.0f, sum = 0.0f, comp = 0.0f;
+  auto merge = [&](float nb, float mb, float qb) {
+    if (nb == 0.0f) return;
+    if (n == 0.0f) {
+      n = nb;
+      m = mb;
+      m2 = qb;
+      return;
+    }
+    const float tot = n + nb, d = mb - m;
+    m += d * (nb / tot);
+    m2 += qb + d * d * (n * nb / tot);
+    n = tot;
+  };
+  if (q < G && c < O) {
+    const int64_t t0 = q * gper, t1 = t0 + gper < tiles ? t0 + gper : tiles;
+    for (int64_t t = t0; t < t1; t++) {
+      const float nb = (float)(N - t * T < T ? N - t * T : T), mb = part[t * 2 * O + c];
+      merge(nb, mb, part[(t * 2 + 1) * O + c]);
+      kahan_add(sum, comp, nb * mb);
+    }
+  }
+  Sn[q][cl] = n;
+  Sm[q][cl] = m;
+  Sq[q][cl] = m2;
+  Ss[q][cl] = sum;
+  Sc[q][cl] = comp;
+  __syncthreads();
+  if (q != 0 || c >= O) return;
+  for (int k = 1; k < G; k++) {
+    merge(Sn[k][cl], Sm[k][cl], Sq[k][cl]);
+    kahan_add(sum, comp, Ss[k][cl]);
+    kahan_add(sum, comp, -Sc[k][cl]);
+  }
+  m = (sum - comp) / (float)N;
+  mean[c] = m;
+  rstd[c] = 1.0f / sqrtf(m2 / (float)N + eps);
+  if (rmean) {  // one thread per column, plain stores
+    rmean[c] = (1.0f - momentum) * rmean[c] + momentum * m;
+    rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (m2 / (float)(N - 1));
+    if (c == 0) tracked[0] += 1;
+  }
+}
+
+// ---- forward: apply ------------------------------------------------------------------------------------------------------
+// one thread per 16 bytes of y; o4 = O / 4.  FROM_VAR: `spread` is a variance (eval, w == NULL), else it is rstd.
+template <bool FROM_VAR>
+__global__ __launch_bounds__(256) void k_seam_apply(const float* __restrict__ z, int64_t zs, const float* __restrict__ mean,
+                                                    const float* __restrict__ spread, float eps,
+                                                    const float* __restrict__ gam, const float* __restrict__ bet, int act,
+                                                    int64_t N, int o4, float* __restrict__ y, int64_t ys,
+                                                    float* __restrict__ rstd_out) {
+  const int64_t base = (int64_t)blockIdx.x * 256, r0 = base / o4;  // uniform: one wide division per wave
+  const unsigned local = (unsigned)(base - r0 * o4) + threadIdx.x;
+  const int64_t r = r0 + local / (unsigned)o4;
+  const int c = 4 * (int)(local % (unsigned)o4);
+  if (r >= N) return;
+  const f4 rs = FROM_VAR ? seam_rstd4(ld4(spread + c), eps) : ld4(spread + c);
+  st4(y + r * ys + c, seam_act4(ld4(z + r * zs + c), ld4(mean + c), rs, ld4(gam + c), ld4(bet + c), act != 0));
+  if (FROM_VAR && rstd_out && r == 0) st4(rstd_out + c, rs);
+}
+
+// ---- backward: dh, dg -----------------------------------------------------------------------------------------------------
+// grid (tiles, blocks of 64 columns); thread = (16 rows, column); a tile's record [2][O] = dh, dg
+__global__ __launch_bounds__(256) void k_seam_bwd_part(const float* __restrict__ dy, int64_t dys, const float* __restrict__ z,
+                                                       int64_t zs, const float* __restrict__ mean,
+                                                       const float* __restrict__ rstd, const float* __restrict__ gam,
+                                                       const float* __restrict__ bet, int act, int64_t N, int O,
+                                                       float* __restrict__ part) {
+  __shared__ float Sh[4][T], Sg[4][T];
+  const int cl = threadIdx.x & 63, rq = threadIdx.x >> 6, c = blockIdx.y * T + cl;
+  const int64_t row0 = (int64_t)blockIdx.x * T + 16 * rq;
+  float sh = 0.0f, sg = 0.0f;
+  if (c < O) {
+    const float mu = mean[c], rs = rstd[c], ga = gam[c], be = bet[c];
+    for (int k = 0; k < 16; k++) {
+      const int64_t r = row0 + k;
+      if (r >= N) break;
+      const float zh = (z[r * zs + c] - mu) * rs;
+      float du = dy[r * dys + c];
+      if (act) du = du * gelu_grad_f(zh * ga + be);
+      sh += du;
+      sg += du * zh;
+    }
+  }
+  Sh[rq][cl] = sh;
+  Sg[rq][cl] = sg;
+  __syncthreads();
+  if (rq == 0 && c < O) {
+    float* rec = part + (int64_t)blockIdx.x * 2 * O;
+    rec[c] = ((Sh[0][cl] + Sh[1][cl]) + Sh[2][cl]) + Sh[3][cl];
+    rec[O + c] = ((Sg[0][cl] + Sg[1][cl]) + Sg[2][cl]) + Sg[3][cl];
+  }
+}
+
+// k_seam_stats' layout with plain sums; `keep` [2][O] = dh, dg for the kernels that form dz
+__global__ __launch_bounds__(256) void k_seam_bwd_fold(const float* __restrict__ part, int64_t tiles, int O, int G,
+                                                       int64_t gper, float* __restrict__ dg, float* __restrict__ dh,
+                                                       float* __restrict__ keep) {
+  __shared__ float Sh[kSeamGroups][4], Sg[kSeamGroups][4];
+  const int q = threadIdx.x >> 2, cl = threadIdx.x & 3, c = blockIdx.x * 4 + cl;
+  float sh = 0.0f, sg = 0.0f;
+  if (q < G && c < O) {
+    const int64_t t0 = q * gper, t1 = t0 + gper < tiles ? t0 + gper : tiles;
+    for (int64_t t = t0; t < t1; t++) {
+      sh += part[t * 2 * O + c];
+      sg += part[(t * 2 + 1) * O + c];
+    }
+  }
+  Sh[q][cl] = sh;
+  Sg[q][cl] = sg;
+  __syncthreads();
+  if (q != 0 || c >= O) return;
+  for (int k = 1; k < G; k++) {
+    sh += Sh[k][cl];
+    sg += Sg[k][cl];
+  }
+  if (dh) dh[c] = sh;
+  if (dg) dg[c] = sg;
+  keep[c] = sh;
+  keep[O + c] = sg;
+}
+
+// what the kernels that form dz share; kh, kg: dh and dg [O], both NULL under running statistics
+struct SeamDz {
+  const float *dy, *z, *mean, *rstd, *gam, *bet, *kh, *kg;
+  int64_t dys, zs;
+  float inv_n;
+  int act;
+  __device__ __forceinline__ f4 at(int64_t r, int c) const {
+    f4 mh = zero4(), mg = zero4();
+    if (kh) {
+      mh = ld4(kh + c) * inv_n;
+      mg = ld4(kg + c) * inv_n;
+    }
+    return seam_dz4(ld4(dy + r * dys + c), ld4(z + r * zs + c), ld4(mean + c), ld4(rstd + c), ld4(gam + c), ld4(bet + c), mh,
+                    mg, act != 0, kh != nullptr);
+  }
+};
+
+// ---- backward: dx ---------------------------------------------------------------------------------------------------------
+// w == NULL: dx is dz; one thread per 16 bytes, o4 = O / 4
+__global__ __launch_bounds__(256) void k_seam_dz(SeamDz d, int64_t N, int o4, float* __restrict__ dx, int64_t dxs) {
+  const int64_t base = (int64_t)blockIdx.x * 256, r0 = base / o4;
+  const unsigned local = (unsigned)(base - r0 * o4) + threadIdx.x;
+  const int64_t r = r0 + local / (unsigned)o4;
+  const int c = 4 * (int)(local % (unsigned)o4);
+  if (r >= N) return;
+  st4(dx + r * dxs + c, d.at(r, c));
+}
+
+// k_mid_bwd_rows' shape: 256 threads own T = 64 rows and CT = 32 NJ columns of dx (grid.y walks I); the outputs are the
+// summed index, walked in chunks of <= 128 of dz staged in LDS.
+template <int NJ>
+__global__ __launch_bounds__(256, 2) void k_seam_dx(SeamDz d, const float* __restrict__ w, int64_t N, int I, int O,
+                                                    float* __restrict__ dx, int64_t dxs) {
+  constexpr int CT = 32 * NJ, XP = kSeamChunk + 4, WP = CT + 16, NV = NJ > 2 ? NJ / 2 : 1, CQ = CT / 4;
+  __shared__ __attribute__((aligned(16))) float Ds[T * XP];   // dz: rows x a chunk of outputs
+  __shared__ __attribute__((aligned(16))) float Ws[KC * WP];  // a 16-deep slice of W: summed index in rows
+  const int tid = threadIdx.x;
+  const WaveTile g;
+  const int wcn = (g.wc >> 5) * 16 * NJ;
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int col0 = blockIdx.y * CT;
+
+  f4 vw[NV];
+  f4 acc[2][NJ], tot[2][NJ];
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < NJ; j++) tot[i][j] = zero4();
+
+  for (int o0 = 0; o0 < O; o0 += kSeamChunk) {
+    const int cw = O - o0 < kSeamChunk ? O - o0 : kSeamChunk;
+    const int Cr = (cw + KC - 1) / KC * KC, c4 = Cr >> 2;
+    for (int e = tid; e < T * c4; e += 256) {
+      const int r = e / c4, c = 4 * (e % c4);
+      f4 v = zero4();
+      if (row0 + r < N && o0 + c < O) v = d.at(row0 + r, o0 + c);
+      *reinterpret_cast<f4*>(&Ds[r * XP + c]) = v;
+    }
+    auto fetchw = [&](int k0) {  // slice of W [O][I]: row o0 + k0 + e / CQ, four columns at col0 + 4 * (e % CQ)
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int e = tid + 256 * u, o = o0 + k0 + e / CQ, c = col0 + 4 * (e % CQ);
+        vw[u] = (e < KC * CQ && o < O && c < I) ? ld4(w + (int64_t)o * I + c) : zero4();
+      }
+    };
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < NJ; j++) acc[i][j] = zero4();
+    fetchw(0);
+    for (int k0 = 0; k0 < Cr; k0 += KC) {
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int e = tid + 256 * u;
+        if (e < KC * CQ) *reinterpret_cast<f4*>(&Ws[(e / CQ) * WP + 4 * (e % CQ)]) = vw[u];
+      }
+      __syncthreads();
+      if (k0 + KC < Cr) fetchw(k0 + KC);
+#pragma unroll
+      for (int kk = 0; kk < KC; kk += 4) {
+        float fa[2], fb[NJ];
+#pragma unroll
+        for (int i = 0; i < 2; i++) fa[i] = Ds[(g.wr + 16 * i + g.fl) * XP + k0 + kk + g.fk];
+#pragma unroll
+        for (int j = 0; j < NJ; j++) fb[j] = Ws[(kk + g.fk) * WP + wcn + 16 * j + g.fl];
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+          for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < NJ; j++) tot[i][j] = tot[i][j] + acc[i][j];
+  }
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const int64_t row = row0 + g.wr + 16 * i + 4 * g.fk + v;
+      if (row >= N) continue;
+#pragma unroll
+      for (int j = 0; j < NJ; j++) {
+        const int c = col0 + wcn + 16 * j + g.fl;
+        if (c < I) dx[row * dxs + c] = tot[i][j][v];
+      }
+    }
+}
+
+// ---- backward: the weight gradient ----------------------------------------------------------------------------------------
+// A slice's record in `part`: dW [O][I], db [O].
+__host__ __device__ inline int64_t seam_record(int I, int O) { return (int64_t)O * I + O; }
+
+// grid: (tiles of 64 x 64 over O x I, row slices): dW[o][i] = sum_r dz[r][o] x[r][i], db[o] = sum_r dz[r][o]
+__global__ __launch_bounds__(256) void k_seam_dw(SeamDz d, const float* __restrict__ x, int64_t xs, int64_t N, int I, int O,
+                                                 int64_t per, float* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float Ds[KC * kPitchT];
+  __shared__ __attribute__((aligned(16))) float Xs[KC * kPitchT];
+  float* rec = part + (int64_t)blockIdx.y * seam_record(I, O);
+  const int tiles_i = (I + T - 1) / T;
+  const int o0 = (blockIdx.x / tiles_i) * T, i0 = (blockIdx.x % tiles_i) * T;
+  const int64_t p0 = blockIdx.y * per, p1 = p0 + per < N ? p0 + per : N;
+  const int sc = 4 * (threadIdx.x & 15);
+  auto fetch = [&](int64_t r, bool od, bool ix, f4& vd, f4& vx) {
+    if (od) vd = d.at(r, o0 + sc);
+    if (ix) vx = ld4(x + r * xs + i0 + sc);
+  };
+  dw_slice_tile(fetch, O, I, o0, i0, p0, p1, rec, rec + (int64_t)O * I, Ds, Xs);
+}
+
+// ---- host: the plans and the launches -----------------------------------------------------------------------------------
+struct SeamPlan {
+  int64_t tiles;  // row tiles
+  int G;          // groups of consecutive tiles (1: one level)
+  int64_t gper;   // tiles per group
+  int sw;         // row slices of the weight gradient
+  unsigned wt;    // 64 x 64 tiles of the weight gradient
+  size_t part, keep, wpart, total;  // backward; the forward's workspace is `part` alone
+};
+SeamPlan seam_plan(int64_t N, int32_t I, int32_t O) {
+  SeamPlan p;
+  p.tiles = (N + T - 1) / T;
+  p.G = p.tiles > kSeamFoldTiles ? (int)std::min<int64_t>(kSeamGroups, (p.tiles + kSeamFoldTiles - 1) / kSeamFoldTiles) : 1;
+  p.gper = (p.tiles + p.G - 1) / p.G;
+  p.wt = (unsigned)((O + T - 1) / T) * (unsigned)((I + T - 1) / T);
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(kFfnMaxSlices, 1024 / p.wt));
+  p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 63) / 64));
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  p.part = take((size_t)std::max<int64_t>(p.tiles, 1) * 2 * O * 4);
+  p.keep = take((size_t)2 * O * 4);
+  p.wpart = take((size_t)p.sw * (size_t)seam_record(I, O) * 4);
+  p.total = off;
+  return p;
+}
+size_t seam_forward_bytes(int64_t N, int32_t O) { return seam_plan(N, 4, O).keep; }  // the tiles' records, rounded
+
+// the column block: the narrowest template that holds C, else 128 columns a block
+template <bool EVAL, typename... A>
+void seam_launch_forward(int O, unsigned tiles, hipStream_t st, A... args) {
+  if (O <= 32) k_seam_forward<1, EVAL><<<dim3(tiles, 1), 256, 0, st>>>(args...);
+  else if (O <= 64) k_seam_forward<2, EVAL><<<dim3(tiles, 1), 256, 0, st>>>(args...);
+  else k_seam_forward<4, EVAL><<<dim3(tiles, blocks_for(O, 128)), 256, 0, st>>>(args...);
+}
+template <typename... A>
+void seam_launch_dx(int I, unsigned tiles, hipStream_t st, A... args) {
+  if (I <= 32) k_seam_dx<1><<<dim3(tiles, 1), 256, 0, st>>>(args...);
+  else if (I <= 64) k_seam_dx<2><<<dim3(tiles, 1), 256, 0, st>>>(args...);
+  else k_seam_dx<4><<<dim3(tiles, blocks_for(I, 128)), 256, 0, st>>>(args...);
+}
+
+}  // namespace

@@ -21,6 +21,7 @@ import threading
 import torch
 
 from . import _native_s as S
+from . import point_seam
 from ._loader import current_stream as _stream
 
 REDUCES = ("sum", "mean", "min", "max")
@@ -228,10 +229,11 @@ def _fused(*tensors):
     return all(t.is_cuda for t in tensors) and all(t.dtype in _DTYPES for t in tensors if t.is_floating_point())
 
 
-def _pooling_forward(original, point_class):
+def _pooling_forward(original, point_class, pt_v3_module):
     def forward(self, point):
         """SerializedPooling.forward over gcs_pool_plan_* and the gathered reduce; a point set on the CPU or in another
-        dtype than float32 / float16 goes to the original method."""
+        dtype than float32 / float16 goes to the original method.  With point_seam's marker on the module, the norm / act
+        tail is one fused call when the two containers are that pair."""
         pooling_depth = (math.ceil(self.stride) - 1).bit_length()
         if pooling_depth > point.serialized_depth:
             pooling_depth = 0
@@ -269,6 +271,10 @@ def _pooling_forward(original, point_class):
             point_dict["pooling_plan"] = plan
         _STATS["pooling_fused"] += 1
         point = point_class(point_dict)
+        if (getattr(pt_v3_module, point_seam._MARK, False) and self.norm is not None and self.act is not None
+                and point.feat.size(0) != 1 and point_seam.pooling_tail(self.norm, self.act, point)):
+            point.sparsify()
+            return point
         if self.norm is not None and point.feat.size(0) != 1:
             point = self.norm(point)
         if self.act is not None:
@@ -315,7 +321,7 @@ def install(pt_v3_module):
     pooling, unpooling = pt_v3_module.SerializedPooling, pt_v3_module.SerializedUnpooling
     originals = (pooling.forward, unpooling.forward)
     setattr(pt_v3_module, _ORIGINALS, originals)
-    pooling.forward = _pooling_forward(originals[0], pt_v3_module.Point)
+    pooling.forward = _pooling_forward(originals[0], pt_v3_module.Point, pt_v3_module)
     unpooling.forward = _unpooling_forward(originals[1])
 
 

@@ -162,6 +162,55 @@
  *     gcm_mid_backward_workspace_bytes(N, C) bytes (never 0 for arguments in range), 256-byte aligned; what it held before
  *     does not matter.  One launch for da, two for dwp / dbp, whatever N is.  The slices depend on N and C alone: every
  *     output is bit-identical from run to run and independent of how many workgroups the device holds at a time.
+ *
+ * ---- The seams between the PTv3 stages (models/pt_v3.py: Embedding.stem's tail, SerializedPooling's norm / act,
+ * SerializedUnpooling.proj and proj_skip) -------------------------------------------------------------
+ * Linear -> BatchNorm1d -> GELU as one operator, for N rows, I inputs, O outputs, float32:
+ *     z = x W^T + b                      w [O][I] contiguous, b [O] or NULL;  w == NULL: z is x itself and I == O
+ *     batch statistics (training)        mean_c = (1/N) sum_r z_rc;  var_c = (1/N) sum_r (z_rc - mean_c)^2
+ *     running statistics (eval)          mean_c = running_mean_c;  var_c = running_var_c
+ *     rstd = 1 / sqrt(var + eps);  u = ((z - mean) rstd) g + h             g, h = bn_w, bn_b [O]
+ *     y = act ? u (1 + erf(u / sqrt 2)) / 2 : u
+ *     training also: running_mean = (1 - m) running_mean + m mean;  running_var = (1 - m) running_var + m var N / (N - 1);
+ *     num_batches_tracked += 1
+ *   x, y, dy and dx are row-strided under the rule above; z is [N][O] contiguous where the library writes it and carries a
+ *   stride where it reads it (with w == NULL the caller passes x and its stride as z).  Float pointers are 16-byte aligned,
+ *   the int64 counter 8-byte.  I and O are positive multiples of 4, at most gcm_seam_max_channels(); N is refused at 2^31
+ *   and above; w == NULL with I != O is refused, as are b, z, dw or db without w.  Training refuses N == 1 (torch raises
+ *   there); with N == 0 the forwards queue nothing and the backward queues only the clears of the parameter gradients
+ *   asked for.  Arguments are checked before anything is queued; no call allocates or waits.
+ *
+ * gcm_seam_max_channels (host only): the largest I and O, 512 in this build; never 0.
+ * gcm_seam_forward_eval: ONE launch; nothing but y reaches memory unless z [N][O] or rstd [O] is given (a caller that wants a
+ *     gradient in eval mode gives both).  z is one fp32 chain from 0 over the inputs in ascending order on
+ *     v_mfma_f32_16x16x4_f32 -- the accumulators carry across the chunks of 128 inputs staged at a time -- and b is added
+ *     after the chain.  rstd = 1 / sqrt(var + eps) with IEEE division and square root; u is a subtraction, two multiplies
+ *     and an add in the order written above, not contracted.  With w == NULL the launch is elementwise.
+ * gcm_seam_forward_train: three launches whatever N is.  (1) the product stores z and, per tile of 64 rows and column, the
+ *     tile's mean over its valid rows in ascending order, taken about the tile's first row (z0 + sum (z - z0) / n: a column
+ *     whose mean is many standard deviations keeps its digits), and, about that mean, the centred second moment M2 (with
+ *     w == NULL this launch only reads x).  (2) per column the tiles' (count, mean, M2) are merged in ascending tile order
+ *     with the parallel-variance merge -- sum z^2 - (sum z)^2 / N is never formed -- beyond 64 tiles in at most 64 groups of
+ *     consecutive tiles, each merged in order, the groups then merged in ascending order; the mean itself is a compensated
+ *     (Kahan) sum of count_t mean_t in the same order divided by N, as the tile's mean is one of z - z0; this launch
+ *     writes mean and rstd [O] and, when the three buffers are given (all or none), the running statistics and the counter, plain stores from
+ *     one thread per column.  (3) y from z in 16-byte accesses.  workspace is gcm_seam_forward_workspace_bytes(N, O) bytes
+ *     (never 0 for arguments in range), 256-byte aligned; what it held before does not matter.
+ * gcm_seam_backward: from x, z, mean, rstd and dy, all only read: the call may be repeated.  batch_stats says whether mean
+ *     and rstd were the batch's.  With zhat = (z - mean) rstd and u = zhat g + h recomputed from z:
+ *       du = act ? dy (Phi(u) + u phi(u)) : dy;  dbn_b = sum_r du;  dbn_w = sum_r du zhat
+ *       dz = (g rstd) (du - dbn_b / N - zhat dbn_w / N) under batch statistics, dz = (g rstd) du under running ones
+ *       dx = dz W;  dw [O][I] = dz^T x;  db = sum_r dz
+ *     dbn_b and dbn_w: per tile of 64 rows four chains of 16 rows added in order, the tiles added in ascending order, beyond
+ *     64 tiles in groups as the statistics; two launches, and none under running statistics when neither is asked for.
+ *     dx: one launch; dz is staged in LDS per 64 rows and never stored.  dx is, per chunk of 128 outputs, one fp32 chain
+ *     from 0 over the chunk's outputs in ascending order, and the chunks' results are added in ascending order (O <= 128:
+ *     one chain).  dw and db: sums over at most 64 row slices added in the feed-forward's pairwise tree, inside a slice
+ *     every 32 consecutive rows one chain (the bias sums as db1 / db2 above); two launches.  Five launches under batch
+ *     statistics whatever N is; no float atomics.  Every output is written whole; a NULL output is skipped and skips its
+ *     launches.  With w == NULL dx is dz (one elementwise launch) and there is no dw or db.  workspace is
+ *     gcm_seam_backward_workspace_bytes(N, I, O) bytes, 256-byte aligned.  Slices and groups depend on N, I and O alone:
+ *     every output is bit-identical from run to run and independent of how many workgroups the device holds at a time.
  */
 #ifndef GCM_H
 #define GCM_H
@@ -253,6 +302,29 @@ size_t gcm_mid_backward_workspace_bytes(int64_t N, int32_t C);
 int gcm_mid_backward(const float* a, int64_t a_stride, const int64_t* inverse, const int32_t* extra, const float* dy,
                      int64_t dy_stride, const float* wp, const float* row_scale, int64_t N, int64_t T, int32_t C,
                      float* da, float* dwp, float* dbp, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+int gcm_seam_max_channels(void);
+
+int gcm_seam_forward_eval(const float* x, int64_t x_stride, const float* w, const float* b, const float* running_mean,
+                          const float* running_var, float eps, const float* bn_w, const float* bn_b, int act, int64_t N,
+                          int32_t I, int32_t O, float* y, int64_t y_stride, float* z, float* rstd, void* hip_stream);
+
+/* 0 with a message in gcm_last_error() when an argument is out of range */
+size_t gcm_seam_forward_workspace_bytes(int64_t N, int32_t O);
+
+int gcm_seam_forward_train(const float* x, int64_t x_stride, const float* w, const float* b, float eps, float momentum,
+                           const float* bn_w, const float* bn_b, int act, int64_t N, int32_t I, int32_t O, float* z, float* y,
+                           int64_t y_stride, float* mean, float* rstd, float* running_mean, float* running_var,
+                           int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* 0 with a message in gcm_last_error() when an argument is out of range */
+size_t gcm_seam_backward_workspace_bytes(int64_t N, int32_t I, int32_t O);
+
+int gcm_seam_backward(const float* x, int64_t x_stride, const float* z, int64_t z_stride, const float* mean,
+                      const float* rstd, const float* dy, int64_t dy_stride, const float* w, const float* bn_w,
+                      const float* bn_b, int act, int batch_stats, int64_t N, int32_t I, int32_t O, float* dx,
+                      int64_t dx_stride, float* dw, float* db, float* dbn_w, float* dbn_b, void* workspace,
+                      size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
