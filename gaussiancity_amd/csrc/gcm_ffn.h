@@ -1,9 +1,9 @@
 // gcm_ffn.h -- the feed-forward third of a PTv3 Block (gcm_ffn_*, include/gcm.h): y = x + s o (GELU(LN(x) W1^T + b1) W2^T + b2)
-// in ONE launch, and its deterministic backward in a handful of launches whatever N is.  Included by gcm_modlinear.hip,
-// whose WaveTile, kPitch / kPitchT images and fetch-ahead it uses; device code and launch helpers only, the C ABI stays
-// in gcm_modlinear.hip.  DESIGN.md section 18.
+// in ONE launch, and its deterministic backward in a handful of launches whatever N is.  Included by gcm_modlinear.hip
+// after gcm_tile.h, which holds the tile, the product loop and the LayerNorm lane rule; device code and the plan only, the
+// C ABI stays in gcm_modlinear.hip.  DESIGN.md section 18.
 //
-// A workgroup (256 threads, 4 waves as 2 x 2) owns T = 64 rows.  CT = 32 NJ (NJ = 1, 2, 4) is the channel width a kernel
+// A workgroup owns T = 64 rows.  CT = 32 NJ (NJ = 1, 2, 4) is the channel width a kernel
 // instantiation holds; C <= CT, channels beyond C and rows beyond N are staged as zeros, the summed index over the
 // channels runs to C rounded up to 16 only.
 //   forward   x tile -> LDS, normalised in place (4 lanes per row, fixed order).  Per chunk of 64 hidden features:
@@ -15,38 +15,14 @@
 //             dx = dy + ..., and the tile's column sums of dxn o xhat and dxn (row groups in ascending order).
 //             k_ffn_dw: dW1 = da^T xn and dW2 = dt^T GELU(a) in row slices (k_modlinear_dw's scheme, both in one
 //             launch), with db1 / db2 as the column sums of the slice's da / dt.  k_ffn_fold_params adds the slices
-//             pairwise, a fixed tree; k_ffn_fold_groups / k_ffn_fold_ln add the tiles' LayerNorm partials in tile order.
+//             pairwise, a fixed tree; fold_ln_partials (gcm_tile.h) adds the tiles' LayerNorm partials in tile order.
 // Nothing depends on how many workgroups are resident: every sum has a fixed set of terms in a fixed order.
 #pragma once
 
 namespace {
 
-constexpr int FH = 64;                 // hidden features per chunk
-constexpr int kPitchG = FH + 4;        // words between rows of the g / da chunk image (rows x hidden)
 constexpr int kFfnMaxChannels = 128;   // widest instantiation (NJ = 4)
-constexpr int kFfnFoldTiles = 64;      // LayerNorm partials: up to this many tiles fold in one level
 constexpr int kFfnSumRows = 32;        // weight gradients: a chain runs over this many rows, the chains' results are added in order
-constexpr int kFfnMaxSlices = 64;      // weight gradients: at most this many row slices, the leaves of k_ffn_fold_params' tree
-
-__device__ __forceinline__ float gelu_f(float a) { return 0.5f * a * (1.0f + erff(a * 0.70710678118654752f)); }
-// d/da of gelu: Phi(a) + a phi(a)
-__device__ __forceinline__ float gelu_grad_f(float a) {
-  const float cdf = 0.5f * (1.0f + erff(a * 0.70710678118654752f));
-  const float pdf = 0.3989422804014327f * expf(-0.5f * a * a);
-  return cdf + a * pdf;
-}
-__device__ __forceinline__ float sum4(float acc, f4 v) {  // one chain, element order
-  acc += v[0];
-  acc += v[1];
-  acc += v[2];
-  acc += v[3];
-  return acc;
-}
-__device__ __forceinline__ float quad_sum(float v) {  // the 4 lanes of a row: the same bits in all four
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  return v;
-}
 
 // ---- forward ----------------------------------------------------------------------------------------------------------
 template <int NJ>
@@ -57,154 +33,64 @@ __global__ __launch_bounds__(256, 2) void k_ffn_forward(const float* __restrict_
                                                         int C, int Hd, float* __restrict__ y, int64_t ys,
                                                         float* __restrict__ mean, float* __restrict__ rstd,
                                                         float* __restrict__ a) {
-  constexpr int CT = 32 * NJ, XP = CT + 4, NV = NJ > 2 ? NJ / 2 : 1;
+  constexpr int CT = 32 * NJ, XP = CT + 4;
   __shared__ __attribute__((aligned(16))) float Xs[T * XP];                    // x, then LN(x): rows x channels
   __shared__ __attribute__((aligned(16))) float Gs[T * kPitchG];               // GELU(a) of one chunk: rows x hidden
   __shared__ __attribute__((aligned(16))) float Ws[(CT > T ? CT : T) * kPitch];  // a 16-deep slice of W1, then of W2
   const int tid = threadIdx.x;
   const WaveTile g;
-  const int wcn = (g.wc >> 5) * 16 * NJ;  // the wave's first y channel
   const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC, c4 = Cr >> 2;
+  const int Cr = (C + KC - 1) / KC * KC;
 
-  for (int e = tid; e < T * c4; e += 256) {
-    const int r = e / c4, c = 4 * (e % c4);
-    *reinterpret_cast<f4*>(&Xs[r * XP + c]) = (row0 + r < N && c < C) ? ld4(x + (row0 + r) * xs + c) : zero4();
-  }
+  stage_rows(Xs, XP, Cr >> 2, [&](int r, int c) { return (row0 + r < N && c < C) ? ld4(x + (row0 + r) * xs + c) : zero4(); });
   __syncthreads();
-  {  // LayerNorm in place: lane q of a row owns the elements 4 q + 16 k .. + 3
+  {  // LayerNorm in place
     const int r = tid >> 2, q = tid & 3;
     const bool live = row0 + r < N;
-    float sum = 0.0f;
-    for (int c = 4 * q; c < C; c += 16) sum = sum4(sum, *reinterpret_cast<const f4*>(&Xs[r * XP + c]));
-    const float mu = quad_sum(sum) / (float)C;
-    float sq = 0.0f;
-    for (int c = 4 * q; c < C; c += 16) {
-      const f4 d = *reinterpret_cast<const f4*>(&Xs[r * XP + c]) - mu;
-      sq = sum4(sq, d * d);
-    }
-    const float rs = 1.0f / sqrtf(quad_sum(sq) / (float)C + eps);
-    for (int c = 4 * q; c < C; c += 16) {
-      const f4 d = *reinterpret_cast<const f4*>(&Xs[r * XP + c]) - mu;
-      *reinterpret_cast<f4*>(&Xs[r * XP + c]) = live ? d * rs * ld4(lnw + c) + ld4(lnb + c) : zero4();
-    }
+    const RowStat st = ln_rows_forward(
+        &Xs[r * XP], q, C, eps, [](int, f4) {}, [&](int c, f4 h) { return live ? h * ld4(lnw + c) + ld4(lnb + c) : zero4(); });
     if (live && q == 0 && mean) {
-      mean[row0 + r] = mu;
-      rstd[row0 + r] = rs;
+      mean[row0 + r] = st.mean;
+      rstd[row0 + r] = st.rstd;
     }
   }
-  // (the first __syncthreads of the slice loop below orders these writes before the fragment reads)
 
-  const int br = tid >> 2, bc = 4 * (tid & 3);  // W1 slice: hidden row tid / 4, four channels at 4 * (tid % 4)
-  f4 vb, vw[NV];
-  auto fetch1 = [&](int h0, int c0) {
-    const int h = h0 + br, c = c0 + bc;
-    vb = (h < Hd && c < C) ? ld4(w1 + (int64_t)h * C + c) : zero4();
-  };
-  auto fetch2 = [&](int h0, int k0) {  // W2 slice: channel row e / 4, four hidden features at 4 * (e % 4)
-#pragma unroll
-    for (int u = 0; u < NV; u++) {
-      const int e = tid + 256 * u, c = e >> 2, h = h0 + k0 + 4 * (e & 3);
-      vw[u] = (e < 4 * CT && c < C && h < Hd) ? ld4(w2 + (int64_t)c * Hd + h) : zero4();
-    }
-  };
-
+  Chain<2, false> up;     // a = xn W1^T: 64 hidden features of the chunk, summed over the channels
+  Chain<NJ, false> down;  // t = g W2^T: the channels, summed over the chunk's hidden features
   f4 yacc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) yacc[i][j] = zero4();
-
+  clear_acc(yacc);
   for (int h0 = 0; h0 < Hd; h0 += FH) {
+    auto w1_at = [&](int hl, int c) { return (h0 + hl < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + hl) * C + c) : zero4(); };
+    auto w2_at = [&](int c, int k) { return (c < C && h0 + k < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + k) : zero4(); };
     f4 acc[2][2];
     clear_acc(acc);
-    fetch1(h0, 0);
-    for (int c0 = 0; c0 < Cr; c0 += KC) {
-      *reinterpret_cast<f4*>(&Ws[br * kPitch + bc]) = vb;
-      __syncthreads();
-      if (c0 + KC < Cr) fetch1(h0, c0 + KC);
-      else fetch2(h0, 0);
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        float fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i] = Xs[(g.wr + 16 * i + g.fl) * XP + c0 + kk + g.fk];
-#pragma unroll
-        for (int j = 0; j < 2; j++) fb[j] = Ws[(g.wc + 16 * j + g.fl) * kPitch + kk + g.fk];
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    up.first(w1_at);
+    up.run(acc, g, Xs, XP, Cr, Ws, w1_at, [&]() { down.first(w2_at); });
+    for_each_output(acc, g, [&](int rl, int hl, float v) {
+      const int64_t row = row0 + rl;
+      const int h = h0 + hl;
+      float gv = 0.0f;
+      if (h < Hd) {
+        const float av = v + b1[h];
+        if (a && row < N) a[row * Hd + h] = av;
+        gv = gelu_f(av);
       }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) {
-        const int rl = g.wr + 16 * i + 4 * g.fk + v;
-        const int64_t row = row0 + rl;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          const int hl = g.wc + 16 * j + g.fl, h = h0 + hl;
-          float gv = 0.0f;
-          if (h < Hd) {
-            const float av = acc[i][j][v] + b1[h];
-            if (a && row < N) a[row * Hd + h] = av;
-            gv = gelu_f(av);
-          }
-          Gs[rl * kPitchG + hl] = gv;
-        }
-      }
+      Gs[rl * kPitchG + hl] = gv;
+    });
     const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
     f4 tacc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) tacc[i][j] = zero4();
-    for (int k0 = 0; k0 < kend; k0 += KC) {
-#pragma unroll
-      for (int u = 0; u < NV; u++) {
-        const int e = tid + 256 * u;
-        if (e < 4 * CT) *reinterpret_cast<f4*>(&Ws[(e >> 2) * kPitch + 4 * (e & 3)]) = vw[u];
-      }
-      __syncthreads();
-      if (k0 + KC < kend) fetch2(h0, k0 + KC);
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        float fa[2], fb[NJ];
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i] = Gs[(g.wr + 16 * i + g.fl) * kPitchG + k0 + kk + g.fk];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) fb[j] = Ws[(wcn + 16 * j + g.fl) * kPitch + kk + g.fk];
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < NJ; j++) tacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], tacc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) yacc[i][j] = yacc[i][j] + tacc[i][j];
+    clear_acc(tacc);
+    down.run(tacc, g, Gs, kPitchG, kend, Ws, w2_at);
+    add_acc(yacc, tacc);
   }
 
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int64_t row = row0 + g.wr + 16 * i + 4 * g.fk + v;
-      if (row >= N) continue;
-      const float sr = s ? s[row] : 1.0f;
-#pragma unroll
-      for (int j = 0; j < NJ; j++) {
-        const int c = wcn + 16 * j + g.fl;
-        if (c >= C) continue;
-        const float t = yacc[i][j][v] + b2[c];
-        y[row * ys + c] = x[row * xs + c] + (s ? sr * t : t);
-      }
-    }
+  for_each_output(
+      yacc, g, [&](int rl) { return scaled_row(row0 + rl, N, s); },
+      [&](ScaledRow r, int c, float v) {
+        if (r.row < 0 || c >= C) return;
+        const float t = v + b2[c];
+        y[r.row * ys + c] = x[r.row * xs + c] + (s ? r.scale * t : t);
+      });
 }
 
 // ---- backward, the row tiles --------------------------------------------------------------------------------------------
@@ -217,195 +103,69 @@ __global__ __launch_bounds__(256, 2) void k_ffn_bwd_rows(const float* __restrict
                                                          const float* __restrict__ w2, int64_t N, int C, int Hd,
                                                          float* __restrict__ dx, int64_t dxs, float* __restrict__ da,
                                                          float* __restrict__ lnpart) {
-  constexpr int CT = 32 * NJ, XP = CT + 4, WP = CT + 16, NV = NJ > 2 ? NJ / 2 : 1;
-  constexpr int CQ = CT / 4, GROUPS = 256 / CQ, RPG = T / GROUPS;  // column sums: f4 columns, row groups, rows per group
-  static_assert(GROUPS * 2 * CT <= T * kPitchG, "the column partials live in the chunk image");
+  constexpr int CT = 32 * NJ, XP = CT + 4;
   __shared__ __attribute__((aligned(16))) float Ds[T * XP];                    // dt, then dxn: rows x channels
   __shared__ __attribute__((aligned(16))) float Gs[T * kPitchG];               // da of one chunk; then the column partials
-  __shared__ __attribute__((aligned(16))) float Ws[KC * ((CT > T ? CT : T) + 16)];  // a slice of W2 (kPitchT), then of W1 (WP)
+  __shared__ __attribute__((aligned(16))) float Ws[KC * ((CT > T ? CT : T) + 16)];  // a slice of W2, then of W1
   __shared__ float sMean[T], sRstd[T];
   const int tid = threadIdx.x;
   const WaveTile g;
-  const int wcn = (g.wc >> 5) * 16 * NJ;
   const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC, c4 = Cr >> 2;
+  const int Cr = (C + KC - 1) / KC * KC;
 
   if (tid < T) {
     const bool live = row0 + tid < N;
     sMean[tid] = live ? mean[row0 + tid] : 0.0f;
     sRstd[tid] = live ? rstd[row0 + tid] : 0.0f;
   }
-  for (int e = tid; e < T * c4; e += 256) {
-    const int r = e / c4, c = 4 * (e % c4);
+  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
     f4 v = zero4();
     if (row0 + r < N && c < C) {
       v = ld4(dy + (row0 + r) * dys + c);
       if (s) v = v * s[row0 + r];
     }
-    *reinterpret_cast<f4*>(&Ds[r * XP + c]) = v;
-  }
-  // (ordered before the fragment reads by the first __syncthreads of the slice loop)
+    return v;
+  });
 
-  const int br = tid >> 4, bc = 4 * (tid & 15);  // W2 slice: channel row tid / 16, four hidden features at 4 * (tid % 16)
-  f4 vb, vw[NV];
-  auto fetch2 = [&](int h0, int c0) {
-    const int c = c0 + br, h = h0 + bc;
-    vb = (c < C && h < Hd) ? ld4(w2 + (int64_t)c * Hd + h) : zero4();
-  };
-  auto fetch1 = [&](int h0, int k0) {  // W1 slice: hidden row e / CQ, four channels at 4 * (e % CQ)
-#pragma unroll
-    for (int u = 0; u < NV; u++) {
-      const int e = tid + 256 * u, h = h0 + k0 + e / CQ, c = 4 * (e % CQ);
-      vw[u] = (e < KC * CQ && h < Hd && c < C) ? ld4(w1 + (int64_t)h * C + c) : zero4();
-    }
-  };
-
+  Chain<2, true> back2;   // dg = dt W2: 64 hidden features of the chunk, summed over the channels
+  Chain<NJ, true> back1;  // dxn = da W1: the channels, summed over the chunk's hidden features
   f4 xacc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) xacc[i][j] = zero4();
-
+  clear_acc(xacc);
   for (int h0 = 0; h0 < Hd; h0 += FH) {
+    auto w2_at = [&](int hl, int c) { return (c < C && h0 + hl < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + hl) : zero4(); };
+    auto w1_at = [&](int c, int k) { return (h0 + k < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + k) * C + c) : zero4(); };
     f4 acc[2][2];
     clear_acc(acc);
-    fetch2(h0, 0);
-    for (int c0 = 0; c0 < Cr; c0 += KC) {
-      *reinterpret_cast<f4*>(&Ws[br * kPitchT + bc]) = vb;
-      __syncthreads();
-      if (c0 + KC < Cr) fetch2(h0, c0 + KC);
-      else fetch1(h0, 0);
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        float fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i] = Ds[(g.wr + 16 * i + g.fl) * XP + c0 + kk + g.fk];
-#pragma unroll
-        for (int j = 0; j < 2; j++) fb[j] = Ws[(kk + g.fk) * kPitchT + g.wc + 16 * j + g.fl];
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    back2.first(w2_at);
+    back2.run(acc, g, Ds, XP, Cr, Ws, w2_at, [&]() { back1.first(w1_at); });
+    for_each_output(acc, g, [&](int rl, int hl, float v) {
+      const int64_t row = row0 + rl;
+      const int h = h0 + hl;
+      float dv = 0.0f;
+      if (h < Hd && row < N) {
+        dv = v * gelu_grad_f(a[row * Hd + h]);
+        da[row * Hd + h] = dv;
       }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) {
-        const int rl = g.wr + 16 * i + 4 * g.fk + v;
-        const int64_t row = row0 + rl;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          const int hl = g.wc + 16 * j + g.fl, h = h0 + hl;
-          float dv = 0.0f;
-          if (h < Hd && row < N) {
-            dv = acc[i][j][v] * gelu_grad_f(a[row * Hd + h]);
-            da[row * Hd + h] = dv;
-          }
-          Gs[rl * kPitchG + hl] = dv;
-        }
-      }
+      Gs[rl * kPitchG + hl] = dv;
+    });
     const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
     f4 tacc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) tacc[i][j] = zero4();
-    for (int k0 = 0; k0 < kend; k0 += KC) {
-#pragma unroll
-      for (int u = 0; u < NV; u++) {
-        const int e = tid + 256 * u;
-        if (e < KC * CQ) *reinterpret_cast<f4*>(&Ws[(e / CQ) * WP + 4 * (e % CQ)]) = vw[u];
-      }
-      __syncthreads();
-      if (k0 + KC < kend) fetch1(h0, k0 + KC);
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        float fa[2], fb[NJ];
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i] = Gs[(g.wr + 16 * i + g.fl) * kPitchG + k0 + kk + g.fk];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) fb[j] = Ws[(kk + g.fk) * WP + wcn + 16 * j + g.fl];
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < NJ; j++) tacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], tacc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) xacc[i][j] = xacc[i][j] + tacc[i][j];
+    clear_acc(tacc);
+    back1.run(tacc, g, Gs, kPitchG, kend, Ws, w1_at);
+    add_acc(xacc, tacc);
   }
 
-  // dxn over dt's image (its last fragment read is behind the __syncthreads that closed the last chain over C)
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int rl = g.wr + 16 * i + 4 * g.fk + v;
-#pragma unroll
-      for (int j = 0; j < NJ; j++) Ds[rl * XP + wcn + 16 * j + g.fl] = xacc[i][j][v];
-    }
+  for_each_output(xacc, g, [&](int rl, int c, float v) { Ds[rl * XP + c] = v; });  // dxn over dt's image
   __syncthreads();
 
-  if (dx) {  // LayerNorm backward: lane q of a row owns the elements 4 q + 16 k .. + 3
+  if (dx) {  // LayerNorm backward
     const int r = tid >> 2, q = tid & 3;
     const int64_t row = row0 + r;
-    const bool live = row < N;
-    const float mu = sMean[r], rs = sRstd[r];
-    f4 xh[2 * NJ], wd[2 * NJ];
-    float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 2 * NJ; k++) {
-      const int c = 4 * q + 16 * k;
-      xh[k] = zero4();
-      wd[k] = zero4();
-      if (live && c < C) {
-        xh[k] = (ld4(x + row * xs + c) - mu) * rs;
-        wd[k] = *reinterpret_cast<const f4*>(&Ds[r * XP + c]) * ld4(lnw + c);
-        s1 = sum4(s1, wd[k]);
-        s2 = sum4(s2, wd[k] * xh[k]);
-      }
-    }
-    const float c1 = quad_sum(s1) / (float)C, c2 = quad_sum(s2) / (float)C;
-#pragma unroll
-    for (int k = 0; k < 2 * NJ; k++) {
-      const int c = 4 * q + 16 * k;
-      if (live && c < C)
-        *reinterpret_cast<f4*>(dx + row * dxs + c) = ld4(dy + row * dys + c) + (wd[k] - c1 - xh[k] * c2) * rs;
-    }
+    ln_rows_backward<NJ>(
+        &Ds[r * XP], q, C, row < N, {sMean[r], sRstd[r]}, lnw, [&](int c) { return ld4(x + row * xs + c); },
+        [&](int c, f4 v) { st4(dx + row * dxs + c, ld4(dy + row * dys + c) + v); }, [](int) {});
   }
-  if (!lnpart) return;
-
-  {  // the tile's column sums: thread (row group, f4 column) sums its RPG rows in order, then the groups in order
-    const int cq = tid % CQ, grp = tid / CQ, c = 4 * cq;
-    f4 pg = zero4(), pb = zero4();
-    if (c < C) {
-#pragma unroll
-      for (int k = 0; k < RPG; k++) {
-        const int r = grp * RPG + k;
-        if (row0 + r >= N) break;
-        const f4 d = *reinterpret_cast<const f4*>(&Ds[r * XP + c]);
-        const f4 h = (ld4(x + (row0 + r) * xs + c) - sMean[r]) * sRstd[r];
-        pg = pg + d * h;
-        pb = pb + d;
-      }
-    }
-    *reinterpret_cast<f4*>(&Gs[(grp * 2 + 0) * CT + c]) = pg;
-    *reinterpret_cast<f4*>(&Gs[(grp * 2 + 1) * CT + c]) = pb;
-  }
-  __syncthreads();
-  if (tid < 2 * CT) {
-    const int which = tid / CT, c = tid % CT;
-    if (c < C) {
-      float v = Gs[which * CT + c];
-      for (int grp = 1; grp < GROUPS; grp++) v += Gs[(grp * 2 + which) * CT + c];
-      lnpart[((int64_t)blockIdx.x * 2 + which) * C + c] = v;
-    }
-  }
+  if (lnpart) ln_col_sums<CT>(Ds, x, xs, sMean, sRstd, row0, N, C, Gs, lnpart + (int64_t)blockIdx.x * 2 * C);
 }
 
 // ---- backward, the two weight gradients ---------------------------------------------------------------------------------
@@ -435,21 +195,16 @@ __device__ __forceinline__ void dw_slice_tile(Fetch fetch_row, int Od, int I, in
   clear_acc(tot);
   float bsum = 0.0f, btot = 0.0f;
   auto flush = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        tot[i][j] = tot[i][j] + acc[i][j];
-        acc[i][j] = zero4();
-      }
+    add_acc(tot, acc);
+    clear_acc(acc);
     btot += bsum;
     bsum = 0.0f;
   };
   fetch(p0);
   for (int64_t p = p0; p < p1; p += KC) {
     if (p != p0 && (p - p0) % kFfnSumRows == 0) flush();
-    *reinterpret_cast<f4*>(&Ds[sp * kPitchT + sc]) = vd;
-    *reinterpret_cast<f4*>(&Xs[sp * kPitchT + sc]) = vx;
+    st4(&Ds[sp * kPitchT + sc], vd);
+    st4(&Xs[sp * kPitchT + sc], vx);
     __syncthreads();
     if (p + KC < p1) fetch(p + KC);
 #pragma unroll
@@ -477,18 +232,9 @@ __device__ __forceinline__ void dw_slice_tile(Fetch fetch_row, int Od, int I, in
     __syncthreads();
   }
   flush();
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int o = o0 + g.wr + 16 * i + 4 * g.fk + v;
-      if (o >= Od) continue;
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        const int c = i0 + g.wc + 16 * j + g.fl;
-        if (c < I) dst[(int64_t)o * I + c] = tot[i][j][v];
-      }
-    }
+  for_each_output(tot, g, [&](int ol, int cl, float v) {
+    if (o0 + ol < Od && i0 + cl < I) dst[(int64_t)(o0 + ol) * I + i0 + cl] = v;
+  });
   if (i0 == 0 && tid < T && o0 + tid < Od) bias[o0 + tid] = btot;
 }
 
@@ -568,28 +314,6 @@ __global__ void k_ffn_fold_params(const float* __restrict__ part, int S, int64_t
   *out = v[0];
 }
 
-// out[q][e] = sum of part[s][e] over the `per` records of group q (blockIdx.y), s ascending
-__global__ void k_ffn_fold_groups(const float* __restrict__ part, int64_t S, int len, int64_t per, float* __restrict__ out) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= len) return;
-  const int64_t s0 = blockIdx.y * per, s1 = s0 + per < S ? s0 + per : S;
-  float v = 0.0f;
-  for (int64_t s = s0; s < s1; s++) v += part[s * len + e];
-  out[(int64_t)blockIdx.y * len + e] = v;
-}
-
-// dgamma, dbeta: the records [2][C] in order
-__global__ void k_ffn_fold_ln(const float* __restrict__ part, int64_t S, int C, float* __restrict__ dlnw,
-                              float* __restrict__ dlnb) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= 2 * C) return;
-  float* out = e < C ? (dlnw ? dlnw + e : nullptr) : (dlnb ? dlnb + (e - C) : nullptr);
-  if (!out) return;
-  float v = part[e];
-  for (int64_t s = 1; s < S; s++) v += part[s * 2 * C + e];
-  *out = v;
-}
-
 // ---- host: the plan and the launches ------------------------------------------------------------------------------------
 struct FfnPlan {
   int64_t tiles;   // row tiles
@@ -601,36 +325,15 @@ struct FfnPlan {
 FfnPlan ffn_plan(int64_t N, int32_t C, int32_t Hd) {
   FfnPlan p;
   p.tiles = (N + T - 1) / T;
-  p.groups = p.tiles > kFfnFoldTiles ? std::min<int64_t>(256, (p.tiles + kFfnFoldTiles - 1) / kFfnFoldTiles) : 0;
-  p.gper = p.groups ? (p.tiles + p.groups - 1) / p.groups : 0;
-  const int64_t wt = (int64_t)((Hd + T - 1) / T) * ((C + T - 1) / T);
-  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(kFfnMaxSlices, 1024 / wt));
-  p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 63) / 64));
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 255) / 256 * 256;
-    return at;
-  };
-  p.da = take((size_t)N * Hd * 4);
-  p.lnpart = take((size_t)p.tiles * 2 * C * 4);
-  p.lngroup = take((size_t)p.groups * 2 * C * 4);
-  p.wpart = take((size_t)p.sw * (size_t)ffn_record(C, Hd) * 4);
-  p.total = off;
+  fold_groups(p.tiles, p.groups, p.gper);
+  p.sw = weight_slices((int64_t)((Hd + T - 1) / T) * ((C + T - 1) / T), N);
+  Carve ws;
+  p.da = ws.take((size_t)N * Hd * 4);
+  p.lnpart = ws.take((size_t)p.tiles * 2 * C * 4);
+  p.lngroup = ws.take((size_t)p.groups * 2 * C * 4);
+  p.wpart = ws.take((size_t)p.sw * (size_t)ffn_record(C, Hd) * 4);
+  p.total = ws.off;
   return p;
-}
-
-template <typename... A>
-void ffn_launch_forward(int C, dim3 grid, hipStream_t st, A... args) {
-  if (C <= 32) k_ffn_forward<1><<<grid, 256, 0, st>>>(args...);
-  else if (C <= 64) k_ffn_forward<2><<<grid, 256, 0, st>>>(args...);
-  else k_ffn_forward<4><<<grid, 256, 0, st>>>(args...);
-}
-template <typename... A>
-void ffn_launch_bwd_rows(int C, dim3 grid, hipStream_t st, A... args) {
-  if (C <= 32) k_ffn_bwd_rows<1><<<grid, 256, 0, st>>>(args...);
-  else if (C <= 64) k_ffn_bwd_rows<2><<<grid, 256, 0, st>>>(args...);
-  else k_ffn_bwd_rows<4><<<grid, 256, 0, st>>>(args...);
 }
 
 }  // namespace

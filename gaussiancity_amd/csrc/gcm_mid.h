@@ -1,8 +1,8 @@
 // gcm_mid.h -- the middle of a PTv3 Block around its attention (gcm_mid_*, include/gcm.h): the gather of the projected rows
 // into patch order, and, after the attention, the scatter back to point order, the output projection, DropPath and the
 // residual add in ONE launch; the deterministic backward of both in two or three launches whatever N is.  Included by
-// gcm_modlinear.hip after gcm_front.h, whose forward shape, slice images and row-sliced weight gradient it uses; device
-// code and launch helpers only, the C ABI stays in gcm_modlinear.hip.  DESIGN.md section 20.
+// gcm_modlinear.hip after gcm_tile.h (the tile and the product loop) and gcm_ffn.h (the row-sliced weight gradient); device
+// code and the plan only, the C ABI stays in gcm_modlinear.hip.  DESIGN.md section 20.
 //
 // The two index vectors: order [T] (slot -> row, T >= N, one entry per padded slot) and inverse [N] (row -> its own slot),
 // with order[inverse[n]] == n.  A slot j with inverse[order[j]] != j is a duplicate slot; a row has at most one, extra[n]
@@ -66,85 +66,43 @@ __global__ __launch_bounds__(256) void k_mid_gather_backward(const float* __rest
 }
 
 // ---- forward --------------------------------------------------------------------------------------------------------------
-// k_front_forward's shape: 256 threads own T = 64 rows, CT = 32 NJ channels, the same two LDS images.
+// 256 threads own T = 64 rows and CT = 32 NJ channels.
 template <int NJ>
 __global__ __launch_bounds__(256, 2) void k_mid_forward(const float* __restrict__ a, int64_t as, const int64_t* __restrict__ inverse,
                                                         const float* __restrict__ x, int64_t xs, const float* __restrict__ wp,
                                                         const float* __restrict__ bp, const float* __restrict__ rscale,
                                                         int64_t N, int C, float* __restrict__ y, int64_t ys) {
-  constexpr int CT = 32 * NJ, XP = CT + 4, NV = NJ > 2 ? NJ / 2 : 1;
+  constexpr int CT = 32 * NJ, XP = CT + 4;
   __shared__ __attribute__((aligned(16))) float Xs[T * XP];                      // a[inverse]: rows x channels
   __shared__ __attribute__((aligned(16))) float Ws[(CT > T ? CT : T) * kPitch];  // a 16-deep slice of Wp
-  const int tid = threadIdx.x;
   const WaveTile g;
-  const int wcn = (g.wc >> 5) * 16 * NJ;  // the wave's first output channel
   const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC, c4 = Cr >> 2;
+  const int Cr = (C + KC - 1) / KC * KC;
 
-  for (int e = tid; e < T * c4; e += 256) {
-    const int r = e / c4, c = 4 * (e % c4);
+  stage_rows(Xs, XP, Cr >> 2, [&](int r, int c) {
     f4 v = zero4();
     if (row0 + r < N && c < C) {
       const int64_t j = inverse[row0 + r];
       if (j >= 0) v = ld4(a + j * as + c);
     }
-    *reinterpret_cast<f4*>(&Xs[r * XP + c]) = v;
-  }
-  // (ordered before the fragment reads by the first __syncthreads of the slice loop)
+    return v;
+  });
 
-  f4 vw[NV];
-  auto fetch = [&](int k0) {  // Wp slice: output channel row e / 4, four input channels at 4 * (e % 4)
-#pragma unroll
-    for (int u = 0; u < NV; u++) {
-      const int e = tid + 256 * u, c = e >> 2, k = k0 + 4 * (e & 3);
-      vw[u] = (e < 4 * CT && c < C && k < C) ? ld4(wp + (int64_t)c * C + k) : zero4();
-    }
-  };
+  Chain<NJ, false> proj;  // p = a Wp^T
+  auto wp_at = [&](int c, int k) { return (c < C && k < C) ? ld4(wp + (int64_t)c * C + k) : zero4(); };
   f4 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) acc[i][j] = zero4();
-  fetch(0);
-  for (int k0 = 0; k0 < Cr; k0 += KC) {
-#pragma unroll
-    for (int u = 0; u < NV; u++) {
-      const int e = tid + 256 * u;
-      if (e < 4 * CT) *reinterpret_cast<f4*>(&Ws[(e >> 2) * kPitch + 4 * (e & 3)]) = vw[u];
-    }
-    __syncthreads();
-    if (k0 + KC < Cr) fetch(k0 + KC);
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += 4) {
-      float fa[2], fb[NJ];
-#pragma unroll
-      for (int i = 0; i < 2; i++) fa[i] = Xs[(g.wr + 16 * i + g.fl) * XP + k0 + kk + g.fk];
-#pragma unroll
-      for (int j = 0; j < NJ; j++) fb[j] = Ws[(wcn + 16 * j + g.fl) * kPitch + kk + g.fk];
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  clear_acc(acc);
+  proj.first(wp_at);
+  proj.run(acc, g, Xs, XP, Cr, Ws, wp_at);
 
   // p = chain + bp; y = x + p, or x + (p r): a multiply, then an add (the file is built without contraction)
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int64_t row = row0 + g.wr + 16 * i + 4 * g.fk + v;
-      if (row >= N) continue;
-      const float sr = rscale ? rscale[row] : 1.0f;
-#pragma unroll
-      for (int j = 0; j < NJ; j++) {
-        const int c = wcn + 16 * j + g.fl;
-        if (c >= C) continue;
-        const float p = acc[i][j][v] + bp[c];
-        y[row * ys + c] = x[row * xs + c] + (rscale ? p * sr : p);
-      }
-    }
+  for_each_output(
+      acc, g, [&](int rl) { return scaled_row(row0 + rl, N, rscale); },
+      [&](ScaledRow r, int c, float v) {
+        if (r.row < 0 || c >= C) return;
+        const float p = v + bp[c];
+        y[r.row * ys + c] = x[r.row * xs + c] + (rscale ? p * r.scale : p);
+      });
 }
 
 // ---- backward, the row tiles --------------------------------------------------------------------------------------------
@@ -155,24 +113,22 @@ __global__ __launch_bounds__(256, 2) void k_mid_bwd_rows(const float* __restrict
                                                          const int32_t* __restrict__ extra, const float* __restrict__ wp,
                                                          const float* __restrict__ rscale, int64_t N, int64_t Tn, int C,
                                                          float* __restrict__ da) {
-  constexpr int CT = 32 * NJ, XP = CT + 4, WP = CT + 16, NV = NJ > 2 ? NJ / 2 : 1, CQ = CT / 4;
-  __shared__ __attribute__((aligned(16))) float Ds[T * XP];   // g = r o dy: rows x channels
-  __shared__ __attribute__((aligned(16))) float Ws[KC * WP];  // a 16-deep slice of Wp: summed index in rows
+  constexpr int CT = 32 * NJ, XP = CT + 4;
+  __shared__ __attribute__((aligned(16))) float Ds[T * XP];                   // g = r o dy: rows x channels
+  __shared__ __attribute__((aligned(16))) float Ws[Chain<NJ, true>::kWords];  // a 16-deep slice of Wp
   const int tid = threadIdx.x;
   const WaveTile g;
-  const int wcn = (g.wc >> 5) * 16 * NJ;
   const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC, c4 = Cr >> 2;
+  const int Cr = (C + KC - 1) / KC * KC;
 
-  for (int e = tid; e < T * c4; e += 256) {
-    const int r = e / c4, c = 4 * (e % c4);
+  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
     f4 v = zero4();
     if (row0 + r < N && c < C) {
       v = ld4(dy + (row0 + r) * dys + c);
       if (rscale) v = v * rscale[row0 + r];
     }
-    *reinterpret_cast<f4*>(&Ds[r * XP + c]) = v;
-  }
+    return v;
+  });
   {  // the duplicate slots of the tile's rows: exact zeros, four lanes per row
     const int r = tid >> 2, q = tid & 3;
     if (row0 + r < N) {
@@ -182,56 +138,22 @@ __global__ __launch_bounds__(256, 2) void k_mid_bwd_rows(const float* __restrict
     }
   }
 
-  f4 vw[NV];
-  auto fetchw = [&](int k0) {  // slice of Wp [C][C]: row k0 + e / CQ, four channels
-#pragma unroll
-    for (int u = 0; u < NV; u++) {
-      const int e = tid + 256 * u, o = k0 + e / CQ, c = 4 * (e % CQ);
-      vw[u] = (e < KC * CQ && o < C && c < C) ? ld4(wp + (int64_t)o * C + c) : zero4();
-    }
-  };
+  Chain<NJ, true> back;  // da = g Wp
+  auto wp_at = [&](int c, int k) { return (k < C && c < C) ? ld4(wp + (int64_t)k * C + c) : zero4(); };
   f4 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) acc[i][j] = zero4();
-  fetchw(0);
-  for (int k0 = 0; k0 < Cr; k0 += KC) {
-#pragma unroll
-    for (int u = 0; u < NV; u++) {
-      const int e = tid + 256 * u;
-      if (e < KC * CQ) *reinterpret_cast<f4*>(&Ws[(e / CQ) * WP + 4 * (e % CQ)]) = vw[u];
-    }
-    __syncthreads();
-    if (k0 + KC < Cr) fetchw(k0 + KC);
-#pragma unroll
-    for (int kk = 0; kk < KC; kk += 4) {
-      float fa[2], fb[NJ];
-#pragma unroll
-      for (int i = 0; i < 2; i++) fa[i] = Ds[(g.wr + 16 * i + g.fl) * XP + k0 + kk + g.fk];
-#pragma unroll
-      for (int j = 0; j < NJ; j++) fb[j] = Ws[(kk + g.fk) * WP + wcn + 16 * j + g.fl];
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int64_t row = row0 + g.wr + 16 * i + 4 * g.fk + v;
-      if (row >= N) continue;
-      const int64_t slot = inverse[row];
-      if (slot < 0 || slot >= Tn) continue;
-#pragma unroll
-      for (int j = 0; j < NJ; j++) {
-        const int c = wcn + 16 * j + g.fl;
-        if (c < C) da[slot * C + c] = acc[i][j][v];
-      }
-    }
+  clear_acc(acc);
+  back.first(wp_at);
+  back.run(acc, g, Ds, XP, Cr, Ws, wp_at);
+  for_each_output(
+      acc, g,
+      [&](int rl) -> int64_t {  // the row's slot, -1 without one
+        if (row0 + rl >= N) return -1;
+        const int64_t slot = inverse[row0 + rl];
+        return slot < Tn ? slot : -1;
+      },
+      [&](int64_t slot, int c, float v) {
+        if (slot >= 0 && c < C) da[slot * C + c] = v;
+      });
 }
 
 // ---- backward, the weight gradient ----------------------------------------------------------------------------------------
@@ -262,7 +184,7 @@ __global__ __launch_bounds__(256) void k_mid_dw(const float* __restrict__ a, int
   dw_slice_tile(fetch, C, C, o0, i0, p0, p1, rec, rec + (int64_t)C * C, Ds, Xs);
 }
 
-// ---- host: the plan and the launches ------------------------------------------------------------------------------------
+// ---- host: the plan ------------------------------------------------------------------------------------
 struct MidPlan {
   int64_t tiles;  // row tiles
   int sw;         // row slices of the weight gradient
@@ -273,23 +195,9 @@ MidPlan mid_plan(int64_t N, int32_t C) {
   MidPlan p;
   p.tiles = (N + T - 1) / T;
   p.wt = (unsigned)((C + T - 1) / T) * (unsigned)((C + T - 1) / T);
-  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(kFfnMaxSlices, 1024 / p.wt));
-  p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 63) / 64));
-  p.total = ((size_t)p.sw * (size_t)mid_record(C) * 4 + 255) / 256 * 256;
+  p.sw = weight_slices(p.wt, N);
+  p.total = round256((size_t)p.sw * (size_t)mid_record(C) * 4);
   return p;
-}
-
-template <typename... A>
-void mid_launch_forward(int C, dim3 grid, hipStream_t st, A... args) {
-  if (C <= 32) k_mid_forward<1><<<grid, 256, 0, st>>>(args...);
-  else if (C <= 64) k_mid_forward<2><<<grid, 256, 0, st>>>(args...);
-  else k_mid_forward<4><<<grid, 256, 0, st>>>(args...);
-}
-template <typename... A>
-void mid_launch_bwd_rows(int C, dim3 grid, hipStream_t st, A... args) {
-  if (C <= 32) k_mid_bwd_rows<1><<<grid, 256, 0, st>>>(args...);
-  else if (C <= 64) k_mid_bwd_rows<2><<<grid, 256, 0, st>>>(args...);
-  else k_mid_bwd_rows<4><<<grid, 256, 0, st>>>(args...);
 }
 
 }  // namespace

@@ -28,32 +28,27 @@
 // patch gather, and the scatter back, the output projection, DropPath and the residual in one launch), is gcm_mid.h.
 // DESIGN.md section 20.  The fifth, the seams between the backbone's stages (gcm_seam_*: Linear, BatchNorm1d and GELU as
 // one operator up to 512 channels), is gcm_seam.h, included last.  DESIGN.md section 21.
+// What the five share -- the 64-row tile, the product loop of the four fused operators, the host rules of the plans -- is
+// gcm_tile.h, included first.  DESIGN.md section 17a.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/gcm.h"
 #define GC_ERR_HIP GCM_ERR_HIP
 #include "gc_host.h"
+#include "gcm_tile.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int KC = 16;            // depth of a staged slice
-constexpr int T = 64;             // workgroup tile, both ways
-constexpr int kPitch = KC + 4;    // words between rows of an image that holds the summed index contiguously
-constexpr int kPitchT = T + 16;   // words between rows of an image that holds the summed index in rows
 constexpr int kSortRows = 256;    // rows per block of the counting sort
 constexpr int64_t kMaxRows = (int64_t)1 << 31;
 constexpr int kMaxFeatures = 65536;
 constexpr int kMaxGroups = 1 << 20;
-
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ f4 zero4() { return f4{0.0f, 0.0f, 0.0f, 0.0f}; }
 
 // group of a row: 0 without a group vector, -1 for a value outside 0 .. G-1
 __device__ __forceinline__ int32_t row_group(const int32_t* __restrict__ group, int64_t r, int G) {
@@ -68,24 +63,6 @@ __device__ __forceinline__ f4 dpre4(f4 dy, f4 y, float slope) {
 #pragma unroll
   for (int k = 0; k < 4; k++) r[k] = y[k] > 0.0f ? dy[k] : dy[k] * slope;
   return r;
-}
-
-struct WaveTile {  // wave (wr, wc): tile-relative corner of the wave's 32 x 32 outputs; (fl, fk): the lane in a fragment
-  int wr, wc, fl, fk;
-  __device__ __forceinline__ WaveTile() {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wr = (wave >> 1) * 32;
-    wc = (wave & 1) * 32;
-    fl = lane & 15;
-    fk = lane >> 4;
-  }
-};
-
-__device__ __forceinline__ void clear_acc(f4 (&acc)[2][2]) {
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++) acc[i][j] = zero4();
 }
 
 // ---- forward and dX -------------------------------------------------------------------------------------------------
@@ -448,8 +425,42 @@ __global__ __launch_bounds__(256) void k_head_out(const float* __restrict__ f, i
 // ---- host -------------------------------------------------------------------------------------------------------------
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool stride_ok(int64_t s, int width) { return s > 0 && s % 4 == 0 && s >= width; }
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+// The checks every entry point repeats, each with the one message it has always had.
+struct Stride {
+  int64_t s;
+  int width;
+  bool used = true;  // false: the tensor it belongs to was not passed
+};
+int check_strides(const std::string& w, std::initializer_list<Stride> strides) {
+  for (const Stride& x : strides)
+    if (x.used && !stride_ok(x.s, x.width))
+      return fail(GCM_ERR_INVALID_ARGUMENT, w + ": strides must be positive multiples of 4 elements, at least the row's width");
+  return 0;
+}
+int check_aligned16(const std::string& w, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": float pointers must be 16-byte aligned");
+  return 0;
+}
+int check_workspace(const std::string& w, const void* workspace, size_t bytes, size_t need, const char* sizer) {
+  if (bytes < need || !workspace) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": workspace smaller than " + sizer);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, w + ": workspace must be 256-byte aligned");
+  return 0;
+}
+// N == 0: the outputs that are sums over the rows are zeros; a null output is skipped
+struct Clear {
+  void* p;
+  size_t bytes;
+  const char* what;
+};
+int clear_outputs(hipStream_t st, std::initializer_list<Clear> outs) {
+  for (const Clear& c : outs)
+    if (c.p) HIP_TRY(hipMemsetAsync(c.p, 0, c.bytes, st), c.what);
+  return GCM_OK;
+}
 
 int check_shape(const std::string& w, int64_t N, int32_t I, int32_t O, int32_t G) {
   if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
@@ -479,19 +490,14 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
   p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 127) / 128));
   p.sg = (int)std::max<int64_t>(1, std::min<int64_t>(256, (N + 64 * (int64_t)G - 1) / (64 * (int64_t)G)));
   p.nb = (N + kSortRows - 1) / kSortRows;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += round256(bytes);
-    return at;
-  };
-  p.t = take((size_t)N * I * 4);
-  p.wpart = take(p.sw > 1 ? (size_t)p.sw * O * I * 4 : 0);
-  p.cnt = take((size_t)p.nb * G * 4);
-  p.start = take(((size_t)G + 1) * 4);
-  p.perm = take((size_t)N * 4);
-  p.gpart = take((size_t)p.sg * G * ((size_t)I + O) * 4);
-  p.total = off;
+  Carve ws;
+  p.t = ws.take((size_t)N * I * 4);
+  p.wpart = ws.take(p.sw > 1 ? (size_t)p.sw * O * I * 4 : 0);
+  p.cnt = ws.take((size_t)p.nb * G * 4);
+  p.start = ws.take(((size_t)G + 1) * 4);
+  p.perm = ws.take((size_t)N * 4);
+  p.gpart = ws.take((size_t)p.sg * G * ((size_t)I + O) * 4);
+  p.total = ws.off;
   return p;
 }
 
@@ -534,7 +540,6 @@ int check_mid_width(const std::string& w, int64_t rows, int32_t W) {
   if ((rows * (W / 4) + 255) / 256 >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": rows * W / 4 does not fit 39 bits");
   return 0;
 }
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 int check_seam_shape(const std::string& w, int64_t N, int32_t I, int32_t O, bool product) {
   if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
   if (I <= 0 || I % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": I must be a positive multiple of 4");
@@ -571,10 +576,8 @@ int gcm_modlinear_forward(const float* x, int64_t x_stride, const float* w, int6
   const std::string who("gcm_modlinear_forward");
   if (int rc = check_shape(who, N, I, O, G)) return rc;
   if (!std::isfinite(slope) || slope <= 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": slope must be finite and > 0");
-  if (!stride_ok(x_stride, I) || !stride_ok(w_stride, I) || !stride_ok(y_stride, O))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(w) || !aligned16(alpha) || !aligned16(beta) || !aligned16(bias) || !aligned16(y))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, I}, {w_stride, I}, {y_stride, O}})) return rc;
+  if (int rc = check_aligned16(who, {x, w, alpha, beta, bias, y})) return rc;
   if (N == 0) return GCM_OK;
   if (!x || !w || !y) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, w or y");
   const dim3 grid(blocks_for(N, T), blocks_for(O, T));
@@ -601,26 +604,18 @@ int gcm_modlinear_backward(const float* x, int64_t x_stride, const float* y, int
   if (int rc = check_shape(who, N, I, O, G)) return rc;
   if (int rc = check_sort(who, N, G)) return rc;
   if (!std::isfinite(slope) || slope <= 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": slope must be finite and > 0");
-  if (!stride_ok(x_stride, I) || !stride_ok(y_stride, O) || !stride_ok(dy_stride, O) || !stride_ok(w_stride, I) ||
-      (dx && !stride_ok(dx_stride, I)))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(y) || !aligned16(dy) || !aligned16(w) || !aligned16(alpha) || !aligned16(dx) ||
-      !aligned16(dw) || !aligned16(dalpha) || !aligned16(dbeta) || !aligned16(dbias))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, I}, {y_stride, O}, {dy_stride, O}, {w_stride, I}, {dx_stride, I, dx != nullptr}}))
+    return rc;
+  if (int rc = check_aligned16(who, {x, y, dy, w, alpha, dx, dw, dalpha, dbeta, dbias})) return rc;
   const BackwardPlan p = plan_backward(N, I, O, G);
-  if (workspace_bytes < p.total || (p.total && !workspace))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_modlinear_backward_workspace_bytes");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_modlinear_backward_workspace_bytes")) return rc;
   if (N > 0 && (!x || !y || !dy || !w)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, y, dy or w");
   hipStream_t st = (hipStream_t)hip_stream;
-  if (N == 0) {  // nothing to sum: the outputs that do not depend on N are zeros
-    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)O * I * 4, st), "backward clear dw");
-    if (dalpha) HIP_TRY(hipMemsetAsync(dalpha, 0, (size_t)G * I * 4, st), "backward clear dalpha");
-    if (dbeta) HIP_TRY(hipMemsetAsync(dbeta, 0, (size_t)G * O * 4, st), "backward clear dbeta");
-    if (dbias) HIP_TRY(hipMemsetAsync(dbias, 0, (size_t)O * 4, st), "backward clear dbias");
-    return GCM_OK;
-  }
+  if (N == 0)  // nothing to sum: the outputs that do not depend on N are zeros
+    return clear_outputs(st, {{dw, (size_t)O * I * 4, "backward clear dw"},
+                              {dalpha, (size_t)G * I * 4, "backward clear dalpha"},
+                              {dbeta, (size_t)G * O * 4, "backward clear dbeta"},
+                              {dbias, (size_t)O * 4, "backward clear dbias"}});
   char* ws = (char*)workspace;
   float* t = dalpha ? (float*)(ws + p.t) : nullptr;
   if (dx || t) {
@@ -630,7 +625,7 @@ int gcm_modlinear_backward(const float* x, int64_t x_stride, const float* y, int
     HIP_TRY(hipGetLastError(), "modlinear dx launch");
   }
   if (dw) {
-    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    const int64_t per = slice_rows(N, p.sw);
     float* part = p.sw > 1 ? (float*)(ws + p.wpart) : nullptr;
     const dim3 grid(blocks_for(O, T) * blocks_for(I, T), (unsigned)p.sw);
     k_modlinear_dw<<<grid, 256, 0, st>>>(x, x_stride, y, y_stride, dy, dy_stride, alpha, group, N, I, O, G, slope, per,
@@ -671,9 +666,8 @@ int gcm_head_out(const float* f, int64_t f_stride, const float* w_out, const flo
   if (kind != GCM_XYZ && kind != GCM_RGB && kind != GCM_SCALE && kind != GCM_OPACITY)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": unknown kind");
   if (!std::isfinite(factor)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": factor is not finite");
-  if (!stride_ok(f_stride, I))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(f) || !aligned16(w_out)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{f_stride, I}})) return rc;
+  if (int rc = check_aligned16(who, {f, w_out})) return rc;
   if (N == 0) return GCM_OK;
   if (!f || !w_out || !out) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null f, w_out or out");
   hipStream_t st = (hipStream_t)hip_stream;
@@ -691,18 +685,17 @@ int gcm_ffn_forward(const float* x, int64_t x_stride, const float* ln_w, const f
   const std::string who("gcm_ffn_forward");
   if (int rc = check_ffn_shape(who, N, C, Hd)) return rc;
   if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
-  if (!stride_ok(x_stride, C) || !stride_ok(y_stride, C))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(ln_w) || !aligned16(ln_b) || !aligned16(w1) || !aligned16(b1) || !aligned16(w2) ||
-      !aligned16(b2) || !aligned16(y) || !aligned16(a))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, C}, {y_stride, C}})) return rc;
+  if (int rc = check_aligned16(who, {x, ln_w, ln_b, w1, b1, w2, b2, y, a})) return rc;
   if (N == 0) return GCM_OK;
   if (!x || !ln_w || !ln_b || !w1 || !b1 || !w2 || !b2 || !y)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, ln_w, ln_b, w1, b1, w2, b2 or y");
   if ((mean == nullptr) != (rstd == nullptr) || (a && !mean))
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": mean and rstd come together, and a needs both");
-  ffn_launch_forward(C, dim3(blocks_for(N, T)), (hipStream_t)hip_stream, x, x_stride, ln_w, ln_b, eps, w1, b1, w2, b2, row_scale,
-                     N, (int)C, (int)Hd, y, y_stride, mean, rstd, a);
+  with_nj(C, [&](auto nj) {
+    k_ffn_forward<decltype(nj)::value><<<blocks_for(N, T), 256, 0, (hipStream_t)hip_stream>>>(
+        x, x_stride, ln_w, ln_b, eps, w1, b1, w2, b2, row_scale, N, C, Hd, y, y_stride, mean, rstd, a);
+  });
   HIP_TRY(hipGetLastError(), "ffn forward launch");
   return GCM_OK;
 }
@@ -720,53 +713,39 @@ int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const 
                      size_t workspace_bytes, void* hip_stream) {
   const std::string who("gcm_ffn_backward");
   if (int rc = check_ffn_shape(who, N, C, Hd)) return rc;
-  if (!stride_ok(x_stride, C) || !stride_ok(dy_stride, C) || (dx && !stride_ok(dx_stride, C)))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(a) || !aligned16(dy) || !aligned16(ln_w) || !aligned16(ln_b) || !aligned16(w1) ||
-      !aligned16(w2) || !aligned16(dx) || !aligned16(dln_w) || !aligned16(dln_b) || !aligned16(dw1) || !aligned16(db1) ||
-      !aligned16(dw2) || !aligned16(db2))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, C}, {dy_stride, C}, {dx_stride, C, dx != nullptr}})) return rc;
+  if (int rc = check_aligned16(who, {x, a, dy, ln_w, ln_b, w1, w2, dx, dln_w, dln_b, dw1, db1, dw2, db2})) return rc;
   const FfnPlan p = ffn_plan(N, C, Hd);
-  if (workspace_bytes < p.total || !workspace)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_ffn_backward_workspace_bytes");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_ffn_backward_workspace_bytes")) return rc;
   if (N > 0 && (!x || !mean || !rstd || !a || !dy || !ln_w || !ln_b || !w1 || !w2))
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, mean, rstd, a, dy, ln_w, ln_b, w1 or w2");
   hipStream_t st = (hipStream_t)hip_stream;
   if (N == 0) {  // nothing to sum: the parameter gradients are zeros
-    const size_t CH = (size_t)C * Hd * 4;
-    if (dln_w) HIP_TRY(hipMemsetAsync(dln_w, 0, (size_t)C * 4, st), "ffn backward clear dln_w");
-    if (dln_b) HIP_TRY(hipMemsetAsync(dln_b, 0, (size_t)C * 4, st), "ffn backward clear dln_b");
-    if (dw1) HIP_TRY(hipMemsetAsync(dw1, 0, CH, st), "ffn backward clear dw1");
-    if (db1) HIP_TRY(hipMemsetAsync(db1, 0, (size_t)Hd * 4, st), "ffn backward clear db1");
-    if (dw2) HIP_TRY(hipMemsetAsync(dw2, 0, CH, st), "ffn backward clear dw2");
-    if (db2) HIP_TRY(hipMemsetAsync(db2, 0, (size_t)C * 4, st), "ffn backward clear db2");
-    return GCM_OK;
+    const size_t CH = (size_t)C * Hd * 4, C4 = (size_t)C * 4;
+    return clear_outputs(st, {{dln_w, C4, "ffn backward clear dln_w"},
+                              {dln_b, C4, "ffn backward clear dln_b"},
+                              {dw1, CH, "ffn backward clear dw1"},
+                              {db1, (size_t)Hd * 4, "ffn backward clear db1"},
+                              {dw2, CH, "ffn backward clear dw2"},
+                              {db2, C4, "ffn backward clear db2"}});
   }
   char* ws = (char*)workspace;
   float* da = (float*)(ws + p.da);
   const bool ln = dln_w || dln_b, first = dw1 || db1, params = first || dw2 || db2;
   if (dx || ln || first) {
     float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
-    ffn_launch_bwd_rows(C, dim3((unsigned)p.tiles), st, x, x_stride, mean, rstd, a, dy, dy_stride, row_scale, ln_w, w1, w2, N,
-                        (int)C, (int)Hd, dx, dx_stride, da, lnpart);
+    with_nj(C, [&](auto nj) {
+      k_ffn_bwd_rows<decltype(nj)::value><<<(unsigned)p.tiles, 256, 0, st>>>(x, x_stride, mean, rstd, a, dy, dy_stride, row_scale,
+                                                                            ln_w, w1, w2, N, C, Hd, dx, dx_stride, da, lnpart);
+    });
     HIP_TRY(hipGetLastError(), "ffn backward rows launch");
     if (ln) {
-      const float* rec = lnpart;
-      int64_t count = p.tiles;
-      if (p.groups) {
-        float* grouped = (float*)(ws + p.lngroup);
-        k_ffn_fold_groups<<<dim3(blocks_for(2 * C, 256), (unsigned)p.groups), 256, 0, st>>>(lnpart, p.tiles, 2 * C, p.gper, grouped);
-        rec = grouped;
-        count = p.groups;
-      }
-      k_ffn_fold_ln<<<blocks_for(2 * C, 256), 256, 0, st>>>(rec, count, (int)C, dln_w, dln_b);
+      fold_ln_partials(lnpart, (float*)(ws + p.lngroup), p.tiles, p.groups, p.gper, 2, C, dln_w, dln_b, nullptr, nullptr, st);
       HIP_TRY(hipGetLastError(), "ffn backward LayerNorm fold launch");
     }
   }
   if (params) {
-    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    const int64_t per = slice_rows(N, p.sw);
     float* part = (float*)(ws + p.wpart);
     const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
     k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
@@ -789,21 +768,19 @@ int gcm_front_forward(const float* x, int64_t x_stride, const float* s, int64_t 
   if (int rc = check_front_shape(who, N, C, O)) return rc;
   if (!std::isfinite(eps_c) || eps_c < 0.0f || !std::isfinite(eps_1) || eps_1 < 0.0f)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps_c and eps_1 must be finite and >= 0");
-  if (!stride_ok(x_stride, C) || !stride_ok(s_stride, C) || !stride_ok(feat_stride, C) || !stride_ok(qkv_stride, O))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(s) || !aligned16(wc) || !aligned16(bc) || !aligned16(lnc_w) || !aligned16(lnc_b) ||
-      !aligned16(ln1_w) || !aligned16(ln1_b) || !aligned16(wq) || !aligned16(bq) || !aligned16(feat) || !aligned16(qkv) ||
-      !aligned16(t))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, C}, {s_stride, C}, {feat_stride, C}, {qkv_stride, O}})) return rc;
+  if (int rc = check_aligned16(who, {x, s, wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq, feat, qkv, t})) return rc;
   if (N == 0) return GCM_OK;
   if (!x || !s || !wc || !bc || !lnc_w || !lnc_b || !ln1_w || !ln1_b || !wq || !bq || !feat || !qkv)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, s, wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq, feat or qkv");
   const int stats = (mean_c != nullptr) + (rstd_c != nullptr) + (mean_1 != nullptr) + (rstd_1 != nullptr);
   if ((stats != 0 && stats != 4) || (t != nullptr) != (stats == 4))
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": t and the four statistics come together, all or none");
-  front_launch_forward(C, dim3(blocks_for(N, T)), (hipStream_t)hip_stream, x, x_stride, s, s_stride, wc, bc, lnc_w, lnc_b, eps_c,
-                       ln1_w, ln1_b, eps_1, wq, bq, N, (int)C, (int)O, feat, feat_stride, qkv, qkv_stride, t, mean_c, rstd_c,
-                       mean_1, rstd_1);
+  with_nj(C, [&](auto nj) {
+    k_front_forward<decltype(nj)::value><<<blocks_for(N, T), 256, 0, (hipStream_t)hip_stream>>>(
+        x, x_stride, s, s_stride, wc, bc, lnc_w, lnc_b, eps_c, ln1_w, ln1_b, eps_1, wq, bq, N, C, O, feat, feat_stride, qkv,
+        qkv_stride, t, mean_c, rstd_c, mean_1, rstd_1);
+  });
   HIP_TRY(hipGetLastError(), "front forward launch");
   return GCM_OK;
 }
@@ -823,59 +800,48 @@ int gcm_front_backward(const float* s, int64_t s_stride, const float* feat, int6
                        size_t workspace_bytes, void* hip_stream) {
   const std::string who("gcm_front_backward");
   if (int rc = check_front_shape(who, N, C, O)) return rc;
-  if (!stride_ok(s_stride, C) || !stride_ok(feat_stride, C) || !stride_ok(dfeat_stride, C) || !stride_ok(dqkv_stride, O) ||
-      (dx && !stride_ok(dx_stride, C)) || (ds && !stride_ok(ds_stride, C)))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(s) || !aligned16(feat) || !aligned16(t) || !aligned16(dfeat) || !aligned16(dqkv) || !aligned16(wc) ||
-      !aligned16(lnc_w) || !aligned16(ln1_w) || !aligned16(ln1_b) || !aligned16(wq) || !aligned16(dx) || !aligned16(ds) ||
-      !aligned16(dwc) || !aligned16(dbc) || !aligned16(dlnc_w) || !aligned16(dlnc_b) || !aligned16(dln1_w) ||
-      !aligned16(dln1_b) || !aligned16(dwq) || !aligned16(dbq))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{s_stride, C}, {feat_stride, C}, {dfeat_stride, C}, {dqkv_stride, O},
+                                   {dx_stride, C, dx != nullptr}, {ds_stride, C, ds != nullptr}}))
+    return rc;
+  if (int rc = check_aligned16(who, {s,  feat, t,   dfeat, dqkv,   wc,     lnc_w,  ln1_w,  ln1_b, wq,
+                                     dx, ds,   dwc, dbc,   dlnc_w, dlnc_b, dln1_w, dln1_b, dwq,   dbq}))
+    return rc;
   const FrontPlan p = front_plan(N, C, O);
-  if (workspace_bytes < p.total || !workspace)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_front_backward_workspace_bytes");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_front_backward_workspace_bytes")) return rc;
   if (N > 0 && (!s || !feat || !t || !mean_c || !rstd_c || !mean_1 || !rstd_1 || !dfeat || !dqkv || !wc || !lnc_w || !ln1_w ||
                 !ln1_b || !wq))
     return fail(GCM_ERR_INVALID_ARGUMENT,
                 who + ": null s, feat, t, mean_c, rstd_c, mean_1, rstd_1, dfeat, dqkv, wc, lnc_w, ln1_w, ln1_b or wq");
   hipStream_t st = (hipStream_t)hip_stream;
   if (N == 0) {  // nothing to sum: the parameter gradients are zeros
-    if (dwc) HIP_TRY(hipMemsetAsync(dwc, 0, (size_t)C * C * 4, st), "front backward clear dwc");
-    if (dbc) HIP_TRY(hipMemsetAsync(dbc, 0, (size_t)C * 4, st), "front backward clear dbc");
-    if (dlnc_w) HIP_TRY(hipMemsetAsync(dlnc_w, 0, (size_t)C * 4, st), "front backward clear dlnc_w");
-    if (dlnc_b) HIP_TRY(hipMemsetAsync(dlnc_b, 0, (size_t)C * 4, st), "front backward clear dlnc_b");
-    if (dln1_w) HIP_TRY(hipMemsetAsync(dln1_w, 0, (size_t)C * 4, st), "front backward clear dln1_w");
-    if (dln1_b) HIP_TRY(hipMemsetAsync(dln1_b, 0, (size_t)C * 4, st), "front backward clear dln1_b");
-    if (dwq) HIP_TRY(hipMemsetAsync(dwq, 0, (size_t)O * C * 4, st), "front backward clear dwq");
-    if (dbq) HIP_TRY(hipMemsetAsync(dbq, 0, (size_t)O * 4, st), "front backward clear dbq");
-    return GCM_OK;
+    const size_t C4 = (size_t)C * 4;
+    return clear_outputs(st, {{dwc, C4 * C, "front backward clear dwc"},
+                              {dbc, C4, "front backward clear dbc"},
+                              {dlnc_w, C4, "front backward clear dlnc_w"},
+                              {dlnc_b, C4, "front backward clear dlnc_b"},
+                              {dln1_w, C4, "front backward clear dln1_w"},
+                              {dln1_b, C4, "front backward clear dln1_b"},
+                              {dwq, C4 * O, "front backward clear dwq"},
+                              {dbq, (size_t)O * 4, "front backward clear dbq"}});
   }
   char* ws = (char*)workspace;
   float* dt = (float*)(ws + p.dt);
   const bool ln = dln1_w || dln1_b || dlnc_w || dlnc_b, conv = dwc || dbc, proj = dwq || dbq;
   if (dx || ds || ln || conv) {
     float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
-    front_launch_bwd_rows(C, dim3((unsigned)p.tiles), st, feat, feat_stride, t, mean_c, rstd_c, mean_1, rstd_1, dfeat,
-                          dfeat_stride, dqkv, dqkv_stride, wc, lnc_w, ln1_w, wq, N, (int)C, (int)O, dx, dx_stride, ds, ds_stride,
-                          dt, lnpart);
+    with_nj(C, [&](auto nj) {
+      k_front_bwd_rows<decltype(nj)::value><<<(unsigned)p.tiles, 256, 0, st>>>(
+          feat, feat_stride, t, mean_c, rstd_c, mean_1, rstd_1, dfeat, dfeat_stride, dqkv, dqkv_stride, wc, lnc_w, ln1_w, wq, N,
+          C, O, dx, dx_stride, ds, ds_stride, dt, lnpart);
+    });
     HIP_TRY(hipGetLastError(), "front backward rows launch");
     if (ln) {
-      const float* rec = lnpart;
-      int64_t count = p.tiles;
-      if (p.groups) {
-        float* grouped = (float*)(ws + p.lngroup);
-        k_ffn_fold_groups<<<dim3(blocks_for(4 * C, 256), (unsigned)p.groups), 256, 0, st>>>(lnpart, p.tiles, 4 * C, p.gper, grouped);
-        rec = grouped;
-        count = p.groups;
-      }
-      k_front_fold_ln<<<blocks_for(4 * C, 256), 256, 0, st>>>(rec, count, (int)C, dln1_w, dln1_b, dlnc_w, dlnc_b);
+      fold_ln_partials(lnpart, (float*)(ws + p.lngroup), p.tiles, p.groups, p.gper, 4, C, dln1_w, dln1_b, dlnc_w, dlnc_b, st);
       HIP_TRY(hipGetLastError(), "front backward LayerNorm fold launch");
     }
   }
   if (conv || proj) {
-    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    const int64_t per = slice_rows(N, p.sw);
     float* part = (float*)(ws + p.wpart);
     const dim3 grid(p.wt, (unsigned)p.sw, (conv ? 1u : 0u) + (proj ? 1u : 0u));
     k_front_dw<<<grid, 256, 0, st>>>(s, s_stride, feat, feat_stride, mean_1, rstd_1, ln1_w, ln1_b, dqkv, dqkv_stride, dt, N,
@@ -911,9 +877,8 @@ int gcm_mid_gather_forward(const float* x, int64_t x_stride, const int64_t* orde
   const std::string who("gcm_mid_gather_forward");
   if (T_slots < 0 || T_slots >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T out of range");
   if (int rc = check_mid_width(who, T_slots, W)) return rc;
-  if (!stride_ok(x_stride, W))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(y)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, W}})) return rc;
+  if (int rc = check_aligned16(who, {x, y})) return rc;
   if (!aligned8(order)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": order must be 8-byte aligned");
   if (T_slots == 0) return GCM_OK;
   if (!x || !order || !y) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, order or y");
@@ -928,9 +893,8 @@ int gcm_mid_gather_backward(const float* dy, int64_t dy_stride, const int64_t* i
   const std::string who("gcm_mid_gather_backward");
   if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": N out of range");
   if (int rc = check_mid_width(who, N, W)) return rc;
-  if (!stride_ok(dy_stride, W))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(dy) || !aligned16(dx)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{dy_stride, W}})) return rc;
+  if (int rc = check_aligned16(who, {dy, dx})) return rc;
   if (!aligned8(inverse) || (reinterpret_cast<uintptr_t>(extra) & 3u) != 0)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": inverse must be 8-byte aligned, extra 4-byte aligned");
   if (N == 0) return GCM_OK;
@@ -946,15 +910,15 @@ int gcm_mid_forward(const float* a, int64_t a_stride, const int64_t* inverse, co
                     int64_t y_stride, void* hip_stream) {
   const std::string who("gcm_mid_forward");
   if (int rc = check_mid_shape(who, N, C)) return rc;
-  if (!stride_ok(a_stride, C) || !stride_ok(x_stride, C) || !stride_ok(y_stride, C))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(a) || !aligned16(x) || !aligned16(wp) || !aligned16(bp) || !aligned16(y))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{a_stride, C}, {x_stride, C}, {y_stride, C}})) return rc;
+  if (int rc = check_aligned16(who, {a, x, wp, bp, y})) return rc;
   if (!aligned8(inverse)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": inverse must be 8-byte aligned");
   if (N == 0) return GCM_OK;
   if (!a || !inverse || !x || !wp || !bp || !y) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null a, inverse, x, wp, bp or y");
-  mid_launch_forward(C, dim3(blocks_for(N, T)), (hipStream_t)hip_stream, a, a_stride, inverse, x, x_stride, wp, bp, row_scale, N,
-                     (int)C, y, y_stride);
+  with_nj(C, [&](auto nj) {
+    k_mid_forward<decltype(nj)::value><<<blocks_for(N, T), 256, 0, (hipStream_t)hip_stream>>>(a, a_stride, inverse, x, x_stride, wp,
+                                                                                             bp, row_scale, N, C, y, y_stride);
+  });
   HIP_TRY(hipGetLastError(), "mid forward launch");
   return GCM_OK;
 }
@@ -972,32 +936,28 @@ int gcm_mid_backward(const float* a, int64_t a_stride, const int64_t* inverse, c
   if (int rc = check_mid_shape(who, N, C)) return rc;
   if (T_slots < 0 || T_slots >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T out of range");
   if (T_slots < N) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": T below N");
-  if (!stride_ok(a_stride, C) || !stride_ok(dy_stride, C))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(a) || !aligned16(dy) || !aligned16(wp) || !aligned16(da) || !aligned16(dwp) || !aligned16(dbp))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{a_stride, C}, {dy_stride, C}})) return rc;
+  if (int rc = check_aligned16(who, {a, dy, wp, da, dwp, dbp})) return rc;
   if (!aligned8(inverse) || (reinterpret_cast<uintptr_t>(extra) & 3u) != 0)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": inverse must be 8-byte aligned, extra 4-byte aligned");
   const MidPlan p = mid_plan(N, C);
-  if (workspace_bytes < p.total || !workspace)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_mid_backward_workspace_bytes");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_mid_backward_workspace_bytes")) return rc;
   if (N > 0 && (!a || !inverse || !extra || !dy || !wp))
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null a, inverse, extra, dy or wp");
   hipStream_t st = (hipStream_t)hip_stream;
-  if (N == 0) {  // no row owns a slot: every gradient is zeros
-    if (da && T_slots) HIP_TRY(hipMemsetAsync(da, 0, (size_t)T_slots * C * 4, st), "mid backward clear da");
-    if (dwp) HIP_TRY(hipMemsetAsync(dwp, 0, (size_t)C * C * 4, st), "mid backward clear dwp");
-    if (dbp) HIP_TRY(hipMemsetAsync(dbp, 0, (size_t)C * 4, st), "mid backward clear dbp");
-    return GCM_OK;
-  }
+  if (N == 0)  // no row owns a slot: every gradient is zeros
+    return clear_outputs(st, {{T_slots ? da : nullptr, (size_t)T_slots * C * 4, "mid backward clear da"},
+                              {dwp, (size_t)C * C * 4, "mid backward clear dwp"},
+                              {dbp, (size_t)C * 4, "mid backward clear dbp"}});
   if (da) {
-    mid_launch_bwd_rows(C, dim3((unsigned)p.tiles), st, dy, dy_stride, inverse, extra, wp, row_scale, N, T_slots, (int)C, da);
+    with_nj(C, [&](auto nj) {
+      k_mid_bwd_rows<decltype(nj)::value><<<(unsigned)p.tiles, 256, 0, st>>>(dy, dy_stride, inverse, extra, wp, row_scale, N,
+                                                                            T_slots, C, da);
+    });
     HIP_TRY(hipGetLastError(), "mid backward rows launch");
   }
   if (dwp || dbp) {
-    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    const int64_t per = slice_rows(N, p.sw);
     float* part = (float*)workspace;
     k_mid_dw<<<dim3(p.wt, (unsigned)p.sw), 256, 0, st>>>(a, a_stride, inverse, dy, dy_stride, row_scale, N, T_slots, (int)C, per,
                                                          part);
@@ -1016,19 +976,19 @@ int gcm_seam_forward_eval(const float* x, int64_t x_stride, const float* w, cons
   const std::string who("gcm_seam_forward_eval");
   if (int rc = check_seam_shape(who, N, I, O, w != nullptr)) return rc;
   if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
-  if (!stride_ok(x_stride, I) || !stride_ok(y_stride, O))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(w) || !aligned16(b) || !aligned16(running_mean) || !aligned16(running_var) ||
-      !aligned16(bn_w) || !aligned16(bn_b) || !aligned16(y) || !aligned16(z) || !aligned16(rstd))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, I}, {y_stride, O}})) return rc;
+  if (int rc = check_aligned16(who, {x, w, b, running_mean, running_var, bn_w, bn_b, y, z, rstd})) return rc;
   if (!w && (b || z)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": b and z need w (without it z is x itself)");
   if (N == 0) return GCM_OK;
   if (!x || !running_mean || !running_var || !bn_w || !bn_b || !y)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, running_mean, running_var, bn_w, bn_b or y");
   hipStream_t st = (hipStream_t)hip_stream;
   if (w) {
-    seam_launch_forward<true>(O, blocks_for(N, T), st, x, x_stride, w, b, running_mean, running_var, eps, bn_w, bn_b, act, N,
-                              (int)I, (int)O, z, y, y_stride, rstd, (float*)nullptr);
+    with_nj(O, [&](auto nj) {  // the column block: the narrowest instantiation that holds O, else 128 columns a block
+      constexpr int NJ = decltype(nj)::value;
+      k_seam_forward<NJ, true><<<dim3(blocks_for(N, T), blocks_for(O, 32 * NJ)), 256, 0, st>>>(
+          x, x_stride, w, b, running_mean, running_var, eps, bn_w, bn_b, act, N, I, O, z, y, y_stride, rstd, nullptr);
+    });
   } else {
     k_seam_apply<true><<<blocks_for(N * (O / 4), 256), 256, 0, st>>>(x, x_stride, running_mean, running_var, eps, bn_w, bn_b, act,
                                                                      N, O / 4, y, y_stride, rstd);
@@ -1052,11 +1012,8 @@ int gcm_seam_forward_train(const float* x, int64_t x_stride, const float* w, con
   if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
   if (!std::isfinite(momentum) || momentum < 0.0f || momentum > 1.0f)
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": momentum must be in 0..1");
-  if (!stride_ok(x_stride, I) || !stride_ok(y_stride, O))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(w) || !aligned16(b) || !aligned16(bn_w) || !aligned16(bn_b) || !aligned16(z) ||
-      !aligned16(y) || !aligned16(mean) || !aligned16(rstd) || !aligned16(running_mean) || !aligned16(running_var))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, I}, {y_stride, O}})) return rc;
+  if (int rc = check_aligned16(who, {x, w, b, bn_w, bn_b, z, y, mean, rstd, running_mean, running_var})) return rc;
   if (!aligned8(num_batches_tracked)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": num_batches_tracked must be 8-byte aligned");
   if (!w && (b || z)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": b and z need w (without it z is x itself)");
   const int buffers = (running_mean != nullptr) + (running_var != nullptr) + (num_batches_tracked != nullptr);
@@ -1065,18 +1022,18 @@ int gcm_seam_forward_train(const float* x, int64_t x_stride, const float* w, con
   if (N == 0) return GCM_OK;
   if (N < 2) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": batch statistics need N >= 2");
   const size_t need = seam_forward_bytes(N, O);
-  if (workspace_bytes < need || !workspace)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_seam_forward_workspace_bytes");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (int rc = check_workspace(who, workspace, workspace_bytes, need, "gcm_seam_forward_workspace_bytes")) return rc;
   if (!x || !bn_w || !bn_b || !y || !mean || !rstd || (w && !z))
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, bn_w, bn_b, y, mean, rstd or (with w) z");
   hipStream_t st = (hipStream_t)hip_stream;
   const SeamPlan p = seam_plan(N, I, O);
   float* part = (float*)workspace;
   if (w) {
-    seam_launch_forward<false>(O, (unsigned)p.tiles, st, x, x_stride, w, b, (const float*)nullptr, (const float*)nullptr, eps,
-                               bn_w, bn_b, act, N, (int)I, (int)O, z, (float*)nullptr, (int64_t)0, (float*)nullptr, part);
+    with_nj(O, [&](auto nj) {
+      constexpr int NJ = decltype(nj)::value;
+      k_seam_forward<NJ, false><<<dim3((unsigned)p.tiles, blocks_for(O, 32 * NJ)), 256, 0, st>>>(
+          x, x_stride, w, b, nullptr, nullptr, eps, bn_w, bn_b, act, N, I, O, z, nullptr, 0, nullptr, part);
+    });
   } else {
     k_seam_tile_stats<<<dim3((unsigned)p.tiles, blocks_for(O, kSeamChunk)), 256, 0, st>>>(x, x_stride, N, (int)O, part);
   }
@@ -1103,29 +1060,20 @@ int gcm_seam_backward(const float* x, int64_t x_stride, const float* z, int64_t 
                       size_t workspace_bytes, void* hip_stream) {
   const std::string who("gcm_seam_backward");
   if (int rc = check_seam_shape(who, N, I, O, w != nullptr)) return rc;
-  if (!stride_ok(x_stride, I) || !stride_ok(z_stride, O) || !stride_ok(dy_stride, O) || (dx && !stride_ok(dx_stride, I)))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": strides must be positive multiples of 4 elements, at least the row's width");
-  if (!aligned16(x) || !aligned16(z) || !aligned16(mean) || !aligned16(rstd) || !aligned16(dy) || !aligned16(w) ||
-      !aligned16(bn_w) || !aligned16(bn_b) || !aligned16(dx) || !aligned16(dw) || !aligned16(db) || !aligned16(dbn_w) ||
-      !aligned16(dbn_b))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": float pointers must be 16-byte aligned");
+  if (int rc = check_strides(who, {{x_stride, I}, {z_stride, O}, {dy_stride, O}, {dx_stride, I, dx != nullptr}})) return rc;
+  if (int rc = check_aligned16(who, {x, z, mean, rstd, dy, w, bn_w, bn_b, dx, dw, db, dbn_w, dbn_b})) return rc;
   if (!w && (dw || db)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": dw and db need w");
   if (batch_stats && N == 1) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": batch statistics need N >= 2");
   const SeamPlan p = seam_plan(N, I, O);
-  if (workspace_bytes < p.total || !workspace)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace smaller than gcm_seam_backward_workspace_bytes");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": workspace must be 256-byte aligned");
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_seam_backward_workspace_bytes")) return rc;
   if (N > 0 && (!z || !mean || !rstd || !dy || !bn_w || !bn_b || (w && !x)))
     return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null z, mean, rstd, dy, bn_w, bn_b or (with w) x");
   hipStream_t st = (hipStream_t)hip_stream;
-  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
-    if (dw) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)O * I * 4, st), "seam backward clear dw");
-    if (db) HIP_TRY(hipMemsetAsync(db, 0, (size_t)O * 4, st), "seam backward clear db");
-    if (dbn_w) HIP_TRY(hipMemsetAsync(dbn_w, 0, (size_t)O * 4, st), "seam backward clear dbn_w");
-    if (dbn_b) HIP_TRY(hipMemsetAsync(dbn_b, 0, (size_t)O * 4, st), "seam backward clear dbn_b");
-    return GCM_OK;
-  }
+  if (N == 0)  // nothing to sum: the parameter gradients are zeros
+    return clear_outputs(st, {{dw, (size_t)O * I * 4, "seam backward clear dw"},
+                              {db, (size_t)O * 4, "seam backward clear db"},
+                              {dbn_w, (size_t)O * 4, "seam backward clear dbn_w"},
+                              {dbn_b, (size_t)O * 4, "seam backward clear dbn_b"}});
   char* ws = (char*)workspace;
   float* keep = (float*)(ws + p.keep);
   const bool rows = dx || dw || db;  // what reads dz
@@ -1141,12 +1089,16 @@ int gcm_seam_backward(const float* x, int64_t x_stride, const float* z, int64_t 
   d.kh = batch_stats ? keep : nullptr, d.kg = batch_stats ? keep + O : nullptr;
   d.dys = dy_stride, d.zs = z_stride, d.inv_n = 1.0f / (float)N, d.act = act;
   if (dx) {
-    if (w) seam_launch_dx(I, (unsigned)p.tiles, st, d, w, N, (int)I, (int)O, dx, dx_stride);
+    if (w)
+      with_nj(I, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        k_seam_dx<NJ><<<dim3((unsigned)p.tiles, blocks_for(I, 32 * NJ)), 256, 0, st>>>(d, w, N, I, O, dx, dx_stride);
+      });
     else k_seam_dz<<<blocks_for(N * (O / 4), 256), 256, 0, st>>>(d, N, O / 4, dx, dx_stride);
     HIP_TRY(hipGetLastError(), "seam backward dx launch");
   }
   if (dw || db) {
-    const int64_t per = ((N + p.sw - 1) / p.sw + KC - 1) / KC * KC;
+    const int64_t per = slice_rows(N, p.sw);
     float* part = (float*)(ws + p.wpart);
     k_seam_dw<<<dim3(p.wt, (unsigned)p.sw), 256, 0, st>>>(d, x, x_stride, N, (int)I, (int)O, per, part);
     k_ffn_fold_params<<<blocks_for(seam_record(I, O), 256), 256, 0, st>>>(part, p.sw, (int64_t)O * I, O, 0, 0, dw, db, nullptr,

@@ -1,7 +1,8 @@
 // gcm_seam.h -- the seams between the PTv3 stages (gcm_seam_*, include/gcm.h): Linear -> BatchNorm1d -> GELU as one
 // operator, y = act(bn(x W^T + b)), up to 512 channels either way; eval mode in ONE launch, training mode in three, the
-// deterministic backward in five, whatever N is.  Included by gcm_modlinear.hip after gcm_mid.h, whose forward shape and
-// row-sliced weight gradient it uses; device code and launch helpers only, the C ABI stays in gcm_modlinear.hip.
+// deterministic backward in five, whatever N is.  Included by gcm_modlinear.hip after gcm_tile.h (the tile and the
+// product loop) and gcm_ffn.h (the row-sliced weight gradient); device code and the plans only, the C ABI stays in
+// gcm_modlinear.hip.
 // DESIGN.md section 21.
 //
 //   product    k_seam_forward: 256 threads own T = 64 rows and a block of CT = 32 NJ <= 128 output columns (grid.y walks
@@ -96,82 +97,47 @@ __global__ __launch_bounds__(256, 2) void k_seam_forward(const float* __restrict
                                                          const float* __restrict__ gam, const float* __restrict__ bet, int act,
                                                          int64_t N, int I, int O, float* __restrict__ z, float* __restrict__ y,
                                                          int64_t ys, float* __restrict__ rstd_out, float* __restrict__ part) {
-  constexpr int CT = 32 * NJ, XP = kSeamChunk + 4, ZP = CT + 4, NV = NJ > 2 ? NJ / 2 : 1, CQ = CT / 4;
+  constexpr int CT = 32 * NJ, XP = kSeamChunk + 4, ZP = CT + 4, CQ = CT / 4;
   __shared__ __attribute__((aligned(16))) float Xs[T * XP];       // a chunk of x: rows x inputs; afterwards the tile of z
-  __shared__ __attribute__((aligned(16))) float Ws[CT * kPitch];  // a 16-deep slice of W
+  __shared__ __attribute__((aligned(16))) float Ws[Chain<NJ, false>::kWords];  // a 16-deep slice of W
   const int tid = threadIdx.x;
   const WaveTile g;
-  const int wcn = (g.wc >> 5) * 16 * NJ;  // the wave's first output column inside the block
   const int64_t row0 = (int64_t)blockIdx.x * T;
   const int col0 = blockIdx.y * CT;
 
-  f4 vw[NV];
+  Chain<NJ, false> prod;  // z = x W^T: the accumulators carry across the chunks of inputs
   f4 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) acc[i][j] = zero4();
-
+  clear_acc(acc);
   for (int i0 = 0; i0 < I; i0 += kSeamChunk) {
     const int cw = I - i0 < kSeamChunk ? I - i0 : kSeamChunk;
-    const int Cr = (cw + KC - 1) / KC * KC, c4 = Cr >> 2;
-    for (int e = tid; e < T * c4; e += 256) {
-      const int r = e / c4, c = 4 * (e % c4);
-      f4 v = zero4();
-      if (row0 + r < N && i0 + c < I) v = ld4(x + (row0 + r) * xs + i0 + c);
-      *reinterpret_cast<f4*>(&Xs[r * XP + c]) = v;
-    }
-    // (ordered before the fragment reads by the first __syncthreads of the slice loop)
-    auto fetch = [&](int k0) {  // W slice: output column col0 + e / 4, four inputs at i0 + k0 + 4 * (e % 4)
-#pragma unroll
-      for (int u = 0; u < NV; u++) {
-        const int e = tid + 256 * u, c = col0 + (e >> 2), k = i0 + k0 + 4 * (e & 3);
-        vw[u] = (e < 4 * CT && c < O && k < I) ? ld4(w + (int64_t)c * I + k) : zero4();
-      }
+    const int Cr = (cw + KC - 1) / KC * KC;
+    stage_rows(Xs, XP, Cr >> 2, [&](int r, int c) {
+      return (row0 + r < N && i0 + c < I) ? ld4(x + (row0 + r) * xs + i0 + c) : zero4();
+    });
+    auto w_at = [&](int cl, int k) {
+      return (col0 + cl < O && i0 + k < I) ? ld4(w + (int64_t)(col0 + cl) * I + i0 + k) : zero4();
     };
-    fetch(0);
-    for (int k0 = 0; k0 < Cr; k0 += KC) {
-#pragma unroll
-      for (int u = 0; u < NV; u++) {
-        const int e = tid + 256 * u;
-        if (e < 4 * CT) *reinterpret_cast<f4*>(&Ws[(e >> 2) * kPitch + 4 * (e & 3)]) = vw[u];
-      }
-      __syncthreads();
-      if (k0 + KC < Cr) fetch(k0 + KC);
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        float fa[2], fb[NJ];
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i] = Xs[(g.wr + 16 * i + g.fl) * XP + k0 + kk + g.fk];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) fb[j] = Ws[(wcn + 16 * j + g.fl) * kPitch + kk + g.fk];
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
+    prod.first(w_at);
+    prod.run(acc, g, Xs, XP, Cr, Ws, w_at);
   }
 
-  // z = chain + b into the tile image (the last __syncthreads above freed Xs)
+  // z = chain + b into the tile image (the chain's last barrier freed Xs)
   float* Zs = Xs;
 #pragma unroll
   for (int j = 0; j < NJ; j++) {
-    const int cl = wcn + 16 * j + g.fl;
-    const float bias = (b && col0 + cl < O) ? b[col0 + cl] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) Zs[(g.wr + 16 * i + 4 * g.fk + v) * ZP + cl] = acc[i][j][v] + bias;
+    const int c = col0 + g.first_col<NJ>() + 16 * j + g.fl;
+    const float bias = (b && c < O) ? b[c] : 0.0f;
+    acc[0][j] = acc[0][j] + bias;
+    acc[1][j] = acc[1][j] + bias;
   }
+  for_each_output(acc, g, [&](int rl, int cl, float v) { Zs[rl * ZP + cl] = v; });
   __syncthreads();
 
   for (int e = tid; e < T * CQ; e += 256) {
     const int r = e / CQ, c = col0 + 4 * (e % CQ);
     const int64_t row = row0 + r;
     if (row >= N || c >= O) continue;
-    const f4 zv = *reinterpret_cast<const f4*>(&Zs[r * ZP + 4 * (e % CQ)]);
+    const f4 zv = ld4(&Zs[r * ZP + 4 * (e % CQ)]);
     if (z) st4(z + row * O + c, zv);
     if (EVAL) {
       const f4 rs = seam_rstd4(ld4(var + c), eps);
@@ -194,12 +160,9 @@ __global__ __launch_bounds__(256) void k_seam_tile_stats(const float* __restrict
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * T;
   const int col0 = blockIdx.y * CT;
-  for (int e = tid; e < T * CQ; e += 256) {
-    const int r = e / CQ, c = 4 * (e % CQ);
-    f4 v = zero4();
-    if (row0 + r < N && col0 + c < O) v = ld4(x + (row0 + r) * xs + col0 + c);
-    *reinterpret_cast<f4*>(&Zs[r * ZP + c]) = v;
-  }
+  stage_rows(Zs, ZP, CQ, [&](int r, int c) {
+    return (row0 + r < N && col0 + c < O) ? ld4(x + (row0 + r) * xs + col0 + c) : zero4();
+  });
   __syncthreads();
   if (tid < CT && col0 + tid < O) {
     const int nv = N - row0 < T ? (int)(N - row0) : T;
@@ -370,87 +333,37 @@ __global__ __launch_bounds__(256) void k_seam_dz(SeamDz d, int64_t N, int o4, fl
   st4(dx + r * dxs + c, d.at(r, c));
 }
 
-// k_mid_bwd_rows' shape: 256 threads own T = 64 rows and CT = 32 NJ columns of dx (grid.y walks I); the outputs are the
+// 256 threads own T = 64 rows and CT = 32 NJ columns of dx (grid.y walks I); the outputs are the
 // summed index, walked in chunks of <= 128 of dz staged in LDS.
 template <int NJ>
 __global__ __launch_bounds__(256, 2) void k_seam_dx(SeamDz d, const float* __restrict__ w, int64_t N, int I, int O,
                                                     float* __restrict__ dx, int64_t dxs) {
-  constexpr int CT = 32 * NJ, XP = kSeamChunk + 4, WP = CT + 16, NV = NJ > 2 ? NJ / 2 : 1, CQ = CT / 4;
-  __shared__ __attribute__((aligned(16))) float Ds[T * XP];   // dz: rows x a chunk of outputs
-  __shared__ __attribute__((aligned(16))) float Ws[KC * WP];  // a 16-deep slice of W: summed index in rows
-  const int tid = threadIdx.x;
+  constexpr int CT = 32 * NJ, XP = kSeamChunk + 4;
+  __shared__ __attribute__((aligned(16))) float Ds[T * XP];                   // dz: rows x a chunk of outputs
+  __shared__ __attribute__((aligned(16))) float Ws[Chain<NJ, true>::kWords];  // a 16-deep slice of W
   const WaveTile g;
-  const int wcn = (g.wc >> 5) * 16 * NJ;
   const int64_t row0 = (int64_t)blockIdx.x * T;
   const int col0 = blockIdx.y * CT;
 
-  f4 vw[NV];
+  Chain<NJ, true> back;  // dx = dz W, a chain per chunk of outputs
   f4 acc[2][NJ], tot[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) tot[i][j] = zero4();
-
+  clear_acc(tot);
   for (int o0 = 0; o0 < O; o0 += kSeamChunk) {
     const int cw = O - o0 < kSeamChunk ? O - o0 : kSeamChunk;
-    const int Cr = (cw + KC - 1) / KC * KC, c4 = Cr >> 2;
-    for (int e = tid; e < T * c4; e += 256) {
-      const int r = e / c4, c = 4 * (e % c4);
-      f4 v = zero4();
-      if (row0 + r < N && o0 + c < O) v = d.at(row0 + r, o0 + c);
-      *reinterpret_cast<f4*>(&Ds[r * XP + c]) = v;
-    }
-    auto fetchw = [&](int k0) {  // slice of W [O][I]: row o0 + k0 + e / CQ, four columns at col0 + 4 * (e % CQ)
-#pragma unroll
-      for (int u = 0; u < NV; u++) {
-        const int e = tid + 256 * u, o = o0 + k0 + e / CQ, c = col0 + 4 * (e % CQ);
-        vw[u] = (e < KC * CQ && o < O && c < I) ? ld4(w + (int64_t)o * I + c) : zero4();
-      }
+    const int Cr = (cw + KC - 1) / KC * KC;
+    stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) { return (row0 + r < N && o0 + c < O) ? d.at(row0 + r, o0 + c) : zero4(); });
+    auto w_at = [&](int cl, int k) {
+      return (o0 + k < O && col0 + cl < I) ? ld4(w + (int64_t)(o0 + k) * I + col0 + cl) : zero4();
     };
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) acc[i][j] = zero4();
-    fetchw(0);
-    for (int k0 = 0; k0 < Cr; k0 += KC) {
-#pragma unroll
-      for (int u = 0; u < NV; u++) {
-        const int e = tid + 256 * u;
-        if (e < KC * CQ) *reinterpret_cast<f4*>(&Ws[(e / CQ) * WP + 4 * (e % CQ)]) = vw[u];
-      }
-      __syncthreads();
-      if (k0 + KC < Cr) fetchw(k0 + KC);
-#pragma unroll
-      for (int kk = 0; kk < KC; kk += 4) {
-        float fa[2], fb[NJ];
-#pragma unroll
-        for (int i = 0; i < 2; i++) fa[i] = Ds[(g.wr + 16 * i + g.fl) * XP + k0 + kk + g.fk];
-#pragma unroll
-        for (int j = 0; j < NJ; j++) fb[j] = Ws[(kk + g.fk) * WP + wcn + 16 * j + g.fl];
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-          for (int j = 0; j < NJ; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < NJ; j++) tot[i][j] = tot[i][j] + acc[i][j];
+    clear_acc(acc);
+    back.first(w_at);
+    back.run(acc, g, Ds, XP, Cr, Ws, w_at);
+    add_acc(tot, acc);
   }
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int v = 0; v < 4; v++) {
-      const int64_t row = row0 + g.wr + 16 * i + 4 * g.fk + v;
-      if (row >= N) continue;
-#pragma unroll
-      for (int j = 0; j < NJ; j++) {
-        const int c = col0 + wcn + 16 * j + g.fl;
-        if (c < I) dx[row * dxs + c] = tot[i][j][v];
-      }
-    }
+  for_each_output(tot, g, [&](int rl, int cl, float v) {
+    const int64_t row = row0 + rl;
+    if (row < N && col0 + cl < I) dx[row * dxs + col0 + cl] = v;
+  });
 }
 
 // ---- backward: the weight gradient ----------------------------------------------------------------------------------------
@@ -474,7 +387,7 @@ __global__ __launch_bounds__(256) void k_seam_dw(SeamDz d, const float* __restri
   dw_slice_tile(fetch, O, I, o0, i0, p0, p1, rec, rec + (int64_t)O * I, Ds, Xs);
 }
 
-// ---- host: the plans and the launches -----------------------------------------------------------------------------------
+// ---- host: the plans -----------------------------------------------------------------------------------
 struct SeamPlan {
   int64_t tiles;  // row tiles
   int G;          // groups of consecutive tiles (1: one level)
@@ -489,34 +402,14 @@ SeamPlan seam_plan(int64_t N, int32_t I, int32_t O) {
   p.G = p.tiles > kSeamFoldTiles ? (int)std::min<int64_t>(kSeamGroups, (p.tiles + kSeamFoldTiles - 1) / kSeamFoldTiles) : 1;
   p.gper = (p.tiles + p.G - 1) / p.G;
   p.wt = (unsigned)((O + T - 1) / T) * (unsigned)((I + T - 1) / T);
-  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(kFfnMaxSlices, 1024 / p.wt));
-  p.sw = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (N + 63) / 64));
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 255) / 256 * 256;
-    return at;
-  };
-  p.part = take((size_t)std::max<int64_t>(p.tiles, 1) * 2 * O * 4);
-  p.keep = take((size_t)2 * O * 4);
-  p.wpart = take((size_t)p.sw * (size_t)seam_record(I, O) * 4);
-  p.total = off;
+  p.sw = weight_slices(p.wt, N);
+  Carve ws;
+  p.part = ws.take((size_t)std::max<int64_t>(p.tiles, 1) * 2 * O * 4);
+  p.keep = ws.take((size_t)2 * O * 4);
+  p.wpart = ws.take((size_t)p.sw * (size_t)seam_record(I, O) * 4);
+  p.total = ws.off;
   return p;
 }
 size_t seam_forward_bytes(int64_t N, int32_t O) { return seam_plan(N, 4, O).keep; }  // the tiles' records, rounded
-
-// the column block: the narrowest template that holds C, else 128 columns a block
-template <bool EVAL, typename... A>
-void seam_launch_forward(int O, unsigned tiles, hipStream_t st, A... args) {
-  if (O <= 32) k_seam_forward<1, EVAL><<<dim3(tiles, 1), 256, 0, st>>>(args...);
-  else if (O <= 64) k_seam_forward<2, EVAL><<<dim3(tiles, 1), 256, 0, st>>>(args...);
-  else k_seam_forward<4, EVAL><<<dim3(tiles, blocks_for(O, 128)), 256, 0, st>>>(args...);
-}
-template <typename... A>
-void seam_launch_dx(int I, unsigned tiles, hipStream_t st, A... args) {
-  if (I <= 32) k_seam_dx<1><<<dim3(tiles, 1), 256, 0, st>>>(args...);
-  else if (I <= 64) k_seam_dx<2><<<dim3(tiles, 1), 256, 0, st>>>(args...);
-  else k_seam_dx<4><<<dim3(tiles, blocks_for(I, 128)), 256, 0, st>>>(args...);
-}
 
 }  // namespace

@@ -10,11 +10,16 @@
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
 the HIP library, float32 throughout, and nothing here waits for the device.
 """
+import functools
+
 import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
-from .modlinear import _ptr, _rows
+from .modlinear import _check_float as _check_float_op
+from .modlinear import _grad32, _ptr, _rows, _workspace
+
+_check_float = functools.partial(_check_float_op, op="the fused feed-forward")
 
 _STATS = {"forward_calls": 0, "backward_calls": 0}
 
@@ -62,7 +67,7 @@ class LayerNormMlpResidualFunction(torch.autograd.Function):
         x, mean, rstd, a, row_scale, ln_w, ln_b, w1, w2 = ctx.saved_tensors
         N, C = x.shape
         Hd = w1.shape[0]
-        dy = _rows(dy if dy.dtype == torch.float32 else dy.float())
+        dy = _grad32(dy)
         need = ctx.needs_input_grad
         dx = x.new_empty((N, C)) if need[0] else None
         dln_w = x.new_empty((C,)) if need[1] else None
@@ -73,7 +78,7 @@ class LayerNormMlpResidualFunction(torch.autograd.Function):
         db2 = x.new_empty((C,)) if need[7] else None
         L = M.lib()
         ws_bytes = L.gcm_ffn_backward_workspace_bytes(N, C, Hd)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        ws = _workspace(ws_bytes, x.device)
         with torch.cuda.device(x.device):
             M.check(L.gcm_ffn_backward(x.data_ptr(), x.stride(0), mean.data_ptr(), rstd.data_ptr(), a.data_ptr(), dy.data_ptr(),
                                        dy.stride(0), _ptr(row_scale), ln_w.data_ptr(), ln_b.data_ptr(), w1.data_ptr(),
@@ -81,15 +86,6 @@ class LayerNormMlpResidualFunction(torch.autograd.Function):
                                        _ptr(dw2), _ptr(db2), ws.data_ptr(), ws_bytes, _stream()), "gcm_ffn_backward")
         _STATS["backward_calls"] += 1
         return dx, dln_w, dln_b, None, dw1, db1, dw2, db2, None
-
-
-def _check_float(name, t, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
-    if not t.is_cuda:
-        raise TypeError("the fused feed-forward runs on the GPU; %s must be a CUDA tensor" % name)
-    if tuple(t.shape) != shape:
-        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
 
 
 def layernorm_mlp_residual(x, ln_weight, ln_bias, eps, w1, b1, w2, b2, row_scale=None):

@@ -12,11 +12,16 @@ sparse convolution and its attention.
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
 the HIP library, float32 throughout, and nothing here waits for the device.
 """
+import functools
+
 import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
-from .modlinear import _ptr, _rows
+from .modlinear import _check_float as _check_float_op
+from .modlinear import _grad32, _ptr, _rows, _workspace
+
+_check_float = functools.partial(_check_float_op, op="the fused Block front")
 
 _STATS = {"forward_calls": 0, "backward_calls": 0}
 
@@ -63,15 +68,14 @@ class ConvTailNormQkvFunction(torch.autograd.Function):
         s, feat, t, st, wc, lnc_w, ln1_w, ln1_b, wq = ctx.saved_tensors
         N, C = s.shape
         O = wq.shape[0]
-        dfeat = _rows(dfeat if dfeat.dtype == torch.float32 else dfeat.float())
-        dqkv = _rows(dqkv if dqkv.dtype == torch.float32 else dqkv.float())
+        dfeat, dqkv = _grad32(dfeat), _grad32(dqkv)
         need = ctx.needs_input_grad
         new = lambda i, *shape: s.new_empty(shape) if need[i] else None  # noqa: E731
         dx, ds, dwc, dbc, dlnc_w, dlnc_b = new(0, N, C), new(1, N, C), new(2, C, C), new(3, C), new(4, C), new(5, C)
         dln1_w, dln1_b, dwq, dbq = new(7, C), new(8, C), new(10, O, C), new(11, O)
         L = M.lib()
         ws_bytes = L.gcm_front_backward_workspace_bytes(N, C, O)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=s.device)
+        ws = _workspace(ws_bytes, s.device)
         with torch.cuda.device(s.device):
             M.check(L.gcm_front_backward(s.data_ptr(), s.stride(0), feat.data_ptr(), feat.stride(0), t.data_ptr(),
                                          *_stat_ptrs(st), dfeat.data_ptr(), dfeat.stride(0), dqkv.data_ptr(), dqkv.stride(0),
@@ -88,15 +92,6 @@ def _stat_ptrs(st):
     if st is None:
         return (None,) * 4
     return tuple(st.data_ptr() + 4 * k * st.shape[1] for k in range(4))
-
-
-def _check_float(name, t, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
-    if not t.is_cuda:
-        raise TypeError("the fused Block front runs on the GPU; %s must be a CUDA tensor" % name)
-    if tuple(t.shape) != shape:
-        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
 
 
 def conv_tail_norm_qkv(x, s, wc, bc, lnc_w, lnc_b, lnc_eps, ln1_w, ln1_b, ln1_eps, wq, bq):

@@ -19,11 +19,16 @@ runs around its attention, and the Block's DropPath and residual add after it.
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
 the HIP library, float32 throughout, and nothing here waits for the device unless check=True asks for it.
 """
+import functools
+
 import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
-from .modlinear import _ptr, _rows
+from .modlinear import _check_float as _check_float_op
+from .modlinear import _grad32, _ptr, _rows, _workspace
+
+_check_float = functools.partial(_check_float_op, op=None)  # the device is checked after everything else
 
 _STATS = {"plan_calls": 0, "gather_forward_calls": 0, "gather_backward_calls": 0, "forward_calls": 0, "backward_calls": 0}
 
@@ -51,13 +56,6 @@ def _check_cuda(name, t):
 def _check_index(name, t, dtype=torch.int64):
     if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1:
         raise TypeError("%s must be a 1-d %s tensor" % (name, str(dtype).replace("torch.", "")))
-
-
-def _check_float(name, t, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
-    if tuple(t.shape) != shape:
-        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
 
 
 def _check_pair(order, inverse, extra=None):
@@ -124,7 +122,7 @@ class GatherRowsFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         inverse, extra = ctx.saved_tensors
-        dy = _rows(dy if dy.dtype == torch.float32 else dy.float())
+        dy = _grad32(dy)
         N, W = inverse.shape[0], dy.shape[1]
         dx = dy.new_empty((N, W))
         with torch.cuda.device(dy.device):
@@ -183,14 +181,14 @@ class ProjResidualFunction(torch.autograd.Function):
         dx = dy if need[3] else None  # the shortcut's gradient is the incoming one
         if not (need[0] or need[4] or need[5]):
             return None, None, None, dx, None, None, None
-        g = _rows(dy if dy.dtype == torch.float32 else dy.float())
+        g = _grad32(dy)
         (T, C), N = a.shape, inverse.shape[0]
         da = a.new_empty((T, C)) if need[0] else None
         dwp = a.new_empty((C, C)) if need[4] else None
         dbp = a.new_empty((C,)) if need[5] else None
         L = M.lib()
         ws_bytes = L.gcm_mid_backward_workspace_bytes(N, C)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=a.device)
+        ws = _workspace(ws_bytes, a.device)
         with torch.cuda.device(a.device):
             M.check(L.gcm_mid_backward(a.data_ptr(), a.stride(0), inverse.data_ptr(), extra.data_ptr(), g.data_ptr(),
                                        g.stride(0), wp.data_ptr(), _ptr(row_scale), N, T, C, _ptr(da), _ptr(dwp), _ptr(dbp),

@@ -48,6 +48,28 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _grad32(dy):
+    """An incoming gradient as the library reads it: float32, row-strided."""
+    return _rows(dy if dy.dtype == torch.float32 else dy.float())
+
+
+def _workspace(nbytes, device):
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def _check_float(name, t, shape, op="the modulated linear layer", optional=False):
+    """t is a float32 tensor of `shape`, on the GPU.  op names the operator in the device message; None leaves the device
+    to the caller (the operators that report it after every other check).  optional: None passes."""
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
+    if op is not None and not t.is_cuda:
+        raise TypeError("%s runs on the GPU; %s must be a CUDA tensor" % (op, name))
+    if tuple(t.shape) != shape:
+        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
+
+
 class ModulatedLinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, alpha, beta, bias, group, slope, G):
@@ -73,7 +95,7 @@ class ModulatedLinearFunction(torch.autograd.Function):
         slope, G, has_beta, has_bias = ctx.meta
         N, I = x.shape
         O = weight.shape[0]
-        dy = _rows(dy if dy.dtype == torch.float32 else dy.float())
+        dy = _grad32(dy)
         need = ctx.needs_input_grad
         dx = x.new_empty((N, I)) if need[0] else None
         dw = x.new_empty((O, I)) if need[1] else None
@@ -82,7 +104,7 @@ class ModulatedLinearFunction(torch.autograd.Function):
         dbias = x.new_empty((O,)) if has_bias and need[4] else None
         L = M.lib()
         ws_bytes = L.gcm_modlinear_backward_workspace_bytes(N, I, O, G)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        ws = _workspace(ws_bytes, x.device)
         with torch.cuda.device(x.device):
             M.check(L.gcm_modlinear_backward(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), dy.data_ptr(), dy.stride(0),
                                              weight.data_ptr(), weight.stride(0), _ptr(alpha), _ptr(group), N, I, O, G, slope,
@@ -90,17 +112,6 @@ class ModulatedLinearFunction(torch.autograd.Function):
                                              ws_bytes, _stream()), "gcm_modlinear_backward")
         _STATS["backward_calls"] += 1
         return dx, dw, dalpha, dbeta, dbias, None, None, None
-
-
-def _check_float(name, t, shape):
-    if t is None:
-        return
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
-    if not t.is_cuda:
-        raise TypeError("the modulated linear layer runs on the GPU; %s must be a CUDA tensor" % name)
-    if tuple(t.shape) != shape:
-        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
 
 
 def _check_group(group, n):
@@ -127,9 +138,9 @@ def modulated_linear(x, weight, alpha=None, beta=None, bias=None, group=None, ne
         beta.shape[0] if isinstance(beta, torch.Tensor) and beta.dim() == 2 else 1)
     _check_float("x", x, (N, I))
     _check_float("weight", weight, (O, I))
-    _check_float("alpha", alpha, (G, I))
-    _check_float("beta", beta, (G, O))
-    _check_float("bias", bias, (O,))
+    _check_float("alpha", alpha, (G, I), optional=True)
+    _check_float("beta", beta, (G, O), optional=True)
+    _check_float("bias", bias, (O,), optional=True)
     if G < 1:
         raise ValueError("alpha and beta need at least one group")
     slope = float(negative_slope)
@@ -170,7 +181,7 @@ def head_out(f, weight, bias, group, kind, factor):
         raise ValueError("I must be a positive multiple of 4 and C 1 or 3, got I = %d, C = %d" % (I, Cn))
     _check_float("f", f, (N, I))
     _check_float("weight", weight, (Cn, I))
-    _check_float("bias", bias, (Cn,))
+    _check_float("bias", bias, (Cn,), optional=True)
     group = _check_group(group, N)
     f, weight = _rows(f.detach()), weight.detach().contiguous()
     bias = None if bias is None else bias.detach().contiguous()

@@ -16,11 +16,16 @@ operator.
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
 the HIP library, float32 throughout, and nothing here waits for the device, forward or backward.
 """
+import functools
+
 import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
-from .modlinear import _ptr, _rows
+from .modlinear import _check_float as _check_float_op
+from .modlinear import _grad32, _ptr, _rows, _workspace
+
+_check_float = functools.partial(_check_float_op, op=None)  # the device is checked after everything else
 
 _STATS = {"forward_eval_calls": 0, "forward_train_calls": 0, "backward_calls": 0}
 
@@ -43,17 +48,6 @@ def max_channels():
 def _check_cuda(name, t):
     if not t.is_cuda:
         raise TypeError("the fused stage seam runs on the GPU; %s must be a CUDA tensor" % name)
-
-
-def _check_float(name, t, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError("%s must be a float32 tensor (float16 is not supported)" % name)
-    if tuple(t.shape) != shape:
-        raise ValueError("%s must be %r, got %r" % (name, shape, tuple(t.shape)))
-
-
-def _workspace(nbytes, device):
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
 
 
 class LinearBnGeluFunction(torch.autograd.Function):
@@ -101,7 +95,7 @@ class LinearBnGeluFunction(torch.autograd.Function):
         x, z, mean, rstd, weight, bn_weight, bn_bias = ctx.saved_tensors
         training, act, has_bias = ctx.seam
         need = ctx.needs_input_grad
-        g = _rows(dy if dy.dtype == torch.float32 else dy.float())
+        g = _grad32(dy)
         N, I = x.shape
         O = bn_weight.shape[0]
         product = weight is not None
