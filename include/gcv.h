@@ -92,8 +92,9 @@ int gcv_points_to_volume(int64_t n_points, const int16_t* points, const int32_t*
 int gcv_build_occupancy(const int32_t* volume, int32_t h, int32_t w, int32_t d, uint32_t* occupancy, void* hip_stream);
 
 /* Fused form of scripts/dataset_generator.py:1366-1388 (_get_volume) for rows as the extruder writes them:
- * gcv_points_bounds: per-axis min / max of columns 0..2 of int16 rows with `row_stride` elements (3 or 5);
- *   waits for the result (upstream: six .item() calls).  scratch: gcv_bounds_scratch_bytes() device bytes.
+ * gcv_points_bounds: per-axis min / max of columns 0..2 of n_points > 0 int16 rows of `row_stride` >= 3 elements
+ *   (3: bare points, 5: the extruder's rows; further columns are not read); waits for the result (upstream: six
+ *   .item() calls).  scratch: gcv_bounds_scratch_bytes() device bytes, contents irrelevant.
  * gcv_rows_to_volume: rows [n][5] = (x, y, z, scale, instance); voxel id = row index + 1, position =
  *   (x, y, z) - offset in int16 arithmetic, cube of `scale` voxels per side -- what _get_volume + points_to_volume
  *   produce for scales = get_point_scales(rows[:, 3]) (utils/helpers.py:197-222, no special classes).

@@ -60,3 +60,25 @@ def camera_for_volume(h, w, d, rows, cols, variant=0):
         centre = np.array([h / 2 + 0.5, w / 2 + 0.5, 0.0], np.float32)
     up = np.array([0, 0, 1], np.float32) if variant != 2 else np.array([0, 1, 0], np.float32)
     return ori, (centre - ori).astype(np.float32), up, float(0.9 * cols), [rows / 2.0, cols / 2.0], [rows, cols]
+
+
+def visible_points_oracle(po, points, scales, rig, cam_pos, cam_quat, null_id):
+    """scripts/dataset_generator.py:1414-1461 composed from the oracle's pieces (numpy)."""
+    from gaussiancity_amd import points as P
+    pts = points[:, [0, 1, 2]].astype(np.int16)
+    mn, mx = pts.min(0), pts.max(0)
+    loc = pts.copy()
+    loc[:, 0] -= mn[0]; loc[:, 1] -= mn[1]; loc[:, 2] -= mn[2] - 1
+    w, h, d = int(mx[0]) - int(mn[0]) + 1, int(mx[1]) - int(mn[1]) + 1, int(mx[2]) - int(mn[2]) + 2
+    vol = po.points_to_volume(loc, np.arange(1, len(pts) + 1, dtype=np.int32), scales.astype(np.int16), h, w, d)
+    cam = np.array(cam_pos, np.float64) - mn.astype(np.int16)
+    look = P.get_camera_look_at(cam, cam_quat)
+    ori = np.array([cam[1], cam[0], cam[2]], np.float32)
+    view = np.array([look[1] - cam[1], look[0] - cam[0], look[2] - cam[2]], np.float32)
+    K, sensor = rig["intrinsics"], rig["sensor_size"]
+    vid, _, _ = po.ray_voxel_intersection_perspective(vol, ori, view, np.array([0, 0, 1], np.float32), K[0],
+                                                      [K[5], K[2]], [sensor[1], sensor[0]], 1)
+    vp = vid.squeeze().astype(np.int64) - 1
+    ins = points[:, 4][np.clip(vp, 0, None)].copy()
+    ins[vp == -1] = null_id
+    return vp, ins

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import points_util as U
+import rows_ref as R
 from gaussiancity_amd import points as P
 from gaussiancity_amd import synth
 
@@ -77,12 +78,10 @@ def test_points_to_volume_and_occupancy(cuda_device, po):
         assert np.array_equal(vol.cpu().numpy(), want)
         assert torch.equal(P.points_to_volume(*t, h, w, d), vol)
         # occupancy: exactly the 16^3 macro cells holding a non-zero voxel
-        hb, wb, db = (h + 15) // 16, (w + 15) // 16, (d + 15) // 16
-        pad = np.zeros((hb * 16, wb * 16, db * 16), np.int32)
-        pad[:h, :w, :d] = want
-        brick_any = pad.reshape(hb, 16, wb, 16, db, 16).any(axis=(1, 3, 5)).reshape(-1)
+        brick_any = R.occupancy_cells(want)
         bits = np.unpackbits(occ.cpu().numpy().view(np.uint8), bitorder="little")[:brick_any.size].astype(bool)
         assert np.array_equal(bits, brick_any)
+        assert np.array_equal(occ.cpu().numpy().view(np.uint8), R.reference_occupancy(want))  # the padding bits too
         # the same bitmask from the dense volume alone
         from gaussiancity_amd import _native_v as V
         occ2 = torch.zeros_like(occ)
@@ -185,27 +184,6 @@ def test_traversal_strided_volume_and_errors(cuda_device, po):
         P.ray_voxel_intersection_perspective(vT, cam[0].double(), cam[1], cam[2], f, c, img, 1)
 
 
-def _visible_points_oracle(po, points, scales, rig, cam_pos, cam_quat, null_id):
-    """scripts/dataset_generator.py:1414-1461 composed from the oracle's pieces (numpy)."""
-    pts = points[:, [0, 1, 2]].astype(np.int16)
-    mn, mx = pts.min(0), pts.max(0)
-    loc = pts.copy()
-    loc[:, 0] -= mn[0]; loc[:, 1] -= mn[1]; loc[:, 2] -= mn[2] - 1
-    w, h, d = int(mx[0]) - int(mn[0]) + 1, int(mx[1]) - int(mn[1]) + 1, int(mx[2]) - int(mn[2]) + 2
-    vol = po.points_to_volume(loc, np.arange(1, len(pts) + 1, dtype=np.int32), scales.astype(np.int16), h, w, d)
-    cam = np.array(cam_pos, np.float64) - mn.astype(np.int16)
-    look = P.get_camera_look_at(cam, cam_quat)
-    ori = np.array([cam[1], cam[0], cam[2]], np.float32)
-    view = np.array([look[1] - cam[1], look[0] - cam[0], look[2] - cam[2]], np.float32)
-    K, sensor = rig["intrinsics"], rig["sensor_size"]
-    vid, _, _ = po.ray_voxel_intersection_perspective(vol, ori, view, np.array([0, 0, 1], np.float32), K[0],
-                                                      [K[5], K[2]], [sensor[1], sensor[0]], 1)
-    vp = vid.squeeze().astype(np.int64) - 1
-    ins = points[:, 4][np.clip(vp, 0, None)].copy()
-    ins[vp == -1] = null_id
-    return vp, ins
-
-
 def test_get_visible_points_end_to_end(cuda_device, po):
     """maps -> extruded points -> volume -> traversal, HIP vs oracle, on a 256 px layout."""
     size = 256
@@ -219,7 +197,7 @@ def test_get_visible_points_end_to_end(cuda_device, po):
     scales = np.repeat(points[:, [3]], 3, axis=1)  # utils/helpers.get_point_scales without special classes
     rig, cam_pos, cam_quat = synth.layout_camera(size, W=240, H=136)
     vp, ins = P.get_visible_points(points, scales, rig, cam_pos.copy(), cam_quat, null_class_id=0)
-    vp_o, ins_o = _visible_points_oracle(po, points, scales, rig, cam_pos, cam_quat, 0)
+    vp_o, ins_o = U.visible_points_oracle(po, points, scales, rig, cam_pos, cam_quat, 0)
     assert vp.shape == (136, 240) and np.array_equal(vp, vp_o) and np.array_equal(ins, ins_o)
     assert (vp >= 0).mean() > 0.5
     # the device-resident form, plain walk and with empty-space jumps
