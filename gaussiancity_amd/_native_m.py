@@ -4,7 +4,8 @@ of a PTv3 Block (gcm_ffn_*: LayerNorm, MLP and residual in one launch, its backw
 (gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection in one launch, its backward)
 and the middle of the same Block (gcm_mid_*: the patch gather and its gradient, the scatter back, the output projection,
 DropPath and the residual in one launch, its backward) and the seams between the backbone's stages (gcm_seam_*: Linear,
-BatchNorm1d and GELU as one operator in eval and training mode, its backward), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
+BatchNorm1d and GELU as one operator in eval and training mode, its backward) and the attribute head at inference in one
+launch per output key (gcm_head_chain), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
 The library is the product: no Python/CPU fallback -- a missing library or failing call raises RuntimeError."""
 import ctypes as C
 
@@ -53,6 +54,10 @@ _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argt
     "gcm_seam_backward_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "gcm_seam_backward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, C.c_int, _i64, _i32, _i32,
                                     _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcm_head_chain_max_hidden": (C.c_int, []),
+    "gcm_head_chain_max_in": (C.c_int, []),
+    "gcm_head_chain": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                 _i32, _i32, _i32, _i32, _i32, C.c_int, _f32, _f32, _vp, _vp]),
 }
 
 _L = _loader.Library("gcm", "libgcm_hip.so", ABI_VERSION, _SIGNATURES)

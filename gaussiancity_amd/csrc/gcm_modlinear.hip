@@ -27,7 +27,9 @@
 // included after it.  DESIGN.md section 19.  The fourth, the middle of the same Block around its attention (gcm_mid_*: the
 // patch gather, and the scatter back, the output projection, DropPath and the residual in one launch), is gcm_mid.h.
 // DESIGN.md section 20.  The fifth, the seams between the backbone's stages (gcm_seam_*: Linear, BatchNorm1d and GELU as
-// one operator up to 512 channels), is gcm_seam.h, included last.  DESIGN.md section 21.
+// one operator up to 512 channels), is gcm_seam.h.  DESIGN.md section 21.  The sixth is the attribute head itself at
+// inference, its three layers in one launch per output key (gcm_head_chain), gcm_chain.h, included last.  DESIGN.md
+// section 17b.
 // What the five share -- the 64-row tile, the product loop of the four fused operators, the host rules of the plans -- is
 // gcm_tile.h, included first.  DESIGN.md section 17a.
 #include <hip/hip_runtime.h>
@@ -507,6 +509,7 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 #include "gcm_front.h"
 #include "gcm_mid.h"
 #include "gcm_seam.h"
+#include "gcm_chain.h"
 
 namespace {
 
@@ -1105,6 +1108,49 @@ int gcm_seam_backward(const float* x, int64_t x_stride, const float* z, int64_t 
                                                                          nullptr);
     HIP_TRY(hipGetLastError(), "seam backward weight gradient launch");
   }
+  return GCM_OK;
+}
+
+int gcm_head_chain_max_hidden(void) { return kChainMaxHidden; }
+int gcm_head_chain_max_in(void) { return kChainMaxIn; }
+
+int gcm_head_chain(const float* x, int64_t x_stride, const float* onehots, int64_t onehots_stride, const float* w1,
+                   int64_t w1_stride, const float* b1, const float* w_ma, const float* w2, int64_t w2_stride,
+                   const float* alpha, const float* beta, const float* bias2, const int32_t* group, const float* w_out,
+                   const float* b_out, int64_t N, int32_t I, int32_t K, int32_t H, int32_t G, int32_t C, int kind,
+                   float factor, float slope, float* out, void* hip_stream) {
+  const std::string who("gcm_head_chain");
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": N out of range");
+  if (I <= 0 || I % 4 != 0 || I > kChainMaxIn)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": I must be a positive multiple of 4, at most gcm_head_chain_max_in()");
+  if (H <= 0 || H % 4 != 0 || H > kChainMaxHidden)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": H must be a positive multiple of 4, at most gcm_head_chain_max_hidden()");
+  if (K < 1 || K > kChainMaxClasses) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": K must be in 1..32");
+  if (G < 1 || G > kMaxGroups) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": G must be in 1..2^20");
+  if (C != 1 && C != 3) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": C must be 1 or 3");
+  if (kind != GCM_XYZ && kind != GCM_RGB && kind != GCM_SCALE && kind != GCM_OPACITY)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": unknown kind");
+  if (!std::isfinite(factor)) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": factor is not finite");
+  if (!std::isfinite(slope) || slope <= 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": slope must be finite and > 0");
+  if (int rc = check_strides(who, {{x_stride, I}, {w1_stride, I}, {w2_stride, H}})) return rc;
+  if (onehots_stride < K) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": onehots_stride below K");
+  if (int rc = check_aligned16(who, {x, w1, b1, w_ma, w2, alpha, beta, bias2, w_out, b_out, out})) return rc;
+  if ((reinterpret_cast<uintptr_t>(onehots) & 3u) != 0 || (reinterpret_cast<uintptr_t>(group) & 3u) != 0)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": onehots and group must be 4-byte aligned");
+  if (N == 0) return GCM_OK;
+  if (!x || !onehots || !w1 || !b1 || !w_ma || !w2 || !w_out || !out)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, onehots, w1, b1, w_ma, w2, w_out or out");
+  HIP_TRY(chain_lds_attr(), "head_chain LDS attribute");
+  ChainArgs a;
+  a.x = x, a.onehots = onehots, a.w1 = w1, a.b1 = b1, a.wma = w_ma, a.w2 = w2, a.alpha = alpha, a.beta = beta, a.bias2 = bias2;
+  a.wout = w_out, a.bout = b_out, a.group = group, a.out = out;
+  a.xs = x_stride, a.os = onehots_stride, a.w1s = w1_stride, a.w2s = w2_stride, a.N = N;
+  a.I = I, a.K = K, a.H = H, a.G = G, a.kind = kind, a.factor = factor, a.slope = slope;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t lds = chain_lds_bytes(H);
+  if (C == 1) k_head_chain<1><<<blocks_for(N, T), kChainThreads, lds, st>>>(a);
+  else k_head_chain<3><<<blocks_for(N, T), kChainThreads, lds, st>>>(a);
+  HIP_TRY(hipGetLastError(), "head_chain launch");
   return GCM_OK;
 }
 

@@ -2,7 +2,9 @@
 // attribute head in gcm_modlinear.hip, which includes this file first): the 64-row workgroup tile, its accumulators, the
 // ONE product loop on v_mfma_f32_16x16x4_f32 in its two forms, the tile staging loop, the LayerNorm over a row's four
 // lanes both ways with its column sums, and the host rules every plan repeats.  Device code is __forceinline__ and takes
-// its per-operator parts as callables; nothing is called through a pointer.  DESIGN.md section 17a.
+// its per-operator parts as callables; nothing is called through a pointer.  DESIGN.md section 17a.  (gcm_chain.h, the
+// attribute head in one launch, takes the constants, the accumulators and the epilogue nest from here and runs Chain's loop
+// written out for its 512 threads.)
 //
 // The tile.  A workgroup of 256 threads (4 waves as 2 x 2) owns T = 64 rows; a wave owns 32 rows x 16 J columns as
 // f4 acc[2][J] (C/D layout of the MFMA: column = lane & 15, row = 4 * (lane >> 4) + register), J = 1, 2 or 4, its first

@@ -5,6 +5,8 @@
         alpha, beta, bias and group may each be None; gradients for x, weight, alpha, beta and bias, deterministic.
   groups_from_masks(masks, n)     int32 [n]: the largest g whose boolean mask has the row set, -1 where none has
   head_out(f, weight, bias, group, kind, factor)     the head's last linear layer and output transform, inference only
+  head_chain(x, onehots, w1, b1, w_ma, w2, alpha, beta, bias2, group, w_out, b_out, kind, factor, negative_slope)
+        the whole head for one output key in one launch, inference only: neither hidden activation reaches memory
 
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
 the HIP library, float32 throughout, and nothing here waits for the device.
@@ -17,6 +19,7 @@ from ._loader import current_stream as _stream
 KINDS = tuple(M.KINDS)
 
 _STATS = {"forward_calls": 0, "backward_calls": 0, "groups_from_masks_calls": 0, "head_out_calls": 0}
+_CHAIN_STATS = {"head_chain_calls": 0}  # beside stats(), whose keys callers compare as a set
 
 
 def stats():
@@ -24,9 +27,16 @@ def stats():
     return dict(_STATS)
 
 
+def chain_stats():
+    """Counters of this process: calls of head_chain."""
+    return dict(_CHAIN_STATS)
+
+
 def reset_stats():
     for k in _STATS:
         _STATS[k] = 0
+    for k in _CHAIN_STATS:
+        _CHAIN_STATS[k] = 0
 
 
 def dtypes():
@@ -190,4 +200,67 @@ def head_out(f, weight, bias, group, kind, factor):
         M.check(M.lib().gcm_head_out(f.data_ptr(), f.stride(0), weight.data_ptr(), _ptr(bias), _ptr(group), N, I, Cn,
                                      M.KINDS[kind], float(factor), out.data_ptr(), _stream()), "gcm_head_out")
     _STATS["head_out_calls"] += 1
+    return out
+
+
+def head_chain_limits():
+    """(largest I, largest H) head_chain runs in this build.  Loads the library."""
+    L = M.lib()
+    return L.gcm_head_chain_max_in(), L.gcm_head_chain_max_hidden()
+
+
+def head_chain(x, onehots, w1, b1, w_ma, w2, alpha, beta, bias2, group, w_out, b_out, kind, factor, negative_slope):
+    """The attribute head for one output key in ONE launch, inference only (no autograd):
+        f = leaky(x @ w1.T + onehots @ w_ma.T + b1);  h = leaky((f * alpha[group]) @ w2.T + beta[group] + bias2);
+        transform(h @ w_out.T + b_out)
+    for x [N, I], onehots [N, K] (any values), w1 [H, I], b1 [H], w_ma [H, K], w2 [H, H], alpha and beta [G, H] or None,
+    bias2 [H] or None, group int32 [N] or None, w_out [C, H] (C = 1 or 3), b_out [C] or None, kind in KINDS.  I and H are
+    multiples of 4 within head_chain_limits(), K is 1 .. 32; rows of group -1 are zeros.  Returns [N, C]."""
+    if kind not in M.KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(KINDS), kind))
+    for name, t in (("x", x), ("onehots", onehots), ("w1", w1), ("w_ma", w_ma), ("w2", w2), ("w_out", w_out)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError("x must be [N, I], onehots [N, K], w1 [H, I], w_ma [H, K], w2 [H, H] and w_out [C, H]; %s is not "
+                             "a matrix" % name)
+    (N, I), K, H, Cn = x.shape, onehots.shape[1], w1.shape[0], w_out.shape[0]
+    if I % 4 or H % 4 or I == 0 or H == 0 or Cn not in (1, 3) or not 1 <= K <= 32:
+        raise ValueError("I and H must be positive multiples of 4, K in 1..32 and C 1 or 3, got I = %d, H = %d, K = %d, C = %d"
+                         % (I, H, K, Cn))
+    G = alpha.shape[0] if isinstance(alpha, torch.Tensor) and alpha.dim() == 2 else (
+        beta.shape[0] if isinstance(beta, torch.Tensor) and beta.dim() == 2 else 1)
+    op = "the chained head"
+    _check_float("x", x, (N, I), op)
+    _check_float("onehots", onehots, (N, K), op)
+    _check_float("w1", w1, (H, I), op)
+    _check_float("b1", b1, (H,), op)
+    _check_float("w_ma", w_ma, (H, K), op)
+    _check_float("w2", w2, (H, H), op)
+    _check_float("alpha", alpha, (G, H), op, optional=True)
+    _check_float("beta", beta, (G, H), op, optional=True)
+    _check_float("bias2", bias2, (H,), op, optional=True)
+    _check_float("w_out", w_out, (Cn, H), op)
+    _check_float("b_out", b_out, (Cn,), op, optional=True)
+    if G < 1:
+        raise ValueError("alpha and beta need at least one group")
+    max_in, max_hidden = head_chain_limits()
+    if I > max_in or H > max_hidden:
+        raise ValueError("the chained head runs I <= %d and H <= %d, got I = %d, H = %d" % (max_in, max_hidden, I, H))
+    slope = float(negative_slope)
+    if not slope > 0.0:
+        raise ValueError("negative_slope must be > 0, got %r" % slope)
+    group = _check_group(group, N)
+    dense = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+    x, w1, w2 = _rows(x.detach()), _rows(w1.detach()), _rows(w2.detach())
+    onehots = onehots.detach()
+    if N and (onehots.stride(1) != 1 or onehots.stride(0) < K):
+        onehots = onehots.contiguous()
+    b1, w_ma, alpha, beta, bias2, w_out, b_out = (dense(t) for t in (b1, w_ma, alpha, beta, bias2, w_out, b_out))
+    out = x.new_empty((N, Cn))
+    with torch.cuda.device(x.device):
+        M.check(M.lib().gcm_head_chain(x.data_ptr(), x.stride(0), onehots.data_ptr(), onehots.stride(0) if N else K,
+                                       w1.data_ptr(), w1.stride(0), b1.data_ptr(), w_ma.data_ptr(), w2.data_ptr(), w2.stride(0),
+                                       _ptr(alpha), _ptr(beta), _ptr(bias2), _ptr(group), w_out.data_ptr(), _ptr(b_out), N, I, K,
+                                       H, G, Cn, M.KINDS[kind], float(factor), slope, out.data_ptr(), _stream()),
+                "gcm_head_chain")
+    _CHAIN_STATS["head_chain_calls"] += 1
     return out

@@ -211,6 +211,28 @@
  *     launches.  With w == NULL dx is dz (one elementwise launch) and there is no dw or db.  workspace is
  *     gcm_seam_backward_workspace_bytes(N, I, O) bytes, 256-byte aligned.  Slices and groups depend on N, I and O alone:
  *     every output is bit-identical from run to run and independent of how many workgroups the device holds at a time.
+ *
+ * ---- The attribute head at inference in one launch per output key --------------------------------
+ * For N rows, I input features, K class columns, H hidden features and C = 1 or 3 outputs, all float32, g = group[r]
+ * (group == NULL: every row has g = 0):
+ *     f   = leaky(x[r] W1^T + onehots[r] Wma^T + b1)          w1 [H][I] row stride w1_stride, b1 [H], w_ma [H][K] contiguous
+ *     h   = leaky((f o alpha[g]) W2^T + beta[g] + bias2)      w2 [H][H] row stride w2_stride; alpha, beta [G][H], bias2 [H]
+ *     out = T(h Wout^T + bout)                                w_out [C][H] contiguous, b_out [C]; T by gcm_kind as gcm_head_out
+ *   alpha, beta, bias2 and b_out may each be NULL (ones, zeros, zeros, zeros): a plain Linear is alpha = beta = NULL with
+ *   bias2 its bias, a ModLinear(output_mode, mod_bias, bias=None) is alpha and beta with bias2 = NULL.  A row whose group is
+ *   outside 0 .. G-1 gives exact zeros.  I and H are positive multiples of 4, I <= gcm_head_chain_max_in() (256 in this
+ *   build) and H <= gcm_head_chain_max_hidden() (512); 1 <= K <= 32.  x is row-strided under the rule above; onehots is
+ *   dense float32 [N][K] of ANY values with a row stride in elements of at least K, 4-byte aligned; every other float
+ *   pointer is 16-byte aligned.  out is contiguous [N][C].  slope is finite and > 0, factor finite.
+ * gcm_head_chain: one launch, no workspace; neither f nor h reaches memory.  N == 0 returns 0 and queues nothing.  Every
+ *     product runs on v_mfma_f32_16x16x4_f32: f is one fp32 chain from 0 over x's features in ascending order (I rounded
+ *     up to 16 with zeros) and then over the K class columns, b1 added after the chain; h is one chain over H, then beta,
+ *     then bias2; out is, per row and per quarter (64 columns) of every chunk of 256 columns, 16 lanes that each chain fmaf
+ *     over their columns (lane l: l, l + 16, l + 32, l + 48 of the quarter) over the chunks in ascending order, added by a
+ *     fixed exchange tree (lanes 8, 4, 2, 1 apart), the four quarters in ascending order, then b_out; T in double, rounded
+ *     once.  No float atomics: a row's bits depend on that row's inputs and the parameters alone -- not on N, the row's
+ *     position or the run.  The kernel needs up to 157 184 bytes of LDS, which it asks the runtime for on the first call;
+ *     a refusal comes back as GCM_ERR_HIP with the text.
  */
 #ifndef GCM_H
 #define GCM_H
@@ -325,6 +347,14 @@ int gcm_seam_backward(const float* x, int64_t x_stride, const float* z, int64_t 
                       const float* bn_b, int act, int batch_stats, int64_t N, int32_t I, int32_t O, float* dx,
                       int64_t dx_stride, float* dw, float* db, float* dbn_w, float* dbn_b, void* workspace,
                       size_t workspace_bytes, void* hip_stream);
+
+int gcm_head_chain_max_hidden(void);
+int gcm_head_chain_max_in(void);
+int gcm_head_chain(const float* x, int64_t x_stride, const float* onehots, int64_t onehots_stride, const float* w1,
+                   int64_t w1_stride, const float* b1, const float* w_ma, const float* w2, int64_t w2_stride,
+                   const float* alpha, const float* beta, const float* bias2, const int32_t* group, const float* w_out,
+                   const float* b_out, int64_t N, int32_t I, int32_t K, int32_t H, int32_t G, int32_t C, int kind,
+                   float factor, float slope, float* out, void* hip_stream);
 
 #ifdef __cplusplus
 }
