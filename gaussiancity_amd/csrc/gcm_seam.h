@@ -12,16 +12,16 @@
 //              (eval), and a thread per column walks the tile's valid rows in ascending order: the mean (taken about the
 //              tile's first row), then, about that mean, the centred second moment M2.  A tile's record in the workspace:
 //              [2][O] = mean, M2 (the count of tile t is min(64, N - 64 t)).
-//   statistics k_seam_stats: per column the tiles' (count, mean, M2) merged in ascending tile order (the parallel-variance
-//              merge; never sum z^2 - (sum z)^2 / N); beyond 64 tiles, G <= 64 groups of consecutive tiles are merged
-//              first (each by one thread, the same launch) and the groups then in ascending order.  The mean written is
-//              a compensated sum of count_t mean_t in that same order, divided by N.
+//   statistics k_seam_stats: per column two passes over the tiles' records in ascending tile order: the mean, a compensated
+//              sum of count_t mean_t divided by N, then M2 = sum_t (M2_t + count_t (mean_t - mean)^2), compensated (never
+//              sum z^2 - (sum z)^2 / N); beyond 64 tiles, G <= 64 groups of consecutive tiles are summed first (each by
+//              one thread, the same launch) and the groups then in ascending order.
 //   apply      k_seam_apply: y = act(((z - mean) rstd) g + h), 16-byte accesses.
 //   backward   k_seam_bwd_part / k_seam_bwd_fold: dh = sum du, dg = sum du zhat, per tile four chains of 16 rows added in
-//              order, the tiles in ascending order (grouped as the statistics).  k_seam_dx: dz recomputed into LDS per 64
-//              rows and chunk of <= 128 outputs, never stored; dx is, PER CHUNK, one fp32 chain from 0 over the chunk's
-//              outputs in ascending order, the chunks' results added in ascending order.  k_seam_dw: dw_slice_tile with a
-//              fetch that recomputes dz, then k_ffn_fold_params' pairwise tree.
+//              order, the tiles in ascending order with a compensated sum (grouped as the statistics).  k_seam_dx: dz
+//              recomputed into LDS per 64 rows and chunk of <= 128 outputs, never stored; dx is, PER CHUNK, one fp32 chain
+//              from 0 over the chunk's outputs in ascending order, the chunks' results added in ascending order.
+//              k_seam_dw: dw_slice_tile with a fetch that recomputes dz, then k_ffn_fold_params' pairwise tree.
 // Channels beyond I / O and rows beyond N are staged as zeros and never stored.
 #pragma once
 
@@ -171,52 +171,72 @@ __global__ __launch_bounds__(256) void k_seam_tile_stats(const float* __restrict
   }
 }
 
+// fn(t, a, b) for the tiles t0 .. t1 in ascending order with a = part[t][0][c], b = part[t][1][c]: the loads of kSeamAhead
+// tiles are issued before the first of them is consumed (a thread's walk is a chain of dependent sums; its loads are not)
+constexpr int kSeamAhead = 8;
+template <typename Fn>
+__device__ __forceinline__ void seam_walk_records(const float* __restrict__ part, int O, int c, int64_t t0, int64_t t1, Fn fn) {
+  for (int64_t t = t0; t < t1; t += kSeamAhead) {
+    float a[kSeamAhead], b[kSeamAhead];
+#pragma unroll
+    for (int j = 0; j < kSeamAhead; j++) {
+      const bool in = t + j < t1;
+      a[j] = in ? part[(t + j) * 2 * O + c] : 0.0f;
+      b[j] = in ? part[((t + j) * 2 + 1) * O + c] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < kSeamAhead; j++)
+      if (t + j < t1) fn(t + j, a[j], b[j]);
+  }
+}
+
 // ---- forward: the statistics --------------------------------------------------------------------------------------------
-// 256 threads = 64 groups x 4 columns; group q merges its gper consecutive tiles in ascending order, then the thread of
-// group 0 merges the groups in ascending order.  G == 1: one level.  The merge carries (count, mean, M2) -- the
-// parallel-variance merge, whose running mean serves M2's correction term -- and beside it a compensated sum of
-// count_t mean_t in the same order, from which the column's mean is taken: total / N, one rounding.
+// 256 threads = 64 groups x 4 columns, two passes over the tiles' records, both in ascending tile order; group q owns its
+// gper consecutive tiles, G == 1: one level.  Pass 1: a compensated sum of count_t mean_t per group; every thread of a column
+// then adds the groups' sums in ascending order -- the same chain in each, so all hold the same bits -- and the column's
+// mean is total / N, one rounding.  Pass 2: M2 = sum_t (M2_t + count_t (mean_t - mean)^2), the deviations taken about that
+// FINAL mean, compensated per group and across the groups.  A running (count, mean, M2) merge is not used: its correction
+// term (mean_t - running mean)^2 carries the running mean's rounding at first order, tile after tile with one sign, and on
+// rows that drift (a serialised point cloud) that put rstd at up to 10.7 x and running_var at up to 40.5 x torch's error
+// (262 209 rows); about the final mean those first-order terms cancel (sum_t count_t (mean_t - mean)
+// = 0).
 __global__ __launch_bounds__(256) void k_seam_stats(const float* __restrict__ part, int64_t tiles, int64_t N, int O, int G,
                                                     int64_t gper, float eps, float momentum, float* __restrict__ mean,
                                                     float* __restrict__ rstd, float* __restrict__ rmean,
                                                     float* __restrict__ rvar, int64_t* __restrict__ tracked) {
-  __shared__ float Sn[kSeamGroups][4], Sm[kSeamGroups][4], Sq[kSeamGroups][4], Ss[kSeamGroups][4], Sc[kSeamGroups][4];
+  __shared__ float Ss[kSeamGroups][4], Sc[kSeamGroups][4], Sq[kSeamGroups][4], Sd[kSeamGroups][4];
   const int q = threadIdx.x >> 2, cl = threadIdx.x & 3, c = blockIdx.x * 4 + cl;
-  float n = 0.0f, m = 0.0f, m2 = 0.0f, sum = 0.0f, comp = 0.0f;
-  auto merge = [&](float nb, float mb, float qb) {
-    if (nb == 0.0f) return;
-    if (n == 0.0f) {
-      n = nb;
-      m = mb;
-      m2 = qb;
-      return;
-    }
-    const float tot = n + nb, d = mb - m;
-    m += d * (nb / tot);
-    m2 += qb + d * d * (n * nb / tot);
-    n = tot;
-  };
-  if (q < G && c < O) {
-    const int64_t t0 = q * gper, t1 = t0 + gper < tiles ? t0 + gper : tiles;
-    for (int64_t t = t0; t < t1; t++) {
-      const float nb = (float)(N - t * T < T ? N - t * T : T), mb = part[t * 2 * O + c];
-      merge(nb, mb, part[(t * 2 + 1) * O + c]);
-      kahan_add(sum, comp, nb * mb);
-    }
-  }
-  Sn[q][cl] = n;
-  Sm[q][cl] = m;
-  Sq[q][cl] = m2;
+  const bool own = q < G && c < O;
+  const int64_t t0 = q * gper, t1 = t0 + gper < tiles ? t0 + gper : tiles;
+  auto count = [&](int64_t t) { return (float)(N - t * T < T ? N - t * T : T); };
+  float sum = 0.0f, comp = 0.0f;
+  if (own) seam_walk_records(part, O, c, t0, t1, [&](int64_t t, float mt, float) { kahan_add(sum, comp, count(t) * mt); });
   Ss[q][cl] = sum;
   Sc[q][cl] = comp;
   __syncthreads();
-  if (q != 0 || c >= O) return;
+  sum = Ss[0][cl];
+  comp = Sc[0][cl];
   for (int k = 1; k < G; k++) {
-    merge(Sn[k][cl], Sm[k][cl], Sq[k][cl]);
     kahan_add(sum, comp, Ss[k][cl]);
     kahan_add(sum, comp, -Sc[k][cl]);
   }
-  m = (sum - comp) / (float)N;
+  const float m = (sum - comp) / (float)N;
+  float m2 = 0.0f, mc = 0.0f;
+  if (own)
+    seam_walk_records(part, O, c, t0, t1, [&](int64_t t, float mt, float qt) {
+      const float d = mt - m;
+      kahan_add(m2, mc, qt);
+      kahan_add(m2, mc, count(t) * (d * d));
+    });
+  Sq[q][cl] = m2;
+  Sd[q][cl] = mc;
+  __syncthreads();
+  if (q != 0 || c >= O) return;
+  for (int k = 1; k < G; k++) {
+    kahan_add(m2, mc, Sq[k][cl]);
+    kahan_add(m2, mc, -Sd[k][cl]);
+  }
+  m2 -= mc;
   mean[c] = m;
   rstd[c] = 1.0f / sqrtf(m2 / (float)N + eps);
   if (rmean) {  // one thread per column, plain stores
@@ -277,28 +297,35 @@ __global__ __launch_bounds__(256) void k_seam_bwd_part(const float* __restrict__
   }
 }
 
-// k_seam_stats' layout with plain sums; `keep` [2][O] = dh, dg for the kernels that form dz
+// k_seam_stats' layout; compensated sums in the same fixed order (plain sums over 4098 tiles had dbn_b at 5.35 x torch's
+// figure); `keep` [2][O] = dh, dg for the kernels that form dz
 __global__ __launch_bounds__(256) void k_seam_bwd_fold(const float* __restrict__ part, int64_t tiles, int O, int G,
                                                        int64_t gper, float* __restrict__ dg, float* __restrict__ dh,
                                                        float* __restrict__ keep) {
-  __shared__ float Sh[kSeamGroups][4], Sg[kSeamGroups][4];
+  __shared__ float Sh[kSeamGroups][4], Sg[kSeamGroups][4], Ch[kSeamGroups][4], Cg[kSeamGroups][4];
   const int q = threadIdx.x >> 2, cl = threadIdx.x & 3, c = blockIdx.x * 4 + cl;
-  float sh = 0.0f, sg = 0.0f;
+  float sh = 0.0f, sg = 0.0f, ch = 0.0f, cg = 0.0f;
   if (q < G && c < O) {
     const int64_t t0 = q * gper, t1 = t0 + gper < tiles ? t0 + gper : tiles;
-    for (int64_t t = t0; t < t1; t++) {
-      sh += part[t * 2 * O + c];
-      sg += part[(t * 2 + 1) * O + c];
-    }
+    seam_walk_records(part, O, c, t0, t1, [&](int64_t, float ht, float gt) {
+      kahan_add(sh, ch, ht);
+      kahan_add(sg, cg, gt);
+    });
   }
   Sh[q][cl] = sh;
   Sg[q][cl] = sg;
+  Ch[q][cl] = ch;
+  Cg[q][cl] = cg;
   __syncthreads();
   if (q != 0 || c >= O) return;
   for (int k = 1; k < G; k++) {
-    sh += Sh[k][cl];
-    sg += Sg[k][cl];
+    kahan_add(sh, ch, Sh[k][cl]);
+    kahan_add(sh, ch, -Ch[k][cl]);
+    kahan_add(sg, cg, Sg[k][cl]);
+    kahan_add(sg, cg, -Cg[k][cl]);
   }
+  sh -= ch;
+  sg -= cg;
   if (dh) dh[c] = sh;
   if (dg) dg[c] = sg;
   keep[c] = sh;

@@ -27,10 +27,13 @@ def bits(t):
     return t.contiguous().view(torch.int32)
 
 
-def make_inputs(N, I, O, seed, product=True, exact=False):
+def make_inputs(N, I, O, seed, product=True, exact=False, drift=0.0):
     """Seeded normals: w scaled by 1 / sqrt(fan-in), small biases, g = 1 + 0.5 n, non-trivial running statistics and a
     counter at 7.  Column FAR of z gets a mean of 100 standard deviations (through b, or through x without a product): the
-    case that a sum z^2 - (sum z)^2 / N formulation loses.  product=False: x is [N, O]."""
+    case that a sum z^2 - (sum z)^2 / N formulation loses.  product=False: x is [N, O].
+    drift: a ramp linspace(0, drift, N) over the rows, as the features of a serialised point cloud move along its curve:
+    the tiles' means then differ and the correction term of the variance merge carries most of the variance.  With the
+    product it is added to column 0 of x (every column of z drifts through w[:, 0]), without it to column 2 of x."""
     g = torch.Generator().manual_seed(seed)
     n = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
     if not product:
@@ -43,21 +46,23 @@ def make_inputs(N, I, O, seed, product=True, exact=False):
     else:
         inp["w"] = inp["b"] = None
         inp["x"][:, FAR] += 100.0
+    if drift:
+        inp["x"][:, 0 if product else 2] += torch.linspace(0, drift, N)
     return inp
 
 
-def torch_ops(t, buf, training, act):
+def torch_ops(t, buf, training, act, momentum=MOMENTUM):
     z = t["x"] if t["w"] is None else F.linear(t["x"], t["w"], t["b"])
-    u = F.batch_norm(z, buf["running_mean"], buf["running_var"], t["g"], t["h"], training, MOMENTUM, EPS)
+    u = F.batch_norm(z, buf["running_mean"], buf["running_var"], t["g"], t["h"], training, momentum, EPS)
     if training:
         buf["tracked"] += 1
     return F.gelu(u) if act else u
 
 
-def fused(t, buf, training, act):
+def fused(t, buf, training, act, momentum=MOMENTUM):
     from gaussiancity_amd import seam
     return seam.linear_bn_gelu(t["x"], t["w"], t["b"], t["g"], t["h"], buf["running_mean"], buf["running_var"], buf["tracked"],
-                               training=training, momentum=MOMENTUM, eps=EPS, act=act)
+                               training=training, momentum=momentum, eps=EPS, act=act)
 
 
 def _wide(value, extra_cols, fill, need):
@@ -69,9 +74,10 @@ def _wide(value, extra_cols, fill, need):
     return wide, wide[:, :W]
 
 
-def run(fn, inp, device, dtype, training, act, strided=False, need=LEAVES, retain=False, grad=True):
+def run(fn, inp, device, dtype, training, act, strided=False, need=LEAVES, retain=False, grad=True, momentum=MOMENTUM):
     """y, the gradients of `need` and the three buffers after one forward (+ backward) of fn on the device in dtype.
-    strided: x and dy as views of rows 4 elements further apart.  Returns (results on the CPU, live (y, leaves, dy, buf))."""
+    strided: x and dy as views of rows 4 elements further apart.  momentum = 1.0: the buffers afterwards are the batch mean
+    and the unbiased batch variance.  Returns (results on the CPU, live (y, leaves, dy, buf))."""
     t = {k: None if inp[k] is None else inp[k].detach().clone().to(device=device, dtype=dtype).requires_grad_(grad and k in need)
          for k in LEAVES}
     buf = {k: inp[k].clone().to(device=device, dtype=dtype) for k in ("running_mean", "running_var")}
@@ -82,12 +88,12 @@ def run(fn, inp, device, dtype, training, act, strided=False, need=LEAVES, retai
         leaf["x"], t["x"] = _wide(t["x"].detach(), 4, 0.0, grad and "x" in need)
         dy = _wide(dy, 4, 7.0, False)[1]
     if grad:
-        y = fn(t, buf, training, act)
+        y = fn(t, buf, training, act, momentum)
         if y.requires_grad:
             y.backward(dy, retain_graph=retain)
     else:
         with torch.no_grad():
-            y = fn(t, buf, training, act)
+            y = fn(t, buf, training, act, momentum)
     out = {"y": y.detach()}
     for k in LEAVES:
         gr = None if leaf[k] is None else leaf[k].grad
@@ -107,15 +113,15 @@ def figures(got, want, training):
     return fig
 
 
-def check_bar(label, cases, dev, strided=False):
+def check_bar(label, cases, dev, strided=False, momentum=MOMENTUM):
     """cases: (inputs, training, act) that share one (I, O): the worst figure of the operator over the cases against the
     worst of the yardstick, per tensor; the counter exact.  Every figure is printed before anything is asserted."""
     worst_got, worst_yard = dict.fromkeys(TENSORS, 0.0), dict.fromkeys(TENSORS, 0.0)
     wrong = []
     for inp, training, act in cases:
-        want = run(torch_ops, inp, "cpu", torch.float64, training, act)[0]
-        res = run(fused, inp, dev, torch.float32, training, act, strided)[0]
-        yres = run(torch_ops, inp, dev, torch.float32, training, act)[0]
+        want = run(torch_ops, inp, "cpu", torch.float64, training, act, momentum=momentum)[0]
+        res = run(fused, inp, dev, torch.float32, training, act, strided, momentum=momentum)[0]
+        yres = run(torch_ops, inp, dev, torch.float32, training, act, momentum=momentum)[0]
         got, yard = figures(res, want, training), figures(yres, want, training)
         for k in got:
             worst_got[k], worst_yard[k] = max(worst_got[k], got[k]), max(worst_yard[k], yard[k])

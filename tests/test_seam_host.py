@@ -15,6 +15,7 @@ import types
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 import seam_plans as P
 import seam_ref as R
@@ -71,6 +72,50 @@ def test_the_transcribed_plan_carves_what_the_library_asks_for():
         assert lib.gcm_seam_backward_workspace_bytes(10, 8, bad) == 0 and text in lib.gcm_last_error()
     assert lib.gcm_seam_backward_workspace_bytes(10, 6, 8) == 0 and b"I must be" in lib.gcm_last_error()
     assert lib.gcm_seam_backward_workspace_bytes(-1, 8, 8) == 0 and lib.gcm_last_error()
+
+
+def test_the_workspace_queries_equal_the_transcription_for_every_plan_case():
+    lib = M.lib()
+    for N, I, O in P.PLAN_CASES:
+        p = P.seam_plan(N, I, O)
+        assert lib.gcm_seam_forward_workspace_bytes(N, O) == p["forward"], (N, O, p)
+        assert lib.gcm_seam_backward_workspace_bytes(N, I, O) == p["total"], (N, I, O, p)
+        rows = sum(max(min((s + 1) * p["per"], N) - s * p["per"], 0) for s in range(p["sw"]))
+        assert rows == N and p["per"] % P.KC == 0, (N, I, O, p)         # the slices cover every row once
+        tiles = sum(max(min((q + 1) * p["gper"], p["tiles"]) - q * p["gper"], 0) for q in range(p["G"]))
+        assert tiles == p["tiles"] and (p["G"] - 1) * p["gper"] < p["tiles"], (N, I, O, p)   # and the groups every tile
+    assert set(P.NO_PRODUCT_CASES) <= set(P.PLAN_CASES) and set(P.STATISTICS_CASES) <= set(P.NO_PRODUCT_CASES)
+
+
+@pytest.mark.parametrize("shape", sorted(P.PLAN_CASES))
+def test_every_plan_case_reaches_the_branch_it_names(shape):
+    stated, derived = P.PLAN_CASES[shape], P.facts(shape)
+    assert stated and set(stated) <= set(derived)
+    wrong = {k: (v, derived[k]) for k, v in stated.items() if derived[k] != v}
+    assert not wrong, (shape, wrong)
+
+
+@pytest.mark.parametrize("name", [n for n, _ in P.BRANCH_FACTS])
+def test_every_branch_fact_is_held_by_a_plan_case(name):
+    holds = dict(P.BRANCH_FACTS)[name]
+    assert [shape for shape in P.PLAN_CASES if holds(P.facts(shape))], name
+
+
+def test_the_drift_and_momentum_knobs_default_to_the_inputs_and_the_formulation_they_had():
+    for product in (True, False):
+        a, b = R.make_inputs(70, 8, 12, 5, product), R.make_inputs(70, 8, 12, 5, product, drift=50.0)
+        col = 0 if product else 2
+        ramp = torch.linspace(0, 50.0, 70)
+        assert torch.equal(b["x"][:, col], a["x"][:, col] + ramp)
+        b["x"][:, col] = a["x"][:, col]
+        assert all((a[k] is None and b[k] is None) or torch.equal(a[k], b[k]) for k in a)
+    inp = R.make_inputs(70, 8, 12, 5)
+    plain, full = (R.run(R.torch_ops, inp, "cpu", torch.float64, True, True, **kw)[0] for kw in ({}, {"momentum": 1.0}))
+    z = F.linear(inp["x"].double(), inp["w"].double(), inp["b"].double())
+    assert torch.allclose(full["running_mean"], z.mean(0), rtol=1e-12, atol=1e-12)
+    assert torch.allclose(full["running_var"], z.var(0, unbiased=True), rtol=1e-12, atol=1e-12)
+    want = 0.99 * inp["running_mean"].double() + 0.01 * z.mean(0)
+    assert torch.allclose(plain["running_mean"], want, rtol=1e-12, atol=1e-12) and torch.equal(plain["y"], full["y"])
 
 
 @pytest.fixture()
