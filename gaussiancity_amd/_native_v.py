@@ -26,6 +26,23 @@ class ClassRule(C.Structure):
                                                           ("point_scale_factor", C.c_float)]
 
 
+class ModelRule(C.Structure):
+    """gcv_model_rule: class -> model slot (0 BLDG, 1 CAR, 2 REST, -1 dropped; scripts/inference.py:426-452) and the
+    constants of get_projection_uv (utils/helpers.py:183-194)."""
+    _fields_ = [("n_classes", C.c_int32), ("model_of_class", C.c_int8 * 32), ("proj_tlp", C.c_float * 2),
+                ("proj_size", C.c_float)]
+
+
+class GaussianSegment(C.Structure):
+    """gcv_gaussian_segment: one model's rows and the generator's outputs for them (NULL = the key is absent)."""
+    _fields_ = [("n", C.c_int64)] + [(n, C.c_void_p) for n in ("rgb", "dxyz", "scale", "opacity")]
+
+
+class GaussianAttrs(C.Structure):
+    """gcv_gaussian_attrs: up to three segments, passed by value."""
+    _fields_ = [("n_segments", C.c_int32), ("seg", GaussianSegment * 3)]
+
+
 _vp, _i32, _i64, _sz, _f32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_int
 _pi32, _pf32, _seg = C.POINTER(_i32), C.POINTER(_f32), C.POINTER(SegIns)
 _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argtypes)
@@ -48,6 +65,13 @@ _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argt
     "gcv_visible_count": (_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _sz, C.POINTER(_i64), _vp]),
     "gcv_visible_emit": (_int, [_vp, _i64, _vp, _i64, _vp, _i32, C.POINTER(ClassRule), _vp, _sz, _i64, _i64,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gcv_model_split_models": (_int, []),
+    "gcv_model_split_workspace_bytes": (_sz, [_i64, _i64]),
+    "gcv_model_split_count": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, C.POINTER(ModelRule), _vp, _sz,
+                                     C.POINTER(_i64), _vp]),
+    "gcv_model_split_emit": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, C.POINTER(ModelRule), _vp,
+                                    _sz, C.POINTER(_i64)] + [_vp] * 11),
+    "gcv_gaussian_points": (_int, [_vp, _i64, _vp, _i64, _i64, GaussianAttrs, _vp, _vp]),
     "gcv_set_option": (_int, [C.c_char_p, _int]),
     "gcv_get_stage_ms": (_int, [_pf32, _int]),
 }

@@ -6,6 +6,7 @@ codes, one ModLinear per key; every instance in the same launch through the grou
 
   install(generator) / uninstall(generator)   rebind GaussianAttrMLP.forward of a caller's imported models.generator
   stats() / reset_stats()                      forwards that took the chain, forwards passed on to the method bound before
+  grouped_stats()                              chained forwards whose zs was a model_inputs.GroupedCodes (no masks folded)
 
 A second layer beside attr_head, installed separately: attr_head keeps the calls with gradients (and its counters).  The
 method that sees a call first is the one installed last, so install attr_chain after attr_head for the chain to take the
@@ -25,8 +26,10 @@ fc_out: that is the layer the chain runs.  With codes a later instance wins wher
 import torch
 
 from . import attr_head, modlinear
+from .model_inputs import GroupedCodes
 
 _STATS = {"chain_calls": 0, "passed_on_calls": 0}
+_GROUPED_STATS = {"grouped_calls": 0}  # beside stats(), whose two keys callers compare as a whole
 _ORIGINAL = "_gaussiancity_amd_attr_chain_original"
 _BOUND = "_gaussiancity_amd_attr_chain_bound"
 
@@ -36,9 +39,17 @@ def stats():
     return dict(_STATS)
 
 
+def grouped_stats():
+    """Counter of this process: chained forwards whose zs was a model_inputs.GroupedCodes -- its group vector and code
+    table were used as they are, without groups_from_masks and the torch.cat of the codes."""
+    return dict(_GROUPED_STATS)
+
+
 def reset_stats():
     for k in _STATS:
         _STATS[k] = 0
+    for k in _GROUPED_STATS:
+        _GROUPED_STATS[k] = 0
 
 
 def _f32(t):
@@ -85,6 +96,8 @@ def _plan(self, mod_linear, pt_feat, onehots, zs):
     if zs is not None:
         if len(zs) == 0 or pt_feat.shape[0] != 1:
             return None
+        if isinstance(zs, GroupedCodes):
+            return plan if attr_head.grouped_ok(zs, pt_feat.shape[1]) else None
         if not all(_f32(v["z"]) and v["idx"].dtype == torch.bool and v["idx"].is_cuda for v in zs.values()):
             return None
     return plan
@@ -104,7 +117,10 @@ def _forward(original, generator_module):
         x, hot = pt_feat.reshape(b * n, I), onehots.reshape(b * n, onehots.shape[2])
         slope = self.act.negative_slope
         group = codes = None
-        if zs is not None:
+        if isinstance(zs, GroupedCodes):  # the split already holds what the masks would be folded into
+            group, codes = zs.group, zs.codes
+            _GROUPED_STATS["grouped_calls"] += 1
+        elif zs is not None:
             group = modlinear.groups_from_masks([v["idx"] for v in zs.values()], n)
             codes = torch.cat([v["z"].reshape(1, -1) for v in zs.values()])
         output = {}

@@ -6,6 +6,7 @@ on the number of instances, and nothing waits for the device.
 
   install(generator) / uninstall(generator)   rebind GaussianAttrMLP.forward of a caller's imported models.generator
   stats() / reset_stats()                      calls that took the fused path, calls that went to the module's own method
+  grouped_stats()                              fused calls whose zs was a model_inputs.GroupedCodes (no masks folded)
 
 The module's own method runs, untouched, for zs None (the background generator), CPU tensors, autocast or a dtype other
 than float32, a batch other than 1, a layer that is not a ModLinear with output_mode=True, mod_bias=True, bias=None, and
@@ -14,8 +15,10 @@ dimensions that are not multiples of 4.
 import torch
 
 from . import modlinear
+from .model_inputs import GroupedCodes
 
 _STATS = {"fused_calls": 0, "original_calls": 0}
+_GROUPED_STATS = {"grouped_calls": 0}  # beside stats(), whose two keys callers compare as a whole
 _ORIGINAL = "_gaussiancity_amd_attr_head_original"
 
 
@@ -24,9 +27,25 @@ def stats():
     return dict(_STATS)
 
 
+def grouped_stats():
+    """Counter of this process: fused forwards whose zs was a model_inputs.GroupedCodes -- its group vector and code table
+    were used as they are, without groups_from_masks and the torch.cat of the codes."""
+    return dict(_GROUPED_STATS)
+
+
 def reset_stats():
     for k in _STATS:
         _STATS[k] = 0
+    for k in _GROUPED_STATS:
+        _GROUPED_STATS[k] = 0
+
+
+def grouped_ok(zs, n):
+    """zs is a GroupedCodes the kernels can take as it is: a contiguous int32 CUDA group vector of n rows and contiguous
+    float32 CUDA codes."""
+    group, codes = zs.group, zs.codes
+    return (group.is_cuda and group.dtype == torch.int32 and tuple(group.shape) == (n,) and group.is_contiguous()
+            and codes.is_cuda and codes.dtype == torch.float32 and codes.dim() == 2 and codes.is_contiguous())
 
 
 def _layers(self):
@@ -54,6 +73,8 @@ def _fusable(self, mod_linear, pt_feat, onehots, zs):
             return False
     if self.fc_1.weight.dtype != torch.float32 or self.fc_1.weight.shape[0] % 4:
         return False
+    if isinstance(zs, GroupedCodes):
+        return grouped_ok(zs, pt_feat.shape[1])
     return all(v["z"].dtype == torch.float32 and v["z"].is_cuda and v["idx"].dtype == torch.bool and v["idx"].is_cuda
                for v in zs.values())
 
@@ -70,8 +91,12 @@ def _forward(original, mod_linear):
         n = pt_feat.shape[1]
         slope = self.act.negative_slope
         f = self.act(self.fc_1(pt_feat) + self.fc_m_a(onehots))[0]
-        group = modlinear.groups_from_masks([v["idx"] for v in zs.values()], n)
-        codes = torch.cat([v["z"].reshape(1, -1) for v in zs.values()])
+        if isinstance(zs, GroupedCodes):  # the split already holds what the masks would be folded into
+            group, codes = zs.group, zs.codes
+            _GROUPED_STATS["grouped_calls"] += 1
+        else:
+            group = modlinear.groups_from_masks([v["idx"] for v in zs.values()], n)
+            codes = torch.cat([v["z"].reshape(1, -1) for v in zs.values()])
 
         def layer(fc, h):
             alpha = torch.addmm(fc.bias_alpha, codes, fc.weight_alpha.t())

@@ -1,5 +1,6 @@
 // gcv_points.hip -- MI355X (gfx950) kernels + C ABI (include/gcv.h) of the point-generation /
-// visibility path: footprint extruder (K15), points -> volume (K14), ray/voxel traversal (K12), visible point set (K16).
+// visibility path: footprint extruder (K15), points -> volume (K14), ray/voxel traversal (K12), visible point set (K16);
+// gcv_split.h, included at the end: per-model generator inputs (K17) and [N][14] assembly (K18).
 // Reference behaviour: extensions/footprint_extruder/footprint_extruder.cpp ("fe/"),
 // extensions/voxlib/{points_to_volume,ray_voxel_intersection}.cu, voxlib_common.h ("vox/").
 //
@@ -1362,3 +1363,5 @@ int gcv_visible_emit(const int64_t* vp_map, int64_t n_pixels, const int16_t* row
 }
 
 }  // extern "C"
+
+#include "gcv_split.h"  // K17 / K18: per-model generator inputs and [N][14] assembly

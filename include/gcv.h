@@ -18,6 +18,11 @@
  *                                          :345-360 (_get_normalized_pt_cords), :229-237 with :535-598
  *                                          (_instances_to_classes) and utils/helpers.py:197-223 (get_point_scales):
  *                                          numpy / a Python loop over instances upstream (ABI v5)
+ *   gcv_model_split_count / _emit          scripts/inference.py:239-253 up to the generator calls (:399-507 with
+ *                                          utils/helpers.py:127-133 and :183-194): masks, gathers, a Python loop per model
+ *                                          and per visible instance upstream (additive to ABI v5)
+ *   gcv_gaussian_points                    utils/helpers.py:226-247 (get_gaussian_points) and the per-key torch.cat of
+ *                                          scripts/inference.py:500-501
  *   gcv_build_occupancy                    (none upstream: 1 bit per 16x16x16 macro cell; lets the traversal
  *                                           jump across empty macro cells, reproducing the reference walk
  *                                           exactly -- results unchanged)
@@ -169,6 +174,73 @@ int gcv_visible_emit(const int64_t* vp_map, int64_t n_pixels, const int16_t* row
                      size_t workspace_bytes, int64_t n_visible, int64_t n_instances, int64_t* point_index,
                      float* points8, int32_t* batch_index, int16_t* instances, float* classes, float* scales3,
                      void* hip_stream);
+
+/* ---- K17: visible point set -> per-model generator inputs (additive to ABI v5; probe gcv_model_split_models) ----
+ * What scripts/inference.py:239-253 does between the visible set and the generators (_get_pt_indexes_by_models,
+ * _get_pt_attrs_by_models, _get_z, utils/helpers.py get_one_hot and get_projection_uv), for K16's outputs as they lie
+ * on the device.  A row's model is a function of its class; the per-model batch renumbering and the style groups are
+ * prefix counts over K-bit presence tables.
+ *   classes float [M], batch_index int32 [M], instances int16 [K], points8 float [M][8], scales3 float [M][3]: K16's outputs
+ *   lut_has uint8 [n_lut]: 1 = instance id i has a style code; lut float [n_lut][z_dim]: the codes (n_lut may be 0)
+ * gcv_model_rule (HOST): n_classes in [1, 32] (the one-hot's width); model_of_class[c] = 0, 1, 2 for the model slot in
+ * upstream's dict order BLDG, CAR, REST, or -1: rows of that class are dropped (upstream skips a model that is None);
+ * proj_tlp / proj_size of get_projection_uv (a zero tlp is upstream's `proj_tlp is None` branch bit for bit).
+ * gcv_model_split_count enqueues mark + count + scan, waits, and stores
+ *   counts_host = {n_0, n_1, n_2,  B_0, B_1, B_2,  G_0, G_1, G_2}: rows per model, distinct instances per model, and how
+ *   many of those have a code.  A class that is not an integer in [0, n_classes) or a batch_index outside [0, K) raises a
+ *   device flag and is never used as an index: the call returns GCV_ERR_INVALID_ARGUMENT and counts_host is untouched.
+ * gcv_model_split_emit enqueues and returns.  A stable three-way partition: rows of model 0 first, in ascending visible-set
+ * order (a boolean-mask gather), then model 1, then model 2, in ONE set of buffers of N = n_0 + n_1 + n_2 rows, so a
+ * model's tensors are slices.  Outputs (any may be NULL = skipped):
+ *   index      int64 [N]             position in the visible set
+ *   points8    float [N][8]          the row copied (16-byte aligned, as the input)
+ *   batch      int32 [N]             rank of the row's instance among the instances of its own model (:476-480)
+ *   classes    float [N], scales3 float [N][3]
+ *   onehots    float [N][n_classes]  exactly one 1.0 per row
+ *   proj_uv    float [N][2]          ((x - tlp_x) / proj_size) * 2 - 1, likewise y: one rounded fp32 operation each
+ *   group      int32 [N]             rank of the row's instance among its model's instances that have a code; -1: it has none
+ *   group_instances int16 [G]        G = G_0 + G_1 + G_2: per model (model 0's first) the ids that have a code, ascending
+ *   codes      float [G][z_dim]      lut[group_instances[g]]
+ * The workspace (gcv_model_split_workspace_bytes(M, K), 16-byte aligned) carries the tables from _count to _emit; _count
+ * clears what it needs, so one workspace serves frame after frame.  Nothing is allocated inside; integer atomics only (bit
+ * ORs, a counter), so every output is deterministic.  Argument errors (null or misaligned pointers, negative sizes, a small
+ * workspace) come back before anything is queued.  gcv_model_split_workspace_bytes is host only; it returns 0 and sets
+ * gcv_last_error() for negative sizes, M >= 2^31 and K > 65536. */
+typedef struct gcv_model_rule {
+  int32_t n_classes;
+  int8_t model_of_class[32];
+  float proj_tlp[2];
+  float proj_size;
+} gcv_model_rule;
+int gcv_model_split_models(void); /* host only: 3 -- a library that exports it has the entry points of K17 and K18 */
+size_t gcv_model_split_workspace_bytes(int64_t n_visible, int64_t n_instances);
+int gcv_model_split_count(const float* classes, const int32_t* batch_index, int64_t n_visible, const int16_t* instances,
+                          int64_t n_instances, const uint8_t* lut_has, int32_t n_lut, const gcv_model_rule* rule_host,
+                          void* workspace, size_t workspace_bytes, int64_t counts_host[9], void* hip_stream);
+int gcv_model_split_emit(const float* classes, const int32_t* batch_index, const float* points8, const float* scales3,
+                         int64_t n_visible, const int16_t* instances, int64_t n_instances, const uint8_t* lut_has,
+                         const float* lut, int32_t n_lut, int32_t z_dim, const gcv_model_rule* rule_host,
+                         const void* workspace, size_t workspace_bytes, const int64_t counts_host[9], int64_t* index_out,
+                         float* points8_out, int32_t* batch_out, float* classes_out, float* scales3_out, float* onehots_out,
+                         float* proj_uv_out, int32_t* group_out, int16_t* group_instances_out, float* codes_out,
+                         void* hip_stream);
+
+/* ---- K18: [N][14] Gaussians in one launch (utils/helpers.py:226-247 plus the per-key torch.cat of :500-501) ----
+ * out float [n][14] = xyz + dxyz (3), opacity (1), scales * scale (3), rotation (1, 0, 0, 0), rgb (3); one fp32 operation
+ * each, opacity 1.0 where the key is absent.  xyz and scales are read with a row stride in elements (K17's points8: 8, its
+ * scales3: 3).  Up to three segments (the models, in order) whose rows follow each other: per segment its row count and
+ * the generator's outputs rgb [n][3] (required), dxyz [n][3], scale [n][3], opacity [n] -- a key is NULL in every
+ * segment that has rows or in none.  The record is HOST memory passed by value.  Inference only; enqueues and returns. */
+typedef struct gcv_gaussian_segment {
+  int64_t n;
+  const float *rgb, *dxyz, *scale, *opacity;
+} gcv_gaussian_segment;
+typedef struct gcv_gaussian_attrs {
+  int32_t n_segments;
+  gcv_gaussian_segment seg[3];
+} gcv_gaussian_attrs;
+int gcv_gaussian_points(const float* xyz, int64_t xyz_stride, const float* scales, int64_t scales_stride, int64_t n,
+                 gcv_gaussian_attrs attrs, float* out, void* hip_stream);
 
 /* avg device ms per stage since the last call (option "timing" of gcv_set_option; hipEvent pairs on the caller's
  * stream, a ring of 8 pairs per stage, so recording never waits for a stage still in flight):
