@@ -31,6 +31,13 @@ _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argt
     "gcm_ffn_backward_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "gcm_ffn_backward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gcm_ffn_split_max_channels": (C.c_int, []),
+    "gcm_ffn_split_plan": (C.c_int, [_i64, _i32, _i32, C.POINTER(_i64)]),
+    "gcm_ffn_split_workspace_bytes": (C.c_int, [_i64, _i32, _i32, C.POINTER(_sz), C.POINTER(_sz)]),
+    "gcm_ffn_split_forward": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp,
+                                        _vp, _vp, _vp, _sz, _vp]),
+    "gcm_ffn_split_backward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp,
+                                         _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gcm_front_max_channels": (C.c_int, []),
     "gcm_front_forward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _i64, _i32, _i32,
                                     _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -18,6 +18,7 @@
 //             pairwise, a fixed tree; fold_ln_partials (gcm_tile.h) adds the tiles' LayerNorm partials in tile order.
 // Nothing depends on how many workgroups are resident: every sum has a fixed set of terms in a fixed order.
 #pragma once
+#include <atomic>
 
 namespace {
 
@@ -334,6 +335,317 @@ FfnPlan ffn_plan(int64_t N, int32_t C, int32_t Hd) {
   p.wpart = ws.take((size_t)p.sw * (size_t)ffn_record(C, Hd) * 4);
   p.total = ws.off;
   return p;
+}
+
+// ---- the same operator up to 512 channels, the hidden width split across workgroups (gcm_ffn_split_*) -------------------
+// The row-side kernels above walk every chunk of 64 hidden features in one workgroup per 64 rows: 17 workgroups at
+// N = 1063.  Here the grid is (row tiles, hidden groups) and a chunk's second product leaves the workgroup as a partial
+// record [chunk][N][C]; a second kernel adds the records in ascending chunk order from +0 -- the order k_ffn_forward adds
+// tacc onto its cleared yacc -- and ends the operator.  Two modes, chosen by the plan from N, C and Hd alone:
+//   split  one chunk per workgroup, P = ceil(Hd / 64) records            (tiles x chunks <= kFfnSplitLimit)
+//   rows   a workgroup walks all chunks and adds them in registers, P = 1 (the workspace stays bounded)
+// Both are "per chunk one chain from 0, the chunks added in ascending order", so the mode never shows in the bits, and at
+// C <= 128 the bits are those of the kernels above.  CT = 32 NJ NB: NB column blocks of 32 NJ for the second product
+// (NB = 1 up to 128 channels; NJ = 4 and NB = 2, 4 for CT = 256, 512).  LDS is dynamic: the row image alone is 132 096
+// bytes at CT = 512.
+#ifndef GCM_FFN_SPLIT_LIMIT
+#define GCM_FFN_SPLIT_LIMIT 2048
+#endif
+constexpr int kFfnSplitMaxChannels = 512;
+constexpr int64_t kFfnSplitLimit = GCM_FFN_SPLIT_LIMIT;  // tiles x chunks beyond which a workgroup walks its chunks
+
+constexpr int split_slice_cols(int NJ) { return 32 * NJ > T ? 32 * NJ : T; }
+constexpr size_t split_fwd_lds(int NJ, int NB) { return (size_t)(T * (32 * NJ * NB + 4) + T * kPitchG + split_slice_cols(NJ) * kPitch) * 4; }
+constexpr size_t split_bwd_lds(int NJ, int NB) { return (size_t)(T * (32 * NJ * NB + 4) + T * kPitchG + KC * (split_slice_cols(NJ) + 16)) * 4; }
+constexpr size_t split_ln_lds(int NJ, int NB) { return (size_t)(T * (32 * NJ * NB + 4) + T * kPitchG) * 4; }
+
+// part[rec][row][c] = acc for the tile's live rows and the live columns of column block cb
+template <int NJ>
+__device__ __forceinline__ void split_store(const f4 (&acc)[2][NJ], const WaveTile& g, float* __restrict__ part, int64_t rec,
+                                            int64_t row0, int64_t N, int C, int cb) {
+  for_each_output(acc, g, [&](int rl, int cl, float v) {
+    const int64_t row = row0 + rl;
+    const int c = cb + cl;
+    if (row < N && c < C) part[(rec * N + row) * C + c] = v;
+  });
+}
+
+// the P records' four floats at `at` (a record is `rs` floats) added in ascending order from +0; the loads of up to 16
+// records are in flight together, the adds are one chain
+__device__ __forceinline__ f4 split_fold(const float* __restrict__ at, int64_t rs, int P) {
+  f4 v = zero4();
+  int p = 0;
+  for (; p + 16 <= P; p += 16) {
+    f4 t[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) t[k] = ld4(at + (p + k) * rs);
+#pragma unroll
+    for (int k = 0; k < 16; k++) v = v + t[k];
+  }
+  for (; p + 4 <= P; p += 4) {
+    f4 t[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) t[k] = ld4(at + (p + k) * rs);
+#pragma unroll
+    for (int k = 0; k < 4; k++) v = v + t[k];
+  }
+  for (; p < P; p++) v = v + ld4(at + p * rs);
+  return v;
+}
+
+// grid (row tiles, SPLIT ? chunks : 1).  mean, rstd (from the workgroups of group 0) and a when not null.
+template <int NJ, int NB, bool SPLIT>
+__global__ __launch_bounds__(256, NB > 1 ? 1 : 2) void k_ffn_split_forward(
+    const float* __restrict__ x, int64_t xs, const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
+    const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, int64_t N, int C, int Hd,
+    float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ a, float* __restrict__ part) {
+  constexpr int CB = 32 * NJ, CT = CB * NB, XP = CT + 4, WN = split_slice_cols(NJ) * kPitch;
+  extern __shared__ __attribute__((aligned(16))) float split_lds[];
+  float* Xs = split_lds;                                                // x, then LN(x): rows x channels
+  float* Gs = Xs + T * XP;                                              // GELU(a) of one chunk: rows x hidden
+  float(&Ws)[WN] = *reinterpret_cast<float(*)[WN]>(Gs + T * kPitchG);   // a 16-deep slice of W1, then of W2
+  const int tid = threadIdx.x;
+  const WaveTile g;
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int Cr = (C + KC - 1) / KC * KC;
+  const int hbeg = SPLIT ? (int)blockIdx.y * FH : 0, hend = SPLIT ? (hbeg + FH < Hd ? hbeg + FH : Hd) : Hd;
+
+  stage_rows(Xs, XP, Cr >> 2, [&](int r, int c) { return (row0 + r < N && c < C) ? ld4(x + (row0 + r) * xs + c) : zero4(); });
+  __syncthreads();
+  {  // LayerNorm in place; every workgroup of a tile forms the same statistics, group 0 stores them
+    const int r = tid >> 2, q = tid & 3;
+    const bool live = row0 + r < N;
+    const RowStat st = ln_rows_forward(
+        &Xs[r * XP], q, C, eps, [](int, f4) {}, [&](int c, f4 h) { return live ? h * ld4(lnw + c) + ld4(lnb + c) : zero4(); });
+    if (live && q == 0 && mean && blockIdx.y == 0) {
+      mean[row0 + r] = st.mean;
+      rstd[row0 + r] = st.rstd;
+    }
+  }
+
+  Chain<2, false> up;     // a = xn W1^T: the chunk's 64 hidden features, summed over the channels
+  Chain<NJ, false> down;  // t = g W2^T: a column block, summed over the chunk's hidden features
+  f4 yacc[SPLIT ? 1 : NB][2][NJ];
+  if (!SPLIT)
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) clear_acc(yacc[nb]);
+  for (int h0 = hbeg; h0 < hend; h0 += FH) {
+    auto w1_at = [&](int hl, int c) { return (h0 + hl < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + hl) * C + c) : zero4(); };
+    auto w2_in = [&](int cb) {
+      return [=](int c, int k) { return (cb + c < C && h0 + k < Hd) ? ld4(w2 + (int64_t)(cb + c) * Hd + h0 + k) : zero4(); };
+    };
+    f4 acc[2][2];
+    clear_acc(acc);
+    up.first(w1_at);
+    up.run(acc, g, Xs, XP, Cr, Ws, w1_at, [&]() { down.first(w2_in(0)); });
+    for_each_output(acc, g, [&](int rl, int hl, float v) {
+      const int64_t row = row0 + rl;
+      const int h = h0 + hl;
+      float gv = 0.0f;
+      if (h < Hd) {
+        const float av = v + b1[h];
+        if (a && row < N) a[row * Hd + h] = av;
+        gv = gelu_f(av);
+      }
+      Gs[rl * kPitchG + hl] = gv;
+    });
+    const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) {
+      if (nb * CB < C) {  // else: a column block without a live channel
+        f4 tacc[2][NJ];
+        clear_acc(tacc);
+        if (nb > 0) down.first(w2_in(nb * CB));
+        down.run(tacc, g, Gs, kPitchG, kend, Ws, w2_in(nb * CB));
+        if (SPLIT) split_store(tacc, g, part, h0 / FH, row0, N, C, nb * CB);
+        else add_acc(yacc[nb], tacc);
+      }
+    }
+  }
+  if (!SPLIT)
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) split_store(yacc[nb], g, part, 0, row0, N, C, nb * CB);
+}
+
+// y = x + s_r ((the P records added in ascending order from +0) + b2): one thread per four channels of a row
+__global__ void k_ffn_split_finish(const float* __restrict__ part, int P, const float* __restrict__ x, int64_t xs,
+                                   const float* __restrict__ b2, const float* __restrict__ s, int64_t N, int C,
+                                   float* __restrict__ y, int64_t ys) {
+  const int c4 = C >> 2;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N * c4) return;
+  const int64_t row = e / c4;
+  const int c = 4 * (int)(e % c4);
+  const f4 t = split_fold(part + row * C + c, N * C, P) + ld4(b2 + c);
+  st4(y + row * ys + c, ld4(x + row * xs + c) + (s ? t * s[row] : t));
+}
+
+// da [N][Hd] for the workgroup's chunk(s), and the chunk's dxn as a partial record (rows mode: the chunks' sum, record 0)
+template <int NJ, int NB, bool SPLIT>
+__global__ __launch_bounds__(256, NB > 1 ? 1 : 2) void k_ffn_split_bwd_rows(
+    const float* __restrict__ a, const float* __restrict__ dy, int64_t dys, const float* __restrict__ s,
+    const float* __restrict__ w1, const float* __restrict__ w2, int64_t N, int C, int Hd, float* __restrict__ da,
+    float* __restrict__ part) {
+  constexpr int CB = 32 * NJ, CT = CB * NB, XP = CT + 4, WN = KC * (split_slice_cols(NJ) + 16);
+  extern __shared__ __attribute__((aligned(16))) float split_lds[];
+  float* Ds = split_lds;                                                // dt: rows x channels
+  float* Gs = Ds + T * XP;                                              // da of one chunk
+  float(&Ws)[WN] = *reinterpret_cast<float(*)[WN]>(Gs + T * kPitchG);   // a slice of W2, then of W1
+  const WaveTile g;
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int Cr = (C + KC - 1) / KC * KC;
+  const int hbeg = SPLIT ? (int)blockIdx.y * FH : 0, hend = SPLIT ? (hbeg + FH < Hd ? hbeg + FH : Hd) : Hd;
+
+  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
+    f4 v = zero4();
+    if (row0 + r < N && c < C) {
+      v = ld4(dy + (row0 + r) * dys + c);
+      if (s) v = v * s[row0 + r];
+    }
+    return v;
+  });
+
+  Chain<2, true> back2;   // dg = dt W2: the chunk's 64 hidden features, summed over the channels
+  Chain<NJ, true> back1;  // dxn = da W1: a column block, summed over the chunk's hidden features
+  f4 xacc[SPLIT ? 1 : NB][2][NJ];
+  if (!SPLIT)
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) clear_acc(xacc[nb]);
+  for (int h0 = hbeg; h0 < hend; h0 += FH) {
+    auto w2_at = [&](int hl, int c) { return (c < C && h0 + hl < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + hl) : zero4(); };
+    auto w1_in = [&](int cb) {
+      return [=](int c, int k) { return (h0 + k < Hd && cb + c < C) ? ld4(w1 + (int64_t)(h0 + k) * C + cb + c) : zero4(); };
+    };
+    f4 acc[2][2];
+    clear_acc(acc);
+    back2.first(w2_at);
+    back2.run(acc, g, Ds, XP, Cr, Ws, w2_at, [&]() { back1.first(w1_in(0)); });
+    for_each_output(acc, g, [&](int rl, int hl, float v) {
+      const int64_t row = row0 + rl;
+      const int h = h0 + hl;
+      float dv = 0.0f;
+      if (h < Hd && row < N) {
+        dv = v * gelu_grad_f(a[row * Hd + h]);
+        da[row * Hd + h] = dv;
+      }
+      Gs[rl * kPitchG + hl] = dv;
+    });
+    const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) {
+      if (nb * CB < C) {
+        f4 tacc[2][NJ];
+        clear_acc(tacc);
+        if (nb > 0) back1.first(w1_in(nb * CB));
+        back1.run(tacc, g, Gs, kPitchG, kend, Ws, w1_in(nb * CB));
+        if (SPLIT) split_store(tacc, g, part, h0 / FH, row0, N, C, nb * CB);
+        else add_acc(xacc[nb], tacc);
+      }
+    }
+  }
+  if (!SPLIT)
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) split_store(xacc[nb], g, part, 0, row0, N, C, nb * CB);
+}
+
+// per row tile: dxn = the P records added in ascending order from +0 -> LDS, the LayerNorm backward, dx = dy + ..., and the
+// tile's column sums, as k_ffn_bwd_rows ends
+template <int NJ, int NB>
+__global__ __launch_bounds__(256, NB > 1 ? 1 : 2) void k_ffn_split_bwd_ln(
+    const float* __restrict__ part, int P, const float* __restrict__ x, int64_t xs, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ dy, int64_t dys, const float* __restrict__ lnw, int64_t N, int C,
+    float* __restrict__ dx, int64_t dxs, float* __restrict__ lnpart) {
+  constexpr int CT = 32 * NJ * NB, XP = CT + 4;
+  extern __shared__ __attribute__((aligned(16))) float split_lds[];
+  float* Ds = split_lds;       // dxn: rows x channels
+  float* Gs = Ds + T * XP;     // the column partials
+  __shared__ float sMean[T], sRstd[T];
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * T;
+  const int Cr = (C + KC - 1) / KC * KC;
+
+  if (tid < T) {
+    const bool live = row0 + tid < N;
+    sMean[tid] = live ? mean[row0 + tid] : 0.0f;
+    sRstd[tid] = live ? rstd[row0 + tid] : 0.0f;
+  }
+  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
+    return (row0 + r < N && c < C) ? split_fold(part + (row0 + r) * C + c, N * C, P) : zero4();
+  });
+  __syncthreads();
+
+  if (dx) {  // LayerNorm backward
+    const int r = tid >> 2, q = tid & 3;
+    const int64_t row = row0 + r;
+    auto src = [&](int c) { return ld4(x + row * xs + c); };
+    auto out = [&](int c, f4 v) { st4(dx + row * dxs + c, ld4(dy + row * dys + c) + v); };
+    if constexpr (NB == 1) ln_rows_backward<NJ>(&Ds[r * XP], q, C, row < N, {sMean[r], sRstd[r]}, lnw, src, out, [](int) {});
+    else ln_rows_backward_reread(&Ds[r * XP], q, C, row < N, {sMean[r], sRstd[r]}, lnw, src, out);
+  }
+  if (lnpart) ln_col_sums<CT>(Ds, x, xs, sMean, sRstd, row0, N, C, Gs, lnpart + (int64_t)blockIdx.x * 2 * C);
+}
+
+// f(std::integral_constant<int, NJ>, std::integral_constant<int, NB>) for the narrowest instantiation that holds C
+template <typename F>
+void with_split_width(int C, F f) {
+  if (C <= 128) with_nj(C, [&](auto nj) { f(nj, std::integral_constant<int, 1>{}); });
+  else if (C <= 256) f(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
+}
+
+struct FfnSplitPlan {
+  bool split;      // one chunk per workgroup
+  int64_t tiles, chunks, records;  // row tiles, chunks of 64 hidden features, partial records P
+  int64_t groups, gper;            // the LayerNorm partials' first level, as FfnPlan
+  int sw;                          // row slices of the weight gradients
+  size_t fwd_total;                // the forward's workspace: the records of t
+  size_t da, part, lnpart, lngroup, wpart, total;  // the backward's carve
+};
+FfnSplitPlan ffn_split_plan(int64_t N, int32_t C, int32_t Hd) {
+  FfnSplitPlan p;
+  p.tiles = (N + T - 1) / T;
+  p.chunks = (Hd + FH - 1) / FH;
+  p.split = p.tiles * p.chunks <= kFfnSplitLimit;
+  p.records = p.split ? p.chunks : 1;
+  fold_groups(p.tiles, p.groups, p.gper);
+  p.sw = weight_slices((int64_t)((Hd + T - 1) / T) * ((C + T - 1) / T), N);
+  const size_t rec = (size_t)p.records * (size_t)N * C * 4;
+  p.fwd_total = round256(rec);
+  Carve ws;
+  p.da = ws.take((size_t)N * Hd * 4);
+  p.part = ws.take(rec);
+  p.lnpart = ws.take((size_t)p.tiles * 2 * C * 4);
+  p.lngroup = ws.take((size_t)p.groups * 2 * C * 4);
+  p.wpart = ws.take((size_t)p.sw * (size_t)ffn_record(C, Hd) * 4);
+  p.total = ws.off;
+  return p;
+}
+
+// more than 64 KB of dynamic LDS has to be asked for, per kernel and per device (asking twice is harmless): the
+// instantiations of CT = 256 and 512
+hipError_t split_lds_attr() {
+  constexpr int kDevices = 64;
+  static std::atomic<bool> done[kDevices];
+  int dev = 0;
+  if (const hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  const bool known = dev >= 0 && dev < kDevices;
+  if (known && done[dev].load(std::memory_order_acquire)) return hipSuccess;
+  hipError_t err = hipSuccess;
+  auto ask = [&](const void* f, size_t bytes) {
+    if (err == hipSuccess) err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  };
+  auto wide = [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    ask((const void*)k_ffn_split_forward<4, NB, true>, split_fwd_lds(4, NB));
+    ask((const void*)k_ffn_split_forward<4, NB, false>, split_fwd_lds(4, NB));
+    ask((const void*)k_ffn_split_bwd_rows<4, NB, true>, split_bwd_lds(4, NB));
+    ask((const void*)k_ffn_split_bwd_rows<4, NB, false>, split_bwd_lds(4, NB));
+    ask((const void*)k_ffn_split_bwd_ln<4, NB>, split_ln_lds(4, NB));
+  };
+  wide(std::integral_constant<int, 2>{});
+  wide(std::integral_constant<int, 4>{});
+  if (err == hipSuccess && known) done[dev].store(true, std::memory_order_release);
+  return err;
 }
 
 }  // namespace

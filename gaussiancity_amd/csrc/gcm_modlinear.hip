@@ -522,6 +522,15 @@ int check_ffn_shape(const std::string& w, int64_t N, int32_t C, int32_t Hd) {
   return 0;
 }
 
+int check_ffn_split_shape(const std::string& w, int64_t N, int32_t C, int32_t Hd) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
+  if (Hd <= 0 || Hd % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd must be a positive multiple of 4");
+  if (C > kFfnSplitMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_ffn_split_max_channels()");
+  if (Hd > 4 * kFfnSplitMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd above 4 * gcm_ffn_split_max_channels()");
+  return 0;
+}
+
 int check_front_shape(const std::string& w, int64_t N, int32_t C, int32_t O) {
   if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
   if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
@@ -756,6 +765,125 @@ int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const 
     k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(part, p.sw, (int64_t)C * Hd, (int64_t)C * Hd, Hd, C, dw1, dw2,
                                                                           db1, db2);
     HIP_TRY(hipGetLastError(), "ffn backward weight gradient launch");
+  }
+  return GCM_OK;
+}
+
+int gcm_ffn_split_max_channels(void) { return kFfnSplitMaxChannels; }
+
+int gcm_ffn_split_plan(int64_t N, int32_t C, int32_t Hd, int64_t plan[8]) {
+  const std::string who("gcm_ffn_split_plan");
+  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
+  if (!plan) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null plan");
+  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
+  const int64_t out[8] = {p.split ? 1 : 0, p.tiles, p.chunks, p.records, p.sw, p.groups, kFfnSplitLimit, 0};
+  std::copy(out, out + 8, plan);
+  return GCM_OK;
+}
+
+int gcm_ffn_split_workspace_bytes(int64_t N, int32_t C, int32_t Hd, size_t* forward_bytes, size_t* backward_bytes) {
+  const std::string who("gcm_ffn_split_workspace_bytes");
+  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
+  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
+  if (forward_bytes) *forward_bytes = std::max<size_t>(p.fwd_total, 256);  // never 0 for arguments in range
+  if (backward_bytes) *backward_bytes = p.total;
+  return GCM_OK;
+}
+
+int gcm_ffn_split_forward(const float* x, int64_t x_stride, const float* ln_w, const float* ln_b, float eps, const float* w1,
+                          const float* b1, const float* w2, const float* b2, const float* row_scale, int64_t N, int32_t C,
+                          int32_t Hd, float* y, int64_t y_stride, float* mean, float* rstd, float* a, void* workspace,
+                          size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_ffn_split_forward");
+  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
+  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
+  if (int rc = check_strides(who, {{x_stride, C}, {y_stride, C}})) return rc;
+  if (int rc = check_aligned16(who, {x, ln_w, ln_b, w1, b1, w2, b2, y, a})) return rc;
+  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, std::max<size_t>(p.fwd_total, 256), "gcm_ffn_split_workspace_bytes"))
+    return rc;
+  if (N == 0) return GCM_OK;
+  if (!x || !ln_w || !ln_b || !w1 || !b1 || !w2 || !b2 || !y)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, ln_w, ln_b, w1, b1, w2, b2 or y");
+  if ((mean == nullptr) != (rstd == nullptr) || (a && !mean))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": mean and rstd come together, and a needs both");
+  HIP_TRY(split_lds_attr(), "ffn split LDS attribute");
+  hipStream_t st = (hipStream_t)hip_stream;
+  float* part = (float*)workspace;
+  with_split_width(C, [&](auto nj, auto nb) {
+    constexpr int NJ = decltype(nj)::value, NB = decltype(nb)::value;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.records);
+    if (p.split)
+      k_ffn_split_forward<NJ, NB, true><<<grid, 256, split_fwd_lds(NJ, NB), st>>>(x, x_stride, ln_w, ln_b, eps, w1, b1, w2, N, C, Hd,
+                                                                                  mean, rstd, a, part);
+    else
+      k_ffn_split_forward<NJ, NB, false><<<grid, 256, split_fwd_lds(NJ, NB), st>>>(x, x_stride, ln_w, ln_b, eps, w1, b1, w2, N, C, Hd,
+                                                                                   mean, rstd, a, part);
+  });
+  HIP_TRY(hipGetLastError(), "ffn split forward launch");
+  k_ffn_split_finish<<<blocks_for(N * (C / 4), 256), 256, 0, st>>>(part, (int)p.records, x, x_stride, b2, row_scale, N, C, y, y_stride);
+  HIP_TRY(hipGetLastError(), "ffn split forward finish launch");
+  return GCM_OK;
+}
+
+int gcm_ffn_split_backward(const float* x, int64_t x_stride, const float* mean, const float* rstd, const float* a,
+                           const float* dy, int64_t dy_stride, const float* row_scale, const float* ln_w, const float* ln_b,
+                           const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
+                           float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                           size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_ffn_split_backward");
+  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
+  if (int rc = check_strides(who, {{x_stride, C}, {dy_stride, C}, {dx_stride, C, dx != nullptr}})) return rc;
+  if (int rc = check_aligned16(who, {x, a, dy, ln_w, ln_b, w1, w2, dx, dln_w, dln_b, dw1, db1, dw2, db2})) return rc;
+  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_ffn_split_workspace_bytes")) return rc;
+  if (N > 0 && (!x || !mean || !rstd || !a || !dy || !ln_w || !ln_b || !w1 || !w2))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, mean, rstd, a, dy, ln_w, ln_b, w1 or w2");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
+    const size_t CH = (size_t)C * Hd * 4, C4 = (size_t)C * 4;
+    return clear_outputs(st, {{dln_w, C4, "ffn split backward clear dln_w"},
+                              {dln_b, C4, "ffn split backward clear dln_b"},
+                              {dw1, CH, "ffn split backward clear dw1"},
+                              {db1, (size_t)Hd * 4, "ffn split backward clear db1"},
+                              {dw2, CH, "ffn split backward clear dw2"},
+                              {db2, C4, "ffn split backward clear db2"}});
+  }
+  HIP_TRY(split_lds_attr(), "ffn split LDS attribute");
+  char* ws = (char*)workspace;
+  float* da = (float*)(ws + p.da);
+  float* part = (float*)(ws + p.part);
+  const bool ln = dln_w || dln_b, first = dw1 || db1, params = first || dw2 || db2;
+  if (dx || ln || first) {
+    float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
+    with_split_width(C, [&](auto nj, auto nb) {
+      constexpr int NJ = decltype(nj)::value, NB = decltype(nb)::value;
+      const dim3 grid((unsigned)p.tiles, (unsigned)p.records);
+      if (p.split)
+        k_ffn_split_bwd_rows<NJ, NB, true><<<grid, 256, split_bwd_lds(NJ, NB), st>>>(a, dy, dy_stride, row_scale, w1, w2, N, C, Hd, da,
+                                                                                     part);
+      else
+        k_ffn_split_bwd_rows<NJ, NB, false><<<grid, 256, split_bwd_lds(NJ, NB), st>>>(a, dy, dy_stride, row_scale, w1, w2, N, C, Hd, da,
+                                                                                      part);
+      if (dx || ln)
+        k_ffn_split_bwd_ln<NJ, NB><<<(unsigned)p.tiles, 256, split_ln_lds(NJ, NB), st>>>(
+            part, (int)p.records, x, x_stride, mean, rstd, dy, dy_stride, ln_w, N, C, dx, dx_stride, lnpart);
+    });
+    HIP_TRY(hipGetLastError(), "ffn split backward rows launch");
+    if (ln) {
+      fold_ln_partials(lnpart, (float*)(ws + p.lngroup), p.tiles, p.groups, p.gper, 2, C, dln_w, dln_b, nullptr, nullptr, st);
+      HIP_TRY(hipGetLastError(), "ffn split backward LayerNorm fold launch");
+    }
+  }
+  if (params) {
+    const int64_t per = slice_rows(N, p.sw);
+    float* wpart = (float*)(ws + p.wpart);
+    const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
+    k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
+                                   wpart);
+    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(wpart, p.sw, (int64_t)C * Hd, (int64_t)C * Hd, Hd, C, dw1,
+                                                                          dw2, db1, db2);
+    HIP_TRY(hipGetLastError(), "ffn split backward weight gradient launch");
   }
   return GCM_OK;
 }

@@ -252,6 +252,26 @@ __device__ __forceinline__ void ln_rows_backward(const float* Dr, int q, int C, 
   }
 }
 
+// The same for widths whose 2 NJ register pairs would not fit (CT = 256, 512): h and u are formed twice, from the same
+// loads by the same operations, so every value and each lane's two sums (element order) are those of the form above.
+template <typename Src, typename Out>
+__device__ __forceinline__ void ln_rows_backward_reread(const float* Dr, int q, int C, bool live, RowStat st,
+                                                        const float* __restrict__ gamma, Src src, Out out) {
+  float s1 = 0.0f, s2 = 0.0f;
+  if (live)
+    for (int c = 4 * q; c < C; c += 16) {
+      const f4 h = (src(c) - st.mean) * st.rstd, wd = ld4(&Dr[c]) * ld4(gamma + c);
+      s1 = sum4(s1, wd);
+      s2 = sum4(s2, wd * h);
+    }
+  const float c1 = quad_sum(s1) / (float)C, c2 = quad_sum(s2) / (float)C;
+  if (live)
+    for (int c = 4 * q; c < C; c += 16) {
+      const f4 h = (src(c) - st.mean) * st.rstd, wd = ld4(&Dr[c]) * ld4(gamma + c);
+      out(c, (wd - c1 - h * c2) * st.rstd);
+    }
+}
+
 // out[0][c] = sum_r d[r][c] h[r][c], out[1][c] = sum_r d[r][c] over the tile's live rows, d the LDS image Ds (pitch CT + 4)
 // and h = (src - mean) rstd read per row: thread (row group, f4 column) sums its RPG rows in order, then the groups in
 // order.  Gs (a chunk image) holds the groups' partials; the caller keeps a __syncthreads between two calls.
@@ -280,8 +300,8 @@ __device__ __forceinline__ void ln_col_sums(const float* Ds, const float* __rest
     st4(&Gs[(grp * 2 + 1) * CT + c], pb);
   }
   __syncthreads();
-  if (tid < 2 * CT) {
-    const int which = tid / CT, c = tid % CT;
+  for (int e = tid; e < 2 * CT; e += 256) {  // one round up to CT = 128
+    const int which = e / CT, c = e % CT;
     if (c < C) {
       float v = Gs[which * CT + c];
       for (int grp = 1; grp < GROUPS; grp++) v += Gs[(grp * 2 + which) * CT + c];

@@ -98,9 +98,9 @@ def _forward(original, pt_v3_module):
             point.feat = feat + point.feat
         _STATS["fused_calls"] += 1
 
-        tail = point_ffn._parts(self, point) if getattr(pt_v3_module, point_ffn._ORIGINAL, None) is not None else None
+        tail = point_ffn._parts(self, point, pt_v3_module) if getattr(pt_v3_module, point_ffn._ORIGINAL, None) is not None else None
         if tail is not None:
-            return point_ffn.fused_tail(point, tail)
+            return point_ffn.fused_tail(point, tail, point_ffn.takes_split(pt_v3_module, point.feat.shape[1]))
         shortcut = point.feat
         point = self.norm2(point)
         point = self.drop_path(self.mlp(point))

@@ -89,6 +89,24 @@
  * slices and groups depend on N, C and Hd alone: every output is bit-identical from run to run and independent of
  * how many workgroups the device holds at a time.
  *
+ * The same operator up to 512 channels, the hidden width split across workgroups (gcm_ffn_split_*).  C <=
+ * gcm_ffn_split_max_channels() (512 in this build) and Hd <= 4 times that; every other argument rule is the one above.
+ * gcm_ffn_split_plan (host only) tells how the row side runs, a function of N, C and Hd alone: in split mode (tiles x
+ *     chunks <= plan[6]) every (tile of 64 rows, chunk of 64 hidden features) pair has a workgroup of its own and leaves
+ *     its t (backward: dxn) as one of P = ceil(Hd / 64) partial records [N][C]; in rows mode a workgroup walks all chunks
+ *     of its tile and leaves one record, so that the workspace stays bounded.
+ * gcm_ffn_split_workspace_bytes (host only): the bytes of the forward's and of the backward's workspace (a NULL
+ *     pointer is skipped), never 0 for arguments in range; the forward's holds P N C floats.
+ * gcm_ffn_split_forward: two launches, gcm_ffn_forward's arguments and a workspace (256-byte aligned; what it held
+ *     before does not matter).  N == 0 returns 0 and queues nothing.
+ * gcm_ffn_split_backward: gcm_ffn_backward's arguments unchanged, the workspace sized by the query above.
+ * Rounding and order: as above, with CT = 32, 64, 128, 256 or 512 the smallest that holds C.  The partial records are
+ * added in ascending chunk order from +0, then b2, s_r and x as above (backward: then the LayerNorm backward), which is
+ * the order the one-launch kernels add their chunks in registers: the mode never shows in the bits, and for C <= 128
+ * every output of the split entry points has the bits of gcm_ffn_forward / gcm_ffn_backward.  At CT = 256 and 512 the
+ * LayerNorm backward forms xhat and u twice (once for the row's two sums, once for dx) by the same operations; each
+ * lane's sums keep their element order, and a tile's column sums are over groups of 16 and 32 consecutive rows.
+ *
  * ---- The front of a PTv3 Block (models/pt_v3.py, Block.forward between the sparse convolution and the attention;
  * DESIGN.md section 19) ---------------------------------------------------------------------------------------------------
  * For N rows, C channels and O projected features, all float32:
@@ -284,6 +302,25 @@ int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const 
                      const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
                      float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
                      size_t workspace_bytes, void* hip_stream);
+
+int gcm_ffn_split_max_channels(void);
+
+/* plan[0] mode (0 rows, 1 split), [1] row tiles, [2] hidden chunks, [3] partial records P, [4] weight-gradient slices,
+   [5] first-level LayerNorm groups, [6] the tiles x chunks limit, [7] 0 */
+int gcm_ffn_split_plan(int64_t N, int32_t C, int32_t Hd, int64_t plan[8]);
+
+int gcm_ffn_split_workspace_bytes(int64_t N, int32_t C, int32_t Hd, size_t* forward_bytes, size_t* backward_bytes);
+
+int gcm_ffn_split_forward(const float* x, int64_t x_stride, const float* ln_w, const float* ln_b, float eps, const float* w1,
+                          const float* b1, const float* w2, const float* b2, const float* row_scale, int64_t N, int32_t C,
+                          int32_t Hd, float* y, int64_t y_stride, float* mean, float* rstd, float* a, void* workspace,
+                          size_t workspace_bytes, void* hip_stream);
+
+int gcm_ffn_split_backward(const float* x, int64_t x_stride, const float* mean, const float* rstd, const float* a,
+                           const float* dy, int64_t dy_stride, const float* row_scale, const float* ln_w, const float* ln_b,
+                           const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
+                           float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                           size_t workspace_bytes, void* hip_stream);
 
 int gcm_front_max_channels(void);
 

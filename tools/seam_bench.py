@@ -126,9 +126,19 @@ def whole_model(dev, a):
     frame = {k: v.to(dev) for k, v in S.sloped_frame(a.model_points, a.model_batches, a.model_depth).items()}
     dout = torch.randn(a.model_points, widths[1] if len(widths) > 1 else widths[0], device=dev)
 
-    def bind(on):
-        for m in (installs if on else reversed(installs)):
-            (m.install if on else m.uninstall)(S.NAMESPACE)
+    wide = a.ffn_max_channels or None   # a third side: point_ffn.install(..., max_channels=wide), the rest as they are
+    sides = ("none", "installed") + (("installed_ffn_wide",) if wide else ())
+
+    def bind(side):
+        for m in reversed(installs):
+            m.uninstall(S.NAMESPACE)
+        if side == "none":
+            return
+        for m in installs:
+            if m is point_ffn and side == "installed_ffn_wide":
+                m.install(S.NAMESPACE, max_channels=wide)
+            else:
+                m.install(S.NAMESPACE)
 
     def one_pass():
         model.zero_grad(set_to_none=True)
@@ -138,34 +148,47 @@ def whole_model(dev, a):
         (out.feat * dout).sum().backward()
         return out.feat.detach(), data["feat"].grad
 
-    res = {}
+    res, stats = {}, {}
     try:
-        for on in (False, True):
-            bind(on)
-            res[on] = one_pass()
-        diff = [float((g - w).abs().max() / w.abs().max()) for g, w in zip(res[True], res[False])]
-        stats = {m.__name__.split(".")[-1]: m.stats() for m in (point_front, point_mid, point_ffn, point_pool, point_seam)}
-        times = {False: [], True: []}
+        for side in sides:
+            bind(side)
+            for m in (point_front, point_mid, point_ffn, point_pool, point_seam):
+                m.reset_stats()
+            res[side] = one_pass()
+            stats[side] = {m.__name__.split(".")[-1]: m.stats() for m in (point_front, point_mid, point_ffn, point_pool, point_seam)}
+            stats[side]["point_ffn_split"] = point_ffn.split_stats()
+        diff = {side: [float((g - w).abs().max() / w.abs().max()) for g, w in zip(res[side], res["none"])] for side in sides[1:]}
+        times = {side: [] for side in sides}
         for _ in range(a.reps):
-            for on in (False, True):
-                bind(on)
+            for side in sides:
+                bind(side)
                 one_pass()  # the side's allocator and autotune state before its block
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(a.model_iters):
                     one_pass()
                 torch.cuda.synchronize()
-                times[on].append(1e3 * (time.perf_counter() - t0) / a.model_iters)
+                times[side].append(1e3 * (time.perf_counter() - t0) / a.model_iters)
     finally:
-        bind(False)
-    none, fused = statistics.median(times[False]), statistics.median(times[True])
-    return {"shape": "whole PTv3 forward + backward (tools/ptv3_stand_in.py), six installs against none", "points": a.model_points,
-            "batches": a.model_batches, "depth": a.model_depth, "widths": list(widths), "orders": a.model_orders,
-            "patch": a.model_patch, "timing": "host wall ms per pass, blocks of %d ending in a synchronise, median of %d rounds"
-            % (a.model_iters, a.reps), "none_ms": round(none, 3), "installed_ms": round(fused, 3),
-            "none_over_installed": round(none / fused, 2), "none_ms_rounds": [round(t, 3) for t in times[False]],
-            "installed_ms_rounds": [round(t, 3) for t in times[True]],
-            "installed_vs_none_max_rel_diff": {"output": diff[0], "input_gradient": diff[1]}, "paths_taken_last_pass": stats}
+        bind("none")
+    none, fused = statistics.median(times["none"]), statistics.median(times["installed"])
+    rec = {"shape": "whole PTv3 forward + backward (tools/ptv3_stand_in.py), six installs against none", "points": a.model_points,
+           "batches": a.model_batches, "depth": a.model_depth, "widths": list(widths), "orders": a.model_orders,
+           "patch": a.model_patch, "timing": "host wall ms per pass, blocks of %d ending in a synchronise, median of %d rounds"
+           % (a.model_iters, a.reps), "none_ms": round(none, 3), "installed_ms": round(fused, 3),
+           "none_over_installed": round(none / fused, 2), "none_ms_rounds": [round(t, 3) for t in times["none"]],
+           "installed_ms_rounds": [round(t, 3) for t in times["installed"]],
+           "installed_vs_none_max_rel_diff": {"output": diff["installed"][0], "input_gradient": diff["installed"][1]},
+           "paths_taken_last_pass": {k: v for k, v in stats["installed"].items() if k != "point_ffn_split"}}
+    if wide:
+        w = statistics.median(times["installed_ffn_wide"])
+        rec.update({"ffn_max_channels": wide, "installed_ffn_wide_ms": round(w, 3), "installed_over_installed_ffn_wide": round(fused / w, 3),
+                    "none_over_installed_ffn_wide": round(none / w, 2),
+                    "installed_ffn_wide_ms_rounds": [round(t, 3) for t in times["installed_ffn_wide"]],
+                    "installed_ffn_wide_vs_none_max_rel_diff": {"output": diff["installed_ffn_wide"][0],
+                                                                "input_gradient": diff["installed_ffn_wide"][1]},
+                    "paths_taken_ffn_wide": stats["installed_ffn_wide"]})
+    return rec
 
 
 def main():
@@ -181,13 +204,16 @@ def main():
     ap.add_argument("--model-orders", type=int, default=1, help="serialization orders (GaussianCity: 1, `cord`)")
     ap.add_argument("--model-patch", type=int, default=1024)
     ap.add_argument("--model-iters", type=int, default=3)
+    ap.add_argument("--ffn-max-channels", type=int, default=0,
+                    help="a third side of the whole model: point_ffn.install(..., max_channels=this), the split feed-forward")
+    ap.add_argument("--model-only", action="store_true", help="skip the seam shapes")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("seam_bench needs a GPU")
     dev = torch.device("cuda:0")
     bench_shape(dev, *SHAPES[0][:4], 100, 3, 50, "process warm-up, not reported")  # clocks up first
     lines = []
-    for rows, I, O, product, label in SHAPES:
+    for rows, I, O, product, label in ([] if a.model_only else SHAPES):
         rec = bench_shape(dev, rows, I, O, product, a.warmup, a.reps, a.iters, label)
         print(json.dumps(rec), flush=True)
         lines.append(rec)
