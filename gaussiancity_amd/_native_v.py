@@ -72,6 +72,8 @@ _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argt
     "gcv_model_split_emit": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, C.POINTER(ModelRule), _vp,
                                     _sz, C.POINTER(_i64)] + [_vp] * 11),
     "gcv_gaussian_points": (_int, [_vp, _i64, _vp, _i64, _i64, GaussianAttrs, _vp, _vp]),
+    "gcv_frame_finish_radius_max": (_int, []),
+    "gcv_frame_finish": (_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _pf32, _vp, _vp, _i32, _vp]),
     "gcv_set_option": (_int, [C.c_char_p, _int]),
     "gcv_get_stage_ms": (_int, [_pf32, _int]),
 }

@@ -288,17 +288,22 @@ class DDPTrainStep:
 
 class InferenceLoop:
     """Shape of the reference's render loop (scripts/inference.py:655-667) around the rasterizer only: for
-    every pose, points [N,14] -> image -> uint8 HWC frame on the host.  The reference does this on the
+    every pose, points [N,14] -> image -> uint8 HWC frame on the host.  The bytes are the frame BEFORE the road blur of
+    scripts/inference.py:255,264-272 unless a `finish_fn` applies it (gaussiancity_amd/finish.py).  The reference does this on the
     legacy default stream with a blocking `tensor_to_image(...).cpu()` per frame; here frames alternate
     over `n_streams` side streams (default 3: the measured optimum of the frame loop, bench.py) and land in as
     many pinned host buffers, so frame f's device->host copy and the host-side consumer overlap the next
     frames' renders.  `render_fn(points, cam_pos, cam_quat) -> [3,H,W]`
     is the rasterizer wrapper (or any stand-in on CPU, which degrades to a plain loop)."""
 
-    def __init__(self, render_fn, device=None, n_streams=3, render_uint8_fn=None, static_scene=False):
+    def __init__(self, render_fn, device=None, n_streams=3, render_uint8_fn=None, static_scene=False, finish_fn=None):
         """`render_uint8_fn(points, cam_pos, cam_quat) -> uint8 [H,W,3]` (optional): a renderer that produces the video
         frame itself (GaussianRasterizerWrapper(..., as_uint8=True): the blend kernel stores the bytes to_uint8_hwc would
-        compute); used instead of render_fn + to_uint8_hwc when given.  `static_scene`: the frames of a run() share one
+        compute, the frame before the road blur); used instead of render_fn + to_uint8_hwc when given.
+        `finish_fn(index, img) -> uint8 [H,W,3]` (optional): applied on the frame's side stream to render_fn's float image
+        in place of to_uint8_hwc -- finish.road_blur(img, ins_map_of(index), road_id, as_uint8=True) gives the bytes
+        scripts/inference.py:264-272 with :665 would; not together with render_uint8_fn (ValueError).
+        `static_scene`: the frames of a run() share one
         point tensor that nobody edits meanwhile AND most of it is off screen in every frame (a whole city's Gaussians
         flown through; not the reference's own loop, which feeds each pose its visible points only) -- the rasterizer
         may keep its cull cache for it (gaussiancity_amd/cull_cache.py: the same frames, the cull streams 16 instead of
@@ -307,6 +312,9 @@ class InferenceLoop:
         self.static_scene = bool(static_scene)
         self.render_fn = render_fn
         self.render_uint8_fn = render_uint8_fn
+        if finish_fn is not None and render_uint8_fn is not None:
+            raise ValueError("finish_fn works on render_fn's float image: it cannot be combined with render_uint8_fn")
+        self.finish_fn = finish_fn
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.cuda = self.device.type == "cuda"
         self.n = max(1, int(n_streams))
@@ -358,6 +366,7 @@ class InferenceLoop:
                     points.record_stream(self.streams[slot])
                 with torch.cuda.stream(self.streams[slot]):
                     frame = (self.render_uint8_fn(points, cam_pos, cam_quat) if self.render_uint8_fn is not None else
+                             self.finish_fn(i, self.render_fn(points, cam_pos, cam_quat)) if self.finish_fn is not None else
                              self.to_uint8_hwc(self.render_fn(points, cam_pos, cam_quat)))
                     if self._pinned[slot] is None or self._pinned[slot].shape != frame.shape:
                         self._pinned[slot] = torch.empty(frame.shape, dtype=torch.uint8, pin_memory=True)
@@ -366,7 +375,8 @@ class InferenceLoop:
                     ev.record(self.streams[slot])
                 pending[slot] = (i, ev)
             else:
-                frame = self.to_uint8_hwc(self.render_fn(points, cam_pos, cam_quat))
+                img = self.render_fn(points, cam_pos, cam_quat)
+                frame = self.finish_fn(i, img) if self.finish_fn is not None else self.to_uint8_hwc(img)
                 self._pinned[slot] = frame.contiguous()
                 pending[slot] = (i, None)
         n = len(poses)

@@ -432,7 +432,9 @@ class GaussianRasterizerWrapper(torch.nn.Module):
         skips the tiles outside it in both directions, and the crop's slice-backward kernels disappear.
         `as_uint8` (not in the reference; inference only): return the uint8 [H,W,3] video frame that
         scripts/inference.py:655-667 derives from the image -- (tensor_to_image(img) * 255).to(uint8) -- stored by the
-        blend kernel itself: the same bytes, without the float image's round trip and five elementwise kernels."""
+        blend kernel itself: the same bytes, without the float image's round trip and five elementwise kernels.  These are the
+        bytes of the frame BEFORE the road blur of scripts/inference.py:255,264-272; a frame with roads in it is finished
+        from the float image by finish.road_blur(..., as_uint8=True) (the blur works on floats)."""
         _, n_channels = points.shape
         assert n_channels == 14, "The input tensor should have 14 channels."
         if as_uint8:

@@ -23,6 +23,8 @@
  *                                          and per visible instance upstream (additive to ABI v5)
  *   gcv_gaussian_points                    utils/helpers.py:226-247 (get_gaussian_points) and the per-key torch.cat of
  *                                          scripts/inference.py:500-501
+ *   gcv_frame_finish                       scripts/inference.py:255,264-272 (GaussianBlur through the road mask) and :665-667
+ *                                          (the uint8 frame): torchvision + ten torch kernels upstream (additive to ABI v5)
  *   gcv_build_occupancy                    (none upstream: 1 bit per 16x16x16 macro cell; lets the traversal
  *                                           jump across empty macro cells, reproducing the reference walk
  *                                           exactly -- results unchanged)
@@ -241,6 +243,33 @@ typedef struct gcv_gaussian_attrs {
 } gcv_gaussian_attrs;
 int gcv_gaussian_points(const float* xyz, int64_t xyz_stride, const float* scales, int64_t scales_stride, int64_t n,
                  gcv_gaussian_attrs attrs, float* out, void* hip_stream);
+
+/* ---- K19: frame finish -- road-mask blur, composite and the video bytes in one launch (additive to ABI v5; probe
+ * gcv_frame_finish_radius_max) ----
+ * scripts/inference.py:255,264-272 -- blurrer(img) * road_mask + img * (1 - road_mask) with GaussianBlur's reflect padding
+ * -- and the uint8 conversion of :665-667, for a float image and an instance map that are already on the device.
+ *   img      float, pixel (b, c, y, x) at img[b * batch_stride + c * channel_stride + y * row_stride + x]: strides in
+ *            elements, not negative, pixel stride 1, three channels
+ *   ins_map  int16 [height][width] per image, image b's at ins_map + b * map_batch_stride (0: one map for every image)
+ *   road     pixel (b, y, x) shows a road where ins_map[b][y][flip_mask_x ? width - 1 - x : x] == road_id
+ *   weights_host  HOST float [(2 * radius + 1)^2], row-major; they travel in the kernel's arguments
+ * A pixel that shows no road keeps its three floats bit for bit.  A road pixel becomes, per channel,
+ *   sum over dy, dx of w[dy][dx] * img[c][refl(y + dy - radius)][refl(x + dx - radius)],   refl(-1) = 1, refl(n) = n - 2
+ * (torch's "reflect" padding), in float32, row-major tap order, starting from the first product, one rounding per product
+ * and per addition -- a pixel's bits do not depend on how the launch is tiled.
+ * Outputs, either or both:
+ *   out_f32  float [batch][3][height][width], contiguous; must not overlap the image's extent (not in place)
+ *   out_u8   uint8 [batch][height][width][3] = (int)((clamp(v, -1, 1) / 2 + 0.5) * 255) of the value above, a NaN -> 0: the
+ *            expression of gcr's out_u8 store; bgr != 0 stores the channels reversed (img[..., ::-1] of :666-667)
+ * One launch; does not wait, does not allocate, no atomics, no workspace.  GCV_ERR_INVALID_ARGUMENT before anything is
+ * queued for: a null img, ins_map or weights_host; both outputs null; a radius outside 1..gcv_frame_finish_radius_max();
+ * a non-positive dimension; height or width <= radius (torch's own condition for reflect padding); a negative stride;
+ * batch > 65535; out_f32 overlapping the image.  gcv_frame_finish_radius_max is host only and returns 3. */
+int gcv_frame_finish_radius_max(void);
+int gcv_frame_finish(const float* img, int64_t batch_stride, int64_t channel_stride, int64_t row_stride, int32_t batch,
+                     int32_t height, int32_t width, const int16_t* ins_map, int64_t map_batch_stride, int32_t road_id,
+                     int32_t flip_mask_x, int32_t radius, const float* weights_host, float* out_f32, uint8_t* out_u8,
+                     int32_t bgr, void* hip_stream);
 
 /* avg device ms per stage since the last call (option "timing" of gcv_set_option; hipEvent pairs on the caller's
  * stream, a ring of 8 pairs per stage, so recording never waits for a stage still in flight):
