@@ -1,31 +1,201 @@
-// gcm_ffn.h -- the feed-forward third of a PTv3 Block (gcm_ffn_*, include/gcm.h): y = x + s o (GELU(LN(x) W1^T + b1) W2^T + b2)
-// in ONE launch, and its deterministic backward in a handful of launches whatever N is.  Included by gcm_modlinear.hip
-// after gcm_tile.h, which holds the tile, the product loop and the LayerNorm lane rule; device code and the plan only, the
-// C ABI stays in gcm_modlinear.hip.  DESIGN.md section 18.
+// gcm_ffn.h -- the feed-forward third of a PTv3 Block (gcm_ffn_* and gcm_ffn_split_*, include/gcm.h):
+// y = x + s o (GELU(LN(x) W1^T + b1) W2^T + b2) and its deterministic backward in a handful of launches whatever N is.
+// Included by gcm_modlinear.hip after gcm_tile.h, which holds the tile, the product loop and the LayerNorm lane rule; device
+// code and the plan only, the C ABI stays in gcm_modlinear.hip.  DESIGN.md section 18.
 //
-// A workgroup owns T = 64 rows.  CT = 32 NJ (NJ = 1, 2, 4) is the channel width a kernel
-// instantiation holds; C <= CT, channels beyond C and rows beyond N are staged as zeros, the summed index over the
-// channels runs to C rounded up to 16 only.
-//   forward   x tile -> LDS, normalised in place (4 lanes per row, fixed order).  Per chunk of 64 hidden features:
-//             a = xn W1^T (one chain over C) + b1 -> stored when the caller asks -> g = GELU(a) in registers -> LDS;
-//             t_chunk = g W2^T (one chain over the chunk's 64 features), y accumulators += t_chunk.  The end adds b2,
-//             multiplies by s_r, adds x and stores.  A wave's y tile is 32 rows x 16 NJ channels.
-//   backward  k_ffn_bwd_rows: dt = s o dy -> LDS; per chunk dg = dt W2 (chain over C), da = dg o gelu'(a) -> workspace
-//             and LDS, dxn accumulators += da W1 (chain over the chunk); then dxn -> LDS, the LayerNorm backward per row,
-//             dx = dy + ..., and the tile's column sums of dxn o xhat and dxn (row groups in ascending order).
-//             k_ffn_dw: dW1 = da^T xn and dW2 = dt^T GELU(a) in row slices (k_modlinear_dw's scheme, both in one
-//             launch), with db1 / db2 as the column sums of the slice's da / dt.  k_ffn_fold_params adds the slices
-//             pairwise, a fixed tree; fold_ln_partials (gcm_tile.h) adds the tiles' LayerNorm partials in tile order.
+// A workgroup owns T = 64 rows.  CT = 32 NJ NB is the channel width a kernel instantiation holds: NB column blocks of 32 NJ
+// (NJ = 1, 2, 4 and NB = 1 up to 128 channels; NJ = 4 and NB = 2, 4 for CT = 256, 512).  C <= CT, channels beyond C and
+// rows beyond N are staged as zeros, the summed index over the channels runs to C rounded up to 16 only.
+//
+// The arithmetic exists once, as __forceinline__ bodies (FfnRows .. ffn_ln_tail below) under two families of kernels:
+//   forward   ffn_row_image: x tile -> LDS, normalised in place (4 lanes per row, fixed order).  ffn_forward_chunk, per
+//             chunk of 64 hidden features: a = xn W1^T (one chain over C) + b1 -> stored when the caller asks ->
+//             g = GELU(a) in registers -> LDS; per column block t_chunk = g W2^T (one chain from 0 over the chunk's 64
+//             features), handed to the kernel's sink.  A wave's tile of a column block is 32 rows x 16 NJ channels.
+//   backward  ffn_stage_dt: dt = s o dy -> LDS.  ffn_backward_chunk: dg = dt W2 (chain over C), da = dg o gelu'(a) ->
+//             workspace and LDS, per column block dxn_chunk = da W1 (chain over the chunk) -> the sink.  ffn_ln_tail: from
+//             dxn in LDS the LayerNorm backward per row, dx = dy + ..., and the tile's column sums of dxn o xhat and dxn
+//             (row groups in ascending order).
+//   one launch (gcm_ffn_*, C <= 128)  k_ffn_forward, k_ffn_bwd_rows: a workgroup walks every chunk, the sink adds the chunk
+//             onto cleared accumulators in registers, and the kernel ends the operator itself: + b2, o s_r, + x; or dxn ->
+//             LDS and the tail.
+//   split (gcm_ffn_split_*, C <= 512)  the grid is (row tiles, hidden groups) and the second product leaves the workgroup as
+//             a partial record [chunk][N][C] (SplitWalk); k_ffn_split_finish and k_ffn_split_bwd_ln add the records in
+//             ascending chunk order from +0 -- the order the one-launch kernels add onto their cleared accumulators -- and
+//             end the operator.  Two modes, chosen by the plan from N, C and Hd alone:
+//               split  one chunk per workgroup, P = ceil(Hd / 64) records            (tiles x chunks <= kFfnSplitLimit)
+//               rows   a workgroup walks all chunks and adds them in registers, P = 1 (the workspace stays bounded)
+//             Every path is "per chunk one chain from 0, the chunks added in ascending order", so neither the mode nor the
+//             family shows in the bits.  LDS is dynamic here: the row image alone is 132 096 bytes at CT = 512.
+//   weights   k_ffn_dw: dW1 = da^T xn and dW2 = dt^T GELU(a) in row slices (k_modlinear_dw's scheme, both in one launch),
+//             with db1 / db2 as the column sums of the slice's da / dt.  k_ffn_fold_params adds the slices pairwise, a fixed
+//             tree; fold_ln_partials (gcm_tile.h) adds the tiles' LayerNorm partials in tile order.  Both families use them.
 // Nothing depends on how many workgroups are resident: every sum has a fixed set of terms in a fixed order.
 #pragma once
 #include <atomic>
 
 namespace {
 
-constexpr int kFfnMaxChannels = 128;   // widest instantiation (NJ = 4)
+constexpr int kFfnMaxChannels = 128;   // widest one-launch instantiation (NJ = 4)
 constexpr int kFfnSumRows = 32;        // weight gradients: a chain runs over this many rows, the chains' results are added in order
 
-// ---- forward ----------------------------------------------------------------------------------------------------------
+// ---- the bodies both kernel families run -------------------------------------------------------------------------------
+// The workgroup's row tile and the extents every body needs.  The bodies take it by value: behind a reference the widest
+// rows-mode instantiations spent up to 90 more registers.
+struct FfnRows {
+  WaveTile g;
+  int64_t row0, N;
+  int C, Hd, Cr;  // Cr: C rounded up to whole slices, the extent of a chain over the channels
+  __device__ __forceinline__ FfnRows(int64_t N_, int C_, int Hd_)
+      : row0((int64_t)blockIdx.x * T), N(N_), C(C_), Hd(Hd_), Cr((C_ + KC - 1) / KC * KC) {}
+};
+
+// The row image: the tile's x rows -> Xs (pitch XP), LayerNorm in place.  Every workgroup of a tile forms the same
+// statistics; the one whose `stores` holds writes mean and rstd, when they are not null.
+__device__ __forceinline__ void ffn_row_image(const FfnRows t, float* Xs, int XP, const float* __restrict__ x, int64_t xs,
+                                              const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
+                                              bool stores, float* __restrict__ mean, float* __restrict__ rstd) {
+  stage_rows(Xs, XP, t.Cr >> 2,
+             [&](int r, int c) { return (t.row0 + r < t.N && c < t.C) ? ld4(x + (t.row0 + r) * xs + c) : zero4(); });
+  __syncthreads();
+  const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
+  const bool live = t.row0 + r < t.N;
+  const RowStat st = ln_rows_forward(
+      &Xs[r * XP], q, t.C, eps, [](int, f4) {}, [&](int c, f4 h) { return live ? h * ld4(lnw + c) + ld4(lnb + c) : zero4(); });
+  if (live && q == 0 && mean && stores) {
+    mean[t.row0 + r] = st.mean;
+    rstd[t.row0 + r] = st.rstd;
+  }
+}
+
+// The second product of a chunk, either direction.  Per column block nb with a live channel: tacc = Gs . wb_in(first column)
+// as ONE chain from 0 over the chunk's features (whole slices of them: kend), then sink(nb, tacc) -- run() is never handed
+// anything but a cleared tacc.  The caller has issued two.first(wb_in(0)) from the tail of the first product; the later
+// blocks' first slices are fetched in front of their chains.
+template <int NJ, int NB, bool TFORM, int WN, typename WB, typename Sink>
+__device__ __forceinline__ void ffn_column_blocks(Chain<NJ, TFORM>& two, const FfnRows t, int h0, const float* Gs, float (&Ws)[WN],
+                                                  WB wb_in, Sink sink) {
+  constexpr int CB = 32 * NJ;
+  const int kend = t.Hd - h0 < FH ? (t.Hd - h0 + KC - 1) / KC * KC : FH;
+#pragma unroll
+  for (int nb = 0; nb < NB; nb++) {
+    if (NB == 1 || nb * CB < t.C) {  // else: a column block without a live channel
+      f4 tacc[2][NJ];
+      clear_acc(tacc);
+      if (nb > 0) two.first(wb_in(nb * CB));
+      two.run(tacc, t.g, Gs, kPitchG, kend, Ws, wb_in(nb * CB));
+      sink(nb, tacc);
+    }
+  }
+}
+
+// One chunk of FH hidden features, forward: a = xn W1^T + b1 as one chain over the channels of the row image Xs (pitch
+// 32 NJ NB + 4), stored when `a` is not null; g = GELU(a) -> Gs; then t = g W2^T per column block -> sink.
+template <int NJ, int NB, int WN, typename Sink>
+__device__ __forceinline__ void ffn_forward_chunk(const FfnRows t, int h0, const float* Xs, float* Gs, float (&Ws)[WN],
+                                                  const float* __restrict__ w1, const float* __restrict__ b1,
+                                                  const float* __restrict__ w2, float* __restrict__ a, Sink sink) {
+  const int64_t N = t.N;
+  const int C = t.C, Hd = t.Hd;
+  auto w1_at = [&](int hl, int c) { return (h0 + hl < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + hl) * C + c) : zero4(); };
+  auto w2_in = [&](int cb) {
+    return [=](int c, int k) { return (cb + c < C && h0 + k < Hd) ? ld4(w2 + (int64_t)(cb + c) * Hd + h0 + k) : zero4(); };
+  };
+  Chain<2, false> up;     // the chunk's 64 hidden features, summed over the channels
+  Chain<NJ, false> down;  // a column block, summed over the chunk's hidden features
+  f4 acc[2][2];
+  clear_acc(acc);
+  up.first(w1_at);
+  up.run(acc, t.g, Xs, 32 * NJ * NB + 4, t.Cr, Ws, w1_at, [&]() { down.first(w2_in(0)); });
+  for_each_output(acc, t.g, [&](int rl, int hl, float v) {
+    const int64_t row = t.row0 + rl;
+    const int h = h0 + hl;
+    float gv = 0.0f;
+    if (h < Hd) {
+      const float av = v + b1[h];
+      if (a && row < N) a[row * Hd + h] = av;
+      gv = gelu_f(av);
+    }
+    Gs[rl * kPitchG + hl] = gv;
+  });
+  ffn_column_blocks<NJ, NB>(down, t, h0, Gs, Ws, w2_in, sink);
+}
+
+// The same backward: dg = dt W2 as one chain over the channels of dt's image Ds, da = dg o gelu'(a) -> workspace (always)
+// and Gs; then dxn = da W1 per column block -> sink.
+template <int NJ, int NB, int WN, typename Sink>
+__device__ __forceinline__ void ffn_backward_chunk(const FfnRows t, int h0, const float* Ds, float* Gs, float (&Ws)[WN],
+                                                   const float* __restrict__ a, const float* __restrict__ w1,
+                                                   const float* __restrict__ w2, float* __restrict__ da, Sink sink) {
+  const int64_t N = t.N;
+  const int C = t.C, Hd = t.Hd;
+  auto w2_at = [&](int hl, int c) { return (c < C && h0 + hl < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + hl) : zero4(); };
+  auto w1_in = [&](int cb) {
+    return [=](int c, int k) { return (h0 + k < Hd && cb + c < C) ? ld4(w1 + (int64_t)(h0 + k) * C + cb + c) : zero4(); };
+  };
+  Chain<2, true> back2;   // the chunk's 64 hidden features, summed over the channels
+  Chain<NJ, true> back1;  // a column block, summed over the chunk's hidden features
+  f4 acc[2][2];
+  clear_acc(acc);
+  back2.first(w2_at);
+  back2.run(acc, t.g, Ds, 32 * NJ * NB + 4, t.Cr, Ws, w2_at, [&]() { back1.first(w1_in(0)); });
+  for_each_output(acc, t.g, [&](int rl, int hl, float v) {
+    const int64_t row = t.row0 + rl;
+    const int h = h0 + hl;
+    float dv = 0.0f;
+    if (h < Hd && row < N) {
+      dv = v * gelu_grad_f(a[row * Hd + h]);
+      da[row * Hd + h] = dv;
+    }
+    Gs[rl * kPitchG + hl] = dv;
+  });
+  ffn_column_blocks<NJ, NB>(back1, t, h0, Gs, Ws, w1_in, sink);
+}
+
+// the backward's row image dt = s o dy -> Ds (pitch XP), and the rows' saved statistics -> sMean, sRstd
+__device__ __forceinline__ void ffn_stage_dt(const FfnRows t, float* Ds, int XP, const float* __restrict__ dy, int64_t dys,
+                                             const float* __restrict__ s) {
+  stage_rows(Ds, XP, t.Cr >> 2, [&](int r, int c) {
+    f4 v = zero4();
+    if (t.row0 + r < t.N && c < t.C) {
+      v = ld4(dy + (t.row0 + r) * dys + c);
+      if (s) v = v * s[t.row0 + r];
+    }
+    return v;
+  });
+}
+__device__ __forceinline__ void ffn_load_stats(const FfnRows t, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                               float* sMean, float* sRstd) {
+  const int tid = threadIdx.x;
+  if (tid < T) {
+    const bool live = t.row0 + tid < t.N;
+    sMean[tid] = live ? mean[t.row0 + tid] : 0.0f;
+    sRstd[tid] = live ? rstd[t.row0 + tid] : 0.0f;
+  }
+}
+
+// The end of the backward's row side, from dxn in Ds (pitch 32 NJ NB + 4; written by the caller, the barrier is here) and
+// the statistics in sMean / sRstd: the LayerNorm backward per row and dx = dy + ... when dx is not null (in registers up to
+// 128 channels, re-reading beyond), the tile's column sums into lnpart [tiles][2][C] when that is not null.
+template <int NJ, int NB>
+__device__ __forceinline__ void ffn_ln_tail(const FfnRows t, const float* Ds, float* Gs, const float* sMean, const float* sRstd,
+                                            const float* __restrict__ x, int64_t xs, const float* __restrict__ dy, int64_t dys,
+                                            const float* __restrict__ lnw, float* __restrict__ dx, int64_t dxs,
+                                            float* __restrict__ lnpart) {
+  constexpr int CT = 32 * NJ * NB, XP = CT + 4;
+  __syncthreads();
+  if (dx) {
+    const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
+    const int64_t row = t.row0 + r;
+    auto src = [&](int c) { return ld4(x + row * xs + c); };
+    auto out = [&](int c, f4 v) { st4(dx + row * dxs + c, ld4(dy + row * dys + c) + v); };
+    if constexpr (NB == 1) ln_rows_backward<NJ>(&Ds[r * XP], q, t.C, row < t.N, {sMean[r], sRstd[r]}, lnw, src, out, [](int) {});
+    else ln_rows_backward_reread(&Ds[r * XP], q, t.C, row < t.N, {sMean[r], sRstd[r]}, lnw, src, out);
+  }
+  if (lnpart) ln_col_sums<CT>(Ds, x, xs, sMean, sRstd, t.row0, t.N, t.C, Gs, lnpart + (int64_t)blockIdx.x * 2 * t.C);
+}
+
+// ---- one launch per direction, up to 128 channels -------------------------------------------------------------------------
 template <int NJ>
 __global__ __launch_bounds__(256, 2) void k_ffn_forward(const float* __restrict__ x, int64_t xs, const float* __restrict__ lnw,
                                                         const float* __restrict__ lnb, float eps, const float* __restrict__ w1,
@@ -38,63 +208,23 @@ __global__ __launch_bounds__(256, 2) void k_ffn_forward(const float* __restrict_
   __shared__ __attribute__((aligned(16))) float Xs[T * XP];                    // x, then LN(x): rows x channels
   __shared__ __attribute__((aligned(16))) float Gs[T * kPitchG];               // GELU(a) of one chunk: rows x hidden
   __shared__ __attribute__((aligned(16))) float Ws[(CT > T ? CT : T) * kPitch];  // a 16-deep slice of W1, then of W2
-  const int tid = threadIdx.x;
-  const WaveTile g;
-  const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC;
+  const FfnRows t(N, C, Hd);
+  ffn_row_image(t, Xs, XP, x, xs, lnw, lnb, eps, true, mean, rstd);
 
-  stage_rows(Xs, XP, Cr >> 2, [&](int r, int c) { return (row0 + r < N && c < C) ? ld4(x + (row0 + r) * xs + c) : zero4(); });
-  __syncthreads();
-  {  // LayerNorm in place
-    const int r = tid >> 2, q = tid & 3;
-    const bool live = row0 + r < N;
-    const RowStat st = ln_rows_forward(
-        &Xs[r * XP], q, C, eps, [](int, f4) {}, [&](int c, f4 h) { return live ? h * ld4(lnw + c) + ld4(lnb + c) : zero4(); });
-    if (live && q == 0 && mean) {
-      mean[row0 + r] = st.mean;
-      rstd[row0 + r] = st.rstd;
-    }
-  }
-
-  Chain<2, false> up;     // a = xn W1^T: 64 hidden features of the chunk, summed over the channels
-  Chain<NJ, false> down;  // t = g W2^T: the channels, summed over the chunk's hidden features
   f4 yacc[2][NJ];
   clear_acc(yacc);
-  for (int h0 = 0; h0 < Hd; h0 += FH) {
-    auto w1_at = [&](int hl, int c) { return (h0 + hl < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + hl) * C + c) : zero4(); };
-    auto w2_at = [&](int c, int k) { return (c < C && h0 + k < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + k) : zero4(); };
-    f4 acc[2][2];
-    clear_acc(acc);
-    up.first(w1_at);
-    up.run(acc, g, Xs, XP, Cr, Ws, w1_at, [&]() { down.first(w2_at); });
-    for_each_output(acc, g, [&](int rl, int hl, float v) {
-      const int64_t row = row0 + rl;
-      const int h = h0 + hl;
-      float gv = 0.0f;
-      if (h < Hd) {
-        const float av = v + b1[h];
-        if (a && row < N) a[row * Hd + h] = av;
-        gv = gelu_f(av);
-      }
-      Gs[rl * kPitchG + hl] = gv;
-    });
-    const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
-    f4 tacc[2][NJ];
-    clear_acc(tacc);
-    down.run(tacc, g, Gs, kPitchG, kend, Ws, w2_at);
-    add_acc(yacc, tacc);
-  }
+  for (int h0 = 0; h0 < Hd; h0 += FH)
+    ffn_forward_chunk<NJ, 1>(t, h0, Xs, Gs, Ws, w1, b1, w2, a, [&](int, const f4(&tacc)[2][NJ]) { add_acc(yacc, tacc); });
 
   for_each_output(
-      yacc, g, [&](int rl) { return scaled_row(row0 + rl, N, s); },
+      yacc, t.g, [&](int rl) { return scaled_row(t.row0 + rl, N, s); },
       [&](ScaledRow r, int c, float v) {
         if (r.row < 0 || c >= C) return;
-        const float t = v + b2[c];
-        y[r.row * ys + c] = x[r.row * xs + c] + (s ? r.scale * t : t);
+        const float tv = v + b2[c];
+        y[r.row * ys + c] = x[r.row * xs + c] + (s ? r.scale * tv : tv);
       });
 }
 
-// ---- backward, the row tiles --------------------------------------------------------------------------------------------
 // da [N][Hd] is always written; dx and lnpart [tiles][2][C] (column sums of dxn o xhat, then of dxn) when not null.
 template <int NJ>
 __global__ __launch_bounds__(256, 2) void k_ffn_bwd_rows(const float* __restrict__ x, int64_t xs, const float* __restrict__ mean,
@@ -109,64 +239,17 @@ __global__ __launch_bounds__(256, 2) void k_ffn_bwd_rows(const float* __restrict
   __shared__ __attribute__((aligned(16))) float Gs[T * kPitchG];               // da of one chunk; then the column partials
   __shared__ __attribute__((aligned(16))) float Ws[KC * ((CT > T ? CT : T) + 16)];  // a slice of W2, then of W1
   __shared__ float sMean[T], sRstd[T];
-  const int tid = threadIdx.x;
-  const WaveTile g;
-  const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC;
+  const FfnRows t(N, C, Hd);
+  ffn_load_stats(t, mean, rstd, sMean, sRstd);
+  ffn_stage_dt(t, Ds, XP, dy, dys, s);
 
-  if (tid < T) {
-    const bool live = row0 + tid < N;
-    sMean[tid] = live ? mean[row0 + tid] : 0.0f;
-    sRstd[tid] = live ? rstd[row0 + tid] : 0.0f;
-  }
-  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
-    f4 v = zero4();
-    if (row0 + r < N && c < C) {
-      v = ld4(dy + (row0 + r) * dys + c);
-      if (s) v = v * s[row0 + r];
-    }
-    return v;
-  });
-
-  Chain<2, true> back2;   // dg = dt W2: 64 hidden features of the chunk, summed over the channels
-  Chain<NJ, true> back1;  // dxn = da W1: the channels, summed over the chunk's hidden features
   f4 xacc[2][NJ];
   clear_acc(xacc);
-  for (int h0 = 0; h0 < Hd; h0 += FH) {
-    auto w2_at = [&](int hl, int c) { return (c < C && h0 + hl < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + hl) : zero4(); };
-    auto w1_at = [&](int c, int k) { return (h0 + k < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + k) * C + c) : zero4(); };
-    f4 acc[2][2];
-    clear_acc(acc);
-    back2.first(w2_at);
-    back2.run(acc, g, Ds, XP, Cr, Ws, w2_at, [&]() { back1.first(w1_at); });
-    for_each_output(acc, g, [&](int rl, int hl, float v) {
-      const int64_t row = row0 + rl;
-      const int h = h0 + hl;
-      float dv = 0.0f;
-      if (h < Hd && row < N) {
-        dv = v * gelu_grad_f(a[row * Hd + h]);
-        da[row * Hd + h] = dv;
-      }
-      Gs[rl * kPitchG + hl] = dv;
-    });
-    const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
-    f4 tacc[2][NJ];
-    clear_acc(tacc);
-    back1.run(tacc, g, Gs, kPitchG, kend, Ws, w1_at);
-    add_acc(xacc, tacc);
-  }
+  for (int h0 = 0; h0 < Hd; h0 += FH)
+    ffn_backward_chunk<NJ, 1>(t, h0, Ds, Gs, Ws, a, w1, w2, da, [&](int, const f4(&tacc)[2][NJ]) { add_acc(xacc, tacc); });
 
-  for_each_output(xacc, g, [&](int rl, int c, float v) { Ds[rl * XP + c] = v; });  // dxn over dt's image
-  __syncthreads();
-
-  if (dx) {  // LayerNorm backward
-    const int r = tid >> 2, q = tid & 3;
-    const int64_t row = row0 + r;
-    ln_rows_backward<NJ>(
-        &Ds[r * XP], q, C, row < N, {sMean[r], sRstd[r]}, lnw, [&](int c) { return ld4(x + row * xs + c); },
-        [&](int c, f4 v) { st4(dx + row * dxs + c, ld4(dy + row * dys + c) + v); }, [](int) {});
-  }
-  if (lnpart) ln_col_sums<CT>(Ds, x, xs, sMean, sRstd, row0, N, C, Gs, lnpart + (int64_t)blockIdx.x * 2 * C);
+  for_each_output(xacc, t.g, [&](int rl, int c, float v) { Ds[rl * XP + c] = v; });  // dxn over dt's image
+  ffn_ln_tail<NJ, 1>(t, Ds, Gs, sMean, sRstd, x, xs, dy, dys, lnw, dx, dxs, lnpart);
 }
 
 // ---- backward, the two weight gradients ---------------------------------------------------------------------------------
@@ -315,39 +398,7 @@ __global__ void k_ffn_fold_params(const float* __restrict__ part, int S, int64_t
   *out = v[0];
 }
 
-// ---- host: the plan and the launches ------------------------------------------------------------------------------------
-struct FfnPlan {
-  int64_t tiles;   // row tiles
-  int64_t groups;  // first-level groups of the LayerNorm partials (0: one level)
-  int64_t gper;    // tiles per group
-  int sw;          // row slices of the weight gradients
-  size_t da, lnpart, lngroup, wpart, total;
-};
-FfnPlan ffn_plan(int64_t N, int32_t C, int32_t Hd) {
-  FfnPlan p;
-  p.tiles = (N + T - 1) / T;
-  fold_groups(p.tiles, p.groups, p.gper);
-  p.sw = weight_slices((int64_t)((Hd + T - 1) / T) * ((C + T - 1) / T), N);
-  Carve ws;
-  p.da = ws.take((size_t)N * Hd * 4);
-  p.lnpart = ws.take((size_t)p.tiles * 2 * C * 4);
-  p.lngroup = ws.take((size_t)p.groups * 2 * C * 4);
-  p.wpart = ws.take((size_t)p.sw * (size_t)ffn_record(C, Hd) * 4);
-  p.total = ws.off;
-  return p;
-}
-
-// ---- the same operator up to 512 channels, the hidden width split across workgroups (gcm_ffn_split_*) -------------------
-// The row-side kernels above walk every chunk of 64 hidden features in one workgroup per 64 rows: 17 workgroups at
-// N = 1063.  Here the grid is (row tiles, hidden groups) and a chunk's second product leaves the workgroup as a partial
-// record [chunk][N][C]; a second kernel adds the records in ascending chunk order from +0 -- the order k_ffn_forward adds
-// tacc onto its cleared yacc -- and ends the operator.  Two modes, chosen by the plan from N, C and Hd alone:
-//   split  one chunk per workgroup, P = ceil(Hd / 64) records            (tiles x chunks <= kFfnSplitLimit)
-//   rows   a workgroup walks all chunks and adds them in registers, P = 1 (the workspace stays bounded)
-// Both are "per chunk one chain from 0, the chunks added in ascending order", so the mode never shows in the bits, and at
-// C <= 128 the bits are those of the kernels above.  CT = 32 NJ NB: NB column blocks of 32 NJ for the second product
-// (NB = 1 up to 128 channels; NJ = 4 and NB = 2, 4 for CT = 256, 512).  LDS is dynamic: the row image alone is 132 096
-// bytes at CT = 512.
+// ---- up to 512 channels, the hidden width split across workgroups (gcm_ffn_split_*) ---------------------------------------
 #ifndef GCM_FFN_SPLIT_LIMIT
 #define GCM_FFN_SPLIT_LIMIT 2048
 #endif
@@ -393,78 +444,59 @@ __device__ __forceinline__ f4 split_fold(const float* __restrict__ at, int64_t r
   return v;
 }
 
-// grid (row tiles, SPLIT ? chunks : 1).  mean, rstd (from the workgroups of group 0) and a when not null.
+// Which chunks a workgroup of the grid (row tiles, SPLIT ? chunks : 1) walks, hbeg .. hend, and where their second products
+// go.  SPLIT: the chunk blockIdx.y, each column block into the chunk's record.  Rows mode: every chunk, added in ascending
+// order onto cleared accumulators, which finish() puts into record 0.
+template <int NJ, int NB, bool SPLIT>
+struct SplitWalk {
+  static constexpr int CB = 32 * NJ;
+  const FfnRows& t;
+  float* __restrict__ part;
+  int hbeg, hend;
+  f4 sum[SPLIT ? 1 : NB][2][NJ];
+  __device__ __forceinline__ SplitWalk(const FfnRows& t_, float* part_) : t(t_), part(part_) {
+    hbeg = SPLIT ? (int)blockIdx.y * FH : 0;
+    hend = SPLIT ? (hbeg + FH < t.Hd ? hbeg + FH : t.Hd) : t.Hd;
+    if (!SPLIT)
+#pragma unroll
+      for (int nb = 0; nb < NB; nb++) clear_acc(sum[nb]);
+  }
+  // Where chunk h0's column blocks go.  SPLIT: the callable holds copies of what it needs and nothing of this object --
+  // read through the object, N and C were loaded again after every store to `part` and each record address was formed
+  // anew: a fifth more instructions at CT = 512 and 3 % of the forward's time.
+  __device__ __forceinline__ auto sink(int h0) {
+    if constexpr (SPLIT) {
+      const FfnRows r = t;
+      float* p = part;
+      return [=](int nb, const f4(&tacc)[2][NJ]) { split_store(tacc, r.g, p, h0 / FH, r.row0, r.N, r.C, nb * CB); };
+    } else {
+      return [this](int nb, const f4(&tacc)[2][NJ]) { add_acc(sum[nb], tacc); };
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    if (!SPLIT)
+#pragma unroll
+      for (int nb = 0; nb < NB; nb++) split_store(sum[nb], t.g, part, 0, t.row0, t.N, t.C, nb * CB);
+  }
+};
+
+// the chunks' t as partial records; mean, rstd (from the workgroups of group 0) and a when not null
 template <int NJ, int NB, bool SPLIT>
 __global__ __launch_bounds__(256, NB > 1 ? 1 : 2) void k_ffn_split_forward(
     const float* __restrict__ x, int64_t xs, const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
     const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, int64_t N, int C, int Hd,
     float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ a, float* __restrict__ part) {
-  constexpr int CB = 32 * NJ, CT = CB * NB, XP = CT + 4, WN = split_slice_cols(NJ) * kPitch;
+  constexpr int XP = 32 * NJ * NB + 4, WN = split_slice_cols(NJ) * kPitch;
   extern __shared__ __attribute__((aligned(16))) float split_lds[];
   float* Xs = split_lds;                                                // x, then LN(x): rows x channels
   float* Gs = Xs + T * XP;                                              // GELU(a) of one chunk: rows x hidden
   float(&Ws)[WN] = *reinterpret_cast<float(*)[WN]>(Gs + T * kPitchG);   // a 16-deep slice of W1, then of W2
-  const int tid = threadIdx.x;
-  const WaveTile g;
-  const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC;
-  const int hbeg = SPLIT ? (int)blockIdx.y * FH : 0, hend = SPLIT ? (hbeg + FH < Hd ? hbeg + FH : Hd) : Hd;
-
-  stage_rows(Xs, XP, Cr >> 2, [&](int r, int c) { return (row0 + r < N && c < C) ? ld4(x + (row0 + r) * xs + c) : zero4(); });
-  __syncthreads();
-  {  // LayerNorm in place; every workgroup of a tile forms the same statistics, group 0 stores them
-    const int r = tid >> 2, q = tid & 3;
-    const bool live = row0 + r < N;
-    const RowStat st = ln_rows_forward(
-        &Xs[r * XP], q, C, eps, [](int, f4) {}, [&](int c, f4 h) { return live ? h * ld4(lnw + c) + ld4(lnb + c) : zero4(); });
-    if (live && q == 0 && mean && blockIdx.y == 0) {
-      mean[row0 + r] = st.mean;
-      rstd[row0 + r] = st.rstd;
-    }
-  }
-
-  Chain<2, false> up;     // a = xn W1^T: the chunk's 64 hidden features, summed over the channels
-  Chain<NJ, false> down;  // t = g W2^T: a column block, summed over the chunk's hidden features
-  f4 yacc[SPLIT ? 1 : NB][2][NJ];
-  if (!SPLIT)
-#pragma unroll
-    for (int nb = 0; nb < NB; nb++) clear_acc(yacc[nb]);
-  for (int h0 = hbeg; h0 < hend; h0 += FH) {
-    auto w1_at = [&](int hl, int c) { return (h0 + hl < Hd && c < C) ? ld4(w1 + (int64_t)(h0 + hl) * C + c) : zero4(); };
-    auto w2_in = [&](int cb) {
-      return [=](int c, int k) { return (cb + c < C && h0 + k < Hd) ? ld4(w2 + (int64_t)(cb + c) * Hd + h0 + k) : zero4(); };
-    };
-    f4 acc[2][2];
-    clear_acc(acc);
-    up.first(w1_at);
-    up.run(acc, g, Xs, XP, Cr, Ws, w1_at, [&]() { down.first(w2_in(0)); });
-    for_each_output(acc, g, [&](int rl, int hl, float v) {
-      const int64_t row = row0 + rl;
-      const int h = h0 + hl;
-      float gv = 0.0f;
-      if (h < Hd) {
-        const float av = v + b1[h];
-        if (a && row < N) a[row * Hd + h] = av;
-        gv = gelu_f(av);
-      }
-      Gs[rl * kPitchG + hl] = gv;
-    });
-    const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
-#pragma unroll
-    for (int nb = 0; nb < NB; nb++) {
-      if (nb * CB < C) {  // else: a column block without a live channel
-        f4 tacc[2][NJ];
-        clear_acc(tacc);
-        if (nb > 0) down.first(w2_in(nb * CB));
-        down.run(tacc, g, Gs, kPitchG, kend, Ws, w2_in(nb * CB));
-        if (SPLIT) split_store(tacc, g, part, h0 / FH, row0, N, C, nb * CB);
-        else add_acc(yacc[nb], tacc);
-      }
-    }
-  }
-  if (!SPLIT)
-#pragma unroll
-    for (int nb = 0; nb < NB; nb++) split_store(yacc[nb], g, part, 0, row0, N, C, nb * CB);
+  const FfnRows t(N, C, Hd);
+  ffn_row_image(t, Xs, XP, x, xs, lnw, lnb, eps, blockIdx.y == 0, mean, rstd);
+  SplitWalk<NJ, NB, SPLIT> walk(t, part);
+  for (int h0 = walk.hbeg; h0 < walk.hend; h0 += FH)
+    ffn_forward_chunk<NJ, NB>(t, h0, Xs, Gs, Ws, w1, b1, w2, a, walk.sink(h0));
+  walk.finish();
 }
 
 // y = x + s_r ((the P records added in ascending order from +0) + b2): one thread per four channels of a row
@@ -480,111 +512,45 @@ __global__ void k_ffn_split_finish(const float* __restrict__ part, int P, const 
   st4(y + row * ys + c, ld4(x + row * xs + c) + (s ? t * s[row] : t));
 }
 
-// da [N][Hd] for the workgroup's chunk(s), and the chunk's dxn as a partial record (rows mode: the chunks' sum, record 0)
+// da [N][Hd] for the workgroup's chunk(s), and the chunks' dxn as partial records
 template <int NJ, int NB, bool SPLIT>
 __global__ __launch_bounds__(256, NB > 1 ? 1 : 2) void k_ffn_split_bwd_rows(
     const float* __restrict__ a, const float* __restrict__ dy, int64_t dys, const float* __restrict__ s,
     const float* __restrict__ w1, const float* __restrict__ w2, int64_t N, int C, int Hd, float* __restrict__ da,
     float* __restrict__ part) {
-  constexpr int CB = 32 * NJ, CT = CB * NB, XP = CT + 4, WN = KC * (split_slice_cols(NJ) + 16);
+  constexpr int XP = 32 * NJ * NB + 4, WN = KC * (split_slice_cols(NJ) + 16);
   extern __shared__ __attribute__((aligned(16))) float split_lds[];
   float* Ds = split_lds;                                                // dt: rows x channels
   float* Gs = Ds + T * XP;                                              // da of one chunk
   float(&Ws)[WN] = *reinterpret_cast<float(*)[WN]>(Gs + T * kPitchG);   // a slice of W2, then of W1
-  const WaveTile g;
-  const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC;
-  const int hbeg = SPLIT ? (int)blockIdx.y * FH : 0, hend = SPLIT ? (hbeg + FH < Hd ? hbeg + FH : Hd) : Hd;
-
-  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
-    f4 v = zero4();
-    if (row0 + r < N && c < C) {
-      v = ld4(dy + (row0 + r) * dys + c);
-      if (s) v = v * s[row0 + r];
-    }
-    return v;
-  });
-
-  Chain<2, true> back2;   // dg = dt W2: the chunk's 64 hidden features, summed over the channels
-  Chain<NJ, true> back1;  // dxn = da W1: a column block, summed over the chunk's hidden features
-  f4 xacc[SPLIT ? 1 : NB][2][NJ];
-  if (!SPLIT)
-#pragma unroll
-    for (int nb = 0; nb < NB; nb++) clear_acc(xacc[nb]);
-  for (int h0 = hbeg; h0 < hend; h0 += FH) {
-    auto w2_at = [&](int hl, int c) { return (c < C && h0 + hl < Hd) ? ld4(w2 + (int64_t)c * Hd + h0 + hl) : zero4(); };
-    auto w1_in = [&](int cb) {
-      return [=](int c, int k) { return (h0 + k < Hd && cb + c < C) ? ld4(w1 + (int64_t)(h0 + k) * C + cb + c) : zero4(); };
-    };
-    f4 acc[2][2];
-    clear_acc(acc);
-    back2.first(w2_at);
-    back2.run(acc, g, Ds, XP, Cr, Ws, w2_at, [&]() { back1.first(w1_in(0)); });
-    for_each_output(acc, g, [&](int rl, int hl, float v) {
-      const int64_t row = row0 + rl;
-      const int h = h0 + hl;
-      float dv = 0.0f;
-      if (h < Hd && row < N) {
-        dv = v * gelu_grad_f(a[row * Hd + h]);
-        da[row * Hd + h] = dv;
-      }
-      Gs[rl * kPitchG + hl] = dv;
-    });
-    const int kend = Hd - h0 < FH ? (Hd - h0 + KC - 1) / KC * KC : FH;
-#pragma unroll
-    for (int nb = 0; nb < NB; nb++) {
-      if (nb * CB < C) {
-        f4 tacc[2][NJ];
-        clear_acc(tacc);
-        if (nb > 0) back1.first(w1_in(nb * CB));
-        back1.run(tacc, g, Gs, kPitchG, kend, Ws, w1_in(nb * CB));
-        if (SPLIT) split_store(tacc, g, part, h0 / FH, row0, N, C, nb * CB);
-        else add_acc(xacc[nb], tacc);
-      }
-    }
-  }
-  if (!SPLIT)
-#pragma unroll
-    for (int nb = 0; nb < NB; nb++) split_store(xacc[nb], g, part, 0, row0, N, C, nb * CB);
+  const FfnRows t(N, C, Hd);
+  ffn_stage_dt(t, Ds, XP, dy, dys, s);
+  SplitWalk<NJ, NB, SPLIT> walk(t, part);
+  for (int h0 = walk.hbeg; h0 < walk.hend; h0 += FH)
+    ffn_backward_chunk<NJ, NB>(t, h0, Ds, Gs, Ws, a, w1, w2, da, walk.sink(h0));
+  walk.finish();
 }
 
-// per row tile: dxn = the P records added in ascending order from +0 -> LDS, the LayerNorm backward, dx = dy + ..., and the
-// tile's column sums, as k_ffn_bwd_rows ends
+// per row tile: dxn = the P records added in ascending order from +0 -> LDS, then the tail k_ffn_bwd_rows ends with
 template <int NJ, int NB>
 __global__ __launch_bounds__(256, NB > 1 ? 1 : 2) void k_ffn_split_bwd_ln(
     const float* __restrict__ part, int P, const float* __restrict__ x, int64_t xs, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ dy, int64_t dys, const float* __restrict__ lnw, int64_t N, int C,
     float* __restrict__ dx, int64_t dxs, float* __restrict__ lnpart) {
-  constexpr int CT = 32 * NJ * NB, XP = CT + 4;
+  constexpr int XP = 32 * NJ * NB + 4;
   extern __shared__ __attribute__((aligned(16))) float split_lds[];
   float* Ds = split_lds;       // dxn: rows x channels
   float* Gs = Ds + T * XP;     // the column partials
   __shared__ float sMean[T], sRstd[T];
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * T;
-  const int Cr = (C + KC - 1) / KC * KC;
-
-  if (tid < T) {
-    const bool live = row0 + tid < N;
-    sMean[tid] = live ? mean[row0 + tid] : 0.0f;
-    sRstd[tid] = live ? rstd[row0 + tid] : 0.0f;
-  }
-  stage_rows(Ds, XP, Cr >> 2, [&](int r, int c) {
-    return (row0 + r < N && c < C) ? split_fold(part + (row0 + r) * C + c, N * C, P) : zero4();
+  const FfnRows t(N, C, 0);  // no hidden width is walked here
+  ffn_load_stats(t, mean, rstd, sMean, sRstd);
+  stage_rows(Ds, XP, t.Cr >> 2, [&](int r, int c) {
+    return (t.row0 + r < N && c < C) ? split_fold(part + (t.row0 + r) * C + c, N * C, P) : zero4();
   });
-  __syncthreads();
-
-  if (dx) {  // LayerNorm backward
-    const int r = tid >> 2, q = tid & 3;
-    const int64_t row = row0 + r;
-    auto src = [&](int c) { return ld4(x + row * xs + c); };
-    auto out = [&](int c, f4 v) { st4(dx + row * dxs + c, ld4(dy + row * dys + c) + v); };
-    if constexpr (NB == 1) ln_rows_backward<NJ>(&Ds[r * XP], q, C, row < N, {sMean[r], sRstd[r]}, lnw, src, out, [](int) {});
-    else ln_rows_backward_reread(&Ds[r * XP], q, C, row < N, {sMean[r], sRstd[r]}, lnw, src, out);
-  }
-  if (lnpart) ln_col_sums<CT>(Ds, x, xs, sMean, sRstd, row0, N, C, Gs, lnpart + (int64_t)blockIdx.x * 2 * C);
+  ffn_ln_tail<NJ, NB>(t, Ds, Gs, sMean, sRstd, x, xs, dy, dys, lnw, dx, dxs, lnpart);
 }
 
+// ---- host: the plan and the launches ------------------------------------------------------------------------------------
 // f(std::integral_constant<int, NJ>, std::integral_constant<int, NB>) for the narrowest instantiation that holds C
 template <typename F>
 void with_split_width(int C, F f) {
@@ -593,20 +559,23 @@ void with_split_width(int C, F f) {
   else f(std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
 }
 
-struct FfnSplitPlan {
+// One plan for both families.  with_records: the split entry points, whose row-side kernels leave P partial records; the
+// one-launch entry points are the case "no records, no forward workspace" (records = 0, `part` an empty piece).
+struct FfnPlan {
   bool split;      // one chunk per workgroup
   int64_t tiles, chunks, records;  // row tiles, chunks of 64 hidden features, partial records P
-  int64_t groups, gper;            // the LayerNorm partials' first level, as FfnPlan
-  int sw;                          // row slices of the weight gradients
+  int64_t groups;  // first-level groups of the LayerNorm partials (0: one level)
+  int64_t gper;    // tiles per group
+  int sw;          // row slices of the weight gradients
   size_t fwd_total;                // the forward's workspace: the records of t
   size_t da, part, lnpart, lngroup, wpart, total;  // the backward's carve
 };
-FfnSplitPlan ffn_split_plan(int64_t N, int32_t C, int32_t Hd) {
-  FfnSplitPlan p;
+FfnPlan ffn_plan(int64_t N, int32_t C, int32_t Hd, bool with_records) {
+  FfnPlan p;
   p.tiles = (N + T - 1) / T;
   p.chunks = (Hd + FH - 1) / FH;
-  p.split = p.tiles * p.chunks <= kFfnSplitLimit;
-  p.records = p.split ? p.chunks : 1;
+  p.split = with_records && p.tiles * p.chunks <= kFfnSplitLimit;
+  p.records = !with_records ? 0 : p.split ? p.chunks : 1;
   fold_groups(p.tiles, p.groups, p.gper);
   p.sw = weight_slices((int64_t)((Hd + T - 1) / T) * ((C + T - 1) / T), N);
   const size_t rec = (size_t)p.records * (size_t)N * C * 4;

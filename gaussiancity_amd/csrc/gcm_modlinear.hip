@@ -21,8 +21,10 @@
 // then each row's rank inside its block) gives `perm`, the rows in group order and ascending inside a group; the sum
 // of a group is S slices of its rows, each one chain in that order, folded in slice order.
 //
-// The library's second row-wise MLP, the feed-forward third of a PTv3 Block (gcm_ffn_*), has its kernels in gcm_ffn.h,
-// included below; its C ABI functions are at the end of this file.  DESIGN.md section 18.  The third, the front of the same
+// The library's second row-wise MLP, the feed-forward third of a PTv3 Block (gcm_ffn_* in one launch per direction up to 128
+// channels, gcm_ffn_split_* with the hidden width split across workgroups up to 512), has its kernels and its one plan in
+// gcm_ffn.h, included below; its C ABI functions are at the end of this file, thin wrappers over one argument check of the
+// forward (check_ffn_forward) and one backward (ffn_backward).  DESIGN.md sections 18 and 18a.  The third, the front of the same
 // Block (gcm_front_*: the convolution's Linear and LayerNorm, the residual, norm1 and the qkv projection), is gcm_front.h,
 // included after it.  DESIGN.md section 19.  The fourth, the middle of the same Block around its attention (gcm_mid_*: the
 // patch gather, and the scatter back, the output projection, DropPath and the residual in one launch), is gcm_mid.h.
@@ -513,22 +515,113 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 
 namespace {
 
-int check_ffn_shape(const std::string& w, int64_t N, int32_t C, int32_t Hd) {
+// split: the gcm_ffn_split_* entry points, whose cap is their own
+int check_ffn_shape(const std::string& w, bool split, int64_t N, int32_t C, int32_t Hd) {
+  const int cap = split ? kFfnSplitMaxChannels : kFfnMaxChannels;
+  const std::string query = split ? "gcm_ffn_split_max_channels()" : "gcm_ffn_max_channels()";
   if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
   if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
   if (Hd <= 0 || Hd % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd must be a positive multiple of 4");
-  if (C > kFfnMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_ffn_max_channels()");
-  if (Hd > 4 * kFfnMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd above 4 * gcm_ffn_max_channels()");
+  if (C > cap) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above " + query);
+  if (Hd > 4 * cap) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd above 4 * " + query);
   return 0;
 }
 
-int check_ffn_split_shape(const std::string& w, int64_t N, int32_t C, int32_t Hd) {
-  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
-  if (C <= 0 || C % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C must be a positive multiple of 4");
-  if (Hd <= 0 || Hd % 4 != 0) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd must be a positive multiple of 4");
-  if (C > kFfnSplitMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": C above gcm_ffn_split_max_channels()");
-  if (Hd > 4 * kFfnSplitMaxChannels) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": Hd above 4 * gcm_ffn_split_max_channels()");
+// The arguments of either forward entry point, and the plan.  The split one has a workspace: the partial records.  After
+// a 0 the caller returns at once when N == 0 -- the pointers are looked at for N > 0 only.
+int check_ffn_forward(const std::string& who, bool split, const float* x, int64_t x_stride, const float* ln_w, const float* ln_b,
+                      float eps, const float* w1, const float* b1, const float* w2, const float* b2, int64_t N, int32_t C,
+                      int32_t Hd, const float* y, int64_t y_stride, const float* mean, const float* rstd, const float* a,
+                      const void* workspace, size_t workspace_bytes, FfnPlan& p) {
+  if (int rc = check_ffn_shape(who, split, N, C, Hd)) return rc;
+  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
+  if (int rc = check_strides(who, {{x_stride, C}, {y_stride, C}})) return rc;
+  if (int rc = check_aligned16(who, {x, ln_w, ln_b, w1, b1, w2, b2, y, a})) return rc;
+  p = ffn_plan(N, C, Hd, split);
+  if (split)
+    if (int rc = check_workspace(who, workspace, workspace_bytes, std::max<size_t>(p.fwd_total, 256), "gcm_ffn_split_workspace_bytes"))
+      return rc;
+  if (N == 0) return 0;
+  if (!x || !ln_w || !ln_b || !w1 || !b1 || !w2 || !b2 || !y)
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, ln_w, ln_b, w1, b1, w2, b2 or y");
+  if ((mean == nullptr) != (rstd == nullptr) || (a && !mean))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": mean and rstd come together, and a needs both");
   return 0;
+}
+
+// Either backward entry point.  split chooses the plan, the workspace query the message names, the row-side launches -- one
+// kernel, or partial records and the kernel that folds them -- and the prefix of the HIP error labels; the checks, the N == 0
+// clears, the gating of the launches, the LayerNorm fold and the weight-gradient half are the same.
+int ffn_backward(const std::string& who, bool split, const float* x, int64_t x_stride, const float* mean, const float* rstd,
+                 const float* a, const float* dy, int64_t dy_stride, const float* row_scale, const float* ln_w, const float* ln_b,
+                 const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride, float* dln_w,
+                 float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
+                 void* hip_stream) {
+  const std::string label = split ? "ffn split backward " : "ffn backward ";
+  auto at = [&](const char* what) { return label + what; };
+  if (int rc = check_ffn_shape(who, split, N, C, Hd)) return rc;
+  if (int rc = check_strides(who, {{x_stride, C}, {dy_stride, C}, {dx_stride, C, dx != nullptr}})) return rc;
+  if (int rc = check_aligned16(who, {x, a, dy, ln_w, ln_b, w1, w2, dx, dln_w, dln_b, dw1, db1, dw2, db2})) return rc;
+  const FfnPlan p = ffn_plan(N, C, Hd, split);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total,
+                               split ? "gcm_ffn_split_workspace_bytes" : "gcm_ffn_backward_workspace_bytes"))
+    return rc;
+  if (N > 0 && (!x || !mean || !rstd || !a || !dy || !ln_w || !ln_b || !w1 || !w2))
+    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, mean, rstd, a, dy, ln_w, ln_b, w1 or w2");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
+    const size_t CH = (size_t)C * Hd * 4, C4 = (size_t)C * 4;
+    return clear_outputs(st, {{dln_w, C4, at("clear dln_w").c_str()},  // the labels live to the end of this statement
+                              {dln_b, C4, at("clear dln_b").c_str()},
+                              {dw1, CH, at("clear dw1").c_str()},
+                              {db1, (size_t)Hd * 4, at("clear db1").c_str()},
+                              {dw2, CH, at("clear dw2").c_str()},
+                              {db2, C4, at("clear db2").c_str()}});
+  }
+  if (split) HIP_TRY(split_lds_attr(), "ffn split LDS attribute");
+  char* ws = (char*)workspace;
+  float* da = (float*)(ws + p.da);
+  const bool ln = dln_w || dln_b, first = dw1 || db1, params = first || dw2 || db2;
+  if (dx || ln || first) {
+    float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
+    if (!split) {
+      with_nj(C, [&](auto nj) {
+        k_ffn_bwd_rows<decltype(nj)::value><<<(unsigned)p.tiles, 256, 0, st>>>(x, x_stride, mean, rstd, a, dy, dy_stride, row_scale,
+                                                                              ln_w, w1, w2, N, C, Hd, dx, dx_stride, da, lnpart);
+      });
+    } else {
+      float* part = (float*)(ws + p.part);
+      with_split_width(C, [&](auto nj, auto nb) {
+        constexpr int NJ = decltype(nj)::value, NB = decltype(nb)::value;
+        const dim3 grid((unsigned)p.tiles, (unsigned)p.records);
+        if (p.split)
+          k_ffn_split_bwd_rows<NJ, NB, true><<<grid, 256, split_bwd_lds(NJ, NB), st>>>(a, dy, dy_stride, row_scale, w1, w2, N, C, Hd, da,
+                                                                                       part);
+        else
+          k_ffn_split_bwd_rows<NJ, NB, false><<<grid, 256, split_bwd_lds(NJ, NB), st>>>(a, dy, dy_stride, row_scale, w1, w2, N, C, Hd, da,
+                                                                                        part);
+        if (dx || ln)
+          k_ffn_split_bwd_ln<NJ, NB><<<(unsigned)p.tiles, 256, split_ln_lds(NJ, NB), st>>>(
+              part, (int)p.records, x, x_stride, mean, rstd, dy, dy_stride, ln_w, N, C, dx, dx_stride, lnpart);
+      });
+    }
+    HIP_TRY(hipGetLastError(), at("rows launch").c_str());
+    if (ln) {
+      fold_ln_partials(lnpart, (float*)(ws + p.lngroup), p.tiles, p.groups, p.gper, 2, C, dln_w, dln_b, nullptr, nullptr, st);
+      HIP_TRY(hipGetLastError(), at("LayerNorm fold launch").c_str());
+    }
+  }
+  if (params) {
+    const int64_t per = slice_rows(N, p.sw);
+    float* wpart = (float*)(ws + p.wpart);
+    const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
+    k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
+                                   wpart);
+    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(wpart, p.sw, (int64_t)C * Hd, (int64_t)C * Hd, Hd, C, dw1,
+                                                                          dw2, db1, db2);
+    HIP_TRY(hipGetLastError(), at("weight gradient launch").c_str());
+  }
+  return GCM_OK;
 }
 
 int check_front_shape(const std::string& w, int64_t N, int32_t C, int32_t O) {
@@ -694,18 +787,13 @@ int gcm_ffn_max_channels(void) { return kFfnMaxChannels; }
 int gcm_ffn_forward(const float* x, int64_t x_stride, const float* ln_w, const float* ln_b, float eps, const float* w1,
                     const float* b1, const float* w2, const float* b2, const float* row_scale, int64_t N, int32_t C,
                     int32_t Hd, float* y, int64_t y_stride, float* mean, float* rstd, float* a, void* hip_stream) {
-  const std::string who("gcm_ffn_forward");
-  if (int rc = check_ffn_shape(who, N, C, Hd)) return rc;
-  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
-  if (int rc = check_strides(who, {{x_stride, C}, {y_stride, C}})) return rc;
-  if (int rc = check_aligned16(who, {x, ln_w, ln_b, w1, b1, w2, b2, y, a})) return rc;
+  FfnPlan p;
+  if (int rc = check_ffn_forward("gcm_ffn_forward", false, x, x_stride, ln_w, ln_b, eps, w1, b1, w2, b2, N, C, Hd, y, y_stride, mean,
+                                 rstd, a, nullptr, 0, p))
+    return rc;
   if (N == 0) return GCM_OK;
-  if (!x || !ln_w || !ln_b || !w1 || !b1 || !w2 || !b2 || !y)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, ln_w, ln_b, w1, b1, w2, b2 or y");
-  if ((mean == nullptr) != (rstd == nullptr) || (a && !mean))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": mean and rstd come together, and a needs both");
   with_nj(C, [&](auto nj) {
-    k_ffn_forward<decltype(nj)::value><<<blocks_for(N, T), 256, 0, (hipStream_t)hip_stream>>>(
+    k_ffn_forward<decltype(nj)::value><<<(unsigned)p.tiles, 256, 0, (hipStream_t)hip_stream>>>(
         x, x_stride, ln_w, ln_b, eps, w1, b1, w2, b2, row_scale, N, C, Hd, y, y_stride, mean, rstd, a);
   });
   HIP_TRY(hipGetLastError(), "ffn forward launch");
@@ -713,9 +801,9 @@ int gcm_ffn_forward(const float* x, int64_t x_stride, const float* ln_w, const f
 }
 
 size_t gcm_ffn_backward_workspace_bytes(int64_t N, int32_t C, int32_t Hd) {
-  if (check_ffn_shape("gcm_ffn_backward_workspace_bytes", N, C, Hd)) return 0;
+  if (check_ffn_shape("gcm_ffn_backward_workspace_bytes", false, N, C, Hd)) return 0;
   g_err.clear();
-  return ffn_plan(N, C, Hd).total;
+  return ffn_plan(N, C, Hd, false).total;
 }
 
 int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const float* rstd, const float* a,
@@ -723,68 +811,25 @@ int gcm_ffn_backward(const float* x, int64_t x_stride, const float* mean, const 
                      const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
                      float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
                      size_t workspace_bytes, void* hip_stream) {
-  const std::string who("gcm_ffn_backward");
-  if (int rc = check_ffn_shape(who, N, C, Hd)) return rc;
-  if (int rc = check_strides(who, {{x_stride, C}, {dy_stride, C}, {dx_stride, C, dx != nullptr}})) return rc;
-  if (int rc = check_aligned16(who, {x, a, dy, ln_w, ln_b, w1, w2, dx, dln_w, dln_b, dw1, db1, dw2, db2})) return rc;
-  const FfnPlan p = ffn_plan(N, C, Hd);
-  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_ffn_backward_workspace_bytes")) return rc;
-  if (N > 0 && (!x || !mean || !rstd || !a || !dy || !ln_w || !ln_b || !w1 || !w2))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, mean, rstd, a, dy, ln_w, ln_b, w1 or w2");
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
-    const size_t CH = (size_t)C * Hd * 4, C4 = (size_t)C * 4;
-    return clear_outputs(st, {{dln_w, C4, "ffn backward clear dln_w"},
-                              {dln_b, C4, "ffn backward clear dln_b"},
-                              {dw1, CH, "ffn backward clear dw1"},
-                              {db1, (size_t)Hd * 4, "ffn backward clear db1"},
-                              {dw2, CH, "ffn backward clear dw2"},
-                              {db2, C4, "ffn backward clear db2"}});
-  }
-  char* ws = (char*)workspace;
-  float* da = (float*)(ws + p.da);
-  const bool ln = dln_w || dln_b, first = dw1 || db1, params = first || dw2 || db2;
-  if (dx || ln || first) {
-    float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
-    with_nj(C, [&](auto nj) {
-      k_ffn_bwd_rows<decltype(nj)::value><<<(unsigned)p.tiles, 256, 0, st>>>(x, x_stride, mean, rstd, a, dy, dy_stride, row_scale,
-                                                                            ln_w, w1, w2, N, C, Hd, dx, dx_stride, da, lnpart);
-    });
-    HIP_TRY(hipGetLastError(), "ffn backward rows launch");
-    if (ln) {
-      fold_ln_partials(lnpart, (float*)(ws + p.lngroup), p.tiles, p.groups, p.gper, 2, C, dln_w, dln_b, nullptr, nullptr, st);
-      HIP_TRY(hipGetLastError(), "ffn backward LayerNorm fold launch");
-    }
-  }
-  if (params) {
-    const int64_t per = slice_rows(N, p.sw);
-    float* part = (float*)(ws + p.wpart);
-    const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
-    k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
-                                   part);
-    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(part, p.sw, (int64_t)C * Hd, (int64_t)C * Hd, Hd, C, dw1, dw2,
-                                                                          db1, db2);
-    HIP_TRY(hipGetLastError(), "ffn backward weight gradient launch");
-  }
-  return GCM_OK;
+  return ffn_backward("gcm_ffn_backward", false, x, x_stride, mean, rstd, a, dy, dy_stride, row_scale, ln_w, ln_b, w1, w2, N, C, Hd,
+                      dx, dx_stride, dln_w, dln_b, dw1, db1, dw2, db2, workspace, workspace_bytes, hip_stream);
 }
 
 int gcm_ffn_split_max_channels(void) { return kFfnSplitMaxChannels; }
 
 int gcm_ffn_split_plan(int64_t N, int32_t C, int32_t Hd, int64_t plan[8]) {
   const std::string who("gcm_ffn_split_plan");
-  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
+  if (int rc = check_ffn_shape(who, true, N, C, Hd)) return rc;
   if (!plan) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null plan");
-  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
+  const FfnPlan p = ffn_plan(N, C, Hd, true);
   const int64_t out[8] = {p.split ? 1 : 0, p.tiles, p.chunks, p.records, p.sw, p.groups, kFfnSplitLimit, 0};
   std::copy(out, out + 8, plan);
   return GCM_OK;
 }
 
 int gcm_ffn_split_workspace_bytes(int64_t N, int32_t C, int32_t Hd, size_t* forward_bytes, size_t* backward_bytes) {
-  const std::string who("gcm_ffn_split_workspace_bytes");
-  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
-  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
+  if (int rc = check_ffn_shape("gcm_ffn_split_workspace_bytes", true, N, C, Hd)) return rc;
+  const FfnPlan p = ffn_plan(N, C, Hd, true);
   if (forward_bytes) *forward_bytes = std::max<size_t>(p.fwd_total, 256);  // never 0 for arguments in range
   if (backward_bytes) *backward_bytes = p.total;
   return GCM_OK;
@@ -794,19 +839,11 @@ int gcm_ffn_split_forward(const float* x, int64_t x_stride, const float* ln_w, c
                           const float* b1, const float* w2, const float* b2, const float* row_scale, int64_t N, int32_t C,
                           int32_t Hd, float* y, int64_t y_stride, float* mean, float* rstd, float* a, void* workspace,
                           size_t workspace_bytes, void* hip_stream) {
-  const std::string who("gcm_ffn_split_forward");
-  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
-  if (!std::isfinite(eps) || eps < 0.0f) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": eps must be finite and >= 0");
-  if (int rc = check_strides(who, {{x_stride, C}, {y_stride, C}})) return rc;
-  if (int rc = check_aligned16(who, {x, ln_w, ln_b, w1, b1, w2, b2, y, a})) return rc;
-  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
-  if (int rc = check_workspace(who, workspace, workspace_bytes, std::max<size_t>(p.fwd_total, 256), "gcm_ffn_split_workspace_bytes"))
+  FfnPlan p;
+  if (int rc = check_ffn_forward("gcm_ffn_split_forward", true, x, x_stride, ln_w, ln_b, eps, w1, b1, w2, b2, N, C, Hd, y, y_stride,
+                                 mean, rstd, a, workspace, workspace_bytes, p))
     return rc;
   if (N == 0) return GCM_OK;
-  if (!x || !ln_w || !ln_b || !w1 || !b1 || !w2 || !b2 || !y)
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, ln_w, ln_b, w1, b1, w2, b2 or y");
-  if ((mean == nullptr) != (rstd == nullptr) || (a && !mean))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": mean and rstd come together, and a needs both");
   HIP_TRY(split_lds_attr(), "ffn split LDS attribute");
   hipStream_t st = (hipStream_t)hip_stream;
   float* part = (float*)workspace;
@@ -831,61 +868,8 @@ int gcm_ffn_split_backward(const float* x, int64_t x_stride, const float* mean, 
                            const float* w1, const float* w2, int64_t N, int32_t C, int32_t Hd, float* dx, int64_t dx_stride,
                            float* dln_w, float* dln_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
                            size_t workspace_bytes, void* hip_stream) {
-  const std::string who("gcm_ffn_split_backward");
-  if (int rc = check_ffn_split_shape(who, N, C, Hd)) return rc;
-  if (int rc = check_strides(who, {{x_stride, C}, {dy_stride, C}, {dx_stride, C, dx != nullptr}})) return rc;
-  if (int rc = check_aligned16(who, {x, a, dy, ln_w, ln_b, w1, w2, dx, dln_w, dln_b, dw1, db1, dw2, db2})) return rc;
-  const FfnSplitPlan p = ffn_split_plan(N, C, Hd);
-  if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, "gcm_ffn_split_workspace_bytes")) return rc;
-  if (N > 0 && (!x || !mean || !rstd || !a || !dy || !ln_w || !ln_b || !w1 || !w2))
-    return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null x, mean, rstd, a, dy, ln_w, ln_b, w1 or w2");
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (N == 0) {  // nothing to sum: the parameter gradients are zeros
-    const size_t CH = (size_t)C * Hd * 4, C4 = (size_t)C * 4;
-    return clear_outputs(st, {{dln_w, C4, "ffn split backward clear dln_w"},
-                              {dln_b, C4, "ffn split backward clear dln_b"},
-                              {dw1, CH, "ffn split backward clear dw1"},
-                              {db1, (size_t)Hd * 4, "ffn split backward clear db1"},
-                              {dw2, CH, "ffn split backward clear dw2"},
-                              {db2, C4, "ffn split backward clear db2"}});
-  }
-  HIP_TRY(split_lds_attr(), "ffn split LDS attribute");
-  char* ws = (char*)workspace;
-  float* da = (float*)(ws + p.da);
-  float* part = (float*)(ws + p.part);
-  const bool ln = dln_w || dln_b, first = dw1 || db1, params = first || dw2 || db2;
-  if (dx || ln || first) {
-    float* lnpart = ln ? (float*)(ws + p.lnpart) : nullptr;
-    with_split_width(C, [&](auto nj, auto nb) {
-      constexpr int NJ = decltype(nj)::value, NB = decltype(nb)::value;
-      const dim3 grid((unsigned)p.tiles, (unsigned)p.records);
-      if (p.split)
-        k_ffn_split_bwd_rows<NJ, NB, true><<<grid, 256, split_bwd_lds(NJ, NB), st>>>(a, dy, dy_stride, row_scale, w1, w2, N, C, Hd, da,
-                                                                                     part);
-      else
-        k_ffn_split_bwd_rows<NJ, NB, false><<<grid, 256, split_bwd_lds(NJ, NB), st>>>(a, dy, dy_stride, row_scale, w1, w2, N, C, Hd, da,
-                                                                                      part);
-      if (dx || ln)
-        k_ffn_split_bwd_ln<NJ, NB><<<(unsigned)p.tiles, 256, split_ln_lds(NJ, NB), st>>>(
-            part, (int)p.records, x, x_stride, mean, rstd, dy, dy_stride, ln_w, N, C, dx, dx_stride, lnpart);
-    });
-    HIP_TRY(hipGetLastError(), "ffn split backward rows launch");
-    if (ln) {
-      fold_ln_partials(lnpart, (float*)(ws + p.lngroup), p.tiles, p.groups, p.gper, 2, C, dln_w, dln_b, nullptr, nullptr, st);
-      HIP_TRY(hipGetLastError(), "ffn split backward LayerNorm fold launch");
-    }
-  }
-  if (params) {
-    const int64_t per = slice_rows(N, p.sw);
-    float* wpart = (float*)(ws + p.wpart);
-    const dim3 grid(blocks_for(Hd, T) * blocks_for(C, T), (unsigned)p.sw, 2);
-    k_ffn_dw<<<grid, 256, 0, st>>>(x, x_stride, mean, rstd, a, da, dy, dy_stride, row_scale, ln_w, ln_b, N, (int)C, (int)Hd, per,
-                                   wpart);
-    k_ffn_fold_params<<<blocks_for(ffn_record(C, Hd), 256), 256, 0, st>>>(wpart, p.sw, (int64_t)C * Hd, (int64_t)C * Hd, Hd, C, dw1,
-                                                                          dw2, db1, db2);
-    HIP_TRY(hipGetLastError(), "ffn split backward weight gradient launch");
-  }
-  return GCM_OK;
+  return ffn_backward("gcm_ffn_split_backward", true, x, x_stride, mean, rstd, a, dy, dy_stride, row_scale, ln_w, ln_b, w1, w2, N, C,
+                      Hd, dx, dx_stride, dln_w, dln_b, dw1, db1, dw2, db2, workspace, workspace_bytes, hip_stream);
 }
 
 int gcm_front_max_channels(void) { return kFrontMaxChannels; }

@@ -1,5 +1,5 @@
 """The host-side plan of the split feed-forward entry points (gcm_ffn_split_*), transcribed into Python from
-gaussiancity_amd/csrc/gcm_ffn.h (ffn_split_plan), in the style of tests/gcm_plans.py.  The mode limit is a tuning constant
+gaussiancity_amd/csrc/gcm_ffn.h (ffn_plan with records), in the style of tests/gcm_plans.py.  The mode limit is a tuning constant
 of the library: the transcription takes it from the plan query (plan[6]) and never states it.
 
 tests/test_ffn_split_host.py holds the transcription to the library over a grid of shapes."""
@@ -9,7 +9,7 @@ FH = 64               # hidden features per chunk
 
 
 def split_plan(N, C, Hd, limit):
-    """ffn_split_plan: the mode, the records and both workspaces."""
+    """ffn_plan with records: the mode, the records and both workspaces."""
     tiles, chunks = _ceil(N, T), _ceil(Hd, FH)
     split = tiles * chunks <= limit
     records = chunks if split else 1
