@@ -5,7 +5,8 @@ of a PTv3 Block (gcm_ffn_*: LayerNorm, MLP and residual in one launch, its backw
 and the middle of the same Block (gcm_mid_*: the patch gather and its gradient, the scatter back, the output projection,
 DropPath and the residual in one launch, its backward) and the seams between the backbone's stages (gcm_seam_*: Linear,
 BatchNorm1d and GELU as one operator in eval and training mode, its backward) and the attribute head at inference in one
-launch per output key (gcm_head_chain), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
+launch per output key (gcm_head_chain) and the head's output layers in a training step (gcm_head_train_*: up to four keys,
+the transform and the [N, 14] record in one launch, a backward of two), all float32.  The declarations; gaussiancity_amd/_loader.py loads it.
 The library is the product: no Python/CPU fallback -- a missing library or failing call raises RuntimeError."""
 import ctypes as C
 
@@ -15,6 +16,16 @@ ABI_VERSION = 1
 KINDS = {"xyz": 0, "rgb": 1, "scale": 2, "opacity": 3}  # enum gcm_kind, by the head's name of the attribute
 
 _vp, _sz, _i32, _i64, _f32 = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_float
+
+
+class HeadKey(C.Structure):
+    """gcm_head_key: one key of gcm_head_train_forward / gcm_head_train_backward (strides in elements)."""
+    _fields_ = [("kind", _i32), ("factor", _f32), ("h", _vp), ("h_stride", _i64), ("w", _vp), ("b", _vp), ("out", _vp),
+                ("out_stride", _i64), ("dout", _vp), ("dout_stride", _i64), ("dh", _vp), ("dh_stride", _i64), ("dw", _vp),
+                ("db", _vp)]
+
+
+_keys = C.POINTER(HeadKey)
 _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argtypes)
     "gcm_abi_version": (C.c_int, []),
     "gcm_last_error": (C.c_char_p, []),
@@ -65,6 +76,12 @@ _SIGNATURES = {  # every function include/gcm.h declares: name -> (restype, argt
     "gcm_head_chain_max_in": (C.c_int, []),
     "gcm_head_chain": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                  _i32, _i32, _i32, _i32, _i32, C.c_int, _f32, _f32, _vp, _vp]),
+    "gcm_head_train_max_in": (C.c_int, []),
+    "gcm_head_train_pre_floats": (C.c_int, []),
+    "gcm_head_train_plan": (C.c_int, [_i64, _i32, C.POINTER(_i64)]),
+    "gcm_head_train_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "gcm_head_train_forward": (C.c_int, [_keys, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gcm_head_train_backward": (C.c_int, [_keys, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
 }
 
 _L = _loader.Library("gcm", "libgcm_hip.so", ABI_VERSION, _SIGNATURES)

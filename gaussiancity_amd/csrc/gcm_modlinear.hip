@@ -31,7 +31,8 @@
 // DESIGN.md section 20.  The fifth, the seams between the backbone's stages (gcm_seam_*: Linear, BatchNorm1d and GELU as
 // one operator up to 512 channels), is gcm_seam.h.  DESIGN.md section 21.  The sixth is the attribute head itself at
 // inference, its three layers in one launch per output key (gcm_head_chain), gcm_chain.h, included last.  DESIGN.md
-// section 17b.
+// section 17b.  The seventh is the head's output layers in a training step, forward and backward for up to four keys
+// (gcm_head_train_*), gcm_head.h.  DESIGN.md section 17c.
 // What the five share -- the 64-row tile, the product loop of the four fused operators, the host rules of the plans -- is
 // gcm_tile.h, included first.  DESIGN.md section 17a.
 #include <hip/hip_runtime.h>
@@ -512,6 +513,7 @@ BackwardPlan plan_backward(int64_t N, int32_t I, int32_t O, int32_t G) {
 #include "gcm_mid.h"
 #include "gcm_seam.h"
 #include "gcm_chain.h"
+#include "gcm_head.h"
 
 namespace {
 
@@ -1267,3 +1269,128 @@ int gcm_head_chain(const float* x, int64_t x_stride, const float* onehots, int64
 }
 
 }  // extern "C"
+
+int gcm_head_train_max_in(void) { return kHeadTrainMaxIn; }
+int gcm_head_train_pre_floats(void) { return kHeadPreFloats; }
+
+namespace {
+
+int check_head_train_shape(const std::string& w, int64_t N, int32_t I) {
+  if (N < 0 || N >= kMaxRows) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": N out of range");
+  if (I <= 0 || I % 4 != 0 || I > kHeadTrainMaxIn)
+    return fail(GCM_ERR_INVALID_ARGUMENT, w + ": I must be a positive multiple of 4, at most gcm_head_train_max_in()");
+  return 0;
+}
+
+// what the forward and the backward ask of every key; packed: the [N][14] form, so no key may carry out / dout
+int check_head_keys(const std::string& w, const gcm_head_key* keys, int32_t n_keys, int64_t N, int32_t I, bool backward,
+                    bool packed, HeadKeys& hk) {
+  if (n_keys < 1 || n_keys > 4) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": n_keys must be in 1..4");
+  if (!keys) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": null keys");
+  int seen = 0;
+  for (int k = 0; k < n_keys; k++) {
+    const gcm_head_key& key = keys[k];
+    if (key.kind != GCM_XYZ && key.kind != GCM_RGB && key.kind != GCM_SCALE && key.kind != GCM_OPACITY)
+      return fail(GCM_ERR_INVALID_ARGUMENT, w + ": unknown kind");
+    if (seen >> key.kind & 1) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": a kind is given twice");
+    seen |= 1 << key.kind;
+    if (!std::isfinite(key.factor)) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": factor is not finite");
+    const int C = head_channels(key.kind);
+    if (int rc = check_strides(w, {{key.h_stride, I}, {key.dh_stride, I, backward && key.dh != nullptr}})) return rc;
+    const void* form = backward ? (const void*)key.dout : (const void*)key.out;
+    if (form ? packed : (!packed && N > 0))  // without rows torch's empty tensors are null pointers: no form to tell
+      return fail(GCM_ERR_INVALID_ARGUMENT,
+                  w + (backward ? ": give every key's dout or dpoints14, not both and not neither"
+                                : ": give every key's out or points14, not both and not neither"));
+    if (form && (backward ? key.dout_stride : key.out_stride) < C)
+      return fail(GCM_ERR_INVALID_ARGUMENT, w + ": the row stride of out / dout must be at least C");
+    if (int rc = check_aligned16(w, {key.h, key.w})) return rc;
+    if (backward)
+      if (int rc = check_aligned16(w, {key.dh, key.dw})) return rc;
+    if (N > 0 && (!key.h || !key.w)) return fail(GCM_ERR_INVALID_ARGUMENT, w + ": null h or w");
+    hk.k[k] = key;
+  }
+  hk.n = n_keys;
+  return 0;
+}
+
+}  // namespace
+
+int gcm_head_train_plan(int64_t N, int32_t I, int64_t* plan) {
+  const std::string who("gcm_head_train_plan");
+  if (int rc = check_head_train_shape(who, N, I)) return rc;
+  if (!plan) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null plan");
+  const HeadTrainPlan p = head_train_plan(N, I);
+  const int64_t v[8] = {p.tiles, p.tpb, p.records, p.groups, p.per, p.levels, p.rec_floats, p.key_floats};
+  std::copy(v, v + 8, plan);
+  return GCM_OK;
+}
+
+size_t gcm_head_train_workspace_bytes(int64_t N, int32_t I, int32_t n_keys) {
+  const std::string who("gcm_head_train_workspace_bytes");
+  if (check_head_train_shape(who, N, I)) return 0;
+  if (n_keys < 1 || n_keys > 4) {
+    fail(GCM_ERR_INVALID_ARGUMENT, who + ": n_keys must be in 1..4");
+    return 0;
+  }
+  g_err.clear();
+  return round256((size_t)head_train_plan(N, I).key_floats * n_keys * 4);
+}
+
+int gcm_head_train_forward(const gcm_head_key* keys, int32_t n_keys, const int32_t* group, int64_t N, int32_t I, float* pre,
+                           const float* xyz, int64_t xyz_stride, const float* scales, int64_t scales_stride,
+                           float* points14, void* hip_stream) {
+  const std::string who("gcm_head_train_forward");
+  if (int rc = check_head_train_shape(who, N, I)) return rc;
+  HeadKeys hk;
+  if (int rc = check_head_keys(who, keys, n_keys, N, I, false, points14 != nullptr, hk)) return rc;
+  if (points14) {
+    bool rgb = false;
+    for (int k = 0; k < n_keys; k++) rgb = rgb || keys[k].kind == GCM_RGB;
+    if (!rgb || !xyz || !scales) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": points14 needs the rgb key, xyz and scales");
+    if (xyz_stride < 3 || scales_stride < 3)
+      return fail(GCM_ERR_INVALID_ARGUMENT, who + ": the row strides of xyz and scales must be at least 3");
+  }
+  if (N == 0) return GCM_OK;
+  k_head_train_fwd<<<blocks_for(N, 16), 256, 0, (hipStream_t)hip_stream>>>(hk, group, N, I, pre, xyz, xyz_stride, scales,
+                                                                           scales_stride, points14);
+  HIP_TRY(hipGetLastError(), "head train forward launch");
+  return GCM_OK;
+}
+
+int gcm_head_train_backward(const gcm_head_key* keys, int32_t n_keys, const int32_t* group, int64_t N, int32_t I,
+                            const float* pre, const float* scales, int64_t scales_stride, const float* dpoints14,
+                            int64_t dpoints_stride, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const std::string who("gcm_head_train_backward");
+  if (int rc = check_head_train_shape(who, N, I)) return rc;
+  HeadKeys hk;
+  if (int rc = check_head_keys(who, keys, n_keys, N, I, true, dpoints14 != nullptr, hk)) return rc;
+  if (dpoints14) {
+    if (dpoints_stride < 14) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": dpoints_stride must be at least 14");
+    for (int k = 0; k < n_keys; k++)
+      if (keys[k].kind == GCM_SCALE && (!scales || scales_stride < 3))
+        return fail(GCM_ERR_INVALID_ARGUMENT, who + ": dpoints14 with the scale key needs scales, row stride at least 3");
+  }
+  const HeadTrainPlan p = head_train_plan(N, I);
+  const size_t need = round256((size_t)p.key_floats * n_keys * 4);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, need, "gcm_head_train_workspace_bytes")) return rc;
+  if (N > 0 && !pre) return fail(GCM_ERR_INVALID_ARGUMENT, who + ": null pre");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (N == 0) {
+    for (int k = 0; k < n_keys; k++) {
+      const size_t C = (size_t)head_channels(keys[k].kind);
+      if (int rc = clear_outputs(st, {{keys[k].dw, C * I * 4, "head train clear dw"}, {keys[k].db, C * 4, "head train clear db"}}))
+        return rc;
+    }
+    return GCM_OK;
+  }
+  float* records = (float*)workspace;
+  k_head_train_rows<<<dim3((unsigned)p.records, (unsigned)n_keys), 256, 0, st>>>(
+      hk, group, N, I, pre, scales, scales_stride, dpoints14, dpoints_stride, p.tiles, (int)p.tpb, p.rec_floats, p.key_floats,
+      records);
+  HIP_TRY(hipGetLastError(), "head train rows launch");
+  k_head_train_fold<<<dim3(blocks_for(3 * (int64_t)I + 3, 16), (unsigned)n_keys), 256, 0, st>>>(
+      hk, I, p.records, p.per, (int)p.groups, p.rec_floats, p.key_floats, records);
+  HIP_TRY(hipGetLastError(), "head train fold launch");
+  return GCM_OK;
+}

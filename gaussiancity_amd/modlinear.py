@@ -7,6 +7,10 @@
   head_out(f, weight, bias, group, kind, factor)     the head's last linear layer and output transform, inference only
   head_chain(x, onehots, w1, b1, w_ma, w2, alpha, beta, bias2, group, w_out, b_out, kind, factor, negative_slope)
         the whole head for one output key in one launch, inference only: neither hidden activation reaches memory
+  head_attrs(keys, group=None)                    {kind: [N, C]} for keys = {kind: (h, weight, bias or None, factor)}: the
+        output layers and transforms of up to four keys in one launch, with gradients for every h, weight and bias
+  head_points14(keys, xyz, scales, group=None)    the same, written as the rasterizer's [N, 14] record (helpers.
+        get_gaussian_points on those values, xyz and scales untouched); the backward takes the record's gradient as it is
 
 torch supplies device memory (the caching allocator), autograd plumbing and the current stream; the computation is in
 the HIP library, float32 throughout, and nothing here waits for the device.
@@ -20,6 +24,7 @@ KINDS = tuple(M.KINDS)
 
 _STATS = {"forward_calls": 0, "backward_calls": 0, "groups_from_masks_calls": 0, "head_out_calls": 0}
 _CHAIN_STATS = {"head_chain_calls": 0}  # beside stats(), whose keys callers compare as a set
+_HEAD_TRAIN_STATS = {"forward_calls": 0, "backward_calls": 0, "pre_stored": 0, "dh_outputs": 0, "dw_outputs": 0, "db_outputs": 0}
 
 
 def stats():
@@ -32,11 +37,20 @@ def chain_stats():
     return dict(_CHAIN_STATS)
 
 
+def head_train_stats():
+    """Counters of this process: calls of gcm_head_train_forward and gcm_head_train_backward (head_attrs and head_points14
+    together), forwards that stored `pre` for a backward, and the gradient tensors the backwards allocated -- an input that
+    asks for no gradient gets none."""
+    return dict(_HEAD_TRAIN_STATS)
+
+
 def reset_stats():
     for k in _STATS:
         _STATS[k] = 0
     for k in _CHAIN_STATS:
         _CHAIN_STATS[k] = 0
+    for k in _HEAD_TRAIN_STATS:
+        _HEAD_TRAIN_STATS[k] = 0
 
 
 def dtypes():
@@ -264,3 +278,146 @@ def head_chain(x, onehots, w1, b1, w_ma, w2, alpha, beta, bias2, group, w_out, b
                 "gcm_head_chain")
     _CHAIN_STATS["head_chain_calls"] += 1
     return out
+
+
+# ---- the head's output layers in a training step -------------------------------------------------
+def head_train_limit():
+    """The largest hidden width head_attrs / head_points14 run in this build.  Loads the library."""
+    return M.lib().gcm_head_train_max_in()
+
+
+def _key_array(kinds, factors, hs, ws, bs):
+    keys = (M.HeadKey * len(kinds))()
+    for key, kind, factor, h, w, b in zip(keys, kinds, factors, hs, ws, bs):
+        key.kind, key.factor, key.h, key.h_stride, key.w, key.b = M.KINDS[kind], factor, h.data_ptr(), h.stride(0), w.data_ptr(), _ptr(b)
+    return keys
+
+
+class HeadTrainFunction(torch.autograd.Function):
+    """flat = (h, weight, bias) per key, in the order of kinds.  packed: the result is the [N, 14] record (one tensor),
+    otherwise one [N, C] tensor per key."""
+
+    @staticmethod
+    def forward(ctx, kinds, factors, group, xyz, scales, packed, *flat):
+        hs = [_rows(t) for t in flat[0::3]]
+        ws = [t.contiguous() for t in flat[1::3]]
+        bs = [None if t is None else t.contiguous() for t in flat[2::3]]
+        N, I = hs[0].shape
+        keys = _key_array(kinds, factors, hs, ws, bs)
+        grad = any(ctx.needs_input_grad)
+        L = M.lib()
+        pre = hs[0].new_empty((N, L.gcm_head_train_pre_floats())) if grad else None
+        if packed:
+            outs = (hs[0].new_empty((N, 14)),)
+        else:
+            outs = tuple(hs[0].new_empty((N, w.shape[0])) for w in ws)
+            for key, out in zip(keys, outs):
+                key.out, key.out_stride = out.data_ptr(), out.shape[1]
+        with torch.cuda.device(hs[0].device):
+            M.check(L.gcm_head_train_forward(keys, len(kinds), _ptr(group), N, I, _ptr(pre), _ptr(xyz),
+                                             xyz.stride(0) if packed and N else 3, _ptr(scales),
+                                             scales.stride(0) if packed and N else 3, outs[0].data_ptr() if packed else None,
+                                             _stream()), "gcm_head_train_forward")
+        _HEAD_TRAIN_STATS["forward_calls"] += 1
+        if grad:
+            _HEAD_TRAIN_STATS["pre_stored"] += 1
+            ctx.save_for_backward(pre, group, scales, *hs, *ws)
+            ctx.meta = (kinds, factors, packed, [b is not None for b in bs])
+        return outs[0] if packed else outs
+
+    @staticmethod
+    def backward(ctx, *douts):
+        kinds, factors, packed, has_b = ctx.meta
+        pre, group, scales = ctx.saved_tensors[:3]
+        n = len(kinds)
+        hs, ws = ctx.saved_tensors[3:3 + n], ctx.saved_tensors[3 + n:]
+        N, I = hs[0].shape
+        keys = _key_array(kinds, factors, hs, ws, [None] * n)
+        need = ctx.needs_input_grad[6:]
+        if packed:
+            dp = douts[0] if douts[0].dtype == torch.float32 else douts[0].float()
+            if N and (dp.stride(1) != 1 or dp.stride(0) < 14):
+                dp = dp.contiguous()
+        else:
+            dp, held = None, []
+            for key, w, d in zip(keys, ws, douts):
+                d = d if d.dtype == torch.float32 else d.float()
+                if N and (d.stride(1) != 1 or d.stride(0) < w.shape[0]):
+                    d = d.contiguous()
+                held.append(d)
+                key.dout, key.dout_stride = d.data_ptr(), d.stride(0) if N else w.shape[0]
+        grads = []
+        for k, (key, h, w) in enumerate(zip(keys, hs, ws)):
+            dh = h.new_empty((N, I)) if need[3 * k] else None
+            dw = h.new_empty(tuple(w.shape)) if need[3 * k + 1] else None
+            db = h.new_empty((w.shape[0],)) if has_b[k] and need[3 * k + 2] else None
+            key.dh, key.dh_stride, key.dw, key.db = _ptr(dh), I, _ptr(dw), _ptr(db)
+            for name, t in (("dh_outputs", dh), ("dw_outputs", dw), ("db_outputs", db)):
+                _HEAD_TRAIN_STATS[name] += t is not None
+            grads += [dh, dw, db]
+        L = M.lib()
+        ws_bytes = L.gcm_head_train_workspace_bytes(N, I, n)
+        work = _workspace(ws_bytes, hs[0].device)
+        with torch.cuda.device(hs[0].device):
+            M.check(L.gcm_head_train_backward(keys, n, _ptr(group), N, I, pre.data_ptr(), _ptr(scales),
+                                              scales.stride(0) if scales is not None and N else 3, _ptr(dp),
+                                              dp.stride(0) if packed and N else 14, work.data_ptr(), ws_bytes, _stream()),
+                    "gcm_head_train_backward")
+        _HEAD_TRAIN_STATS["backward_calls"] += 1
+        return (None, None, None, None, None, None, *grads)
+
+
+def _check_head_keys(keys):
+    """keys as head_attrs / head_points14 take them -> (kinds, factors, flat (h, weight, bias) per key, N)."""
+    if not hasattr(keys, "items") or not 1 <= len(keys) <= 4:
+        raise ValueError("keys must map one to four of %s to (h, weight, bias or None, factor)" % ", ".join(KINDS))
+    kinds, factors, flat, shape = [], [], [], None
+    limit = head_train_limit()
+    for kind, entry in keys.items():
+        if kind not in M.KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (", ".join(KINDS), kind))
+        h, w, b, factor = entry
+        if not isinstance(h, torch.Tensor) or h.dim() != 2 or not isinstance(w, torch.Tensor) or w.dim() != 2:
+            raise ValueError("%s: h must be [N, I] and weight [C, I]" % kind)
+        shape = tuple(h.shape) if shape is None else shape
+        (N, I), Cn = shape, 1 if kind == "opacity" else 3
+        if I % 4 or I == 0 or I > limit:
+            raise ValueError("I must be a positive multiple of 4, at most %d, got %d" % (limit, I))
+        op = "the head's output layers"
+        _check_float(kind + ": h", h, (N, I), op)
+        _check_float(kind + ": weight", w, (Cn, I), op)
+        _check_float(kind + ": bias", b, (Cn,), op, optional=True)
+        kinds.append(kind)
+        factors.append(float(factor))
+        flat += [h, w, b]
+    return tuple(kinds), tuple(factors), flat, shape[0]
+
+
+def head_attrs(keys, group=None):
+    """The head's output layers for up to four attributes in ONE launch, with gradients: keys maps kind (of KINDS, each at
+    most once, any order) to (h [N, I], weight [C, I], bias [C] or None, factor), C = 1 for opacity and 3 otherwise, all
+    float32 on the GPU with the same N and I (a multiple of 4 within head_train_limit()).  Returns {kind: [N, C]} in the
+    keys' order: transform(h @ weight.T + bias) with head_out's bits, exact zeros for a row whose group is negative.
+    Every h, weight and bias that requires a gradient gets one; two keys may pass the same h."""
+    kinds, factors, flat, N = _check_head_keys(keys)
+    outs = HeadTrainFunction.apply(kinds, factors, _check_group(group, N), None, None, False, *flat)
+    return dict(zip(kinds, outs))
+
+
+def head_points14(keys, xyz, scales, group=None):
+    """head_attrs written as the rasterizer's record [N, 14]: columns 0-2 xyz + attrs.xyz, 3 opacity (1 without the key), 4-6
+    scales * attrs.scale, 7-10 (1, 0, 0, 0), 11-13 rgb -- helpers.get_gaussian_points on head_attrs' values, except that xyz
+    and scales [N, >= 3] are read and left as they are.  keys needs "rgb"; xyz and scales are data and must not require a
+    gradient.  The backward reads the [N, >= 14] gradient of the record as the rasterizer's node returns it."""
+    kinds, factors, flat, N = _check_head_keys(keys)
+    if "rgb" not in kinds:
+        raise ValueError("head_points14 needs the rgb key")
+    for name, t in (("xyz", xyz), ("scales", scales)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != N or t.shape[1] < 3:
+            raise ValueError("%s must be [%d, >= 3]" % (name, N))
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise TypeError("%s must be a float32 CUDA tensor" % name)
+        if t.requires_grad:
+            raise ValueError("%s is data here: it gets no gradient and must not require one" % name)
+    dense = lambda t: t if t.shape[0] == 0 or t.stride(1) == 1 else t.contiguous()  # noqa: E731
+    return HeadTrainFunction.apply(kinds, factors, _check_group(group, N), dense(xyz), dense(scales), True, *flat)

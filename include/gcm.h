@@ -251,6 +251,40 @@
  *     once.  No float atomics: a row's bits depend on that row's inputs and the parameters alone -- not on N, the row's
  *     position or the run.  The kernel needs up to 157 184 bytes of LDS, which it asks the runtime for on the first call;
  *     a refusal comes back as GCM_ERR_HIP with the text.
+ *
+ * ---- The head's output layers in a training step ----------------------------------------------------
+ * Up to four keys (gcm_kind: xyz, rgb, scale, opacity), each at most once, in the caller's order, over the same N rows and
+ * the same hidden width I (a positive multiple of 4, at most gcm_head_train_max_in(): 512 in this build).  A key is a
+ * gcm_head_key: h [N][I] row-strided under the rule above, w [C][I] contiguous with C = 1 for opacity and 3 otherwise,
+ * b [C] or NULL, factor finite; h, w, dh and dw are 16-byte aligned, out / dout have a row stride of at least C elements.
+ * group is int32 [N] or NULL; only "group[r] >= 0" matters, as in gcm_head_out.
+ *     pre = h[r] . w[c] + b[c]                       gcm_head_out's summation, so out has gcm_head_out's bits
+ *     out = T(pre) by kind, exact zeros for a row without a group
+ * gcm_head_train_forward: ONE launch whatever n_keys is.  The values go EITHER to every key's out (points14 == NULL) OR to
+ *     points14, contiguous [N][14], the rasterizer's record (every key's out == NULL; needs the rgb key, xyz and scales,
+ *     [N][>= 3] with row strides in elements, read and never written):
+ *         0..2  xyz + out.xyz (xyz without the key)     3  out.opacity (1 without the key)
+ *         4..6  scales * out.scale (scales without it)  7..10  1, 0, 0, 0     11..13  out.rgb
+ *     in float32 on the bits above.  pre, when not NULL, is [N][gcm_head_train_pre_floats()] float32 and receives pre at
+ *     columns 3 * kind + c: what the backward reads.  N == 0 returns 0 and queues nothing (out, points14 and dout may
+ *     then all be NULL).
+ * gcm_head_train_backward: the incoming gradient is EITHER every key's dout [N][C] (dpoints14 == NULL) OR dpoints14
+ *     [N][>= 14] with row stride dpoints_stride as the rasterizer's node returns it (every key's dout == NULL; the scale
+ *     key's dout is then dpoints14[r][4..6] * scales[r], so scales is needed with that key).
+ *         dv = dout * factor * s (1 - s), s = sigmoid(pre) in double, rounded once         xyz, rgb, opacity
+ *         dv = dout * factor where -1 <= pre <= 1 (both ends included), else 0            scale
+ *         dv = 0 for a row without a group: an exact zero row of dh, no term in dw / db
+ *         dh [N][I] (row stride dh_stride) = dv w      dw [C][I] = dv^T h      db [C] = sum over the rows of dv
+ *     Two launches whatever N and n_keys are, no float atomics; each output is written whole by plain stores, a NULL
+ *     output is skipped, inputs are never written.  workspace is gcm_head_train_workspace_bytes(N, I, n_keys) bytes,
+ *     256-byte aligned, and need not be cleared.  N == 0 writes zeros to dw / db.  The row blocks, their records and the
+ *     fold's groups are gcm_head_train_plan's, a function of N and I alone: every output is bit-identical from run to
+ *     run, on any stream.
+ * gcm_head_train_plan fills plan[0..7]: tiles of 64 rows, tiles per row block, row blocks (= records per key), first-level
+ *     groups of the fold, records per group, fold levels (1 or 2), floats between records, floats between the keys' blocks.
+ * Refused with GCM_ERR_INVALID_ARGUMENT and a message before anything is queued: an unknown or repeated kind, n_keys
+ *     outside 1..4, I not a positive multiple of 4 or above the limit, a bad stride or alignment, neither or both
+ *     output / gradient forms, the [N][14] form without rgb, xyz or scales, a workspace that is too small.
  */
 #ifndef GCM_H
 #define GCM_H
@@ -392,6 +426,36 @@ int gcm_head_chain(const float* x, int64_t x_stride, const float* onehots, int64
                    const float* alpha, const float* beta, const float* bias2, const int32_t* group, const float* w_out,
                    const float* b_out, int64_t N, int32_t I, int32_t K, int32_t H, int32_t G, int32_t C, int kind,
                    float factor, float slope, float* out, void* hip_stream);
+
+/* one key of gcm_head_train_*: strides in elements */
+typedef struct gcm_head_key {
+  int32_t kind; /* enum gcm_kind */
+  float factor;
+  const float* h;
+  int64_t h_stride;
+  const float* w;
+  const float* b;
+  float* out; /* forward, per-key form */
+  int64_t out_stride;
+  const float* dout; /* backward, per-key form */
+  int64_t dout_stride;
+  float* dh; /* backward outputs, each may be NULL */
+  int64_t dh_stride;
+  float* dw;
+  float* db;
+} gcm_head_key;
+
+int gcm_head_train_max_in(void);
+int gcm_head_train_pre_floats(void);
+int gcm_head_train_plan(int64_t N, int32_t I, int64_t* plan);
+/* 0 with a message in gcm_last_error() when an argument is out of range */
+size_t gcm_head_train_workspace_bytes(int64_t N, int32_t I, int32_t n_keys);
+int gcm_head_train_forward(const gcm_head_key* keys, int32_t n_keys, const int32_t* group, int64_t N, int32_t I, float* pre,
+                           const float* xyz, int64_t xyz_stride, const float* scales, int64_t scales_stride,
+                           float* points14, void* hip_stream);
+int gcm_head_train_backward(const gcm_head_key* keys, int32_t n_keys, const int32_t* group, int64_t N, int32_t I,
+                            const float* pre, const float* scales, int64_t scales_stride, const float* dpoints14,
+                            int64_t dpoints_stride, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
