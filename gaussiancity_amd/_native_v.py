@@ -45,6 +45,7 @@ class GaussianAttrs(C.Structure):
 
 _vp, _i32, _i64, _sz, _f32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_int
 _pi32, _pf32, _seg = C.POINTER(_i32), C.POINTER(_f32), C.POINTER(SegIns)
+_st3, _st2 = C.POINTER(_i64 * 3), C.POINTER(_i64 * 2)  # HOST element strides {batch, channel, row} / {batch, row}
 _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argtypes)
     "gcv_abi_version": (_int, []),
     "gcv_last_error": (C.c_char_p, []),
@@ -74,6 +75,13 @@ _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argt
     "gcv_gaussian_points": (_int, [_vp, _i64, _vp, _i64, _i64, GaussianAttrs, _vp, _vp]),
     "gcv_frame_finish_radius_max": (_int, []),
     "gcv_frame_finish": (_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _pf32, _vp, _vp, _i32, _vp]),
+    "gcv_image_loss_max_classes": (_int, []),
+    "gcv_image_loss_partials": (_i64, [_i64, _i32]),
+    "gcv_mean_abs_forward": (_int, [_vp, _st3, _vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "gcv_mean_abs_backward": (_int, [_vp, _st3, _vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gcv_gan_loss_forward": (_int, [_vp, _st3, _vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "gcv_gan_loss_backward": (_int, [_vp, _st3, _vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "gcv_label_map": (_int, [_vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "gcv_set_option": (_int, [C.c_char_p, _int]),
     "gcv_get_stage_ms": (_int, [_pf32, _int]),
 }

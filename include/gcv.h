@@ -25,6 +25,9 @@
  *                                          scripts/inference.py:500-501
  *   gcv_frame_finish                       scripts/inference.py:255,264-272 (GaussianBlur through the road mask) and :665-667
  *                                          (the uint8 frame): torchvision + ten torch kernels upstream (additive to ABI v5)
+ *   gcv_mean_abs_* / gcv_gan_loss_* / gcv_label_map   core/train.py:285 (masked L1), losses/gan.py:55-97 (GANLoss.loss) and
+ *                                          models/discriminator.py:177-189 (_smooth_interp): about forty torch kernels per
+ *                                          training iteration upstream (additive to ABI v5)
  *   gcv_build_occupancy                    (none upstream: 1 bit per 16x16x16 macro cell; lets the traversal
  *                                           jump across empty macro cells, reproducing the reference walk
  *                                           exactly -- results unchanged)
@@ -270,6 +273,55 @@ int gcv_frame_finish(const float* img, int64_t batch_stride, int64_t channel_str
                      int32_t height, int32_t width, const int16_t* ins_map, int64_t map_batch_stride, int32_t road_id,
                      int32_t flip_mask_x, int32_t radius, const float* weights_host, float* out_f32, uint8_t* out_u8,
                      int32_t bgr, void* hip_stream);
+
+/* ---- K20-K22: the image losses of a training step (additive to ABI v5; probe gcv_image_loss_max_classes) ----
+ * core/train.py:285 (L1Loss()(a * mask, b * mask)), losses/gan.py:55-97 (GANLoss.loss) and
+ * models/discriminator.py:177-189 (_smooth_interp), for float tensors that are on the device.  Common to all five:
+ *   a tensor is a device pointer and a HOST array of element strides {batch, channel, row} ({batch, row} for a one-channel mask or weight); the
+ *   pixel stride is 1, no stride is negative, the element count is below 2^31;
+ *   nothing is allocated, nothing waits for the device, there are no atomics; GCV_ERR_INVALID_ARGUMENT before anything is
+ *   queued for a null or misaligned pointer, a non-positive size, more than gcv_image_loss_max_classes() classes, a
+ *   negative stride, and an output that overlaps an input or another output.
+ * A loss is two launches: partial sums per workgroup -- 4096 consecutive elements (K20) or 256 consecutive pixels (K21)
+ * each, so the cut depends on the shape alone -- into `partials` (at least gcv_image_loss_partials(n, pixels) doubles,
+ * 8-byte aligned, else GCV_ERR_BUFFER_TOO_SMALL), then one workgroup that adds them in a fixed order, divides by the count
+ * and stores one float in *loss.  Every addition is binary64, and K21's per-pixel log-sum-exp and softmax are evaluated in
+ * binary64 from the float logits: the loss is rounded once.  Two runs give the same bits.  A backward is one launch; it recomputes the terms from the
+ * inputs and reads the incoming gradient from the device (grad_loss: one float).
+ *
+ * K20  loss = sum |t| / (B C H W),  t = fl(fl(a m) - fl(b m)) with mask [B][1][H][W] (any values), a - b with mask NULL
+ *      da = fl(fl(g / count) * sign(t)) * m in float, db = -da (sign(0) = 0): contiguous [B][C][H][W], either may be NULL
+ * K21  pred [B][C+1][H][W], label [B][C][H][W], weight [B][1][H][W] or NULL; per pixel p_0 := 0, lab_0 := 0,
+ *      lse = max + log(sum_c exp(p_c - max)) over c = 0..C;
+ *        real != 0: per = sum_{1 <= c < C} lab_c (lse - p_c)        real == 0: per = lse - p_C
+ *      loss = mean over B H W of weight * per
+ *      dpred contiguous [B][C+1][H][W] = g / count * weight * (softmax_c S - lab_c) (S = sum of the lab_c that count,
+ *      lab_C = 0) or (softmax_c - [c == C]); channel 0 is exactly 0.  There is no gradient to label or weight.
+ * K22  out contiguous [B][C][h][w], h <= H, w <= W: per output pixel the window rows floor(i H / h) .. ceil((i + 1) H / h) - 1
+ *      (columns likewise: adaptive_avg_pool2d's) of seg * mask are summed per channel in row-major order; the channel
+ *      with the largest SUM gets 1.0, the others 0.0, a tie goes to the lowest channel (so does an all-zero window).  The
+ *      inputs are expected to be finite (torch's argmax prefers a NaN; this comparison does not).  One launch.
+ * (K20's entry points are gcv_mean_abs_*: L1Loss is the mean absolute difference, and this library's symbols are letters
+ * and underscores only.)
+ * gcv_image_loss_max_classes and gcv_image_loss_partials are host only; the latter returns 0 and sets gcv_last_error()
+ * for a count outside [1, 2^31). */
+int gcv_image_loss_max_classes(void); /* 32 */
+int64_t gcv_image_loss_partials(int64_t n_items, int32_t items_are_pixels);
+int gcv_mean_abs_forward(const float* a, const int64_t a_strides[3], const float* b, const int64_t b_strides[3], const float* mask,
+                   const int64_t mask_strides[2], int32_t batch, int32_t channels, int32_t height, int32_t width,
+                   double* partials, int64_t n_partials, float* loss, void* hip_stream);
+int gcv_mean_abs_backward(const float* a, const int64_t a_strides[3], const float* b, const int64_t b_strides[3], const float* mask,
+                    const int64_t mask_strides[2], int32_t batch, int32_t channels, int32_t height, int32_t width,
+                    const float* grad_loss, float* da, float* db, void* hip_stream);
+int gcv_gan_loss_forward(const float* pred, const int64_t pred_strides[3], const float* label, const int64_t label_strides[3],
+                         const float* weight, const int64_t weight_strides[2], int32_t batch, int32_t classes, int32_t height,
+                         int32_t width, int32_t real, double* partials, int64_t n_partials, float* loss, void* hip_stream);
+int gcv_gan_loss_backward(const float* pred, const int64_t pred_strides[3], const float* label, const int64_t label_strides[3],
+                          const float* weight, const int64_t weight_strides[2], int32_t batch, int32_t classes, int32_t height,
+                          int32_t width, int32_t real, const float* grad_loss, float* dpred, void* hip_stream);
+int gcv_label_map(const float* seg, const int64_t seg_strides[3], const float* mask, const int64_t mask_strides[2], int32_t batch,
+                  int32_t classes, int32_t height, int32_t width, int32_t out_height, int32_t out_width, float* out,
+                  void* hip_stream);
 
 /* avg device ms per stage since the last call (option "timing" of gcv_set_option; hipEvent pairs on the caller's
  * stream, a ring of 8 pairs per stage, so recording never waits for a stage still in flight):
