@@ -64,6 +64,20 @@ class Library:
         return {self.stage_names[i]: float(buf[i]) for i in range(n)}
 
 
+def fresh(t):
+    """A new tensor of t's values with dense strides, at the allocator's alignment."""
+    import torch
+    out = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+    return out.copy_(t) if out.numel() else out
+
+
+def dense(t, align=16):
+    """t as a library takes a dense operand: t itself when it is contiguous and its first byte `align`-byte aligned, else a
+    fresh copy.  Tensor.contiguous() does not serve: a contiguous view at a storage offset (a parameter inside a flat
+    buffer, `buf[1:].view(N, C)`) is returned as it is, misaligned pointer included."""
+    return t if t.is_contiguous() and t.data_ptr() % align == 0 else fresh(t)
+
+
 def current_stream():
     """The current torch stream as the `void* hip_stream` argument of the libraries' entry points."""
     import torch

@@ -13,6 +13,7 @@ import torch
 
 from . import _native_a as A
 from ._loader import current_stream as _stream
+from ._loader import fresh as _fresh
 
 SUPPORTED_HEAD_DIMS = A.HEAD_DIMS
 
@@ -40,7 +41,7 @@ class VarlenQKVPackedFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, cu_seqlens, max_seqlen, softmax_scale):
-        x = qkv if _kernel_ready(qkv) else qkv.contiguous()
+        x = qkv if _kernel_ready(qkv) else _fresh(qkv)
         cu = cu_seqlens.contiguous()
         total, _, heads, d = x.shape
         nseg = cu.shape[0] - 1
@@ -63,7 +64,7 @@ class VarlenQKVPackedFunction(torch.autograd.Function):
         nseg = cu.shape[0] - 1
         dy = dout if dout.dtype == x.dtype else dout.to(x.dtype)
         if not _kernel_ready(dy):
-            dy = dy.contiguous()
+            dy = _fresh(dy)
         dqkv = x.new_empty((total, 3, heads, d))
         if total:
             L = A.lib()

@@ -21,6 +21,7 @@ import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
+from ._loader import dense as _dense
 from .modlinear import _check_float as _check_float_op
 from .modlinear import _grad32, _ptr, _rows, _workspace
 
@@ -74,8 +75,8 @@ class LayerNormMlpResidualFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, eps, w1, b1, w2, b2, row_scale, split=False):
         x = _rows(x)
-        ln_w, ln_b, w1, b1, w2, b2 = (t.contiguous() for t in (ln_w, ln_b, w1, b1, w2, b2))
-        row_scale = None if row_scale is None else row_scale.contiguous()
+        ln_w, ln_b, w1, b1, w2, b2 = (_dense(t) for t in (ln_w, ln_b, w1, b1, w2, b2))
+        row_scale = None if row_scale is None else _dense(row_scale)
         N, C = x.shape
         Hd = w1.shape[0]
         need = any(ctx.needs_input_grad)

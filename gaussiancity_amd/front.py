@@ -18,6 +18,7 @@ import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
+from ._loader import dense as _dense
 from .modlinear import _check_float as _check_float_op
 from .modlinear import _grad32, _ptr, _rows, _workspace
 
@@ -45,7 +46,7 @@ class ConvTailNormQkvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s, wc, bc, lnc_w, lnc_b, lnc_eps, ln1_w, ln1_b, ln1_eps, wq, bq):
         x, s = _rows(x), _rows(s)
-        wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq = (t.contiguous() for t in (wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq))
+        wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq = (_dense(t) for t in (wc, bc, lnc_w, lnc_b, ln1_w, ln1_b, wq, bq))
         N, C = x.shape
         O = wq.shape[0]
         need = any(ctx.needs_input_grad)

@@ -25,6 +25,7 @@ import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
+from ._loader import dense as _dense
 from .modlinear import _check_float as _check_float_op
 from .modlinear import _grad32, _ptr, _rows, _workspace
 
@@ -162,7 +163,7 @@ class ProjResidualFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, inverse, extra, x, wp, bp, row_scale):
         a, x = _rows(a), _rows(x)
-        wp, bp = wp.contiguous(), bp.contiguous()
+        wp, bp = _dense(wp), _dense(bp)
         N, C = x.shape
         y = x.new_empty((N, C))
         with torch.cuda.device(x.device):
@@ -224,7 +225,7 @@ def proj_residual(a, inverse, extra, x, wp, bp, row_scale=None):
         if isinstance(row_scale, torch.Tensor) and row_scale.dim() == 2 and row_scale.shape[1] == 1:
             row_scale = row_scale[:, 0]
         _check_float("row_scale", row_scale, (N,))
-        row_scale = row_scale.detach().contiguous()
+        row_scale = _dense(row_scale.detach())
     named = {"a": a, "x": x, "wp": wp, "bp": bp, "inverse": inverse, "extra": extra, "row_scale": row_scale}
     _check_cuda_all(**{k: v for k, v in named.items() if v is not None})
     if extra is None:

@@ -23,6 +23,7 @@ import torch
 
 from . import _native_v as V
 from ._loader import current_stream as _stream
+from ._loader import dense as _dense
 
 MODELS = ("BLDG", "CAR", "REST")  # the key order of upstream's `models` dict (scripts/inference.py:470)
 _STATS = {"split_calls": 0, "points14_calls": 0}
@@ -226,7 +227,8 @@ def split_by_model(visible_set, model_rule, style_table=None, proj_tlp=None, pro
         if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
             raise TypeError("visible_set must hold pts float32 [1,M,8], batch_idx int32 [1,M,1], instances int16 [K], "
                             "classes float32 [1,M,1] and scales float32 [1,M,3] on one device")
-    pts, batch_idx, instances, classes, scales = (t.contiguous() for t in (pts, batch_idx, instances, classes, scales))
+    batch_idx, instances, classes, scales = (t.contiguous() for t in (batch_idx, instances, classes, scales))
+    pts = _dense(pts)  # the emit reads a row of pts as two 16-byte pieces
     if isinstance(style_table, dict):
         style_table = _cached_style_table(style_table, dev)
     if style_table is not None and style_table.device != dev:

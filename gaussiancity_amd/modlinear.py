@@ -19,6 +19,8 @@ import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
+from ._loader import dense as _dense
+from ._loader import fresh as _fresh
 
 KINDS = tuple(M.KINDS)
 
@@ -61,11 +63,11 @@ def dtypes():
 
 def _rows(t):
     """t [rows, width] as the library wants a row-strided operand: unit stride along the row, a row stride that is a
-    positive multiple of 4 elements and at least the width, 16-byte aligned; a contiguous copy otherwise."""
+    positive multiple of 4 elements and at least the width, 16-byte aligned; a fresh dense copy otherwise."""
     if t.shape[0] == 0:  # no rows: whatever strides the empty tensor carries (numpy's are 0), the library gets dense ones
         return t.new_empty(t.shape)
     ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= max(t.shape[1], 1) and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
+    return t if ok else _fresh(t)
 
 
 def _ptr(t):
@@ -98,9 +100,7 @@ class ModulatedLinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, alpha, beta, bias, group, slope, G):
         x, weight = _rows(x), _rows(weight)
-        alpha = None if alpha is None else alpha.contiguous()
-        beta = None if beta is None else beta.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        alpha, beta, bias = (None if t is None else _dense(t) for t in (alpha, beta, bias))
         N, I = x.shape
         O = weight.shape[0]
         y = x.new_empty((N, O))
@@ -207,8 +207,8 @@ def head_out(f, weight, bias, group, kind, factor):
     _check_float("weight", weight, (Cn, I))
     _check_float("bias", bias, (Cn,), optional=True)
     group = _check_group(group, N)
-    f, weight = _rows(f.detach()), weight.detach().contiguous()
-    bias = None if bias is None else bias.detach().contiguous()
+    f, weight = _rows(f.detach()), _dense(weight.detach())
+    bias = None if bias is None else _dense(bias.detach())
     out = f.new_empty((N, Cn))
     with torch.cuda.device(f.device):
         M.check(M.lib().gcm_head_out(f.data_ptr(), f.stride(0), weight.data_ptr(), _ptr(bias), _ptr(group), N, I, Cn,
@@ -263,7 +263,7 @@ def head_chain(x, onehots, w1, b1, w_ma, w2, alpha, beta, bias2, group, w_out, b
     if not slope > 0.0:
         raise ValueError("negative_slope must be > 0, got %r" % slope)
     group = _check_group(group, N)
-    dense = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+    dense = lambda t: None if t is None else _dense(t.detach())  # noqa: E731
     x, w1, w2 = _rows(x.detach()), _rows(w1.detach()), _rows(w2.detach())
     onehots = onehots.detach()
     if N and (onehots.stride(1) != 1 or onehots.stride(0) < K):
@@ -300,8 +300,8 @@ class HeadTrainFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, kinds, factors, group, xyz, scales, packed, *flat):
         hs = [_rows(t) for t in flat[0::3]]
-        ws = [t.contiguous() for t in flat[1::3]]
-        bs = [None if t is None else t.contiguous() for t in flat[2::3]]
+        ws = [_dense(t) for t in flat[1::3]]
+        bs = [None if t is None else _dense(t) for t in flat[2::3]]
         N, I = hs[0].shape
         keys = _key_array(kinds, factors, hs, ws, bs)
         grad = any(ctx.needs_input_grad)

@@ -8,8 +8,9 @@ operator.
         act=False the chain without the GELU.  training=False reads the running statistics: one launch, nothing but the
         result reaches memory unless a gradient is needed.  training=True uses the batch's statistics (three launches) and
         updates the three buffers in place on the device, as BatchNorm1d does (the three may all be None: nothing is
-        tracked then); it saves x, z, mean and rstd for the gradient, never u or the result.  Gradients for x, weight, bias,
-        bn_weight and bn_bias, deterministic (no float atomics).
+        tracked then; a buffer that is not 16-byte aligned, such as a view into a flat buffer, is updated through an
+        aligned temporary that the same stream copies back); it saves x, z, mean and rstd for the gradient, never u or the
+        result.  Gradients for x, weight, bias, bn_weight and bn_bias, deterministic (no float atomics).
   max_channels()                  the largest I and O the kernels run
   stats() / reset_stats()
 
@@ -22,6 +23,7 @@ import torch
 
 from . import _native_m as M
 from ._loader import current_stream as _stream
+from ._loader import dense as _dense
 from .modlinear import _check_float as _check_float_op
 from .modlinear import _grad32, _ptr, _rows, _workspace
 
@@ -54,9 +56,11 @@ class LinearBnGeluFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, bn_weight, bn_bias, running_mean, running_var, tracked, training, momentum, eps, act):
         x = _rows(x)
-        weight = None if weight is None else weight.contiguous()
-        bias = None if bias is None else bias.contiguous()
-        bn_weight, bn_bias = bn_weight.contiguous(), bn_bias.contiguous()
+        weight, bias = (None if t is None else _dense(t) for t in (weight, bias))
+        bn_weight, bn_bias = _dense(bn_weight), _dense(bn_bias)
+        # the running statistics as the library takes them (dense, 16-byte aligned): the caller's buffers wherever they
+        # are that, else aligned temporaries, which a training step copies back into the buffers on the same stream
+        stat_mean, stat_var = (None if t is None else _dense(t) for t in (running_mean, running_var))
         N, I = x.shape
         O = I if weight is None else weight.shape[0]
         need = any(ctx.needs_input_grad)
@@ -72,16 +76,19 @@ class LinearBnGeluFunction(torch.autograd.Function):
                 M.check(L.gcm_seam_forward_train(x.data_ptr(), x.stride(0), _ptr(weight), _ptr(bias), eps, momentum,
                                                  bn_weight.data_ptr(), bn_bias.data_ptr(), int(act), N, I, O, _ptr(z),
                                                  y.data_ptr(), y.stride(0), mean.data_ptr(), rstd.data_ptr(),
-                                                 _ptr(running_mean), _ptr(running_var), _ptr(tracked), ws.data_ptr(), ws_bytes,
+                                                 _ptr(stat_mean), _ptr(stat_var), _ptr(tracked), ws.data_ptr(), ws_bytes,
                                                  _stream()), "gcm_seam_forward_train")
+                for buffer, stat in ((running_mean, stat_mean), (running_var, stat_var)):
+                    if stat is not buffer:
+                        buffer.copy_(stat)
                 _STATS["forward_train_calls"] += 1
             else:
                 if need:  # a gradient in eval mode: the launch also leaves z and rstd
                     z = x.new_empty((N, O)) if weight is not None else None
                     rstd = x.new_empty((O,))
-                    mean = running_mean.clone()  # the buffer may be updated in place before the backward runs
-                M.check(L.gcm_seam_forward_eval(x.data_ptr(), x.stride(0), _ptr(weight), _ptr(bias), running_mean.data_ptr(),
-                                                running_var.data_ptr(), eps, bn_weight.data_ptr(), bn_bias.data_ptr(),
+                    mean = stat_mean.clone()  # the buffer may be updated in place before the backward runs
+                M.check(L.gcm_seam_forward_eval(x.data_ptr(), x.stride(0), _ptr(weight), _ptr(bias), stat_mean.data_ptr(),
+                                                stat_var.data_ptr(), eps, bn_weight.data_ptr(), bn_bias.data_ptr(),
                                                 int(act), N, I, O, y.data_ptr(), y.stride(0), _ptr(z), _ptr(rstd), _stream()),
                         "gcm_seam_forward_eval")
                 _STATS["forward_eval_calls"] += 1
