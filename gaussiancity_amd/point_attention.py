@@ -7,6 +7,7 @@ features' own dtype -- float32 features in fp32 throughout, float16 features (au
   stats() / reset_stats()               calls that took the fused path, calls that went to the module's own method
   forward_from_qkv(attn, point, qkv)    the rebound method from the qkv projection on, for a caller that has the
                                         projection already (point_front computes it in the Block front's one launch)
+  patches(attn, point)                  the method's patch size, row orders and patch bounds (point_mid's middle shares them)
 
 Independent of point_index.install: the rebound method calls self.get_padding_and_inverse, whoever provides it.  Relative
 position encoding, active attention dropout, the flash branch, CPU tensors and other dtypes go to the module's own method,
@@ -43,15 +44,22 @@ def _fusable(self, point):
 
 # ---- the method of models/pt_v3.py, written against its behaviour: the attributes it sets, its one wait for the smallest
 # batch element, the keys it reads, and the order of gather, attention, scatter, projection and dropout ----------------
-def forward_from_qkv(self, point, qkv):
-    """SerializedAttention.forward's non-flash branch from the projected qkv [N, 3C] on, over attention.varlen_attention:
-    the caller has checked _fusable(self, point) and that qkv's dtype is one of attention.dtypes().  Counted as a fused call."""
+def patches(self, point):
+    """(order, inverse, cu_seqlens) of the method's patches: the rows in padded serialized order, each point's row there,
+    the patch bounds.  Sets self.patch_size as the method does, which is its one wait."""
     counts = torch.diff(point.offset, prepend=point.offset.new_zeros(1))
-    self.patch_size = min(counts.min().tolist(), self.patch_size_max)  # the method's one wait
-    H, C = self.num_heads, self.channels
+    self.patch_size = min(counts.min().tolist(), self.patch_size_max)
     pad, unpad, cu_seqlens = self.get_padding_and_inverse(point)
     order = point.serialized_order[self.order_index][pad]
     inverse = unpad[point.serialized_inverse[self.order_index]]
+    return order, inverse, cu_seqlens
+
+
+def forward_from_qkv(self, point, qkv):
+    """SerializedAttention.forward's non-flash branch from the projected qkv [N, 3C] on, over attention.varlen_attention:
+    the caller has checked _fusable(self, point) and that qkv's dtype is one of attention.dtypes().  Counted as a fused call."""
+    order, inverse, cu_seqlens = patches(self, point)
+    H, C = self.num_heads, self.channels
     feat = attention.varlen_attention(qkv[order].reshape(-1, 3, H, C // H), cu_seqlens, max_seqlen=self.patch_size,
                                       softmax_scale=self.scale)
     feat = feat.reshape(-1, C)[inverse]

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from gaussiancity_amd import _native_m as M
-from gaussiancity_amd import ffn, point_ffn
+from gaussiancity_amd import ffn, point_block, point_ffn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = -1  # GCM_ERR_INVALID_ARGUMENT
@@ -180,9 +180,11 @@ def test_install_and_uninstall_are_idempotent_and_restore_the_method():
     bound = P.Block.forward
     assert bound is not own
     point_ffn.install(P)
-    assert P.Block.forward is bound and getattr(P, point_ffn._ORIGINAL) is own
+    st = point_block.state(P)
+    assert P.Block.forward is bound and st.bound is bound and st.original is own and st.ffn == (ffn.max_channels(), False)
     point_ffn.uninstall(P)
-    assert P.Block.forward is own and not hasattr(P, point_ffn._ORIGINAL)
+    assert P.Block.forward is own and point_block.state(P) is None
+    assert not [n for n in vars(P) if n.startswith("_gaussiancity_amd")]
     point_ffn.uninstall(P)
     assert P.Block.forward is own
 

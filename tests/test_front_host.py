@@ -17,7 +17,7 @@ import torch
 import front_plans as P
 import front_ref as R
 from gaussiancity_amd import _native_m as M
-from gaussiancity_amd import front, point_ffn, point_front
+from gaussiancity_amd import front, point_block, point_ffn, point_front
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = -1  # GCM_ERR_INVALID_ARGUMENT
@@ -268,7 +268,8 @@ def test_install_and_uninstall_are_idempotent_and_restore_the_method():
     bound = S.Block.forward
     assert bound is not own
     point_front.install(S)
-    assert S.Block.forward is bound and getattr(S, point_front._ORIGINAL) is own
+    st = point_block.state(S)
+    assert S.Block.forward is bound and st.bound is bound and st.original is own and st.front == front.max_channels()
     point_front.uninstall(S)
     assert S.Block.forward is own and not [n for n in vars(S) if n.startswith("_gaussiancity_amd")]
     point_front.uninstall(S)
@@ -302,18 +303,30 @@ def test_point_ffn_and_point_front_compose_in_either_order(install_order, uninst
     assert S.Block.forward is own and not [n for n in vars(S) if n.startswith("_gaussiancity_amd")]
 
 
-def test_install_binds_again_after_another_uninstall_took_its_method_away():
+def test_point_ffns_uninstall_leaves_point_front_running(monkeypatch):
     S = _stand_in()
     own = S.Block.forward
     point_ffn.install(S)
     point_front.install(S)
     first = S.Block.forward
-    point_ffn.uninstall(S)                      # puts the module's own method back, over point_front's
-    assert S.Block.forward is own
-    point_front.install(S)                      # not idempotent now: its method is not the one bound
-    assert S.Block.forward is not own and S.Block.forward is not first and getattr(S, point_front._ORIGINAL) is own
+    point_ffn.uninstall(S)                      # the front stays on, under the same method
+    st = point_block.state(S)
+    assert S.Block.forward is first and st.bound is first and st.original is own and st.ffn is None and st.front is not None
+
+    class Reached(Exception):
+        pass
+
+    def stub(*args):
+        raise Reached
+    monkeypatch.setattr(front, "conv_tail_norm_qkv", stub)
+    block, point = S.Block(), _point()
+    block.cpe[0].forward = lambda sparse: types.SimpleNamespace(features=None)
+    point.sparse_conv_feat = None
+    with pytest.raises(Reached):                # a Block the front accepts reaches the fused front
+        block(point)
     point_front.uninstall(S)
-    assert S.Block.forward is own
+    assert S.Block.forward is own and point_block.state(S) is None
+    assert not [n for n in vars(S) if n.startswith("_gaussiancity_amd")]
 
 
 class _FakeCuda:

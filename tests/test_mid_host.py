@@ -2,7 +2,7 @@
 are in the header, the binding table and the library's dynamic symbols, the capability query answers at least 128, every
 argument error of the header comes back as GCM_ERR_INVALID_ARGUMENT with a message before a device is touched, an empty
 problem returns 0, the workspace query agrees with the transcribed plan of tests/mid_plans.py; mid's operators refuse what
-the library does not run; point_mid.install / uninstall set and remove their marker on a stand-in models.pt_v3, install
+the library does not run; point_mid.install / uninstall turn the middle on and off on a stand-in models.pt_v3, install
 point_front when it is not bound and leave it otherwise, in both orders with point_ffn; torch's own float32 run is fair on
 the inputs of tests/test_mid_gpu.py."""
 import ctypes as C
@@ -17,7 +17,7 @@ import torch
 import mid_plans as P
 import mid_ref as R
 from gaussiancity_amd import _native_m as M
-from gaussiancity_amd import mid, point_ffn, point_front, point_mid
+from gaussiancity_amd import front, mid, point_block, point_ffn, point_front, point_mid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = -1  # GCM_ERR_INVALID_ARGUMENT
@@ -326,11 +326,14 @@ def test_install_installs_point_front_first_and_uninstall_removes_only_the_marke
     assert S.Block.forward is own and not _marks(S)
     point_mid.install(S)
     bound = S.Block.forward
-    assert bound is not own and getattr(S, point_front._BOUND) is bound and getattr(S, point_mid._MARK) is True
+    st = point_block.state(S)
+    assert bound is not own and st.bound is bound and st.original is own and st.mid is True
+    assert st.front == front.max_channels() and st.ffn is None
     point_mid.install(S)                            # idempotent
     assert S.Block.forward is bound
     point_mid.uninstall(S)
-    assert S.Block.forward is bound and point_mid._MARK not in vars(S)      # point_front stays
+    assert S.Block.forward is bound and point_block.state(S).mid is False   # point_front stays
+    assert point_block.state(S).front == front.max_channels()
     point_front.uninstall(S)
     assert S.Block.forward is own and not _marks(S)
 
@@ -341,9 +344,11 @@ def test_install_leaves_a_point_front_binding_and_its_cap_as_they_are():
     point_front.install(S, max_channels=64)
     bound = S.Block.forward
     point_mid.install(S)
-    assert S.Block.forward is bound and getattr(S, point_front._CAP) == 64
-    point_front.uninstall(S)                        # the other order of leaving: the marker alone binds nothing
-    assert S.Block.forward is own and _marks(S) == [point_mid._MARK]
+    assert S.Block.forward is bound and point_block.state(S).front == 64 and point_block.state(S).mid is True
+    point_front.uninstall(S)                        # the other order of leaving: the middle alone binds nothing
+    st = point_block.state(S)
+    assert S.Block.forward is own and len(_marks(S)) == 1
+    assert (st.original, st.bound, st.front, st.mid, st.ffn) == (None, None, None, True, None)
     point_mid.uninstall(S)
     assert not _marks(S)
 
@@ -374,7 +379,7 @@ def test_point_mid_composes_with_point_ffn_and_point_front_in_either_order(insta
 def test_what_the_middle_does_not_compute_is_handed_back_and_counted():
     S = _stand_in()
     point = lambda c=16: types.SimpleNamespace(feat=_FakeCuda((5, c)))  # noqa: E731
-    assert point_mid.accepts(S.Block(), point(), S) is None                     # no marker: nothing is asked or counted
+    assert point_mid.accepts(S.Block(), point(), S) is None                     # not on: nothing is asked or counted
     point_mid.install(S)
     try:
         point_mid.reset_stats()

@@ -189,7 +189,7 @@ PT_V3 = types.SimpleNamespace(Block=Block, spconv=types.SimpleNamespace(
 
 @pytest.fixture()
 def installed():
-    """point_front alone; a test adds point_ffn itself.  Everything is taken off again, in the order that needs the care."""
+    """point_front alone; a test adds point_ffn itself.  Everything is taken off again."""
     from gaussiancity_amd import point_attention, point_ffn, point_front
     own = Block.forward
     point_front.install(PT_V3)
@@ -326,7 +326,7 @@ def test_the_front_the_attention_and_the_tail_compose(dev, installed):
     assert point.sparse_conv_feat.features is point.feat and block.attn.patch_size == PATCH
     assert len(want) == 3 + 16 and set(got) == set(want)
     _hold("composed", got, yard, want)
-    # the other install order: point_ffn's method, bound over point_front's, hands it the Blocks it accepts
+    # the other install order: the same thirds are on, so the same lines run
     point_front.uninstall(PT_V3)
     point_ffn.uninstall(PT_V3)
     assert Block.forward is own

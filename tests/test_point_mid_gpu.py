@@ -140,13 +140,38 @@ def test_the_front_the_middle_and_the_tail_compose(dev, clean, order):
     assert point.sparse_conv_feat.features is point.feat and block.attn.patch_size == PF.PATCH
     assert len(want) == 3 + 16 and set(got) == set(want)
     PF._hold("composed (%s)" % order, got, yard, want)
-    # the no-behaviour-change proof: without the marker the method runs the lines it ran before, to the bit
+    # the no-behaviour-change proof: with the middle off the method runs the lines it ran before, to the bit
     m.middle.uninstall(PT_V3)
     _reset(m)
     after, _, _, _ = PF._run(inp, dev, torch.float32)
     assert m.middle.stats() == {"fused_calls": 0, "original_calls": 0} and m.mid.stats() == dict.fromkeys(m.mid.stats(), 0)
     assert m.front.stats() == {"fused_calls": 1, "original_calls": 0} and m.attention.stats()["fused_calls"] == 1
     assert _bits_equal(after, never)
+
+
+def test_the_six_install_orders_of_the_three_thirds_give_the_same_bits_and_counters(dev, clean):
+    """Which thirds are on decides what runs, not the order they went on in: every output and gradient of the other five
+    orders has the first order's bits, in eval mode and in training mode with DropPath(0.3) from one seed, and every
+    counter its value."""
+    import itertools
+    m = clean
+    inp = PF._inputs()
+    mods = {"front": m.front, "mid": m.middle, "ffn": m.ffn}
+    own, first = Block.forward, None
+    for order in itertools.permutations(mods):
+        for name in order:
+            mods[name].install(PT_V3)
+        _reset(m)
+        got = (PF._run(inp, dev, torch.float32)[0], PF._run(inp, dev, torch.float32, drop_path=0.3, seed=1234)[0])
+        counters = [mod.stats() for mod in (m.mid, m.attention, m.ffn, m.front, m.middle)]
+        for name in order:
+            mods[name].uninstall(PT_V3)
+        assert Block.forward is own
+        if first is None:
+            first = (got, counters)
+            assert m.front.stats() == m.middle.stats() == m.ffn.stats() == {"fused_calls": 2, "original_calls": 0}
+        assert _bits_equal(got[0], first[0][0]) and _bits_equal(got[1], first[0][1]), order
+        assert counters == first[1], order
 
 
 def _hold_worst(label, cases):
