@@ -43,6 +43,16 @@ class GaussianAttrs(C.Structure):
     _fields_ = [("n_segments", C.c_int32), ("seg", GaussianSegment * 3)]
 
 
+class TrainRule(C.Structure):
+    """gcv_train_rule: instance id -> class, the one-hot's width, the special z classes and the constants of
+    get_point_scales' caller and get_projection_uv (core/train.py:207-224)."""
+    _fields_ = [(n, C.c_int32) for n in ("bldg_ins_min", "bldg_ins_max", "car_ins_min", "car_ins_max", "facade_class",
+                                         "roof_class", "car_class", "n_classes")] + [
+        ("special_z_classes", C.c_uint32), ("scale_factor", C.c_float), ("proj_size", C.c_float)]
+
+
+TRAIN_INPUTS_FLAG_OFFSET = 8  # GCV_TRAIN_INPUTS_FLAG_OFFSET: the flag word's byte offset in the workspace
+
 _vp, _i32, _i64, _sz, _f32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_int
 _pi32, _pf32, _seg = C.POINTER(_i32), C.POINTER(_f32), C.POINTER(SegIns)
 _st3, _st2 = C.POINTER(_i64 * 3), C.POINTER(_i64 * 2)  # HOST element strides {batch, channel, row} / {batch, row}
@@ -82,6 +92,10 @@ _SIGNATURES = {  # every function include/gcv.h declares: name -> (restype, argt
     "gcv_gan_loss_forward": (_int, [_vp, _st3, _vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "gcv_gan_loss_backward": (_int, [_vp, _st3, _vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "gcv_label_map": (_int, [_vp, _st3, _vp, _st2, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "gcv_train_inputs_max_classes": (_int, []),
+    "gcv_train_inputs_workspace_bytes": (_sz, [_i64]),
+    "gcv_train_inputs_count": (_int, [_vp, _i64, _i64, _vp, _sz, C.POINTER(_i64), _vp]),
+    "gcv_train_inputs_emit": (_int, [_vp, _i64, _i64, _i64, C.POINTER(TrainRule), _vp, _vp, _sz, _i32, _i64] + [_vp] * 8),
     "gcv_set_option": (_int, [C.c_char_p, _int]),
     "gcv_get_stage_ms": (_int, [_pf32, _int]),
 }

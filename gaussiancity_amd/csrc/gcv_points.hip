@@ -1367,3 +1367,4 @@ int gcv_visible_emit(const int64_t* vp_map, int64_t n_pixels, const int16_t* row
 #include "gcv_split.h"  // K17 / K18: per-model generator inputs and [N][14] assembly
 #include "gcv_finish.h"  // K19: frame finish (road-mask blur, composite, video bytes)
 #include "gcv_loss.h"    // K20-K22: masked L1, the N+1-label GAN loss, the discriminator's label map
+#include "gcv_train.h"   // K23 / K24: the generator's inputs of a training step

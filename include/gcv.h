@@ -28,6 +28,9 @@
  *   gcv_mean_abs_* / gcv_gan_loss_* / gcv_label_map   core/train.py:285 (masked L1), losses/gan.py:55-97 (GANLoss.loss) and
  *                                          models/discriminator.py:177-189 (_smooth_interp): about forty torch kernels per
  *                                          training iteration upstream (additive to ABI v5)
+ *   gcv_train_inputs_count / _emit         core/train.py:207-224 (the slices of pts, instances_to_classes, get_point_scales,
+ *                                          get_one_hot, get_projection_uv and get_z's grouping): about 20 + 3 I torch
+ *                                          kernels and I + 1 host waits per iteration upstream (additive to ABI v5)
  *   gcv_build_occupancy                    (none upstream: 1 bit per 16x16x16 macro cell; lets the traversal
  *                                           jump across empty macro cells, reproducing the reference walk
  *                                           exactly -- results unchanged)
@@ -322,6 +325,61 @@ int gcv_gan_loss_backward(const float* pred, const int64_t pred_strides[3], cons
 int gcv_label_map(const float* seg, const int64_t seg_strides[3], const float* mask, const int64_t mask_strides[2], int32_t batch,
                   int32_t classes, int32_t height, int32_t width, int32_t out_height, int32_t out_width, float* out,
                   void* hip_stream);
+
+/* ---- K23 / K24: the generator's inputs of a training step (additive to ABI v5; probe gcv_train_inputs_max_classes) ----
+ * core/train.py:207-224 -- the slices of pts, instances_to_classes (utils/datasets.py:265-282, :333-352), get_point_scales
+ * (utils/helpers.py:197-223), get_one_hot (:127-133), get_projection_uv (:183-194) and the grouping of get_z (:136-155) --
+ * for the loader's points as they lie on the device.
+ *   pts  float rows (x, y, z, scale, instance, rel_x, rel_y, rel_z, batch); row r starts at pts + r * row_stride (elements,
+ *        at least 9); n_rows = B * rows_per_batch, batch element b owning rows [b * rows_per_batch, (b + 1) * rows_per_batch)
+ * gcv_train_rule (HOST): the dataset's constants.  A row's class is the rule applied to its instance id -- facade for an
+ * even id in [bldg_ins_min, bldg_ins_max), roof for an odd one, then car for an id in [car_ins_min, car_ins_max), every
+ * other id kept -- the masks taken from the id, never from a class already assigned.
+ * Outputs of gcv_train_inputs_emit (any may be NULL = skipped; the columns a skipped output needs are not read):
+ *   classes  float [n_rows]             the class
+ *   scales3  float [n_rows][3]          scale * scale_factor (one fp32 multiply) three times; axis 2 exactly 1 where the class
+ *                                       is an integer c < 32 with bit c of special_z_classes set
+ *   onehots  float [n_rows][n_classes]  exactly one 1.0 per row
+ *   proj_uv  float [n_rows][2]          ((x - tlp_x) / proj_size) * 2 - 1, likewise y: one rounded fp32 operation each (K17's
+ *                                       rule); tlp = proj_tlp[row / rows_per_batch] from DEVICE memory, NULL = upstream's
+ *                                       `proj_tlp is None` branch
+ *   batch    int64 [n_rows]             (int64) of column 8, truncating
+ *   with_groups != 0, after gcv_train_inputs_count on the same rows and workspace:
+ *   group    int32 [n_rows]             the rank of the row's instance among the distinct instances, ascending
+ *   group_instances int16 [n_instances] those ids; n_instances must be the I that _count stored (it bounds the stores)
+ * A row is flagged when its instance is not an integer in [0, 32768) or its class is not an integer in [0, n_classes);
+ * it is never used as an index, its one-hot row is all zeros and its group is -1.  gcv_train_inputs_count enqueues a
+ * clear, mark and scan, waits, and stores counts_host = {I, rows whose instance is flagged} (it has no rule: a class
+ * outside the one-hot is emit's to find).  gcv_train_inputs_emit is one launch and does not wait; its last workgroup
+ * stores the number of rows it flagged as a uint32 at byte GCV_TRAIN_INPUTS_FLAG_OFFSET of the workspace, where it stays
+ * readable until the next call on that workspace.
+ * The workspace (gcv_train_inputs_workspace_bytes(n_rows), 16-byte aligned) holds the 32 768-bit presence table and its
+ * word prefix.  _count clears what it uses, so one workspace serves call after call.  An emit with with_groups == 0 needs
+ * no count in front of it, on a workspace that was zero-filled once (or has been through a _count): every emit leaves its
+ * counters zero again.  Nothing is allocated inside; integer atomics only (bit ORs, counters), so every output is
+ * deterministic.  GCV_ERR_INVALID_ARGUMENT before anything is queued for: a null or misaligned pointer (4 bytes; batch 8,
+ * group_instances 2, the workspace 16), row_stride < 9, n_rows outside [0, 2^31), n_classes outside 1..32, a proj_size
+ * that is zero or no number, a short workspace, rows_per_batch not dividing n_rows, n_instances outside [0, min(n_rows, 32768)].
+ * gcv_train_inputs_max_classes and gcv_train_inputs_workspace_bytes are host only; the latter returns 0 and sets
+ * gcv_last_error() for n_rows < 0 or >= 2^31. */
+#define GCV_TRAIN_INPUTS_FLAG_OFFSET 8
+typedef struct gcv_train_rule {
+  int32_t bldg_ins_min, bldg_ins_max; /* [min, max): facade if even, roof if odd */
+  int32_t car_ins_min, car_ins_max;   /* [min, max): car, applied last as upstream; min >= max: no cars */
+  int32_t facade_class, roof_class, car_class;
+  int32_t n_classes;          /* 1..32: the one-hot's width */
+  uint32_t special_z_classes; /* bit c: class c gets z-scale 1 */
+  float scale_factor;         /* cfg.NETWORK.GAUSSIAN.SCALE_FACTOR, one fp32 multiply */
+  float proj_size;
+} gcv_train_rule;
+int gcv_train_inputs_max_classes(void); /* host only: 32 -- a library that exports it has the entry points of K23 and K24 */
+size_t gcv_train_inputs_workspace_bytes(int64_t n_rows);
+int gcv_train_inputs_count(const float* pts, int64_t row_stride, int64_t n_rows, void* workspace, size_t workspace_bytes,
+                           int64_t counts_host[2], void* hip_stream);
+int gcv_train_inputs_emit(const float* pts, int64_t row_stride, int64_t n_rows, int64_t rows_per_batch,
+                          const gcv_train_rule* rule_host, const float* proj_tlp, void* workspace, size_t workspace_bytes,
+                          int32_t with_groups, int64_t n_instances, float* classes, float* scales3, float* onehots,
+                          float* proj_uv, int64_t* batch, int32_t* group, int16_t* group_instances, void* hip_stream);
 
 /* avg device ms per stage since the last call (option "timing" of gcv_set_option; hipEvent pairs on the caller's
  * stream, a ring of 8 pairs per stage, so recording never waits for a stage still in flight):
